@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- particle-updates/sec of the PIC1D time-step hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -73,16 +73,20 @@ CONFIGS = {
                inp=dict(nx=4096, iptcldist=0, species_density=[1.0], species_v0=[0.0], lx=4.0 * math.pi)),
 }
 
+# --dump-outputs: 2^20 markers x 4 float64 arrays = 32 MiB of samples at most (the field vectors are nx doubles each)
+DUMP_MARKERS = 1 << 20
+DUMP_SEED = 20635
+
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed block of --steps steps is run this many times back to back (each bracketed by "
-                         "barrier + device sync, max over ranks); value and ms_per_step are the MEDIAN block's, "
-                         "ms_per_step_min / _max the spread")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="run the timed block of --steps steps this many times back to back (each bracketed by "
+                         "barrier + device sync, max over ranks; repeats x steps timed steps in all); value and "
+                         "ms_per_step are the MEDIAN block's, ms_per_step_min / _max the spread")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--particles", type=int, default=0,
                     help="override the config's marker count (per GPU for c2/c3/c5, in total for c4)")
@@ -118,6 +122,11 @@ def parse():
                          "passes of this command run as child processes (N = 1 only)")
     ap.add_argument("--cpu-particles", type=int, default=10**7, help="markers of the CPU sample (BASELINE.md 3: C2)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target duration of the all-core CPU sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline engine holds after its last timed step as "
+                         "DIR/<name>.npy (float64): the field (electric, chargeden, mode_re, mode_im, field_energy) and a "
+                         "fixed, seeded sample of the markers (x, v, p, w; %d markers at most, split over the ranks; "
+                         "on several ranks one file per rank, <name>_rank<r>.npy)" % DUMP_MARKERS)
     return ap.parse_args()
 
 
@@ -314,6 +323,36 @@ class Job:
             self.eng.step(nsteps)
         else:
             self.call_sites(nsteps)
+
+
+def dump_sample(np_valid, rank, world):
+    """indices of the markers --dump-outputs writes from a rank holding np_valid of them: all, or a sorted sample fixed by
+    DUMP_SEED and the rank"""
+    import numpy as np
+    k = min(np_valid, DUMP_MARKERS // world)
+    return np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(np_valid, size=k, replace=False))
+
+
+def dump_outputs(eng, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- get_field(), field_energy() and
+    particles_download() -- as float64 .npy files; the markers as a sample whose indices depend only on the marker
+    count, the rank and DUMP_SEED, so that two builds run with the same arguments can be compared file for file"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if rank == 0:           # the field is the same on every rank
+        f = eng.get_field()
+        arrays.update((k, f[k]) for k in ("electric", "chargeden", "mode_re", "mode_im"))
+        arrays["field_energy"] = np.array([eng.field_energy()])
+    _, np_valid = eng.local_sizes()
+    parts = eng.particles_download()
+    idx = dump_sample(np_valid, rank, world)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    arrays.update((name + suffix, parts[name][idx]) for name in "xvpw")
+    del parts
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    return sorted(arrays)
 
 
 def measure_traffic(a, key):
@@ -674,12 +713,14 @@ def main():
     eng.kernel_stats_enable(True)
     eng.timers_reset()
     # R blocks of EXACTLY a.steps steps each, back to back, nothing else inside a timed region: boxes of the pool differ by
-    # +-1.5 % and a 20 ms region is one draw -- the line carries the median block and the spread
+    # +-1.5 % and a 20 ms region is one draw -- --repeats R > 1 gives the median block and the spread;
+    # by default (R = 1) --steps K is the number of timed steps, and what --dump-outputs writes follows the last of them
     repeats = max(1, a.repeats)
     blocks_s = [timed(job, a.steps) for _ in range(repeats)]
     elapsed = sorted(blocks_s)[(repeats - 1) // 2]         # the median block (the lower middle one for an even count)
     ktab = kernel_table(eng)
     eng.kernel_stats_enable(False)
+    dumped = dump_outputs(eng, a.dump_outputs, rank, world) if a.dump_outputs else None
     energy = eng.field_energy()
     _, np_local = eng.local_sizes()
     headline_kind = job.kind
@@ -993,6 +1034,9 @@ def main():
             "attribution": attr,
             "field_energy_end": energy, "steps_before_field_energy_end": settle + a.warmup + repeats * a.steps,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "names": dumped,
+                                     "after_steps": settle + a.warmup + repeats * a.steps}
         # the strong figure is the one measured with the headline's charge sum; the one-hop exchange measured beside
         # it is listed, never promoted
         xs = (exchange or {}).get("strong_1e8_total")

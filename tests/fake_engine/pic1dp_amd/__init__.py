@@ -121,6 +121,22 @@ class Pic1dp:
     def local_sizes(self, isp=0):
         return self.np, self.np
 
+    # -- what bench.py --dump-outputs reads: functions of the step counter and of the global marker index
+    def get_field(self, chargeden=True):
+        import numpy as np
+        nx, nm = self.inp["nx"], self.inp["nmode"]
+        out = dict(electric=np.linspace(0.0, 1.0, nx) * self.steps, mode_re=np.full(nm, float(self.steps)), mode_im=np.zeros(nm))
+        if chargeden:
+            out["chargeden"] = np.full(nx, 1.0 + self.steps)
+        return out
+
+    def particles_download(self, isp=0):
+        import numpy as np
+        n = self.inp["nparticle_max"]
+        first = n // self.nranks * self.rank + min(self.rank, n % self.nranks)
+        g = np.arange(first, first + self.np, dtype=np.float64)
+        return dict(x=g + self.steps, v=-g, p=np.ones(self.np), w=g * 1e-3 * self.steps)
+
     def kernel_stats_enable(self, on=True):
         self.k0 = self.steps
 

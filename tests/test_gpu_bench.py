@@ -54,14 +54,14 @@ def test_bench_contract_line_small(config, nx, kernel, carry):
     same launch priced on the compulsory bytes alone (frac_compulsory)"""
     n = 2_000_000
     d = run_bench(["--config", config, "--particles", str(n), "--strong-total", str(n), "--nx", str(nx), "--steps", "5",
-                   "--warmup", "2", "--no-cpu-baseline", "--no-traffic-pass"])
+                   "--warmup", "2", "--repeats", "5", "--no-cpu-baseline", "--no-traffic-pass"])
     for key in CONTRACT_KEYS:
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "f64"
     assert d["warmup_effective"] == d["warmup"] + d["settle_steps_before_warmup"]
     assert d["vs_baseline"] is None and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert abs(d["value"] - n * 2 * 5 / (d["ms_per_step"] * 5e-3)) < 1e-6 * d["value"]
-    # the timed block of K steps is run R >= 5 times back to back: the line carries the median block and the spread
+    # --repeats R: the timed block of K steps is run R >= 5 times back to back: the line carries the median block and the spread
     assert d["repeats"] >= 5 and len(d["ms_per_step_blocks"]) == d["repeats"]
     assert d["ms_per_step_min"] <= d["ms_per_step"] <= d["ms_per_step_max"]
     assert d["ms_per_step"] == sorted(d["ms_per_step_blocks"])[(d["repeats"] - 1) // 2]
@@ -102,6 +102,38 @@ def test_bench_measures_its_own_traffic():
     if r["traffic"] is None or "measured for this command in this run" not in (r["traffic_source"] or ""):
         pytest.skip("the counter passes were not possible here: %s" % r["traffic_source"])
     assert 0.97 < r["traffic"] / (r["bytes_per_marker"] * n) < 1.25
+
+
+def test_bench_dumps_what_its_last_timed_step_computed(amd, tmp_path):
+    """--dump-outputs DIR after K timed steps (--steps K, one block by default): the field and a seeded sample of the
+    markers are those of one engine stepped as often on the same input"""
+    import numpy as np
+    b = bench_module()
+    n, steps = 2_000_000, 5
+    d = run_bench(["--particles", str(n), "--strong-total", str(n), "--nx", "256", "--steps", str(steps), "--warmup", "2",
+                   "--no-cpu-baseline", "--no-traffic-pass", "--dump-outputs", str(tmp_path / "out")])
+    assert d["repeats"] == 1 and sum(d["config"]["kernel_launches_in_timed_steps"].values()) == steps
+    after = d["dumped_outputs"]["after_steps"]
+    assert after == d["warmup_effective"] + steps == d["steps_before_field_energy_end"]
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in d["dumped_outputs"]["names"]}
+    assert sorted(got) == ["chargeden", "electric", "field_energy", "mode_im", "mode_re", "p", "v", "w", "x"]
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    eng = amd.Pic1dp(amd.make_input(nparticle_max=n, nx=256))
+    eng.particle_load()
+    eng.interaction_collect_charge()
+    eng.field_solve_electric()
+    eng.step(after)
+    assert abs(float(got["field_energy"][0]) / eng.field_energy() - 1.0) < 1e-10
+    f = eng.get_field()
+    for k in ("electric", "chargeden"):
+        assert np.max(np.abs(got[k] - f[k])) <= 1e-10 * np.max(np.abs(f[k])), k
+    _, np_valid = eng.local_sizes()
+    idx = b.dump_sample(np_valid, 0, 1)
+    assert len(idx) == len(got["x"]) == b.DUMP_MARKERS
+    ref = eng.particles_download()
+    assert np.array_equal(got["p"], ref["p"][idx])
+    assert np.max(np.abs(got["x"] - ref["x"][idx])) < 1e-9 and np.max(np.abs(got["v"] - ref["v"][idx])) < 1e-9
+    eng.close()
 
 
 def virtual_rank_energy(amd, kw, npe, nsteps):

@@ -484,3 +484,64 @@ def test_bench_control_plane_at_eight_ranks_with_a_stand_in_engine():
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 4 and d["configs3_c4"]["particles_total"] == 10**8 and d["configs3_c4"]["scaling"] == "strong"
     assert "configs4_c5" not in d
+
+
+def _bench_with_stand_in_engine(args, cwd):
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, PIC1DP_BENCH_ENGINE=os.path.join(ROOT, "tests", "fake_engine"), MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-traffic-pass"] + args,
+                       cwd=str(cwd), env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_steps_are_the_timed_steps_and_the_outputs_are_dumped(tmp_path):
+    """`bench.py --steps K` times exactly K steps (one block unless --repeats asks for more), and --dump-outputs DIR writes
+    what the headline engine holds after the last of them -- the field and a fixed, seeded sample of the markers -- as
+    float64 .npy files of 64 MB at most, the same from run to run.  Control plane only (tests/fake_engine: a step advances a
+    counter, every array is a function of it and of the global marker index)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, steps = 3_000_000, 7
+    base = ["--particles", str(n), "--strong-total", str(n), "--nx", "64", "--steps", str(steps), "--warmup", "2"]
+    runs = []
+    for name in ("a", "b"):
+        d = _bench_with_stand_in_engine(base + ["--dump-outputs", name], tmp_path)      # a relative DIR: from the caller's cwd
+        assert d["repeats"] == 1 and d["steps"] == steps
+        assert sum(d["config"]["kernel_launches_in_timed_steps"].values()) == steps
+        after = d["steps_before_field_energy_end"]
+        assert after == d["warmup_effective"] + steps and d["dumped_outputs"]["after_steps"] == after
+        names = ["chargeden", "electric", "field_energy", "mode_im", "mode_re", "p", "v", "w", "x"]
+        assert d["dumped_outputs"]["names"] == names
+        assert sorted(f[:-4] for f in os.listdir(str(tmp_path / name))) == names
+        out = {k: np.load(str(tmp_path / name / (k + ".npy"))) for k in names}
+        assert all(a.dtype == np.float64 for a in out.values())
+        assert sum(a.nbytes for a in out.values()) <= 64 << 20
+        # the state after the last timed step: the stand-in's field follows its step count, x = marker index + steps
+        idx = bench.dump_sample(n, 0, 1)
+        assert len(idx) == bench.DUMP_MARKERS < n and np.all(np.diff(idx) > 0)
+        assert np.array_equal(out["electric"], np.linspace(0.0, 1.0, 64) * after)
+        assert np.array_equal(out["x"], idx + float(after)) and np.array_equal(out["v"], -idx.astype(np.float64))
+        runs.append(out)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    # --repeats R: R blocks of K steps
+    d = _bench_with_stand_in_engine(base + ["--repeats", "3"], tmp_path)
+    assert d["repeats"] == 3 and sum(d["config"]["kernel_launches_in_timed_steps"].values()) == 3 * steps
+    # several ranks: the field once, every rank's markers in files of their own (all of them here: fewer than the sample)
+    d = _bench_with_stand_in_engine(["--gpus", "2", "--particles", "500", "--strong-total", "1001", "--nx", "64", "--steps", "3",
+                                     "--warmup", "1", "--dump-outputs", "c"], tmp_path)
+    after = d["dumped_outputs"]["after_steps"]
+    got = sorted(f[:-4] for f in os.listdir(str(tmp_path / "c")))
+    assert got == sorted(["chargeden", "electric", "field_energy", "mode_im", "mode_re"] +
+                         ["%s_rank%d" % (k, r) for k in "xvpw" for r in (0, 1)])
+    x = np.concatenate([np.load(str(tmp_path / "c" / ("x_rank%d.npy" % r))) for r in (0, 1)])
+    assert np.array_equal(x, np.arange(1001) + float(after))
