@@ -441,6 +441,33 @@ int pic1dp_hip_ptcldist_finish(pic1dp_ctx *ctx, int32_t ispecies, double *markr_
 int pic1dp_hip_charge_local(pic1dp_ctx *ctx, double *charge2);
 int pic1dp_hip_charge_reduced(pic1dp_ctx *ctx, const double *charge1);
 
+/* ---- exact charge sum (round 7; opt-in) ----------------------
+ * set_charge_sum(kind): 0 FP64 atomics (the reference's sum; default), 1 exact.  In kind 1 every contribution
+ * wl q, (1 - wl) q of the deposit (src/pic1dp_interaction.F90:110,113) is rounded once to a whole number of quanta
+ * 2^e_s of its species, and the integers are summed exactly -- in the LDS, across workgroups, across ranks (RCCL
+ * int64, the one-hop exchange, or the host through the calls below).  Each species' total is converted to double
+ * once (round to nearest even) and times 2^e_s; from there the FP64 path runs as in kind 0 (species sum, nx/lx, the
+ * full-f -Z n0).  chargeden, E, the kept modes and the energy history then have the same bits whatever the launch
+ * shape, step mode, call sites (eager or lazy), reduction, or split of the markers over ranks.
+ *   - Only between time steps (nothing noted or owed, no charge_local pending): PIC1DP_ERR_STATE otherwise.  All ranks
+ *     switch at the same point of the run.  Back to 0 restores kind 0's paths.
+ *   - Kind 1 predicts nothing: step mode 0 runs two passes per step (pic1dp_hip_predict_kind reports 0 while it is
+ *     set), and the diagnostics of output_all are taken in their own pass with their own summation (not exact).
+ *   - A contribution of 2^62 quanta or more (a weight ~2^10 past the input's bound) is not summed: it is counted
+ *     (kernel_stats which = 14) and the next synchronising call returns PIC1DP_ERR_ARG naming the species.
+ *   - charge_local / charge_reduced return PIC1DP_ERR_STATE in kind 1 (a sum of doubles cannot be exact).
+ * charge_quantum: e_s = ceil(log2 B_s) - 52, B_s a bound on the species' |p| and |w| from the input alone (the
+ *   loader's prefactor times the distribution's peak times 1 + sum |perturbation amplitudes|): every rank agrees
+ *   without a collective.  Touches no device. */
+int pic1dp_hip_set_charge_sum(pic1dp_ctx *ctx, int32_t kind);
+int pic1dp_hip_charge_quantum(const pic1dp_input *in, int32_t ispecies, int32_t *log2_quantum);
+/* split phase of kind 1 for a host that owns the reduction (MPI_Allreduce of MPI_INT64_T with MPI_SUM):
+ * charge_local_exact -> limbs[nspecies][2][nx] int64: for species s and cell i, hi = limbs[(2 s) nx + i] and
+ *   lo = limbs[(2 s + 1) nx + i], 0 <= lo < 2^32; the cell's total is (hi 2^32 + lo) quanta 2^e_s.
+ * charge_reduced_exact <- the same array summed element by element over the ranks (lo need not be normalised). */
+int pic1dp_hip_charge_local_exact(pic1dp_ctx *ctx, int64_t *limbs);
+int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *ctx, const int64_t *limbs);
+
 /* ---- multi-GPU: RCCL communicator (replaces MPI_Allreduce at
  * src/pic1dp_interaction.F90:132) ------------------------------------------
  * rank 0 obtains an id, the host distributes the 128 bytes to every rank
@@ -540,7 +567,9 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 13: *launches = terms of the one-pass kernel's prediction tiles (two and three kept modes: 64-bit
  * fixed-point LDS sums scaled by per-species bounds that follow the markers) that lay beyond 16x their bound and
  * were added in doubles straight into the global accumulators -- rare by design, a count that grows with every
- * step says the bounds have lost the population; *ms = the first species' bound on |q| as it stands (waits for the stream) */
+ * step says the bounds have lost the population; *ms = the first species' bound on |q| as it stands (waits for the stream);
+ * which = 14: *launches = contributions of the exact charge sum (set_charge_sum(1)) beyond 2^62 quanta so far, which
+ * were not summed (each batch is reported once as PIC1DP_ERR_ARG), *ms = 0 (waits for the stream) */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

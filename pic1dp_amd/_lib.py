@@ -123,6 +123,10 @@ SIGNATURES = {
     "pic1dp_hip_ptcldist": [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P],
     "pic1dp_hip_charge_local": [_P, _P],
     "pic1dp_hip_charge_reduced": [_P, _P],
+    "pic1dp_hip_set_charge_sum": [_P, C.c_int32],
+    "pic1dp_hip_charge_quantum": [_INP, C.c_int32, C.POINTER(C.c_int32)],
+    "pic1dp_hip_charge_local_exact": [_P, _P],
+    "pic1dp_hip_charge_reduced_exact": [_P, _P],
     "pic1dp_hip_comm_unique_id": [_P],
     "pic1dp_hip_comm_init": [_P, _P],
     "pic1dp_hip_comm_available": [],

@@ -30,7 +30,8 @@ PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_st
     ("kernels_diag.hip", [], "kernels_diag"), ("kernels_opt.hip", [], "kernels_opt"), ("step_dispatch.cpp", [], "step_dispatch"),
     ("capi.cpp", [], "capi"), ("capi_step.cpp", [], "capi_step"), ("capi_comm.cpp", [], "capi_comm"), ("capi_diag.cpp", [], "capi_diag"),
     ("capi_optimize.cpp", [], "capi_optimize"), ("loader.cpp", [], "loader"), ("multirand.cpp", [], "multirand"),
-    ("optimize.cpp", [], "optimize"), ("species.cpp", [], "species"), ("hostcheck.cpp", [], "hostcheck")]
+    ("optimize.cpp", [], "optimize"), ("species.cpp", [], "species"), ("hostcheck.cpp", [], "hostcheck"),
+    ("exact_charge.cpp", [], "exact_charge")]
 PROBE_UNITS = [("probe.hip", [], "probe"), ("optcheck.cpp", [], "optcheck")]
 PROBE_SHARED = ["species", "hostcheck", "optimize", "multirand"]      # objects of the product the probe library links as well
 HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "loader.hpp",

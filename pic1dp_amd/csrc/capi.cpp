@@ -596,6 +596,7 @@ int pic1dp_hip_destroy(pic1dp_ctx *c) {
   if (c->st) (void)hipStreamSynchronize(c->st);
   comm_release(c);
   optimize_release(c);
+  fx_release(c);
   for (auto &S : c->sp) {
     (void)hipFree(S.slab[0]);
     (void)hipFree(S.slab[1]);
@@ -1111,7 +1112,17 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 13) return fail(PIC1DP_ERR_ARG, "which must be 0..13");
+  if (which < 0 || which > 14) return fail(PIC1DP_ERR_ARG, "which must be 0..14");
+  if (which == 14) {  // kind 1 of the charge sum: contributions beyond 2^62 quanta so far (not summed; reported as PIC1DP_ERR_ARG)
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    int64_t n = 0;
+    if (c->h_fx_ovf)
+      for (int s = 0; s < c->in.nspecies; ++s) n += static_cast<int64_t>(reinterpret_cast<volatile unsigned long long *>(c->h_fx_ovf)[s]);
+    if (launches) *launches = n;
+    if (ms) *ms = 0.0;
+    return PIC1DP_OK;
+  }
   if (which == 13) {  // prediction tiles: terms that went past the fixed-point sums (beyond 16x the bound); *ms: the first species' bound on |q|
     HIP_TRY(hipStreamSynchronize(c->st));
     int64_t n = 0;

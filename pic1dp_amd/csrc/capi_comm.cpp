@@ -1,5 +1,6 @@
 // capi_comm.cpp -- the charge sum over ranks: RCCL communicator (bound with dlopen, rccl_dyn.hpp), the one-hop
 // exchange's set-up over IPC-mapped memory, and the helpers the hot path calls (src/pic1dp_interaction.F90:126-135).
+#include <algorithm>
 #include <mutex>
 
 #include "ctx.hpp"
@@ -61,6 +62,9 @@ bool area_lookup(const unsigned char *handle, void **ptr, int *device) {
 
 bool xchg_active(const pic1dp_ctx *c) { return c->allreduce_kind == 2 && c->xc.connected; }
 
+// a slot carries the charge and the prediction's slices (XCHG_MAX_VEC), or kind 1's integer packet (2 nspecies)
+int xchg_vec(const pic1dp_ctx *c) { return std::max(XCHG_MAX_VEC, 2 * c->in.nspecies); }
+
 XchgArgs next_xchg_args(pic1dp_ctx *c) {
   XchgArgs x{};
   for (int q = 0; q < c->lay.nranks; ++q) {
@@ -73,13 +77,14 @@ XchgArgs next_xchg_args(pic1dp_ctx *c) {
   x.timeout_ticks = c->xc.timeout_ticks;
   x.rank = c->lay.rank;
   x.nranks = c->lay.nranks;
-  x.vstride = XCHG_MAX_VEC * c->in.nx;
+  x.vstride = xchg_vec(c) * c->in.nx;
   x.ticks = c->timers_on ? c->xc.ticks : nullptr;
   return x;
 }
 
 // a time-out reported by an exchange kernel (checked wherever the host synchronises)
 int xchg_check(pic1dp_ctx *c) {
+  if (int rc = fx_check(c)) return rc;  // (kind 1's overflow counter: read at the same synchronisation points)
   if (!c->xc.err) return 0;
   const unsigned long long e = *reinterpret_cast<volatile unsigned long long *>(c->xc.err);
   if (e == 0) return 0;
@@ -179,7 +184,7 @@ int pic1dp_hip_xchg_create(pic1dp_ctx *c, unsigned char handle[PIC1DP_XCHG_HANDL
   if (c->lay.nranks > XCHG_MAX_RANKS) return fail(PIC1DP_ERR_ARG, "the exchange serves at most %d ranks", XCHG_MAX_RANKS);
   if (c->xc.local) return fail(PIC1DP_ERR_STATE, "exchange area already created");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t bytes = kXchgFlagBytes + sizeof(double) * 2 * static_cast<size_t>(c->lay.nranks) * XCHG_MAX_VEC * c->in.nx;
+  const size_t bytes = kXchgFlagBytes + sizeof(double) * 2 * static_cast<size_t>(c->lay.nranks) * xchg_vec(c) * c->in.nx;
   // memory the peers' stores and this GPU's polls meet in has to be coherent across agents INSIDE a kernel:
   // fine-grained, else uncached.  Plain (coarse-grained) hipMalloc memory is not -- a stale L2 line of the
   // same-parity slot of exchange e - 2 would be summed without any error showing -- so the automatic chain stops

@@ -6,11 +6,12 @@
 
 namespace {
 
-LaunchCfg particle_launch(const pic1dp_ctx *c, int64_t np, bool with_E, bool with_rho) {
+// exact: the rho tile of kind 1 of the charge sum (two words per cell)
+LaunchCfg particle_launch(const pic1dp_ctx *c, int64_t np, bool with_E, bool with_rho, bool exact = false) {
   const int nx = c->in.nx;
   LaunchCfg lc{};
   lc.lds = sizeof(double) * ((with_E ? static_cast<size_t>((nx + 2) & ~1) : 0) +
-                             (with_rho ? static_cast<size_t>(nx) + 1 : 0));  // + guard cell
+                             (with_rho ? (exact ? 2 : 1) * (static_cast<size_t>(nx) + 1) : 0));  // + guard cell
   int by_lds = lc.lds ? static_cast<int>(kCuLds / (lc.lds + kStaticLds)) : 8;
   if (by_lds < 1) by_lds = 1;
   int threads = c->threads_req > 0 ? c->threads_req : 512;
@@ -45,23 +46,31 @@ PushArgs make_push_args(pic1dp_ctx *c, int isp, int irk, const double *E) {
   a.deltaf = c->in.deltaf;
   a.linear = c->in.linear;
   a.irk = irk;
+  a.fx = fx_args(c, isp);
   return a;
 }
 
+int enqueue_deposit(pic1dp_ctx *c);
+
 int enqueue_push(pic1dp_ctx *c, int irk, bool fused, const double *E = nullptr) {
   if (int rc = ensure_second_set(c)) return rc;
+  // kind 1 of the charge sum: where the E tile and the exact rho tile do not fit the LDS together (nx > 6780), the push
+  // and the deposit run as two launches (same positions and contributions, hence the same integers)
+  const bool exact = c->charge_sum == 1;
+  const bool deposit_apart = fused && exact && particle_launch(c, 2, true, true, true).lds > PARTICLE_LDS_CAP;
+  if (deposit_apart) fused = false;
   c->state_version++;
   for (int s = 0; s < c->in.nspecies; ++s) {
     PushArgs a = make_push_args(c, s, irk, E);
     if (a.np <= 0) continue;
-    LaunchCfg lc = particle_launch(c, a.np, true, fused);
+    LaunchCfg lc = particle_launch(c, a.np, true, fused, exact);
     {  // irk 1 reads x, v, p (+ w); irk 2 also the RK base x (+ v) (+ w); both write x (+ v) (+ w)
       pic1dp_ctx::KernelBytes &kb = c->kbytes[fused ? kTagFused : kTagPush];
       const double pushed = 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0));
       kb.rd = 8.0 * (3 + (c->in.deltaf ? 1 : 0)) + (irk == 2 ? pushed : 0.0);
       kb.wr = pushed;
       kb.carry = 0.0;
-      std::snprintf(kb.name, sizeof kb.name, "%s", fused ? "k_push<FUSED>" : "k_push");
+      std::snprintf(kb.name, sizeof kb.name, "%s", fused ? (exact ? "k_push<FUSED, EXACT>" : "k_push<FUSED>") : "k_push");
     }
     Span tm(c, PIC1DP_IWT_PUSH_PARTICLE, c->timers_on);
     Span ks(c, fused ? kTagFused : kTagPush, c->stats_on);
@@ -70,6 +79,7 @@ int enqueue_push(pic1dp_ctx *c, int irk, bool fused, const double *E = nullptr) 
     if (int rc = tm.end()) return rc;
   }
   c->cur = 1 - c->cur;
+  if (deposit_apart) return enqueue_deposit(c);
   return 0;
 }
 
@@ -80,14 +90,19 @@ int enqueue_deposit(pic1dp_ctx *c) {
     if (S.np <= 0) continue;
     double *x = S.set[c->cur].x;
     const double *q = c->in.deltaf ? S.set[c->cur].w : S.p;  // :84-91
-    LaunchCfg lc = particle_launch(c, S.np, false, true);
+    const bool exact = c->charge_sum == 1;
+    LaunchCfg lc = particle_launch(c, S.np, false, true, exact);
     {
       pic1dp_ctx::KernelBytes &kb = c->kbytes[kTagDeposit];
       kb.rd = 16.0, kb.wr = 8.0, kb.carry = 0.0;  // x, q read; wrapped x written
-      std::snprintf(kb.name, sizeof kb.name, "k_deposit");
+      std::snprintf(kb.name, sizeof kb.name, "%s", exact ? "k_deposit<EXACT>" : "k_deposit");
     }
     Span ks(c, kTagDeposit, c->stats_on);
-    HIP_TRY(launch_deposit(x, q, S.rho, S.np, c->grid, lc, c->st));
+    if (exact) {
+      HIP_TRY(launch_deposit_exact(x, q, fx_args(c, s), S.np, c->grid, lc, c->st));
+    } else {
+      HIP_TRY(launch_deposit(x, q, S.rho, S.np, c->grid, lc, c->st));
+    }
     if (int rc = ks.end()) return rc;
   }
   return 0;
@@ -295,7 +310,9 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   Span tm(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
   if (!noted)
     if (int rc = deposit_or_step(c)) return rc;
-  const bool multi = c->lay.nranks > 1 || c->comm != nullptr;
+  if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
+    if (int rc = fx_settle(c)) return rc;
+  const bool multi = c->charge_sum == 0 && (c->lay.nranks > 1 || c->comm != nullptr);
   if (multi)
     if (int rc = reduce_charge(c)) return rc;
   if (c->lazy_calls) {  // the species sum (one rank) and the scaling: in the launch of the solve_field that follows
@@ -403,8 +420,10 @@ static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
   } else if (int rc = enqueue_push(c, irk, true)) {
     return rc;
   }
-  const bool multi = c->lay.nranks > 1 || c->comm != nullptr;
-  const bool fused_xchg = xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
+  if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
+    if (int rc = fx_settle(c)) return rc;
+  const bool multi = c->charge_sum == 0 && (c->lay.nranks > 1 || c->comm != nullptr);
+  const bool fused_xchg = multi && xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
   if (multi && !fused_xchg)
     if (int rc = reduce_charge(c)) return rc;
   Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
@@ -427,14 +446,15 @@ int pic1dp_hip_substep(pic1dp_ctx *c, int32_t irk) {
 }
 
 // LDS bytes of the whole-step kernels: E0 tile, Eh tile (full only), rho tile
-size_t pic1dp_host::step_lds_bytes(int nx, bool full) {
+size_t pic1dp_host::step_lds_bytes(int nx, bool full, bool exact) {
   const size_t ne = static_cast<size_t>((nx + 2) & ~1);
-  return sizeof(double) * ((full ? 2 : 1) * ne + ((static_cast<size_t>(nx) + 2) & ~static_cast<size_t>(1)) +
+  return sizeof(double) * ((full ? 2 : 1) * ne + (exact ? 2 : 1) * ((static_cast<size_t>(nx) + 2) & ~static_cast<size_t>(1)) +
                            2);  // (+ the drawn chunks' counter, 16-byte slot)
 }
 
+// (kind 1 of the charge sum: its rho tile is twice as large -- up to nx 5080; beyond, the sub-step kernels)
 static bool step_recompute_ok(const pic1dp_ctx *c) {
-  return c->step_mode == 0 && step_lds_bytes(c->in.nx, true) <= PARTICLE_LDS_CAP;
+  return c->step_mode == 0 && step_lds_bytes(c->in.nx, true, c->charge_sum == 1) <= PARTICLE_LDS_CAP;
 }
 
 // Grid of a marker kernel: `resident` workgroups fill the CUs; with a grid of exactly that size the kernel ends
@@ -460,7 +480,7 @@ static int64_t oversubscribed(const pic1dp_ctx *c, int64_t np, int64_t resident,
 
 static LaunchCfg step_launch(const pic1dp_ctx *c, int64_t np, bool full) {
   LaunchCfg lc{};
-  lc.lds = step_lds_bytes(c->in.nx, full);
+  lc.lds = step_lds_bytes(c->in.nx, full, c->charge_sum == 1);
   int by_lds = static_cast<int>(kCuLds / (lc.lds + kStaticLds));
   if (by_lds < 1) by_lds = 1;
   // two workgroups of 768 threads per CU (24 waves): measured inside one process
@@ -498,14 +518,16 @@ static bool output_follows(const pic1dp_ctx *c) { return output_follows_at(c, c-
 // output pays a first-sub-step pass again (k_step_half): 10 steps + output_all at 1e8 markers 10.57 ms against 9.5 for
 // ten plain steps --, whereas k_step_one followed by the diagnostics' own pass (k_ptcldist: it changes no marker, the
 // prediction stays valid) costs that pass alone (profiles/r05/experiments/diag_bench.log).
+// (kind 1 of the charge sum: never -- the diagnostics keep their own pass and summation)
 static bool diag_in_step(const pic1dp_ctx *c) {
-  return c->fuse_output == 2 || (c->fuse_output == 1 && !predict_capable(c));
+  return c->charge_sum == 0 && (c->fuse_output == 2 || (c->fuse_output == 1 && !predict_capable(c)));
 }
 
 // One pass per step (kernels_step.hip k_step_one) needs: the mode-filter solver (the kept modes must
 // describe E), few kept modes, and LDS for E0, Eh, the mode tables and the four accumulators
+// (kind 1 of the charge sum: no prediction -- two passes per step)
 static bool predict_capable(const pic1dp_ctx *c) {
-  return c->predict && c->pred_kind != 0 && c->d_pred && c->field_solver == 0 && step_recompute_ok(c);
+  return c->charge_sum == 0 && c->predict && c->pred_kind != 0 && c->d_pred && c->field_solver == 0 && step_recompute_ok(c);
 }
 static size_t pred_doubles(const pic1dp_ctx *c) {
   return c->pred_kind == 2 ? 8 * PRED_SUM_COPIES : static_cast<size_t>(c->in.nspecies) * (1 + 2 * c->in.nmode) * c->in.nx;
@@ -652,6 +674,7 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
     // the drawn chunk tail of every whole-step kernel: half a workgroup's chunks, all of them for k_step_full (two passes
     // per step at 1e8 markers: 0.913 -> 0.898 ms with 16/16 against 8/16, profiles/r05/experiments/ab_dyn_tail_other.log)
     a.dyn_tail = (full && !pred) ? c->dyn_tail_full : c->dyn_tail;
+    a.fx = fx_args(c, s);
     // a species with general divisor constants and an exp-bearing f0 is FP64-issue-bound: its
     // -f0'/f0 at the step-start velocity goes from the first kernel to the second through
     // memory (8 B per marker) instead of being evaluated twice.  Measured at 1e8 markers
@@ -757,9 +780,9 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
       kb.wr = full ? 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0)) : 0.0;
       kb.carry = 0.0;
       if (a.t2) kb.carry = pred ? (a.t2_mode == 2 ? 16.0 : 8.0) : 8.0;  // k_step_one: 8 read (mode 2) + 8 written
-      std::snprintf(kb.name, sizeof kb.name, "%s%s", pred ? (c->pred_kind == 2 ? (priv ? "k_step_one<sums>" : "k_step_sums") : "k_step_one")
-                                                          : (full ? (diag ? "k_step_full<DIAG>" : "k_step_full") : "k_step_half"),
-                    S.sc.one_exp && c->in.deltaf ? " (one-exp -f0'/f0)" : "");
+      std::snprintf(kb.name, sizeof kb.name, "%s%s%s", pred ? (c->pred_kind == 2 ? (priv ? "k_step_one<sums>" : "k_step_sums") : "k_step_one")
+                                                            : (full ? (diag ? "k_step_full<DIAG>" : "k_step_full") : "k_step_half"),
+                    a.fx.acc ? "<EXACT>" : "", S.sc.one_exp && c->in.deltaf ? " (one-exp -f0'/f0)" : "");
       if (a.fused.on) std::strncat(kb.name, " + field solve", sizeof kb.name - std::strlen(kb.name) - 1);
     }
     Span tm(c, PIC1DP_IWT_PUSH_PARTICLE, c->timers_on);
@@ -883,8 +906,10 @@ static int finish_pending_solve(pic1dp_ctx *c) {
 
 // charge sum over ranks and field solve(s) behind the marker kernel(s) of a sub-step of the whole-step path
 static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
-  const bool multi = c->lay.nranks > 1 || c->comm != nullptr;
-  const bool fused_xchg = xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
+  if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
+    if (int rc = fx_settle(c)) return rc;
+  const bool multi = c->charge_sum == 0 && (c->lay.nranks > 1 || c->comm != nullptr);
+  const bool fused_xchg = multi && xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
   // RCCL path of a one-pass step: everything the two charge sums of the step need in one all-reduce
   const bool will_pack = pred && c->pred_version == c->state_version && multi && !fused_xchg && c->comm != nullptr &&
                          !xchg_active(c) && c->field_solver == 0 && 2 * c->in.nmode <= 256 && Eout == c->d_E;
@@ -1038,7 +1063,12 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT(kCallStateLegal[static_cast<int>(c->seq)][static_cast<int>(c->owed)]);
   INVARIANT(c->seq == Seq::Clean || (c->lazy_calls && c->loaded));    // a push is only noted by the lazy call sites
   INVARIANT(c->owed == Owed::Nothing || c->lazy_calls);
-  INVARIANT(c->owed < Owed::SumScale || one_rank);                    // species sum / prediction left to solve_field: one rank
+  INVARIANT(c->owed < Owed::SumScale || one_rank || c->charge_sum == 1);  // species sum / prediction left to solve_field: one rank
+                                                                      // (or exact sums, already summed over ranks)
+  // kind 1 of the charge sum: no prediction pending, no tiles, sums or half-step field owed
+  INVARIANT(c->charge_sum == 0 || c->pred_version == 0);
+  INVARIANT(c->charge_sum == 0 || (c->owed != Owed::PredTiles && c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField &&
+                                   !pair_of(c->seq)));
   INVARIANT(c->owed != Owed::PredTiles || c->pred_kind == 1);
   INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || (c->pred_kind == 2 && c->in.nmode == 1));
   INVARIANT(!pair_of(c->seq) || (c->call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
@@ -1066,6 +1096,11 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   unsigned ticket = 0;
   HIP_TRY(hipMemcpy(&ticket, c->d_ticket, sizeof ticket, hipMemcpyDeviceToHost));
   INVARIANT(ticket == 0u);
+  if (c->d_fx) {  // the exact accumulators are settled (or handed out) by the call that deposited into them
+    std::vector<long long> fx(2 * static_cast<size_t>(c->in.nspecies) * c->in.nx);
+    HIP_TRY(hipMemcpy(fx.data(), c->d_fx, sizeof(long long) * fx.size(), hipMemcpyDeviceToHost));
+    for (long long v : fx) INVARIANT(v == 0 && "exact deposits nobody is going to sum");
+  }
   // accumulators: the sets the marker kernels do not deposit into are zero; the current one holds something only while
   // a collect_charge has left its end to solve_field (Owed::SumScale, PredTiles: deposits; with a usable prediction: the six sums / tiles)
   auto nonzero = [](const std::vector<double> &v, size_t off, size_t n) {
@@ -1132,6 +1167,8 @@ int pic1dp_host::rebuild_half_step_chargeden(pic1dp_ctx *c) {
   if (int rc = enqueue_push(c, 1, false, c->d_E0)) return rc;
   if (int rc = set_seq(c, Seq::Clean)) return rc;  // memory now holds the half-step state (x not yet wrapped): the deposit wraps and stores it
   if (int rc = enqueue_deposit(c)) return rc;
+  if (c->charge_sum == 1)
+    if (int rc = fx_settle(c)) return rc;
   HIP_TRY(launch_chargeden(c->fa, true, c->st));
   c->cd_kept_mode_only = false;
   // a push(2) that had been noted: memory as the eager calls would have left it (the field it sees, d_E, is the one
@@ -1147,6 +1184,7 @@ int pic1dp_host::rebuild_half_step_chargeden(pic1dp_ctx *c) {
 int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
   CHECK_CTX(c);
   if (!charge2) return fail(PIC1DP_ERR_ARG, "null array");
+  if (c->charge_sum == 1) return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_local_exact");
   if (int rc = require_loaded_keep_lazy(c)) return rc;
   if (pair_of(c->seq) && c->seq != Seq::Push2PairSolved)  // out of sequence (as in collect_charge): memory as the eager calls leave it
     if (int rc = settle_half_pair(c)) return rc;
@@ -1176,6 +1214,7 @@ int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
 int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
   CHECK_CTX(c);
   if (!charge1) return fail(PIC1DP_ERR_ARG, "null array");
+  if (c->charge_sum == 1) return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_reduced_exact");
   if (!c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_reduced without charge_local");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpy(c->d_charge, charge1, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
@@ -1191,3 +1230,35 @@ int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
   return 0;
 }
 
+// kind 1 of the charge sum: the split phase with integers (include/pic1dp_hip.h has the layout)
+int pic1dp_hip_charge_local_exact(pic1dp_ctx *c, int64_t *limbs) {
+  CHECK_CTX(c);
+  if (!limbs) return fail(PIC1DP_ERR_ARG, "null array");
+  if (c->charge_sum != 1) return fail(PIC1DP_ERR_STATE, "charge_local_exact needs the exact charge sum (set_charge_sum(1))");
+  if (int rc = require_loaded_keep_lazy(c)) return rc;
+  c->cd_kept_mode_only = false;
+  if (int rc = deposit_or_step(c)) return rc;
+  const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
+  HIP_TRY(launch_fx_normalise(c->d_fx, c->in.nspecies, c->in.nx, c->st));
+  HIP_TRY(hipMemcpyAsync(limbs, c->d_fx, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_fx, 0, sizeof(int64_t) * n, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  if (int rc = fx_check(c)) return rc;  // (a contribution left out: no charge to hand out)
+  c->charge_pending = true;
+  return 0;
+}
+
+int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *c, const int64_t *limbs) {
+  CHECK_CTX(c);
+  if (!limbs) return fail(PIC1DP_ERR_ARG, "null array");
+  if (c->charge_sum != 1) return fail(PIC1DP_ERR_STATE, "charge_reduced_exact needs the exact charge sum (set_charge_sum(1))");
+  if (!c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_reduced_exact without charge_local_exact");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
+  HIP_TRY(hipMemcpy(c->d_fx, limbs, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+  c->charge_pending = false;
+  HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st));
+  if (c->lazy_calls) return set_owed(c, Owed::SumScale);
+  HIP_TRY(launch_chargeden(c->fa, true, c->st));
+  return 0;
+}

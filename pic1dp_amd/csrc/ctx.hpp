@@ -286,6 +286,16 @@ struct pic1dp_ctx {
     int memkind = 0;                             // 1 fine-grained, 2 uncached, 3 plain hipMalloc
   } xc;
   int allreduce_kind = 0;  // 0 auto (RCCL when a communicator exists), 1 RCCL, 2 one-hop exchange
+  // kind 1 of the charge sum (pic1dp_hip_set_charge_sum, exact_charge.cpp; kernels.hpp FxArgs): the deposits go into
+  // exact integer accumulators, which the settle step (fx_settle) sums over ranks and turns into the species accumulators
+  // before anything reads them -- from there on the FP64 path runs as on one rank.  No prediction, no fused solve, no
+  // tail, no diagnostics inside the step while it is set.
+  int charge_sum = 0;
+  long long *d_fx = nullptr;                 // [nspecies][2][nx] (hi row, lo row); zero between calls
+  unsigned long long *h_fx_ovf = nullptr;    // pinned [8]: contributions beyond 2^62 quanta so far, per species
+  unsigned long long fx_ovf_seen[8] = {0};   // ... of which the host has reported
+  int fx_e[8] = {0};                         // e_s of the quantum 2^e_s
+  double fx_q[8] = {0}, fx_inv_q[8] = {0};   // 2^e_s, 2^-e_s
   // launch
   int threads_req = 0, bpc_req = 0;
   // timing
@@ -387,7 +397,7 @@ int materialize(pic1dp_ctx *c);           // a noted push becomes memory
 int materialize_cd(pic1dp_ctx *c);        // what collect_charge left to the next solve_field becomes field_chargeden
 int rebuild_half_step_chargeden(pic1dp_ctx *c);  // the whole vector where only the kept mode's content was formed
 void field_written(pic1dp_ctx *c, bool by_solve);  // d_E changed: versions, what a noted push may still assume
-size_t step_lds_bytes(int nx, bool full);  // dynamic LDS of a whole-step kernel
+size_t step_lds_bytes(int nx, bool full, bool exact = false);  // dynamic LDS of a whole-step kernel (exact: kind 1's rho tile)
 // ---- capi_comm.cpp ----
 int allreduce_charge(pic1dp_ctx *c);
 int allreduce_doubles(pic1dp_ctx *c, double *d, size_t n);
@@ -407,6 +417,12 @@ void optimize_release(pic1dp_ctx *c);     // the optimisation events' workers (s
 void optimize_due_at(const pic1dp_ctx *c, double time0, bool due[3]);  // which events a step starting at time0 fires
 void optimize_due(const pic1dp_ctx *c, bool due[3]);
 bool optimize_due_any(const pic1dp_ctx *c);
+int xchg_vec(const pic1dp_ctx *c);      // vectors of nx doubles one exchange slot holds
+// ---- exact_charge.cpp (kind 1 of the charge sum) ----
+FxArgs fx_args(const pic1dp_ctx *c, int isp);   // the marker kernels' exact accumulators of species isp (acc null in kind 0)
+int fx_settle(pic1dp_ctx *c);             // deposits -> summed over ranks -> the species accumulators (copy 0)
+int fx_check(pic1dp_ctx *c);              // PIC1DP_ERR_ARG once per batch of contributions beyond 2^62 quanta
+void fx_release(pic1dp_ctx *c);
 // ---- capi_diag.cpp ----
 int diag_buffers(pic1dp_ctx *c);
 int diag_max_blocks(const pic1dp_ctx *c);

@@ -487,9 +487,32 @@ __device__ __forceinline__ One push_one(double x, double v, double w, double p, 
   return push_core<DIST, MODE, POW2, T2MODE>(v, w, p, xb, vb, wb, e, dt, s, dv, t2io);
 }
 
-// wrap + linear deposit of one marker into the LDS copy of rho,
+// Kind 1 of the charge sum (kernels.hpp FxArgs): the workgroup's LDS tile holds two u64 words per cell, (lo, hi) at
+// s[2 i], s[2 i + 1] -- the low 32 bits of every quantised contribution, and its high half as a signed number.  The lo
+// word stays exact for 2^32 contributions per cell, the hi word while the cell's total stays below 2^94 quanta.
+struct RhoFx {
+  unsigned long long *s;
+  double inv_q;
+  unsigned long long *ovf;
+};
+__device__ __forceinline__ void rho_add(double *sR, int i, double c) { lds_add(&sR[i], c); }
+__device__ __forceinline__ void rho_add(const RhoFx &r, int i, double c) {
+  const double t = __builtin_rint(c * r.inv_q);  // c 2^-e is exact; ONE rounding, to nearest even
+  if (!(__builtin_fabs(t) < FX_LIMIT)) {         // (NaN too) not summed: counted, reported by the host
+    __hip_atomic_fetch_add(r.ovf, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return;
+  }
+  const long long n = static_cast<long long>(t);
+  const unsigned long long lo = static_cast<unsigned long long>(n) & 0xffffffffull;
+  const unsigned long long hi = static_cast<unsigned long long>(n >> 32);  // arithmetic shift: two's complement
+  __hip_atomic_fetch_add(&r.s[2 * i], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_fetch_add(&r.s[2 * i + 1], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// wrap + linear deposit of one marker into the LDS copy of rho (R: double *, or RhoFx in kind 1),
 // src/pic1dp_interaction.F90:102-113; returns the wrapped position
-__device__ __forceinline__ double deposit_one(double x, double q, double *sR, const GridConst &g, int *ix_out = nullptr,
+template <class R>
+__device__ __forceinline__ double deposit_one(double x, double q, const R &sR, const GridConst &g, int *ix_out = nullptr,
                                               double *wl_out = nullptr) {
   const double px = wrap(x, g.lx);
   int ix;
@@ -501,8 +524,8 @@ __device__ __forceinline__ double deposit_one(double x, double q, double *sR, co
   }
   // :110, :113.  The right-hand neighbour of the last cell is cell 0: of the next copy of the tile, or the
   // guard cell behind the last copy (flush_rho adds them all) -- no wrap-around of the index, one address
-  lds_add(&sR[ix], wl * q);
-  lds_add(&sR[ix + 1], (1.0 - wl) * q);
+  rho_add(sR, ix, wl * q);
+  rho_add(sR, ix + 1, (1.0 - wl) * q);
   return px;
 }
 
@@ -556,6 +579,39 @@ __device__ __forceinline__ void flush_rho(const double *sR, double *rho, const G
     double val = sR[j];
     if (j == 0) val += sR[nx];  // the guard cell behind the tile is cell 0
     if (val != 0.0) glb_add(&rho[j], val);  // rho: this workgroup's copy of the accumulator
+  }
+}
+
+// the deposit target of a marker kernel's rho tile: the doubles themselves, or (EXACT) RhoFx over the same LDS
+template <bool EXACT>
+__device__ __forceinline__ auto rho_tile(double *sR0, const FxArgs &fx) {
+  if constexpr (EXACT)
+    return RhoFx{reinterpret_cast<unsigned long long *>(sR0), fx.inv_q, fx.ovf};
+  else
+    return sR0;
+}
+// kind 1: the tile of RhoFx (nx cells + the guard cell, two words each)
+__device__ __forceinline__ void zero_rho_fx(unsigned long long *sF, const GridConst &g) {
+  for (int i = threadIdx.x; i < 2 * (g.nx + 1); i += blockDim.x) sF[i] = 0ull;
+}
+// ... added into the species' exact accumulators (hi row acc[0 .. nx), lo row acc[nx .. 2 nx)): lo mod 2^32 into lo,
+// the rest (lo >> 32 + hi) into hi -- two non-returning 64-bit atomics per cell, exact in any order
+__device__ __forceinline__ void flush_rho_fx(const unsigned long long *sF, const FxArgs &fx, const GridConst &g) {
+  const int nx = g.nx;
+  unsigned long long *hi_row = reinterpret_cast<unsigned long long *>(fx.acc), *lo_row = hi_row + nx;
+  const int rot = static_cast<int>((static_cast<long long>(blockIdx.x) * nx) / gridDim.x);
+  for (int i = threadIdx.x; i < nx; i += blockDim.x) {
+    int j = i + rot;
+    if (j >= nx) j -= nx;
+    unsigned long long lo = sF[2 * j], hi = sF[2 * j + 1];
+    if (j == 0) {  // the guard cell behind the tile is cell 0
+      lo += sF[2 * nx];
+      hi += sF[2 * nx + 1];
+    }
+    hi += lo >> 32;
+    lo &= 0xffffffffull;
+    if (lo) __hip_atomic_fetch_add(&lo_row[j], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (hi) __hip_atomic_fetch_add(&hi_row[j], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 

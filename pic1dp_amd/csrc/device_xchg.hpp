@@ -30,7 +30,7 @@ __device__ __forceinline__ void exchange_post(const XchgArgs &x, const double *s
 // Second half: lane q polls flag q of the OWN area until it reads the epoch (bounded by a wall-clock limit: on expiry
 // the host-visible error word is set and the kernel goes on, so the grid always drains); then sV[i] = the slots'
 // values added in rank order -- the same additions in the same order on every GPU.
-__device__ __forceinline__ void exchange_wait_sum(const XchgArgs &x, double *sV, int n) {
+__device__ __forceinline__ void exchange_wait(const XchgArgs &x) {
   const int nr = x.nranks, par = static_cast<int>(x.epoch & 1);
   if (threadIdx.x < nr) {
     const int q = threadIdx.x;
@@ -48,6 +48,10 @@ __device__ __forceinline__ void exchange_wait_sum(const XchgArgs &x, double *sV,
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   __syncthreads();
+}
+__device__ __forceinline__ void exchange_wait_sum(const XchgArgs &x, double *sV, int n) {
+  const int nr = x.nranks, par = static_cast<int>(x.epoch & 1);
+  exchange_wait(x);
   const double *mine = x.slots[x.rank] + static_cast<size_t>(par) * nr * x.vstride;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     double t[XCHG_MAX_RANKS];
@@ -59,6 +63,21 @@ __device__ __forceinline__ void exchange_wait_sum(const XchgArgs &x, double *sV,
     for (int q = 1; q < XCHG_MAX_RANKS; ++q)
       if (q < nr) sum = sum + t[q];
     sV[i] = sum;
+  }
+}
+
+// kind 1 of the charge sum: the slots carry int64 limbs (their bits in the doubles' places); the sum is the integers'
+// -- exact, the same in any order
+__device__ __forceinline__ void exchange_wait_sum_i64(const XchgArgs &x, long long *v, int n) {
+  const int nr = x.nranks, par = static_cast<int>(x.epoch & 1);
+  exchange_wait(x);
+  const double *mine = x.slots[x.rank] + static_cast<size_t>(par) * nr * x.vstride;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    unsigned long long sum = 0ull;
+    for (int q = 0; q < nr; ++q)
+      sum += static_cast<unsigned long long>(
+          __double_as_longlong(__hip_atomic_load(mine + static_cast<size_t>(q) * x.vstride + i, __ATOMIC_RELAXED, PIC1DP_SYS)));
+    v[i] = static_cast<long long>(sum);
   }
 }
 

@@ -99,6 +99,57 @@ inline int64_t slab_doubles(int64_t n) {
   return TILE_LOG2 ? (n + TILE - 1) / TILE * 4 * TILE : 4 * slab_array_stride(n);
 }
 
+// Kind 1 of the charge sum (pic1dp_hip_set_charge_sum): every contribution wl q, (1 - wl) q of the
+// deposit is rounded once to a whole number n = rint(c 2^-e) of quanta 2^e (e per species, from the input alone:
+// pic1dp_hip_charge_quantum) and the integers are summed exactly -- in the LDS as two u64 words per cell (n's low 32
+// bits, unsigned, and its high half, signed), globally as two int64 rows per species (hi, lo), across ranks element by
+// element.  Integer additions commute: the total does not depend on the order of waves, workgroups, launches or ranks.
+// |n| >= 2^62 is not summed: it counts in `ovf` (host-visible), and the next synchronising call reports it.
+struct FxArgs {
+  long long *acc;            // [2][nx] this species' (hi, lo) rows, or null: kind 0 (FP64 atomics)
+  double inv_q;              // 2^-e
+  unsigned long long *ovf;   // host-visible counter of contributions beyond 2^62 quanta
+};
+constexpr double FX_LIMIT = 0x1p62;
+// hi 2^32 + lo (lo any u64: normalised first) -> the nearest double, ties to even: ONE rounding of the exact
+// integer, what Python's float(int) gives.  Integer operations only, and an exact conversion of a < 2^54 integer
+// at the end: nothing here relies on how the compiler lowers a wide integer-to-double conversion.
+__host__ __device__ inline double fx_limbs_to_double(long long hi, unsigned long long lo) {
+  hi += static_cast<long long>(lo >> 32);
+  lo &= 0xffffffffull;
+  const bool neg = hi < 0;
+  unsigned long long uh, ul;  // |value| = uh 2^32 + ul, ul < 2^32
+  if (!neg) {
+    uh = static_cast<unsigned long long>(hi);
+    ul = lo;
+  } else if (lo == 0) {
+    uh = 0ull - static_cast<unsigned long long>(hi);
+    ul = 0;
+  } else {
+    uh = 0ull - static_cast<unsigned long long>(hi) - 1ull;
+    ul = (1ull << 32) - lo;
+  }
+  double r;
+  if (uh < (1ull << 21)) {  // below 2^53: exact
+    r = static_cast<double>(static_cast<long long>((uh << 32) | ul));
+  } else {
+    const int bits = 96 - __builtin_clzll(uh);  // bit length of the magnitude (54 ... 95)
+    const int sh = bits - 53;                   // 1 ... 42
+    unsigned long long top, rem, half;
+    if (sh <= 32) {
+      top = (uh << (32 - sh)) | (ul >> sh);
+      rem = ul & ((1ull << sh) - 1ull);
+    } else {
+      top = uh >> (sh - 32);
+      rem = ((uh & ((1ull << (sh - 32)) - 1ull)) << 32) | ul;
+    }
+    half = 1ull << (sh - 1);
+    if (rem > half || (rem == half && (top & 1ull))) top += 1ull;  // (top may reach 2^53: still exact)
+    r = ldexp(static_cast<double>(static_cast<long long>(top)), sh);
+  }
+  return neg ? -r : r;
+}
+
 // One particle set = the three pushed arrays of a species (array bases inside a slab).
 struct PSet {
   double *x, *v, *w;
@@ -116,6 +167,7 @@ struct PushArgs {
   GridConst g;
   SpeciesConst s;
   int iptcldist, deltaf, linear, irk;
+  FxArgs fx;        // kind 1 of the charge sum: the fused deposit's exact accumulators (acc null: rho)
 };
 
 // geometry of the output_ptcldist histograms (src/pic1dp_output.F90:203-205,243-247)
@@ -263,6 +315,7 @@ struct StepArgs {
   int diag_fx;
   int dyn_tail;      // every whole-step kernel: sixteenths of a workgroup's chunks that its waves draw from an LDS counter (0: all dealt)
   double *fxb;       // pred_kind 1: [2] device bounds on |q|, |c| of this species, for the tiles' fixed-point sums
+  FxArgs fx;         // kind 1 of the charge sum (k_step_half / k_step_full only): the exact accumulators (acc null: rho)
 };
 #ifndef PIC1DP_PRED_MAX_MODES
 #define PIC1DP_PRED_MAX_MODES 3
@@ -312,6 +365,9 @@ hipError_t launch_push(const PushArgs &a, bool fused_deposit, const LaunchCfg &l
 // wrap + deposit of q (= w or p) at x, x stored back
 hipError_t launch_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst &g,
                           const LaunchCfg &lc, hipStream_t st);
+// the same into the exact accumulators of kind 1 (lc.lds: 16 B per cell and the guard cell)
+hipError_t launch_deposit_exact(double *x, const double *q, const FxArgs &fx, int64_t np, const GridConst &g,
+                                const LaunchCfg &lc, hipStream_t st);
 
 
 // vectors of nx doubles one exchange can carry: charge2 + the 1 + 2 * PRED_MAX_MODES prediction slices
@@ -355,6 +411,13 @@ hipError_t launch_charge_exchange(const FieldArgs &f, const XchgArgs &x, hipStre
 // local charge + exchange + chargeden + field solve in one launch
 hipError_t launch_field_solve_xchg(const FieldArgs &f, const XchgArgs &x, hipStream_t st);
 
+// kind 1 of the charge sum.  acc: [nspecies][2][nx] int64 (hi row, lo row per species).
+// normalise: lo <- lo mod 2^32, hi <- hi + (lo >> 32) (the packet a sum over ranks adds element by element)
+hipError_t launch_fx_normalise(long long *acc, int nspecies, int nx, hipStream_t st);
+// rho_sp[s][i] (copy 0) <- the double nearest to (hi 2^32 + lo) times q[s] = 2^e_s; acc re-zeroed
+hipError_t launch_fx_to_rho(long long *acc, double *rho_sp, int nspecies, int nx, const double *q, hipStream_t st);
+// the normalised packet summed over the ranks of the one-hop exchange (slots of at least 2 nspecies nx), in place
+hipError_t launch_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs &x, hipStream_t st);
 // charge2 = sum_s rho_sp[s]*Z_s ; rho_sp = 0      (src/pic1dp_interaction.F90:81-128)
 hipError_t launch_charge_local(const FieldArgs &f, hipStream_t st);
 // chargeden from charge (:138-148) only; with_local folds launch_charge_local in

@@ -41,6 +41,45 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_chargeden(const FieldArgs f) 
     f.chargeden[ix] = chargeden_from(f, WITH_LOCAL ? charge_local_one(f, ix) : f.charge[ix]);
 }
 
+// ---- kind 1 of the charge sum (kernels.hpp FxArgs): the exact accumulators [nspecies][2][nx] (hi row, lo row) ----
+__global__ void __launch_bounds__(FIELD_THREADS) k_fx_normalise(long long *acc, int nspecies, int nx) {
+  const int n = nspecies * nx;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+    long long *hi = acc + static_cast<size_t>(k / nx) * 2 * nx + k % nx, *lo = hi + nx;
+    const unsigned long long l = static_cast<unsigned long long>(*lo);
+    *hi = *hi + static_cast<long long>(l >> 32);
+    *lo = static_cast<long long>(l & 0xffffffffull);
+  }
+}
+// rho_sp copy 0 <- each species' total as the nearest double times 2^e_s (exact); acc re-zeroed.  From here on the FP64
+// path runs as in kind 0: charge_local_one, chargeden_from, the solve.
+struct FxQuanta {
+  double q[8];
+};
+__global__ void __launch_bounds__(FIELD_THREADS) k_fx_to_rho(long long *acc, double *rho_sp, int nspecies, int nx, const FxQuanta fq) {
+  const int n = nspecies * nx;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+    const int s = k / nx, i = k % nx;
+    long long *hi = acc + static_cast<size_t>(s) * 2 * nx + i, *lo = hi + nx;
+    rho_sp[k] = fx_limbs_to_double(*hi, static_cast<unsigned long long>(*lo)) * fq.q[s];
+    *hi = 0;
+    *lo = 0;
+  }
+}
+// the packet over the ranks of the one-hop exchange: normalised, posted into every rank's slot, added up (one workgroup)
+__global__ void __launch_bounds__(FIELD_THREADS) k_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs x) {
+  const int n = 2 * nspecies * nx;
+  for (int k = threadIdx.x; k < nspecies * nx; k += blockDim.x) {
+    long long *hi = acc + static_cast<size_t>(k / nx) * 2 * nx + k % nx, *lo = hi + nx;
+    const unsigned long long l = static_cast<unsigned long long>(*lo);
+    *hi = *hi + static_cast<long long>(l >> 32);
+    *lo = static_cast<long long>(l & 0xffffffffull);
+  }
+  __syncthreads();
+  exchange_post(x, reinterpret_cast<const double *>(acc), n);
+  exchange_wait_sum_i64(x, acc, n);
+}
+
 // k_step_one's prediction turned into this rank's charge2 of the next step's first sub-step:
 //   charge2_h = sum_s Z_s * (R0_s + sum_m re_m RA_sm + im_m RB_sm),   re / im = the kept modes of the
 // field the markers were just advanced to.  The accumulators are consumed (re-zeroed).  The caller
@@ -1116,6 +1155,27 @@ hipError_t launch_field_fd(const double *chargeden, double *E, double *history, 
     big_lds_ok = true;
   }
   hipLaunchKernelGGL(k_field_fd, dim3(1), dim3(FD_THREADS), lds, st, chargeden, E, history, nx, lx, dnx);
+  return hipGetLastError();
+}
+
+hipError_t launch_fx_normalise(long long *acc, int nspecies, int nx, hipStream_t st) {
+  const int n = nspecies * nx;
+  hipLaunchKernelGGL(k_fx_normalise, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx);
+  return hipGetLastError();
+}
+
+hipError_t launch_fx_to_rho(long long *acc, double *rho_sp, int nspecies, int nx, const double *q, hipStream_t st) {
+  FxQuanta fq{};
+  for (int s = 0; s < nspecies && s < 8; ++s) fq.q[s] = q[s];
+  const int n = nspecies * nx;
+  hipLaunchKernelGGL(k_fx_to_rho, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, rho_sp,
+                     nspecies, nx, fq);
+  return hipGetLastError();
+}
+
+hipError_t launch_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs &x, hipStream_t st) {
+  if (2 * nspecies * nx > x.vstride) return hipErrorInvalidValue;  // (the slots are sized for it: capi_comm.cpp xchg_vec)
+  hipLaunchKernelGGL(k_fx_exchange, dim3(1), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx, x);
   return hipGetLastError();
 }
 

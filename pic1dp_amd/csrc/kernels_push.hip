@@ -7,18 +7,23 @@ namespace pic1dp {
 
 namespace {
 
-template <int DIST, int MODE, int POW2, bool IRK2, bool FUSED>
+// EXACT (with FUSED): kind 1 of the charge sum, the tile of RhoFx flushed into a.fx.acc (kernels.hpp FxArgs)
+template <int DIST, int MODE, int POW2, bool IRK2, bool FUSED, bool EXACT = false>
 __global__ void __launch_bounds__(1024) k_push(const PushArgs a) {
+  static_assert(FUSED || !EXACT, "an exact deposit needs one");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   exp_table_init();
   double *sE = reinterpret_cast<double *>(smem);
   const int nx = a.g.nx;
   double *sR0 = sE + ((nx + 2) & ~1);
   for (int i = threadIdx.x; i < nx; i += blockDim.x) sE[i] = a.E[i];
-  if constexpr (FUSED) zero_rho(sR0, a.g);
+  if constexpr (EXACT)
+    zero_rho_fx(reinterpret_cast<unsigned long long *>(sR0), a.g);
+  else if constexpr (FUSED)
+    zero_rho(sR0, a.g);
   if (threadIdx.x == 0) sE[nx] = a.E[0];
   __syncthreads();
-  double *sR = sR0;
+  const auto sR = rho_tile<EXACT>(sR0, a.fx);
 
   constexpr bool HAS_W = (MODE != MODE_FULLF);
   constexpr bool PUSH_V = (MODE != MODE_DF_LIN);
@@ -78,18 +83,25 @@ __global__ void __launch_bounds__(1024) k_push(const PushArgs a) {
   }
   if constexpr (FUSED) {
     __syncthreads();
-    flush_rho(sR0, a.rho, a.g);
+    if constexpr (EXACT)
+      flush_rho_fx(reinterpret_cast<const unsigned long long *>(sR0), a.fx, a.g);
+    else
+      flush_rho(sR0, a.rho, a.g);
   }
 }
 
-// stand-alone wrap + deposit (interaction_collect_charge loop :96-114)
+// stand-alone wrap + deposit (interaction_collect_charge loop :96-114); EXACT: kind 1, into fx.acc
+template <bool EXACT = false>
 __global__ void __launch_bounds__(1024)
-k_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst g) {
+k_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst g, const FxArgs fx) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double *sR0 = reinterpret_cast<double *>(smem);
-  zero_rho(sR0, g);
+  if constexpr (EXACT)
+    zero_rho_fx(reinterpret_cast<unsigned long long *>(sR0), g);
+  else
+    zero_rho(sR0, g);
   __syncthreads();
-  double *sR = sR0;
+  const auto sR = rho_tile<EXACT>(sR0, fx);
   const int64_t npair = np >> 1;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   double2 *x2 = reinterpret_cast<double2 *>(x);
@@ -108,12 +120,15 @@ k_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst g
     x[i] = deposit_one(x[i], q[i], sR, g);
   }
   __syncthreads();
-  flush_rho(sR0, rho, g);
+  if constexpr (EXACT)
+    flush_rho_fx(reinterpret_cast<const unsigned long long *>(sR0), fx, g);
+  else
+    flush_rho(sR0, rho, g);
 }
 
-template <int DIST, int MODE, int POW2, bool IRK2, bool FUSED>
+template <int DIST, int MODE, int POW2, bool IRK2, bool FUSED, bool EXACT = false>
 hipError_t launch_push_t(const PushArgs &a, const LaunchCfg &lc, hipStream_t st) {
-  auto kern = k_push<DIST, MODE, POW2, IRK2, FUSED>;
+  auto kern = k_push<DIST, MODE, POW2, IRK2, FUSED, EXACT>;
   static bool big_lds_ok = false;  // opt in once to > 64 KiB of dynamic LDS (nx >= 4096)
   if (lc.lds > 64 * 1024 && !big_lds_ok) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
@@ -128,6 +143,9 @@ hipError_t launch_push_t(const PushArgs &a, const LaunchCfg &lc, hipStream_t st)
 template <int DIST, int MODE, int POW2>
 hipError_t launch_push_dm(const PushArgs &a, bool fused, const LaunchCfg &lc, hipStream_t st) {
   const bool irk2 = a.irk == 2;
+  if (fused && a.fx.acc)  // kind 1 of the charge sum
+    return irk2 ? launch_push_t<DIST, MODE, POW2, true, true, true>(a, lc, st)
+                : launch_push_t<DIST, MODE, POW2, false, true, true>(a, lc, st);
   if (irk2) {
     return fused ? launch_push_t<DIST, MODE, POW2, true, true>(a, lc, st)
                  : launch_push_t<DIST, MODE, POW2, true, false>(a, lc, st);
@@ -171,12 +189,25 @@ hipError_t launch_deposit(double *x, const double *q, double *rho, int64_t np, c
                           const LaunchCfg &lc, hipStream_t st) {
   static bool big_lds_ok = false;
   if (lc.lds > 64 * 1024 && !big_lds_ok) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_deposit),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_deposit<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     big_lds_ok = true;
   }
-  hipLaunchKernelGGL(k_deposit, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, rho, np, g);
+  hipLaunchKernelGGL(k_deposit<false>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, rho, np, g, FxArgs{});
+  return hipGetLastError();
+}
+
+hipError_t launch_deposit_exact(double *x, const double *q, const FxArgs &fx, int64_t np, const GridConst &g,
+                                const LaunchCfg &lc, hipStream_t st) {
+  static bool big_lds_ok = false;
+  if (lc.lds > 64 * 1024 && !big_lds_ok) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_deposit<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, PARTICLE_LDS_CAP);
+    if (e != hipSuccess) return e;
+    big_lds_ok = true;
+  }
+  hipLaunchKernelGGL(k_deposit<true>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, nullptr, np, g, fx);
   return hipGetLastError();
 }
 

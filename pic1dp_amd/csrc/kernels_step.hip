@@ -85,22 +85,26 @@ namespace {
 // fits the 256 MiB Infinity Cache (+15 % at 2e7 markers); below that, plain
 // accesses keep the state cache-resident between the two kernels of a step
 // (+5 % at the reference's default 6.4e6 markers).  Chosen per launch.
-template <int DIST, int MODE, int POW2, bool NT, bool CARRY>
+// EXACT: kind 1 of the charge sum -- the rho tile holds RhoFx's two words per cell (twice the LDS), flushed into a.fx.acc
+template <int DIST, int MODE, int POW2, bool NT, bool CARRY, bool EXACT = false>
 __global__ void __launch_bounds__(1024) k_step_half(const StepArgsDev a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   exp_table_init();
   double *sE = reinterpret_cast<double *>(smem);
   const int nx = a.g.nx;
   double *sR0 = sE + ((nx + 2) & ~1);
-  unsigned *sDraw = reinterpret_cast<unsigned *>(sR0 + ((nx + 2) & ~1));  // the drawn chunks' counter
+  unsigned *sDraw = reinterpret_cast<unsigned *>(sR0 + (EXACT ? 2 : 1) * ((nx + 2) & ~1));  // the drawn chunks' counter
   for (int i = threadIdx.x; i < nx; i += blockDim.x) sE[i] = a.E0[i];
-  zero_rho(sR0, a.g);
+  if constexpr (EXACT)
+    zero_rho_fx(reinterpret_cast<unsigned long long *>(sR0), a.g);
+  else
+    zero_rho(sR0, a.g);
   if (threadIdx.x == 0) {
     sE[nx] = a.E0[0];
     *sDraw = 0u;
   }
   __syncthreads();
-  double *sR = sR0;
+  const auto sR = rho_tile<EXACT>(sR0, a.fx);
   constexpr bool HAS_W = (MODE != MODE_FULLF);
   const int64_t npair = a.np >> 1;
   const double2 *x2 = reinterpret_cast<const double2 *>(a.x);
@@ -134,13 +138,16 @@ __global__ void __launch_bounds__(1024) k_step_half(const StepArgsDev a) {
     deposit_one(h.x, HAS_W ? h.w : p, sR, a.g);
   }
   __syncthreads();
-  flush_rho(sR0, a.rho, a.g);
+  if constexpr (EXACT)
+    flush_rho_fx(reinterpret_cast<const unsigned long long *>(sR0), a.fx, a.g);
+  else
+    flush_rho(sR0, a.rho, a.g);
 }
 
 // one marker through the second half of the time step
-template <int DIST, int MODE, int POW2, bool CARRY = false, class FH = const double *>
+template <int DIST, int MODE, int POW2, bool CARRY = false, class FH = const double *, class R = double *>
 __device__ __forceinline__ One step_full_one(double x, double v, double w, double p, const double *sE0,
-                                             const FH &sEh, double *sR, const StepArgsDev &a, double t2 = 0.0,
+                                             const FH &sEh, const R &sR, const StepArgsDev &a, double t2 = 0.0,
                                              int *ix_out = nullptr, double *wl_out = nullptr) {
   constexpr bool HAS_W = (MODE != MODE_FULLF);
   // sub-step 1 again (identical arithmetic), with the wrap the deposit applied
@@ -157,9 +164,11 @@ __device__ __forceinline__ One step_full_one(double x, double v, double w, doubl
 // the state just computed, into an LDS copy of the histograms next to the grid tiles (one workgroup
 // of 1024 threads per CU then).
 // FX (DIAG): the LDS copy of the histograms as 64-bit fixed-point sums (device_diag.hpp DistScale), as in k_ptcldist
-template <int DIST, int MODE, int POW2, bool NT, bool CARRY, bool DIAG, bool FX = false>
+// EXACT: kind 1 of the charge sum, as in k_step_half (not with DIAG: kind 1 takes the diagnostics in their own pass)
+template <int DIST, int MODE, int POW2, bool NT, bool CARRY, bool DIAG, bool FX = false, bool EXACT = false>
 __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
   static_assert(!FX || DIAG, "fixed-point sums are the diagnostics'");
+  static_assert(!(EXACT && DIAG), "kind 1 of the charge sum takes the diagnostics in their own pass");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   exp_table_init();
   const int nx = a.g.nx;
@@ -171,7 +180,10 @@ __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
     sE0[i] = a.E0[i];
     sEh[i] = a.Eh[i];
   }
-  zero_rho(sR0, a.g);
+  if constexpr (EXACT)
+    zero_rho_fx(reinterpret_cast<unsigned long long *>(sR0), a.g);
+  else
+    zero_rho(sR0, a.g);
   if (threadIdx.x == 0) {
     sE0[nx] = a.E0[0];
     sEh[nx] = a.Eh[0];
@@ -179,7 +191,7 @@ __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
   constexpr bool HAS_W = (MODE != MODE_FULLF);
   constexpr bool PUSH_V = (MODE != MODE_DF_LIN);
   // behind the rho copies (16-byte aligned): the drawn chunks' counter; DIAG: the histograms, then the block_sum scratch
-  unsigned *sDraw = reinterpret_cast<unsigned *>(sR0 + ((nx + 2) & ~1));
+  unsigned *sDraw = reinterpret_cast<unsigned *>(sR0 + (EXACT ? 2 : 1) * ((nx + 2) & ~1));
   double *sH = sR0 + ((nx + 2) & ~1) + 2;
   const int ntot = DIAG ? 3 * a.dg.nxo * a.dg.nvo + 3 * a.dg.nvo : 0;
   const DistBins bins{sH, a.dg.nxo * a.dg.nvo, a.dg.nvo};
@@ -188,7 +200,7 @@ __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
     for (int i = threadIdx.x; i < ntot; i += blockDim.x) sH[i] = 0.0;
   if (threadIdx.x == 0) *sDraw = 0u;
   __syncthreads();
-  double *sR = sR0;
+  const auto sR = rho_tile<EXACT>(sR0, a.fx);
   const int64_t npair = a.np >> 1;
   double2 *x2 = reinterpret_cast<double2 *>(a.x);
   double2 *v2 = reinterpret_cast<double2 *>(a.v);
@@ -227,7 +239,10 @@ __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
     if constexpr (DIAG) ptcldist_one<true, HAS_W, FX>(n.x, n.v, a.p[i], n.w, a.dg, bins, sums, &a.dscale);
   }
   __syncthreads();
-  flush_rho(sR0, a.rho, a.g);
+  if constexpr (EXACT)
+    flush_rho_fx(reinterpret_cast<const unsigned long long *>(sR0), a.fx, a.g);
+  else
+    flush_rho(sR0, a.rho, a.g);
   if constexpr (DIAG) ptcldist_finish<true, HAS_W, FX, 6>(a.dg, bins, sums, sH + ntot, a.dist_out, a.dist_partial, &a.dscale);
 }
 
@@ -1223,6 +1238,14 @@ hipError_t launch_step_dmp(const StepArgsDev &d, bool full, const LaunchCfg &lc,
     if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
     if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 0>, d, lc, st);
     return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
+  }
+  if (d.fx.acc) {  // kind 1 of the charge sum: two passes, the diagnostics in their own pass (the host sees to both)
+    if (d.pred || d.dist_out) return hipErrorInvalidValue;
+    if (d.nt)
+      return full ? launch_step_kernel(k_step_full<DIST, MODE, POW2, true, CARRY, false, false, true>, d, lc, st)
+                  : launch_step_kernel(k_step_half<DIST, MODE, POW2, true, CARRY, true>, d, lc, st);
+    return full ? launch_step_kernel(k_step_full<DIST, MODE, POW2, false, CARRY, false, false, true>, d, lc, st)
+                : launch_step_kernel(k_step_half<DIST, MODE, POW2, false, CARRY, true>, d, lc, st);
   }
   if (full && d.pred) {  // one pass per step: also predicts the next step's first-sub-step charge
     const int t2m = d.t2 ? d.t2_mode : 0;

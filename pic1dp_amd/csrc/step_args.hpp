@@ -33,6 +33,7 @@ struct StepArgsDev {
   int dyn_tail;                 // sixteenths of a workgroup's chunks drawn from an LDS counter
   double *fxb;                  // k_step_one's tiles: [2] bounds on |q|, |c| of this species (kernels_step.hip FxTiles)
   double fx_markers, fx_cap;    // ... the most markers one workgroup of this launch takes, and 2^61 over it
+  FxArgs fx;                    // kind 1 of the charge sum (k_step_half / k_step_full<EXACT>): acc null in kind 0
 #ifdef PIC1DP_TUNE_STAMPS  // tuning build (tools/stamp_probe.sh): [gridDim][8] wall-clock stamps of the phases of a workgroup
   unsigned long long *stamps;
 #endif

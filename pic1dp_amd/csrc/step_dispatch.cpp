@@ -38,6 +38,7 @@ hipError_t launch_step(const StepArgs &a, bool full, const LaunchCfg &lc, hipStr
   d.tail = a.tail;
   d.dyn_tail = a.dyn_tail;
   d.fxb = a.fxb;
+  d.fx = a.fx;
   {  // rows of pairs a workgroup takes (static grid stride; the drawn chunks are its own rows), two markers a pair
     const int64_t npair = a.np >> 1, stride = static_cast<int64_t>(lc.blocks) * lc.threads;
     // (at least 4096: a term times its scale then stays below 2^49, inside the 2^51 the conversion's magic number covers)

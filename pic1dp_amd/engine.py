@@ -350,6 +350,29 @@ class Pic1dp:
             raise ValueError("charge must have nx entries")
         check(self.L.pic1dp_hip_charge_reduced(self._ctx, _ptr(a)))
 
+    # -- exact charge sum (kind 1, include/pic1dp_hip.h) -------------------------------
+    def set_charge_sum(self, kind):
+        """0: FP64 atomics (default); 1: exact -- contributions rounded once to whole quanta 2^e_s and summed as
+        integers, so the charge does not depend on the order of the sum.  Only between time steps."""
+        check(self.L.pic1dp_hip_set_charge_sum(self._ctx, int(kind)))
+
+    def charge_quantum(self, ispecies=0):
+        """e_s of species ispecies' quantum 2^e_s in the exact charge sum (from the input alone)"""
+        return charge_quantum(self.inp, ispecies)
+
+    def charge_local_exact(self):
+        """kind 1 split phase: this rank's exact deposit as int64 limbs [nspecies][2][nx] (hi, lo; lo < 2^32), to be
+        summed element by element over the ranks and handed to charge_reduced_exact"""
+        out = np.empty((self.inp.nspecies, 2, self.inp.nx), dtype=np.int64)
+        check(self.L.pic1dp_hip_charge_local_exact(self._ctx, _ptr(out)))
+        return out
+
+    def charge_reduced_exact(self, limbs):
+        a = np.ascontiguousarray(limbs, dtype=np.int64)
+        if a.size != 2 * self.inp.nspecies * self.inp.nx:
+            raise ValueError("limbs must have nspecies * 2 * nx entries")
+        check(self.L.pic1dp_hip_charge_reduced_exact(self._ctx, _ptr(a)))
+
     # -- RCCL ------------------------------------------------------------------------
     def comm_unique_id(self):
         buf = (C.c_ubyte * _lib.COMM_ID_BYTES)()
@@ -461,6 +484,14 @@ class Pic1dp:
             if on_output and self.output_due(term):
                 on_output(self)
         return steps
+
+
+def charge_quantum(inp, ispecies=0):
+    """e_s = ceil(log2 B_s) - 52 of the exact charge sum's quantum 2^e_s, B_s a bound on the species' |p| and |w|
+    from the input alone (no device)"""
+    e = C.c_int32()
+    check(_lib.load().pic1dp_hip_charge_quantum(C.byref(inp), int(ispecies), C.byref(e)))
+    return e.value
 
 
 def device_count():

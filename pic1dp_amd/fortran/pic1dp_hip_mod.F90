@@ -389,6 +389,31 @@ interface
     real(c_double), intent(in) :: charge1(*)
     integer(c_int) :: ierr
   end function pic1dp_hip_charge_reduced
+  function pic1dp_hip_set_charge_sum(ctx, kind) bind(C, name="pic1dp_hip_set_charge_sum") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: kind
+    integer(c_int) :: ierr
+  end function pic1dp_hip_set_charge_sum
+  function pic1dp_hip_charge_quantum(inp, ispecies, log2_quantum) bind(C, name="pic1dp_hip_charge_quantum") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), intent(out) :: log2_quantum
+    integer(c_int) :: ierr
+  end function pic1dp_hip_charge_quantum
+  function pic1dp_hip_charge_local_exact(ctx, limbs) bind(C, name="pic1dp_hip_charge_local_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int64_t), intent(out) :: limbs(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_charge_local_exact
+  function pic1dp_hip_charge_reduced_exact(ctx, limbs) bind(C, name="pic1dp_hip_charge_reduced_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int64_t), intent(in) :: limbs(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_charge_reduced_exact
   function pic1dp_hip_comm_unique_id(id) bind(C, name="pic1dp_hip_comm_unique_id") result(ierr)
     import
     integer(c_signed_char), intent(inout) :: id(*)

@@ -55,6 +55,10 @@ call input_fill(inp)
 call ranks_init()                           ! MPI_Comm_rank / MPI_Comm_size, src/pic1dp.F90:50-52
 lay = pic1dp_layout_t(ranks_rank, ranks_size, 0, -1)   ! one process per GPU (device = rank mod visible GPUs)
 call pic1dp_hip_check(pic1dp_hip_create(inp, lay, ctx), 'create')      ! particle_init + field_init
+! PIC1DP_CHARGE_SUM=exact (an option of this host program): the exact charge sum of include/pic1dp_hip.h, whose
+! chargeden, E and field energies do not depend on the order of the deposit's additions (the reference sums in FP64)
+call get_environment_variable('PIC1DP_CHARGE_SUM', buf, status=stat)
+if (stat == 0 .and. buf(1:5) == 'exact') call pic1dp_hip_check(pic1dp_hip_set_charge_sum(ctx, 1_c_int32_t), 'set_charge_sum')
 call get_environment_variable('PIC1DP_ALLREDUCE', buf, status=stat)
 use_rccl = (stat == 0 .and. buf(1:4) == 'rccl')
 if (use_rccl) then
