@@ -98,11 +98,7 @@ int enqueue_deposit(pic1dp_ctx *c) {
       std::snprintf(kb.name, sizeof kb.name, "%s", exact ? "k_deposit<EXACT>" : "k_deposit");
     }
     Span ks(c, kTagDeposit, c->stats_on);
-    if (exact) {
-      HIP_TRY(launch_deposit_exact(x, q, fx_args(c, s), S.np, c->grid, lc, c->st));
-    } else {
-      HIP_TRY(launch_deposit(x, q, S.rho, S.np, c->grid, lc, c->st));
-    }
+    HIP_TRY(launch_deposit(x, q, S.rho, fx_args(c, s), S.np, c->grid, lc, c->st));
     if (int rc = ks.end()) return rc;
   }
   return 0;
@@ -200,7 +196,7 @@ static int enqueue_wrap_only(pic1dp_ctx *c) {
     if (S.np <= 0) continue;
     const double *q = c->in.deltaf ? S.set[c->cur].w : S.p;
     LaunchCfg lc = particle_launch(c, S.np, false, true);
-    HIP_TRY(launch_deposit(S.set[c->cur].x, q, c->d_rho_dummy, S.np, c->grid, lc, c->st));
+    HIP_TRY(launch_deposit(S.set[c->cur].x, q, c->d_rho_dummy, FxArgs{}, S.np, c->grid, lc, c->st));
   }
   return 0;
 }
@@ -654,7 +650,11 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
   for (int s = 0; s < c->in.nspecies; ++s) {
     Species &S = c->sp[s];
     if (S.np <= 0) continue;
-    StepArgs a{};
+    StepArgs sa{};
+    sa.iptcldist = c->in.iptcldist;
+    sa.deltaf = c->in.deltaf;
+    sa.linear = c->in.linear;
+    StepArgsDev &a = sa.d;
     a.x = S.set[c->cur].x;
     a.v = S.set[c->cur].v;
     a.w = S.set[c->cur].w;
@@ -667,10 +667,7 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
     a.dt_full = c->in.dt;        // :192
     a.g = c->grid;
     a.s = S.sc;
-    a.iptcldist = c->in.iptcldist;
-    a.deltaf = c->in.deltaf;
-    a.linear = c->in.linear;
-    a.stream_nt = stream_nt;
+    a.nt = stream_nt;
     // the drawn chunk tail of every whole-step kernel: half a workgroup's chunks, all of them for k_step_full (two passes
     // per step at 1e8 markers: 0.913 -> 0.898 ms with 16/16 against 8/16, profiles/r05/experiments/ab_dyn_tail_other.log)
     a.dyn_tail = (full && !pred) ? c->dyn_tail_full : c->dyn_tail;
@@ -702,11 +699,10 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
     if (pred) {  // k_step_one: the full step + the prediction of the next first sub-step's charge
       a.tabA = c->d_tabA;
       a.tabB = c->d_tabB;
-      a.pred_kind = c->pred_kind;
       a.pred = c->pred_kind == 2 ? c->d_pred  // six sums, all species together (Z folded in)
                                  : c->d_pred + static_cast<size_t>(s) * (1 + 2 * c->in.nmode) * c->in.nx;
       a.pred_nm = c->in.nmode;
-      a.pred_private = priv ? 1 : 0;
+      sa.family = c->pred_kind == 2 ? (priv ? StepFamily::PrivateSums : StepFamily::Sums) : StepFamily::Tiles;
       a.fxb = S.fxb;
       if (c->pred_kind == 2) {
         a.eh_re = c->eh_modes == 2 ? c->d_mode_h : c->fa.mode_re;
@@ -787,7 +783,7 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
     }
     Span tm(c, PIC1DP_IWT_PUSH_PARTICLE, c->timers_on);
     Span ks(c, tag, c->stats_on);
-    HIP_TRY(launch_step(a, full, lc, c->st));
+    HIP_TRY(launch_step(sa, full, lc, c->st));
     if (int rc = ks.end()) return rc;
     if (int rc = tm.end()) return rc;
   }

@@ -530,7 +530,7 @@ __device__ __forceinline__ double deposit_one(double x, double q, const R &sR, c
 }
 
 // The workgroup's pairs: row k = pairs (blockIdx + k gridDim) blockDim ... of the grid-stride split.  `dealt` rows go to
-// its threads as they stand; the 64-pair chunks of the remaining rows (StepArgs::dyn_tail sixteenths of them) are DRAWN:
+// its threads as they stand; the 64-pair chunks of the remaining rows (StepArgsDev::dyn_tail sixteenths of them) are DRAWN:
 // every wave takes the next one from a counter in the LDS (one ds_add_rtn_u32 per chunk, no device-scope traffic), so the
 // waves that run ahead take more and the workgroup meets its final barrier together (round 5: the skew between a
 // workgroup's waves was worth 1.4-4.7 % of k_step_one<PRIV>, which has this loop spelled out for its register budget).

@@ -192,7 +192,8 @@ struct DistScale {
 // false: no fixed-point pass possible (sum in doubles)
 bool make_dist_scale(int64_t np, int blocks, bool deltaf, double bound_p, double bound_w, DistScale *fx, int threads = 1024);
 
-// dynamic LDS a particle kernel may ask for: 160 KiB per CU minus the 1 KiB static exp table
+// dynamic LDS any kernel may ask for: 160 KiB per CU minus 1 KiB, the most static LDS a kernel that asks for more than
+// 64 KiB holds (the particle kernels' exp table; k_field_fd: 144 B)
 constexpr size_t PARTICLE_LDS_CAP = 159 * 1024;
 
 struct LaunchCfg {
@@ -200,6 +201,20 @@ struct LaunchCfg {
   int blocks;    // grid size
   size_t lds;    // dynamic LDS bytes
 };
+
+// Every kernel launch of the library.  Above 64 KiB of dynamic LDS the kernel opts in to PARTICLE_LDS_CAP, on every call
+// (idempotent and cheap, and for whichever device is current); beyond the cap nothing is launched.
+template <typename K, typename... Args>
+hipError_t launch_kernel(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+  if (lds > 64 * 1024) {
+    if (lds > PARTICLE_LDS_CAP) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       PARTICLE_LDS_CAP);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
 
 struct FieldArgs {
   double *rho_sp;        // [rho_copies][nspecies][nx] raw per-species deposits (zeroed after use)
@@ -278,8 +293,9 @@ struct FusedSolve {
   double *zero_pred;
 };
 
-// whole-time-step path: state updated in place, half-step state recomputed
-struct StepArgs {
+// whole-time-step path, state updated in place, half-step state recomputed: what the marker kernels
+// (kernels_step.hip) receive
+struct StepArgsDev {
   double *x, *v, *w;   // particle_x/v/w, updated in place by the full kernel
   const double *p;
   const double *E0;    // field at the start of the step
@@ -289,33 +305,47 @@ struct StepArgs {
   double dt_half, dt_full;
   GridConst g;
   SpeciesConst s;
-  int iptcldist, deltaf, linear;
-  int stream_nt;       // 1: non-temporal loads/stores (state larger than the Infinity Cache)
-  double *t2;          // [np + 2] carry of -f0'/f0 from the first kernel to the second, or null (kernels_step.hip CARRY)
-  // full kernel only: take the diagnostics of output_all in the same pass (kernels_step.hip DIAG); dist_out null = no
+  int nt;              // 1: non-temporal loads/stores (state larger than the Infinity Cache)
+  double *t2;          // [np + 2] -f0'/f0 at the step-start velocity, carried from k_step_half to k_step_full (or null)
+  // full kernel only: the diagnostics of output_all taken on the new state in the same pass (kernels_step.hip DIAG)
   DistGeom dg;
-  double *dist_out, *dist_partial;
-  // full kernel only: also predict the charge of the NEXT step's first sub-step (kernels_step.hip k_step_one);
-  // pred null = no.  tabA/tabB: [pred_nm][nx] mode tables with E = sum_m re_m*A_m + im_m*B_m;
-  // pred: [1 + 2*pred_nm][nx] accumulators of this species (R0, RA_m, RB_m); t2_mode: 0 no carry of
-  // -f0'/f0 through t2, 1 write it for the next step, 2 read this step's and write the next step's
+  double *dist_out;      // histograms [3*nxo*nvo + 3*nvo] of this species (accumulated with atomics), or null
+  double *dist_partial;  // [gridDim][3] kinetic sums per workgroup
+  // full kernel only: also predict the charge of the NEXT step's first sub-step (StepFamily); pred null = no.
+  // tabA/tabB: [pred_nm][nx] mode tables with E = sum_m re_m*A_m + im_m*B_m.  pred: Tiles, [1 + 2*pred_nm][nx]
+  // accumulators of this species (R0, RA_m, RB_m); the six sums, [PRED_SUM_COPIES][8] -- K0c K1c K2c K0s K1s K2s shared
+  // by all species (Z folded in), in copies.  t2_mode: 0 no carry of -f0'/f0 through t2, 1 write it for the next step,
+  // 2 read this step's and write the next step's
   const double *tabA, *tabB;
   double *pred;
-  int pred_nm, t2_mode;
-  // pred_kind 2 (kernels_step.hip k_step_sums, for grids whose prediction tiles outgrow the LDS; one kept mode): pred is
-  // [PRED_SUM_COPIES][8] -- six global sums K0c K1c K2c K0s K1s K2s shared by all species (Z folded in), in copies --, and Eh is not staged
-  // but formed from the tables and its kept mode *eh_re, *eh_im (Eh = re A + im B, bit for bit what the solve wrote)
-  int pred_kind;  // 1 tiles (k_step_one), 2 sums (k_step_sums)
-  int pred_private;  // pred_kind 2 on a grid whose E0, Eh and table tiles fit the LDS: k_step_one<PRIV>, the six sums in
-                     // thread-private LDS slots (Eh staged from memory like k_step_one's)
-  const double *eh_re, *eh_im;
-  FusedSolve fused;  // pred_kind 2 only: the prologue solves the previous step's field (E0, Eh, eh_re / eh_im unused)
-  StepTail tail;     // pred_kind 2 only, several ranks: the last workgroup packs / posts this rank's charge (mode 0: no)
-  DistScale dscale;  // k_step_full<DIAG>: the histograms as fixed-point sums (diag_fx != 0)
+  int pred_nm, t2_mode;         // pred_nm: the kept modes
+  const double *eh_re, *eh_im;  // k_step_sums: Eh is not staged but formed from the tables and its kept mode (Eh = re A +
+                                // im B, bit for bit what the solve wrote)
+  double snx, pred_k;           // the prediction: nx / lx, and dt/2 Z/m (launch_step)
+  FusedSolve fused;             // the six sums only: the prologue solves the previous step's field (E0, Eh, eh_re / eh_im unused)
+  StepTail tail;                // the six sums only, several ranks: the last workgroup packs / posts this rank's charge (mode 0: no)
+  DistScale dscale;             // k_step_full<DIAG>: the histograms as fixed-point sums (diag_fx != 0)
   int diag_fx;
-  int dyn_tail;      // every whole-step kernel: sixteenths of a workgroup's chunks that its waves draw from an LDS counter (0: all dealt)
-  double *fxb;       // pred_kind 1: [2] device bounds on |q|, |c| of this species, for the tiles' fixed-point sums
-  FxArgs fx;         // kind 1 of the charge sum (k_step_half / k_step_full only): the exact accumulators (acc null: rho)
+  int dyn_tail;                 // every whole-step kernel: sixteenths of a workgroup's chunks that its waves draw from an LDS
+                                // counter (0: all dealt)
+  double *fxb;                  // Tiles: [2] device bounds on |q|, |c| of this species, for the tiles' fixed-point sums
+  double fx_markers, fx_cap;    // ... the most markers one workgroup of this launch takes, and 2^61 over it (launch_step)
+  FxArgs fx;                    // kind 1 of the charge sum (k_step_half / k_step_full<EXACT>): the exact accumulators (acc null: rho)
+#ifdef PIC1DP_TUNE_STAMPS  // tuning build (tools/stamp_probe.sh): [gridDim][8] wall-clock stamps of the phases of a workgroup
+  unsigned long long *stamps;
+#endif
+};
+// the kernel family of a full step that predicts (pred non-null); every other launch takes k_step_half / k_step_full
+enum class StepFamily {
+  Tiles,        // k_step_one<NM>: prediction tiles of pred_nm kept modes
+  Sums,         // k_step_sums: one kept mode as six global sums, for grids whose tiles outgrow the LDS
+  PrivateSums,  // k_step_one<PRIV>: the six sums in thread-private LDS slots (E0, Eh and the table tiles fit the LDS)
+};
+// a whole-step launch: the kernel arguments and what picks the instantiation on the host
+struct StepArgs {
+  StepArgsDev d;
+  int iptcldist, deltaf, linear;
+  StepFamily family;
 };
 #ifndef PIC1DP_PRED_MAX_MODES
 #define PIC1DP_PRED_MAX_MODES 3
@@ -358,16 +388,15 @@ inline size_t step_diag_lds_bytes(int nx, int nxo, int nvo) {
 }
 // full = false: first sub-step (deposit of the half-step state, nothing stored)
 // full = true : second sub-step (recompute half-step state, push, deposit, store)
-hipError_t launch_step(const StepArgs &a, bool full, const LaunchCfg &lc, hipStream_t st);
+// (a.d's snx, pred_k, fx_markers and fx_cap are derived here)
+hipError_t launch_step(StepArgs a, bool full, const LaunchCfg &lc, hipStream_t st);
 
 // push (+gather) with or without the fused wrap+deposit
 hipError_t launch_push(const PushArgs &a, bool fused_deposit, const LaunchCfg &lc, hipStream_t st);
-// wrap + deposit of q (= w or p) at x, x stored back
-hipError_t launch_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst &g,
+// wrap + deposit of q (= w or p) at x, x stored back: into rho, or -- fx.acc non-null -- into the exact accumulators
+// of kind 1 (lc.lds: 16 B per cell and the guard cell)
+hipError_t launch_deposit(double *x, const double *q, double *rho, const FxArgs &fx, int64_t np, const GridConst &g,
                           const LaunchCfg &lc, hipStream_t st);
-// the same into the exact accumulators of kind 1 (lc.lds: 16 B per cell and the guard cell)
-hipError_t launch_deposit_exact(double *x, const double *q, const FxArgs &fx, int64_t np, const GridConst &g,
-                                const LaunchCfg &lc, hipStream_t st);
 
 
 // vectors of nx doubles one exchange can carry: charge2 + the 1 + 2 * PRED_MAX_MODES prediction slices

@@ -186,15 +186,9 @@ hipError_t launch_ptcldist(const double *x, const double *v, const double *p, co
   DistScale fx{};
   const bool use_fx = lds && make_dist_scale(np, blocks, deltaf, bound_p, bound_w, &fx);
   if (fixed_point) *fixed_point = use_fx;
-  auto go = [&](auto kern) -> hipError_t {
-    if (lds && bytes > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(threads), bytes, st, x, v, p, w, np, dg, out,
-                       partial, fx, dyn_tail);
-    return hipGetLastError();
+  auto go = [&](auto kern) {
+    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(threads), bytes, st, x, v, p, w, np, dg, out, partial,
+                         fx, dyn_tail);
   };
   if (use_fx) {
     if (nt) return deltaf ? go(k_ptcldist<true, true, true, true>) : go(k_ptcldist<true, false, true, true>);
@@ -219,14 +213,12 @@ __global__ void __launch_bounds__(256) k_pack_record(const PackArgs a, double *o
 }  // namespace
 hipError_t launch_pack_record(const PackArgs &a, double *out, hipStream_t st) {
   if (a.count <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pack_record, dim3(16, a.count), dim3(256), 0, st, a, out);
-  return hipGetLastError();
+  return launch_kernel(k_pack_record, dim3(16, a.count), dim3(256), 0, st, a, out);
 }
 
 hipError_t launch_energy_sums(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
                               double *partial, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL(k_energy_sums, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, partial);
-  return hipGetLastError();
+  return launch_kernel(k_energy_sums, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, partial);
 }
 
 namespace {
@@ -257,18 +249,15 @@ int copy_blocks(int64_t n) {
 
 hipError_t launch_tile_scatter(double *arr, int64_t i0, const double *src, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tile_scatter, dim3(copy_blocks(n)), dim3(256), 0, st, arr, i0, src, n);
-  return hipGetLastError();
+  return launch_kernel(k_tile_scatter, dim3(copy_blocks(n)), dim3(256), 0, st, arr, i0, src, n);
 }
 hipError_t launch_tile_gather(const double *arr, int64_t i0, double *dst, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tile_gather, dim3(copy_blocks(n)), dim3(256), 0, st, arr, i0, dst, n);
-  return hipGetLastError();
+  return launch_kernel(k_tile_gather, dim3(copy_blocks(n)), dim3(256), 0, st, arr, i0, dst, n);
 }
 hipError_t launch_tile_copy(double *dst, const double *src, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tile_copy, dim3(copy_blocks(n)), dim3(256), 0, st, dst, src, n);
-  return hipGetLastError();
+  return launch_kernel(k_tile_copy, dim3(copy_blocks(n)), dim3(256), 0, st, dst, src, n);
 }
 
 hipError_t launch_cell_indices(const double *x, int64_t np, const GridConst &g, int32_t *ix,
@@ -276,8 +265,7 @@ hipError_t launch_cell_indices(const double *x, int64_t np, const GridConst &g, 
   int blocks = static_cast<int>((np + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_cell_indices, dim3(blocks), dim3(256), 0, st, x, np, g, ix, count);
-  return hipGetLastError();
+  return launch_kernel(k_cell_indices, dim3(blocks), dim3(256), 0, st, x, np, g, ix, count);
 }
 
 }  // namespace pic1dp

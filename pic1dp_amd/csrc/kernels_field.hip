@@ -5,6 +5,8 @@
 #include "device_math.hpp"
 #include "device_xchg.hpp"
 
+#include <type_traits>
+
 namespace pic1dp {
 
 // ---------------------------------------------------------------------------
@@ -1132,101 +1134,79 @@ __global__ void __launch_bounds__(64) k_chain_selftest(const double *v, int nrow
 }
 hipError_t launch_chain_selftest(const double *v, int nrows, int n, double *out, hipStream_t st) {
   const size_t lds = sizeof(double) * nrows * ((n + 1) & ~1);
-  if (lds > 64 * 1024) {  // opt in to > 64 KiB of dynamic LDS, as launch_step_kernel does
-    if (lds > 160 * 1024 - 1024) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_chain_selftest),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_chain_selftest, dim3(1), dim3(64), lds, st, v, nrows, n, out);
-  return hipGetLastError();
+  return launch_kernel(k_chain_selftest, dim3(1), dim3(64), lds, st, v, nrows, n, out);
 }
 
 hipError_t launch_field_fd(const double *chargeden, double *E, double *history, int nx, double lx,
                            double dnx, hipStream_t st) {
   if (nx < 3 || nx > FD_MAX_NX) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * 4 * static_cast<size_t>(nx);
-  static bool big_lds_ok = false;
-  if (lds > 64 * 1024 && !big_lds_ok) {
-    // the kernel also holds 136 B of static LDS: leave room for it
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_fd),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) return e;
-    big_lds_ok = true;
-  }
-  hipLaunchKernelGGL(k_field_fd, dim3(1), dim3(FD_THREADS), lds, st, chargeden, E, history, nx, lx, dnx);
-  return hipGetLastError();
+  return launch_kernel(k_field_fd, dim3(1), dim3(FD_THREADS), lds, st, chargeden, E, history, nx, lx, dnx);
 }
 
 hipError_t launch_fx_normalise(long long *acc, int nspecies, int nx, hipStream_t st) {
   const int n = nspecies * nx;
-  hipLaunchKernelGGL(k_fx_normalise, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx);
-  return hipGetLastError();
+  return launch_kernel(k_fx_normalise, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, nspecies,
+                       nx);
 }
 
 hipError_t launch_fx_to_rho(long long *acc, double *rho_sp, int nspecies, int nx, const double *q, hipStream_t st) {
   FxQuanta fq{};
   for (int s = 0; s < nspecies && s < 8; ++s) fq.q[s] = q[s];
   const int n = nspecies * nx;
-  hipLaunchKernelGGL(k_fx_to_rho, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, rho_sp,
-                     nspecies, nx, fq);
-  return hipGetLastError();
+  return launch_kernel(k_fx_to_rho, dim3((n + FIELD_THREADS - 1) / FIELD_THREADS), dim3(FIELD_THREADS), 0, st, acc, rho_sp,
+                       nspecies, nx, fq);
 }
 
 hipError_t launch_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs &x, hipStream_t st) {
   if (2 * nspecies * nx > x.vstride) return hipErrorInvalidValue;  // (the slots are sized for it: capi_comm.cpp xchg_vec)
-  hipLaunchKernelGGL(k_fx_exchange, dim3(1), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx, x);
-  return hipGetLastError();
+  return launch_kernel(k_fx_exchange, dim3(1), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx, x);
 }
 
 hipError_t launch_charge_local(const FieldArgs &f, hipStream_t st) {
-  hipLaunchKernelGGL(k_charge_local, dim3(1), dim3(FIELD_THREADS), 0, st, f);
-  return hipGetLastError();
+  return launch_kernel(k_charge_local, dim3(1), dim3(FIELD_THREADS), 0, st, f);
 }
 
 hipError_t launch_chargeden(const FieldArgs &f, bool with_local, hipStream_t st) {
-  if (with_local) {
-    hipLaunchKernelGGL(k_chargeden<true>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
-  } else {
-    hipLaunchKernelGGL(k_chargeden<false>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
-  }
-  return hipGetLastError();
+  if (with_local) return launch_kernel(k_chargeden<true>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
+  return launch_kernel(k_chargeden<false>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
 }
+
+namespace {
+// dynamic LDS of the one-workgroup mode-filter solves (k_field_solve and its siblings): the grid vector, the modes,
+// scratch, and the tables where they fit (FieldArgs::tab_lds)
+size_t solve_lds_bytes(const FieldArgs &f) {
+  return sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
+                           (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
+}
+}  // namespace
 
 hipError_t launch_field_solve(const FieldArgs &f, bool with_local, bool from_chargeden,
                               hipStream_t st) {
   if (2 * f.nmode > FIELD_THREADS) {  // many modes: chargeden, forward, inverse, energy
-    if (!from_chargeden) {
-      hipError_t e = launch_chargeden(f, with_local, st);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_field_modes_wide, dim3((2 * f.nmode + WIDE_THREADS - 1) / WIDE_THREADS),
-                       dim3(WIDE_THREADS), sizeof(double) * f.nx, st, f);
-    hipLaunchKernelGGL(k_field_inverse_wide, dim3((f.nx + WIDE_THREADS - 1) / WIDE_THREADS), dim3(WIDE_THREADS),
-                       sizeof(double) * 2 * f.nmode, st, f);
-    if (f.history) hipLaunchKernelGGL(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, f.E, f.nx, f.lx, f.dnx, f.history);
-    return hipGetLastError();
+    hipError_t e = from_chargeden ? hipSuccess : launch_chargeden(f, with_local, st);
+    if (e == hipSuccess)
+      e = launch_kernel(k_field_modes_wide, dim3((2 * f.nmode + WIDE_THREADS - 1) / WIDE_THREADS), dim3(WIDE_THREADS),
+                        sizeof(double) * f.nx, st, f);
+    if (e == hipSuccess)
+      e = launch_kernel(k_field_inverse_wide, dim3((f.nx + WIDE_THREADS - 1) / WIDE_THREADS), dim3(WIDE_THREADS),
+                        sizeof(double) * 2 * f.nmode, st, f);
+    if (e == hipSuccess && f.history)
+      e = launch_kernel(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, f.E, f.nx, f.lx, f.dnx, f.history);
+    return e;
   }
-  const size_t lds = sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                                       (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
-  if (from_chargeden) {
-    hipLaunchKernelGGL((k_field_solve<false, true>), dim3(1), dim3(FIELD_THREADS), lds, st, f);
-  } else if (with_local) {
-    hipLaunchKernelGGL((k_field_solve<true, false>), dim3(1), dim3(FIELD_THREADS), lds, st, f);
-  } else {
-    hipLaunchKernelGGL((k_field_solve<false, false>), dim3(1), dim3(FIELD_THREADS), lds, st, f);
-  }
-  return hipGetLastError();
+  const size_t lds = solve_lds_bytes(f);
+  if (from_chargeden) return launch_kernel(k_field_solve<false, true>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
+  if (with_local) return launch_kernel(k_field_solve<true, false>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
+  return launch_kernel(k_field_solve<false, false>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
 }
 
 hipError_t launch_pred_combine(const FieldArgs &f, double *pred, int nm_pred, hipStream_t st) {
-  hipLaunchKernelGGL(k_pred_combine, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred);
-  return hipGetLastError();
+  return launch_kernel(k_pred_combine, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred);
 }
 
 hipError_t launch_charge_exchange(const FieldArgs &f, const XchgArgs &x, hipStream_t st) {
-  hipLaunchKernelGGL(k_charge_exchange, dim3(1), dim3(FIELD_THREADS), sizeof(double) * f.nx, st, f, x);
-  return hipGetLastError();
+  return launch_kernel(k_charge_exchange, dim3(1), dim3(FIELD_THREADS), sizeof(double) * f.nx, st, f, x);
 }
 
 hipError_t launch_field_solve_xchg(const FieldArgs &f, const XchgArgs &x, hipStream_t st) {
@@ -1235,118 +1215,70 @@ hipError_t launch_field_solve_xchg(const FieldArgs &f, const XchgArgs &x, hipStr
     if (e != hipSuccess) return e;
     return launch_field_solve(f, false, false, st);
   }
-  const size_t lds = sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                                       (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
-  hipLaunchKernelGGL(k_field_solve_xchg, dim3(1), dim3(FIELD_THREADS), lds, st, f, x);
-  return hipGetLastError();
+  return launch_kernel(k_field_solve_xchg, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, x);
 }
 
 hipError_t launch_field_solve_pair(const FieldArgs &f, const PairArgs &pa, const XchgArgs *x1, hipStream_t st) {
   if (2 * f.nmode > FIELD_THREADS) return hipErrorInvalidValue;
-  size_t lds = sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                                 (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
   const XchgArgs none{};
+  const XchgArgs &x = x1 ? *x1 : none;
+  // SRC of this rank's charge: 1 the one exchange x1, 2 pa.pack, 0 the local accumulators
+  auto by_src = [&](auto launch) -> hipError_t {
+    if (x1) return launch(std::integral_constant<int, 1>{});
+    if (pa.pack) return launch(std::integral_constant<int, 2>{});
+    return launch(std::integral_constant<int, 0>{});
+  };
+  const size_t ne = (static_cast<size_t>(f.nx) + 1) & ~static_cast<size_t>(1);
+  const size_t npe2 = (2 * static_cast<size_t>(f.npe) + 1) & ~static_cast<size_t>(1);
   if (pa.kind != 2 && f.nmode == 1 && f.tab_lds) {  // the lean kernel of the usual case
-    const size_t ne = (static_cast<size_t>(f.nx) + 1) & ~static_cast<size_t>(1);
-    size_t l1 = sizeof(double) * (2 * ne + (FIELD_THREADS / 64) * 6 + 8 + 16 + ((2 * static_cast<size_t>(f.npe) + 1) & ~static_cast<size_t>(1)));
-    if (x1) {
-      l1 += sizeof(double) * 4 * static_cast<size_t>(f.nx);
-      if (l1 > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_solve_pair1<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(k_field_solve_pair1<1>, dim3(1), dim3(FIELD_THREADS), l1, st, f, *x1, pa);
-    } else if (pa.pack) {
-      hipLaunchKernelGGL(k_field_solve_pair1<2>, dim3(1), dim3(FIELD_THREADS), l1, st, f, none, pa);
-    } else {
-      hipLaunchKernelGGL(k_field_solve_pair1<0>, dim3(1), dim3(FIELD_THREADS), l1, st, f, none, pa);
-    }
-    return hipGetLastError();
+    const size_t lds =
+        sizeof(double) * (2 * ne + (FIELD_THREADS / 64) * 6 + 8 + 16 + npe2 + (x1 ? 4 * static_cast<size_t>(f.nx) : 0));
+    return by_src([&](auto SRC) {
+      return launch_kernel(k_field_solve_pair1<SRC>, dim3(1), dim3(FIELD_THREADS), lds, st, f, x, pa);
+    });
   }
   if (pa.kind == 2) {  // the six sums of ONE kept mode
     if (f.nmode != 1) return hipErrorInvalidValue;
-    const size_t ne = (static_cast<size_t>(f.nx) + 1) & ~static_cast<size_t>(1);
-    size_t l1 = sizeof(double) * (2 * ne + 8 + 16 + ((2 * static_cast<size_t>(f.npe) + 1) & ~static_cast<size_t>(1)));
+    const size_t lds = sizeof(double) * (2 * ne + 8 + 16 + npe2 + (x1 ? pack_doubles(f.nx, 1, 2) : 0));
     const int threads = f.nx > 2048 ? 1024 : (f.nx > 1024 ? 512 : FIELD_THREADS);
-    if (x1) {
-      l1 += sizeof(double) * pack_doubles(f.nx, 1, 2);
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_solve_pair_sums1<1>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_field_solve_pair_sums1<1>, dim3(1), dim3(threads), l1, st, f, *x1, pa);
-    } else if (pa.pack) {
-      if (l1 > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_solve_pair_sums1<2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(k_field_solve_pair_sums1<2>, dim3(1), dim3(threads), l1, st, f, none, pa);
-    } else {
-      if (l1 > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_solve_pair_sums1<0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(k_field_solve_pair_sums1<0>, dim3(1), dim3(threads), l1, st, f, none, pa);
-    }
-    return hipGetLastError();
+    return by_src([&](auto SRC) {
+      return launch_kernel(k_field_solve_pair_sums1<SRC>, dim3(1), dim3(threads), lds, st, f, x, pa);
+    });
   }
-  if (x1) {
-    lds += sizeof(double) * (2 + 2 * static_cast<size_t>(f.nmode)) * f.nx;  // the packed vector
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_field_solve_pair<1>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_field_solve_pair<1>, dim3(1), dim3(FIELD_THREADS), lds, st, f, *x1, pa);
-  } else if (pa.pack) {
-    hipLaunchKernelGGL(k_field_solve_pair<2>, dim3(1), dim3(FIELD_THREADS), lds, st, f, none, pa);
-  } else {
-    hipLaunchKernelGGL(k_field_solve_pair<0>, dim3(1), dim3(FIELD_THREADS), lds, st, f, none, pa);
-  }
-  return hipGetLastError();
+  // (x1: + the packed vector)
+  const size_t lds = solve_lds_bytes(f) + (x1 ? sizeof(double) * (2 + 2 * static_cast<size_t>(f.nmode)) * f.nx : 0);
+  return by_src([&](auto SRC) {
+    return launch_kernel(k_field_solve_pair<SRC>, dim3(1), dim3(FIELD_THREADS), lds, st, f, x, pa);
+  });
 }
 
 hipError_t launch_field_solve_pred(const FieldArgs &f, double *pred, int nm_pred, hipStream_t st) {
   if (2 * f.nmode > FIELD_THREADS) return hipErrorInvalidValue;
-  const size_t lds = sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                                       (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
-  hipLaunchKernelGGL(k_field_solve_pred, dim3(1), dim3(FIELD_THREADS), lds, st, f, pred, nm_pred);
-  return hipGetLastError();
+  return launch_kernel(k_field_solve_pred, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, pred, nm_pred);
 }
 
 hipError_t launch_field_solve_pred_sums(const FieldArgs &f, const PredTab &pt, double *pred, hipStream_t st) {
   if (f.nmode != 1) return hipErrorInvalidValue;
-  const size_t lds = sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                                       (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
-  hipLaunchKernelGGL(k_field_solve_pred_sums, dim3(1), dim3(FIELD_THREADS), lds, st, f, pt, pred);
-  return hipGetLastError();
+  return launch_kernel(k_field_solve_pred_sums, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, pt, pred);
 }
 
 hipError_t launch_charge_pack(const FieldArgs &f, double *pred, int nm_pred, int kind, double *pack, hipStream_t st) {
-  if (kind == 2)
-    hipLaunchKernelGGL(k_charge_pack_sums, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, pack);
-  else
-    hipLaunchKernelGGL(k_charge_pack, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred, pack);
-  return hipGetLastError();
+  if (kind == 2) return launch_kernel(k_charge_pack_sums, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, pack);
+  return launch_kernel(k_charge_pack, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred, pack);
 }
 
 hipError_t launch_pred_chargeden(const FieldArgs &f, const PredTab &pt, double *pred, const double *K, hipStream_t st) {
   if (f.nmode != 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_pred_chargeden, dim3(1), dim3(FIELD_THREADS), 0, st, f, pt, pred, K);
-  return hipGetLastError();
+  return launch_kernel(k_pred_chargeden, dim3(1), dim3(FIELD_THREADS), 0, st, f, pt, pred, K);
 }
 
 hipError_t launch_pred_to_charge(const FieldArgs &f, double *pred, hipStream_t st) {
-  hipLaunchKernelGGL(k_pred_to_charge, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred);
-  return hipGetLastError();
+  return launch_kernel(k_pred_to_charge, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred);
 }
 
 hipError_t launch_field_energy(const double *E, int nx, double lx, double dnx, double *out,
                                hipStream_t st) {
-  hipLaunchKernelGGL(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, E, nx, lx, dnx, out);
-  return hipGetLastError();
+  return launch_kernel(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, E, nx, lx, dnx, out);
 }
 
 }  // namespace pic1dp

@@ -340,36 +340,30 @@ hipError_t opt_hist_block(const OptBlock &b, const OptGrid &g, int64_t np, doubl
   uint32_t *keys = reinterpret_cast<uint32_t *>(base);
   double *vals = reinterpret_cast<double *>(base + align256(sizeof(uint32_t) * 2 * n));
   void *tmp = base + align256(sizeof(uint32_t) * 2 * n) + align256(sizeof(double) * 2 * n);
-  hipLaunchKernelGGL(k_opt_hist_items, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, np, keys, vals);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_kernel(k_opt_hist_items, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, np, keys, vals);
   const int bits = hist_sort_bits(g.nv);
   size_t tmp_bytes = 0;
   if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys + n, vals, vals + n, n, 0, bits, st);
   if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys + n, vals, vals + n, n, 0, bits, st);  // stable
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_opt_hist_fold, dim3((g.nv + OPT_THREADS - 1) / OPT_THREADS), dim3(OPT_THREADS), 0, st, keys + n, vals + n,
-                       static_cast<int64_t>(n), g.nv, hist);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess)
+    e = launch_kernel(k_opt_hist_fold, dim3((g.nv + OPT_THREADS - 1) / OPT_THREADS), dim3(OPT_THREADS), 0, st, keys + n, vals + n,
+                      static_cast<int64_t>(n), g.nv, hist);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   return e;
 }
 
 hipError_t opt_merge_keys(const OptBlock &b, const OptGrid &g, const double *hist, double limit, int64_t np, uint32_t *keys,
                           hipStream_t st) {
-  hipLaunchKernelGGL(k_opt_merge_keys, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, np, keys);
-  return hipGetLastError();
+  return launch_kernel(k_opt_merge_keys, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, np, keys);
 }
 hipError_t opt_remove_vals(const OptBlock &b, const OptGrid &g, const double *hist, double peak, double limit, int by_threshold,
                            int64_t np, uint8_t *skip, double *df, hipStream_t st) {
-  hipLaunchKernelGGL(k_opt_remove_vals, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, peak, limit, by_threshold, np,
-                     skip, df);
-  return hipGetLastError();
+  return launch_kernel(k_opt_remove_vals, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, peak, limit, by_threshold, np,
+                       skip, df);
 }
 hipError_t opt_split_flags(const OptBlock &b, const OptGrid &g, const double *hist, double limit, int64_t np, uint8_t *flag,
                            hipStream_t st) {
-  hipLaunchKernelGGL(k_opt_split_flags, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, np, flag);
-  return hipGetLastError();
+  return launch_kernel(k_opt_split_flags, dim3(opt_blocks(np)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, np, flag);
 }
 size_t opt_holes_scratch_bytes(int64_t np_new) {
   if (np_new <= 0) return 0;
@@ -391,14 +385,11 @@ hipError_t opt_holes(const uint32_t *gone_ids, int64_t ngone, const uint32_t *go
   void *tmp = base + align256(static_cast<size_t>(np_new)) + 256;
   hipError_t e = hipSuccess;
   if (gone_bits) {
-    hipLaunchKernelGGL(k_opt_mark_bits, dim3(opt_blocks(np_new)), dim3(OPT_THREADS), 0, st, gone_bits, np_new, gone);
-    e = hipGetLastError();
+    e = launch_kernel(k_opt_mark_bits, dim3(opt_blocks(np_new)), dim3(OPT_THREADS), 0, st, gone_bits, np_new, gone);
   } else {
     e = hipMemsetAsync(gone, 0, static_cast<size_t>(np_new), st);
-    if (e == hipSuccess && ngone > 0) {
-      hipLaunchKernelGGL(k_opt_mark_ids, dim3(opt_blocks(ngone)), dim3(OPT_THREADS), 0, st, gone_ids, ngone, np_new, gone);
-      e = hipGetLastError();
-    }
+    if (e == hipSuccess && ngone > 0)
+      e = launch_kernel(k_opt_mark_ids, dim3(opt_blocks(ngone)), dim3(OPT_THREADS), 0, st, gone_ids, ngone, np_new, gone);
   }
   size_t tmp_bytes = 0;
   rocprim::counting_iterator<uint32_t> positions(0);
@@ -413,41 +404,42 @@ hipError_t opt_holes(const uint32_t *gone_ids, int64_t ngone, const uint32_t *go
 
 hipError_t opt_moves(const OptBlock &b, const uint32_t *pos, const uint32_t *id, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_opt_moves, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, st, b, pos, id, n);
-  return hipGetLastError();
+  return launch_kernel(k_opt_moves, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, st, b, pos, id, n);
 }
 hipError_t opt_merge_apply(const OptBlock &b, const OptGrid &g, const double *hist, double limit, const uint32_t *dst,
                            const uint32_t *idk, int64_t npairs, const uint32_t *move_pos, const uint32_t *move_id, int64_t nmoves,
                            int64_t ghost, int64_t np_new, double *scratch, hipStream_t st) {
-  if (npairs > 0) hipLaunchKernelGGL(k_opt_merge_save, dim3(opt_blocks(npairs)), dim3(OPT_THREADS), 0, st, b, g.lx, idk, npairs, scratch);
-  if (hipError_t e = opt_moves(b, move_pos, move_id, nmoves, st); e != hipSuccess) return e;
-  if (ghost >= 0 && ghost != np_new) hipLaunchKernelGGL(k_opt_ghost, dim3(1), dim3(64), 0, st, b, ghost, np_new);
+  hipError_t e = hipSuccess;
+  if (npairs > 0)
+    e = launch_kernel(k_opt_merge_save, dim3(opt_blocks(npairs)), dim3(OPT_THREADS), 0, st, b, g.lx, idk, npairs, scratch);
+  if (e == hipSuccess) e = opt_moves(b, move_pos, move_id, nmoves, st);
+  if (e == hipSuccess && ghost >= 0 && ghost != np_new) e = launch_kernel(k_opt_ghost, dim3(1), dim3(64), 0, st, b, ghost, np_new);
   const int64_t nwrap = np_new + (ghost >= 0 ? 1 : 0);  // (the marker looked at last was wrapped before it merged)
-  if (nwrap > 0) hipLaunchKernelGGL(k_opt_merge_wrap, dim3(opt_blocks(nwrap)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, nwrap);
-  if (npairs > 0) hipLaunchKernelGGL(k_opt_merge_combine, dim3(opt_blocks(npairs)), dim3(OPT_THREADS), 0, st, b, dst, scratch, npairs);
-  return hipGetLastError();
+  if (e == hipSuccess && nwrap > 0)
+    e = launch_kernel(k_opt_merge_wrap, dim3(opt_blocks(nwrap)), dim3(OPT_THREADS), 0, st, b, g, hist, limit, nwrap);
+  if (e == hipSuccess && npairs > 0)
+    e = launch_kernel(k_opt_merge_combine, dim3(opt_blocks(npairs)), dim3(OPT_THREADS), 0, st, b, dst, scratch, npairs);
+  return e;
 }
 hipError_t opt_remove_apply(const OptBlock &b, const OptGrid &g, const double *hist, double peak, double limit, int by_threshold,
                             double keep_scale, const uint32_t *move_pos, const uint32_t *move_id, int64_t nmoves, int64_t ghost,
                             int64_t np_new, hipStream_t st) {
-  if (hipError_t e = opt_moves(b, move_pos, move_id, nmoves, st); e != hipSuccess) return e;
-  if (ghost >= 0 && ghost != np_new) hipLaunchKernelGGL(k_opt_ghost, dim3(1), dim3(64), 0, st, b, ghost, np_new);
-  if (np_new > 0)
-    hipLaunchKernelGGL(k_opt_remove_scale, dim3(opt_blocks(np_new)), dim3(OPT_THREADS), 0, st, b, g, hist, peak, limit, by_threshold,
-                       keep_scale, np_new);
-  return hipGetLastError();
+  hipError_t e = opt_moves(b, move_pos, move_id, nmoves, st);
+  if (e == hipSuccess && ghost >= 0 && ghost != np_new) e = launch_kernel(k_opt_ghost, dim3(1), dim3(64), 0, st, b, ghost, np_new);
+  if (e == hipSuccess && np_new > 0)
+    e = launch_kernel(k_opt_remove_scale, dim3(opt_blocks(np_new)), dim3(OPT_THREADS), 0, st, b, g, hist, peak, limit, by_threshold,
+                      keep_scale, np_new);
+  return e;
 }
 hipError_t opt_split_apply(const OptBlock &b, int64_t parents, const uint32_t *ks, const double *dv, int64_t nsplit, int ng, int deltaf,
                            hipStream_t st) {
   if (nsplit <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_opt_split_apply, dim3(opt_blocks(nsplit)), dim3(OPT_THREADS), 0, st, b, parents, ks, dv, nsplit, ng, deltaf);
-  return hipGetLastError();
+  return launch_kernel(k_opt_split_apply, dim3(opt_blocks(nsplit)), dim3(OPT_THREADS), 0, st, b, parents, ks, dv, nsplit, ng, deltaf);
 }
 hipError_t opt_copy_segment(const OptBlock &b, int64_t i0, int64_t n, double *dx, double *dv, double *dp, double *dw, int64_t doff,
                             hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_opt_copy_segment, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, st, b, i0, n, dx, dv, dp, dw, doff);
-  return hipGetLastError();
+  return launch_kernel(k_opt_copy_segment, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, st, b, i0, n, dx, dv, dp, dw, doff);
 }
 
 }  // namespace pic1dp

@@ -128,16 +128,7 @@ k_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst g
 
 template <int DIST, int MODE, int POW2, bool IRK2, bool FUSED, bool EXACT = false>
 hipError_t launch_push_t(const PushArgs &a, const LaunchCfg &lc, hipStream_t st) {
-  auto kern = k_push<DIST, MODE, POW2, IRK2, FUSED, EXACT>;
-  static bool big_lds_ok = false;  // opt in once to > 64 KiB of dynamic LDS (nx >= 4096)
-  if (lc.lds > 64 * 1024 && !big_lds_ok) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PARTICLE_LDS_CAP);
-    if (e != hipSuccess) return e;
-    big_lds_ok = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, a);
-  return hipGetLastError();
+  return launch_kernel(k_push<DIST, MODE, POW2, IRK2, FUSED, EXACT>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, a);
 }
 
 template <int DIST, int MODE, int POW2>
@@ -185,30 +176,10 @@ hipError_t launch_push(const PushArgs &a, bool fused_deposit, const LaunchCfg &l
   }
 }
 
-hipError_t launch_deposit(double *x, const double *q, double *rho, int64_t np, const GridConst &g,
+hipError_t launch_deposit(double *x, const double *q, double *rho, const FxArgs &fx, int64_t np, const GridConst &g,
                           const LaunchCfg &lc, hipStream_t st) {
-  static bool big_lds_ok = false;
-  if (lc.lds > 64 * 1024 && !big_lds_ok) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_deposit<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    big_lds_ok = true;
-  }
-  hipLaunchKernelGGL(k_deposit<false>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, rho, np, g, FxArgs{});
-  return hipGetLastError();
-}
-
-hipError_t launch_deposit_exact(double *x, const double *q, const FxArgs &fx, int64_t np, const GridConst &g,
-                                const LaunchCfg &lc, hipStream_t st) {
-  static bool big_lds_ok = false;
-  if (lc.lds > 64 * 1024 && !big_lds_ok) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_deposit<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PARTICLE_LDS_CAP);
-    if (e != hipSuccess) return e;
-    big_lds_ok = true;
-  }
-  hipLaunchKernelGGL(k_deposit<true>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, nullptr, np, g, fx);
-  return hipGetLastError();
+  if (!fx.acc) return launch_kernel(k_deposit<false>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, rho, np, g, fx);
+  return launch_kernel(k_deposit<true>, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, x, q, nullptr, np, g, fx);
 }
 
 }  // namespace pic1dp

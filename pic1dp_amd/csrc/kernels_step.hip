@@ -17,6 +17,7 @@
 #include "step_args.hpp"
 
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 #ifndef PIC1DP_STEP_DIST
@@ -1114,13 +1115,7 @@ hipError_t launch_step_kernel(K kern, const StepArgsDev &d0, const LaunchCfg &lc
 #else
   const StepArgsDev &d = d0;
 #endif
-  if (lc.lds > 64 * 1024) {  // opt in to > 64 KiB of dynamic LDS (idempotent, cheap)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PARTICLE_LDS_CAP);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, d);
-  return hipGetLastError();
+  return launch_kernel(kern, dim3(lc.blocks), dim3(lc.threads), lc.lds, st, d);
 }
 
 // -f0'/f0 carried to the next step through memory (T2 = 1, 2): what the reference-order form of the exp-bearing
@@ -1141,103 +1136,47 @@ template <int DIST>
 constexpr bool kNoCarryBuilt = !(DIST == 2 || DIST == 3);
 #endif
 
-static_assert(PRED_MAX_MODES == 2 || PRED_MAX_MODES == 3, "k_step_one is instantiated for one and two (three) kept modes");
-static_assert(PRIV_THREADS == STEP_PRIVATE_THREADS, "slot stride of k_step_one<PRIV> = its workgroup size");
-template <int DIST, int MODE, int POW2, int NM>
-hipError_t launch_step_one(const StepArgsDev &d, int t2m, const LaunchCfg &lc, hipStream_t st) {
-  if (d.nt) {
+// The one-pass kernels' run-time pair (non-temporal streams, carry mode t2m) as compile-time arguments: f(NT, T2), two
+// std::integral_constant, for the pairs this unit builds; any other pair has no kernel here
+template <int DIST, class F>
+hipError_t with_nt_t2(bool nt, int t2m, F &&f) {
+  auto by_t2 = [&](auto NT) -> hipError_t {
     if constexpr (kCarryBuilt<DIST>) {
-      if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 2, NM>, d, lc, st);
-      if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 1, NM>, d, lc, st);
+      if (t2m == 2) return f(NT, std::integral_constant<int, 2>{});
+      if (t2m == 1) return f(NT, std::integral_constant<int, 1>{});
     }
     if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-    if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 0, NM>, d, lc, st);
+    if constexpr (kNoCarryBuilt<DIST>) return f(NT, std::integral_constant<int, 0>{});
     return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-  }
-  if constexpr (kCarryBuilt<DIST>) {
-    if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 2, NM>, d, lc, st);
-    if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 1, NM>, d, lc, st);
-  }
-  if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-  if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 0, NM>, d, lc, st);
-  return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
+  };
+  return nt ? by_t2(std::true_type{}) : by_t2(std::false_type{});
 }
 
+static_assert(PRED_MAX_MODES == 2 || PRED_MAX_MODES == 3, "k_step_one is instantiated for one and two (three) kept modes");
+static_assert(PRIV_THREADS == STEP_PRIVATE_THREADS, "slot stride of k_step_one<PRIV> = its workgroup size");
+
 template <int DIST, int MODE, int POW2, bool CARRY = false>
-hipError_t launch_step_dmp(const StepArgsDev &d, bool full, const LaunchCfg &lc, hipStream_t st) {
-  if (full && d.pred && d.pred_nm == -2) {  // one pass per step, six sums in thread-private LDS slots
-    const int t2m = d.t2 ? d.t2_mode : 0;
-    if (d.fused.on) {  // ... and the previous step's field solved in the prologue
-      if (d.nt) {
-        if constexpr (kCarryBuilt<DIST>) {
-          if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 2, 1, true, true>, d, lc, st);
-          if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 1, 1, true, true>, d, lc, st);
-        }
-        if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-        if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 0, 1, true, true>, d, lc, st);
-        return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-      }
-      if constexpr (kCarryBuilt<DIST>) {
-        if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 2, 1, true, true>, d, lc, st);
-        if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 1, 1, true, true>, d, lc, st);
-      }
-      if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-      if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 0, 1, true, true>, d, lc, st);
-      return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-    }
-    if (d.nt) {
-      if constexpr (kCarryBuilt<DIST>) {
-        if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 2, 1, true>, d, lc, st);
-        if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 1, 1, true>, d, lc, st);
-      }
-      if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-      if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, true, 0, 1, true>, d, lc, st);
-      return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-    }
-    if constexpr (kCarryBuilt<DIST>) {
-      if (t2m == 2) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 2, 1, true>, d, lc, st);
-      if (t2m == 1) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 1, 1, true>, d, lc, st);
-    }
-    if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-    if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_one<DIST, MODE, POW2, false, 0, 1, true>, d, lc, st);
-    return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
+hipError_t launch_step_dmp(const StepArgs &a, bool full, const LaunchCfg &lc, hipStream_t st) {
+  const StepArgsDev &d = a.d;
+  const bool one_pass = full && d.pred;  // one pass per step: also predicts the next step's first-sub-step charge
+  const int t2m = d.t2 ? d.t2_mode : 0;
+  if (one_pass && a.family == StepFamily::PrivateSums) {  // six sums in thread-private LDS slots
+    if (d.fused.on)  // ... and the previous step's field solved in the prologue
+      return with_nt_t2<DIST>(d.nt, t2m, [&](auto NT, auto T2) {
+        return launch_step_kernel(k_step_one<DIST, MODE, POW2, NT, T2, 1, true, true>, d, lc, st);
+      });
+    return with_nt_t2<DIST>(d.nt, t2m, [&](auto NT, auto T2) {
+      return launch_step_kernel(k_step_one<DIST, MODE, POW2, NT, T2, 1, true>, d, lc, st);
+    });
   }
-  if (full && d.pred && d.pred_nm < 0) {  // one pass per step, prediction as six sums (large grids)
-    const int t2m = d.t2 ? d.t2_mode : 0;
-    if (d.fused.on) {
-      if (d.nt) {
-        if constexpr (kCarryBuilt<DIST>) {
-          if (t2m == 2) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 2, true>, d, lc, st);
-          if (t2m == 1) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 1, true>, d, lc, st);
-        }
-        if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-        if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 0, true>, d, lc, st);
-        return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-      }
-      if constexpr (kCarryBuilt<DIST>) {
-        if (t2m == 2) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 2, true>, d, lc, st);
-        if (t2m == 1) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 1, true>, d, lc, st);
-      }
-      if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-      if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 0, true>, d, lc, st);
-      return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-    }
-    if (d.nt) {
-      if constexpr (kCarryBuilt<DIST>) {
-        if (t2m == 2) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 2>, d, lc, st);
-        if (t2m == 1) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 1>, d, lc, st);
-      }
-      if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-      if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, true, 0>, d, lc, st);
-      return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
-    }
-    if constexpr (kCarryBuilt<DIST>) {
-      if (t2m == 2) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 2>, d, lc, st);
-      if (t2m == 1) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 1>, d, lc, st);
-    }
-    if (t2m != 0) return hipErrorInvalidValue;  // (a carry this build has no kernel for)
-    if constexpr (kNoCarryBuilt<DIST>) return launch_step_kernel(k_step_sums<DIST, MODE, POW2, false, 0>, d, lc, st);
-    return hipErrorInvalidValue;  // (no carry-less kernel in this unit: its distribution always carries)
+  if (one_pass && a.family == StepFamily::Sums) {  // prediction as six sums (large grids)
+    if (d.fused.on)
+      return with_nt_t2<DIST>(d.nt, t2m, [&](auto NT, auto T2) {
+        return launch_step_kernel(k_step_sums<DIST, MODE, POW2, NT, T2, true>, d, lc, st);
+      });
+    return with_nt_t2<DIST>(d.nt, t2m, [&](auto NT, auto T2) {
+      return launch_step_kernel(k_step_sums<DIST, MODE, POW2, NT, T2>, d, lc, st);
+    });
   }
   if (d.fx.acc) {  // kind 1 of the charge sum: two passes, the diagnostics in their own pass (the host sees to both)
     if (d.pred || d.dist_out) return hipErrorInvalidValue;
@@ -1247,12 +1186,16 @@ hipError_t launch_step_dmp(const StepArgsDev &d, bool full, const LaunchCfg &lc,
     return full ? launch_step_kernel(k_step_full<DIST, MODE, POW2, false, CARRY, false, false, true>, d, lc, st)
                 : launch_step_kernel(k_step_half<DIST, MODE, POW2, false, CARRY, true>, d, lc, st);
   }
-  if (full && d.pred) {  // one pass per step: also predicts the next step's first-sub-step charge
-    const int t2m = d.t2 ? d.t2_mode : 0;
-    if (d.pred_nm == 1) return launch_step_one<DIST, MODE, POW2, 1>(d, t2m, lc, st);
-    if (d.pred_nm == 2) return launch_step_one<DIST, MODE, POW2, 2>(d, t2m, lc, st);
+  if (one_pass) {  // prediction tiles of pred_nm kept modes
+    auto tiles = [&](auto NM) {
+      return with_nt_t2<DIST>(d.nt, t2m, [&](auto NT, auto T2) {
+        return launch_step_kernel(k_step_one<DIST, MODE, POW2, NT, T2, NM>, d, lc, st);
+      });
+    };
+    if (d.pred_nm == 1) return tiles(std::integral_constant<int, 1>{});
+    if (d.pred_nm == 2) return tiles(std::integral_constant<int, 2>{});
     if constexpr (PRED_MAX_MODES >= 3)
-      if (d.pred_nm == 3) return launch_step_one<DIST, MODE, POW2, 3>(d, t2m, lc, st);
+      if (d.pred_nm == 3) return tiles(std::integral_constant<int, 3>{});
     return hipErrorInvalidValue;  // PRED_MAX_MODES
   }
   if (full && d.dist_out) {  // with the diagnostics of output_all (their histograms as fixed-point sums where the host knows bounds)
@@ -1270,38 +1213,37 @@ hipError_t launch_step_dmp(const StepArgsDev &d, bool full, const LaunchCfg &lc,
 }
 
 template <int DIST>
-hipError_t launch_step_d(const StepArgsDev &d, int deltaf, int linear, bool full, const LaunchCfg &lc,
-                         hipStream_t st) {
+hipError_t launch_step_d(const StepArgs &a, bool full, const LaunchCfg &lc, hipStream_t st) {
+  const StepArgsDev &d = a.d;
   const bool pow2 = d.s.pow2 != 0;
   // full-f evaluates no f0 derivative (one instantiation serves all DIST), but
   // still divides by the mass in the v push
-  if (!deltaf) {
+  if (!a.deltaf) {
     if constexpr (DIST == 0)
-      return pow2 ? launch_step_dmp<0, MODE_FULLF, 1>(d, full, lc, st)
-                  : launch_step_dmp<0, MODE_FULLF, 0>(d, full, lc, st);
+      return pow2 ? launch_step_dmp<0, MODE_FULLF, 1>(a, full, lc, st)
+                  : launch_step_dmp<0, MODE_FULLF, 0>(a, full, lc, st);
     return hipErrorInvalidValue;  // step_dispatch.cpp sends every full-f species to the DIST 0 unit
   }
   // general divisor constants and an exp-bearing distribution: -f0'/f0 carried between the kernels
   const bool carry = !pow2 && d.t2 != nullptr && (DIST == 2 || DIST == 3);
-  if (linear) {
+  if (a.linear) {
     if constexpr (DIST == 2 || DIST == 3)
-      if (carry) return launch_step_dmp<DIST, MODE_DF_LIN, 0, true>(d, full, lc, st);
-    return pow2 ? launch_step_dmp<DIST, MODE_DF_LIN, 1>(d, full, lc, st)
-                : launch_step_dmp<DIST, MODE_DF_LIN, 0>(d, full, lc, st);
+      if (carry) return launch_step_dmp<DIST, MODE_DF_LIN, 0, true>(a, full, lc, st);
+    return pow2 ? launch_step_dmp<DIST, MODE_DF_LIN, 1>(a, full, lc, st)
+                : launch_step_dmp<DIST, MODE_DF_LIN, 0>(a, full, lc, st);
   }
-  if (d.s.unit) return launch_step_dmp<DIST, MODE_DF_NL, 2>(d, full, lc, st);
+  if (d.s.unit) return launch_step_dmp<DIST, MODE_DF_NL, 2>(a, full, lc, st);
   if constexpr (DIST == 2 || DIST == 3)
-    if (carry) return launch_step_dmp<DIST, MODE_DF_NL, 0, true>(d, full, lc, st);
-  return pow2 ? launch_step_dmp<DIST, MODE_DF_NL, 1>(d, full, lc, st)
-              : launch_step_dmp<DIST, MODE_DF_NL, 0>(d, full, lc, st);
+    if (carry) return launch_step_dmp<DIST, MODE_DF_NL, 0, true>(a, full, lc, st);
+  return pow2 ? launch_step_dmp<DIST, MODE_DF_NL, 1>(a, full, lc, st)
+              : launch_step_dmp<DIST, MODE_DF_NL, 0>(a, full, lc, st);
 }
 
 }  // namespace
 
 template <>
-hipError_t launch_step_dist<PIC1DP_STEP_DIST>(const StepArgsDev &d, int deltaf, int linear, bool full, const LaunchCfg &lc,
-                                              hipStream_t st) {
-  return launch_step_d<PIC1DP_STEP_DIST>(d, deltaf, linear, full, lc, st);
+hipError_t launch_step_dist<PIC1DP_STEP_DIST>(const StepArgs &a, bool full, const LaunchCfg &lc, hipStream_t st) {
+  return launch_step_d<PIC1DP_STEP_DIST>(a, full, lc, st);
 }
 
 }  // namespace pic1dp
