@@ -322,6 +322,21 @@ int pic1dp_hip_set_output_fusion(pic1dp_ctx *ctx, int32_t on);
  *     (3 <= nx <= 4096).  field_mode_re/im still hold the kept modes of the
  *     mode-filter solve. */
 int pic1dp_hip_set_field_solver(pic1dp_ctx *ctx, int32_t kind);
+/* how the mode-filter solve (solve_field, substep, step; also the kept modes that field solver 1 still reports)
+ * computes the DFT of field_chargeden -- opt-in, per context:
+ *   0 (default) the direct partial DFT against dense cos / -sin tables: the reference's rounding and, with a
+ *     layout of npe ranks, its npe-rank summation order
+ *   1 an FFT: for each kept mode m, bin b = m mod nx of a mixed-radix (2, 3, 4, 5) FFT gives R + i I, and
+ *     mode_re = I / nx * grad_inv, mode_im = -R / nx * grad_inv as in transform 0; E = 2 sum_m (mode_re cos -
+ *     mode_im sin)(2 pi m ix / nx) by the inverse FFT of the Hermitian spectrum.  Twiddles from exactly reduced
+ *     angles.  Independent of npe.  Relative error against the exact sums ~1e-15.  Transform 1 runs none of the
+ *     one-pass (predicted) or fused paths: step mode 0 takes two passes per step -- it is meant for many kept modes.
+ * Supported nx for transform 1: nx = 2^a 3^b 5^c with 2 <= nx <= 8192, odd nx only up to 3375.  Any other transform,
+ * or an unsupported nx, returns PIC1DP_ERR_ARG.  Switching while the half-step field of a call-site pair waits to be
+ * adopted deposits the half-step charge for real instead (as set_field_solver). */
+int pic1dp_hip_set_field_transform(pic1dp_ctx *ctx, int32_t transform);
+/* *supported = 1 if the given transform handles nx, else 0 (host only, no device, no context) */
+int pic1dp_hip_field_transform_supported(int32_t nx, int32_t transform, int32_t *supported);
 /* field_electric as it was between the two sub-steps of the last time step
  * taken by pic1dp_hip_step ([nx]) */
 int pic1dp_hip_get_field_half(pic1dp_ctx *ctx, double *electric_half);

@@ -102,6 +102,8 @@ SIGNATURES = {
     "pic1dp_hip_predict_kind": [_P, C.POINTER(C.c_int32)],
     "pic1dp_hip_get_field_half": [_P, _P],
     "pic1dp_hip_set_field_solver": [_P, C.c_int32],
+    "pic1dp_hip_set_field_transform": [_P, C.c_int32],
+    "pic1dp_hip_field_transform_supported": [C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
     "pic1dp_hip_sync": [_P],
     "pic1dp_hip_get_time": [_P, C.POINTER(C.c_int32), _D],
     "pic1dp_hip_set_time": [_P, C.c_int32, C.c_double],

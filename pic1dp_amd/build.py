@@ -26,7 +26,7 @@ PROBE_LIB = os.path.join(LIBDIR, "libpic1dp_probe.so")
 STEP_DISTS = (0, 1, 2, 3, 4, 5)
 # (source, extra flags, object stem)
 PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_step_d%d" % d) for d in STEP_DISTS] + [
-    ("kernels_push.hip", [], "kernels_push"), ("kernels_field.hip", [], "kernels_field"),
+    ("kernels_push.hip", [], "kernels_push"), ("kernels_field.hip", [], "kernels_field"), ("kernels_fft.hip", [], "kernels_fft"),
     ("kernels_diag.hip", [], "kernels_diag"), ("kernels_opt.hip", [], "kernels_opt"), ("step_dispatch.cpp", [], "step_dispatch"),
     ("capi.cpp", [], "capi"), ("capi_step.cpp", [], "capi_step"), ("capi_comm.cpp", [], "capi_comm"), ("capi_diag.cpp", [], "capi_diag"),
     ("capi_optimize.cpp", [], "capi_optimize"), ("loader.cpp", [], "loader"), ("multirand.cpp", [], "multirand"),

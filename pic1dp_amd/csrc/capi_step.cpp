@@ -121,6 +121,12 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred);
 static bool pred_usable(const pic1dp_ctx *c);
 static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer);
 
+// The fused and predicted paths -- the pair solves, the solve in a marker launch's prologue (kernels.hpp FusedSolve), the
+// prediction tiles and sums, Eh from its kept modes, the tail, the exchange inside the solve's launch -- reproduce the
+// dense-table solve of the mode-filter solver, and only that: not the finite differences (field_solver 1), not the FFT
+// (field_transform 1), under which every solve goes through enqueue_field_solve.
+static bool dft_paths(const pic1dp_ctx *c) { return c->field_solver == 0 && c->field_transform == 0; }
+
 // ---------------------------------------------------------------------------
 // hot path
 // (the entry points are declared extern "C" in include/pic1dp_hip.h; their definitions here inherit that linkage)
@@ -265,7 +271,7 @@ static int deposit_or_step(pic1dp_ctx *c) {
       return set_seq(c, Seq::Clean);
     }
     // Eh = d_E: the kept modes describe it when the mode-filter solve wrote it last
-    c->eh_modes = (c->field_solver == 0 && c->modes_field_version == c->field_version) ? 1 : 0;
+    c->eh_modes = (dft_paths(c) && c->modes_field_version == c->field_version) ? 1 : 0;
     if (int rc = step_particles(c, true, c->d_E0, c->d_E, diag, !diag)) return rc;
     return set_seq(c, Seq::Clean);
   }
@@ -325,12 +331,15 @@ void pic1dp_host::field_written(pic1dp_ctx *c, bool by_solve) {
   if (by_solve && c->field_solver == 0) c->modes_field_version = c->field_version;
 }
 
-// field_solve_electric: the reference's mode-filter solve, optionally followed by
-// the finite-difference alternative overwriting E (field_solver = 1)
+// field_solve_electric: the reference's mode-filter solve (its DFT by the dense tables, or by the FFT under
+// field_transform 1), optionally followed by the finite-difference alternative overwriting E (field_solver = 1)
 static int enqueue_field_solve(pic1dp_ctx *c, FieldArgs f, bool with_local, bool from_chargeden) {
   double *hist = f.history;
   if (c->field_solver == 1) f.history = nullptr;
-  HIP_TRY(launch_field_solve(f, with_local, from_chargeden, c->st));
+  if (c->field_transform == 1)
+    HIP_TRY(launch_field_fft(f, c->fft, with_local, from_chargeden, c->st));
+  else
+    HIP_TRY(launch_field_solve(f, with_local, from_chargeden, c->st));
   if (c->field_solver == 1)
     HIP_TRY(launch_field_fd(f.chargeden, f.E, hist, f.nx, f.lx, f.dnx, c->st));
   return 0;
@@ -347,6 +356,30 @@ int pic1dp_hip_set_field_solver(pic1dp_ctx *c, int32_t kind) {
     if (int rc = set_owed(c, Owed::Nothing)) return rc;
   }
   c->field_solver = kind;
+  return 0;
+}
+
+int pic1dp_hip_field_transform_supported(int32_t nx, int32_t transform, int32_t *supported) {
+  if (!supported) return fail(PIC1DP_ERR_ARG, "null argument");
+  if (transform != 0 && transform != 1) return fail(PIC1DP_ERR_ARG, "field transform must be 0 (direct partial DFT) or 1 (FFT)");
+  *supported = transform == 0 ? (nx >= 2 && nx <= 8192) : fft_supported(nx);
+  return 0;
+}
+
+int pic1dp_hip_set_field_transform(pic1dp_ctx *c, int32_t transform) {
+  CHECK_CTX(c);
+  if (transform != 0 && transform != 1) return fail(PIC1DP_ERR_ARG, "field transform must be 0 (direct partial DFT) or 1 (FFT)");
+  if (transform == 1 && !fft_supported(c->in.nx))
+    return fail(PIC1DP_ERR_ARG, "the FFT field transform needs nx = 2^a 3^b 5^c, even up to %d or odd up to %d (nx = %d)", FFT_MAX_NX,
+                FFT_MAX_ODD_NX, c->in.nx);
+  HIP_TRY(hipSetDevice(c->device));
+  if (transform == 1 && !c->fft.tw)
+    HIP_TRY(fft_plan_upload(c->in.nx, c->in.modes, c->in.nmode, c->fft, &c->d_fft_tw, &c->d_fft_idx));
+  if (c->owed == Owed::AdoptHalfField && transform != c->field_transform) {  // a half-step field of the OTHER transform waits
+    if (int rc = rebuild_half_step_chargeden(c)) return rc;                // to be adopted: the half-step charge is deposited
+    if (int rc = set_owed(c, Owed::Nothing)) return rc;                    // for real instead
+  }
+  c->field_transform = transform;
   return 0;
 }
 
@@ -370,7 +403,7 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   // One rank, behind the collect_charge of push(2) whose kernel has predicted the next half-step charge: BOTH fields in
   // one launch, as pic1dp_hip_step solves them -- the next step's push(1), collect_charge, solve_field then launch nothing
   // and a time step through the three call sites is two launches (round 5; three and a copy before)
-  if (pending == Owed::SumScale && c->call_pair && c->lazy_calls && c->field_solver == 0 && c->seq == Seq::Clean && pred_usable(c) &&
+  if (pending == Owed::SumScale && c->call_pair && c->lazy_calls && dft_paths(c) && c->seq == Seq::Clean && pred_usable(c) &&
       c->pred_kind == 2 && c->in.nmode == 1) {
     PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->pred_kind, c->pred_tab, 0};
     HIP_TRY(launch_field_solve_pair(f, pa, nullptr, c->st));
@@ -382,9 +415,9 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   }
   if (pending == Owed::AdoptHalfField) {  // (the fast path above was left by an inspection in between: the field is adopted by copying)
     if (int rc = adopt_half_field(c)) return rc;
-  } else if (pending == Owed::PredTiles && c->field_solver == 0) {
+  } else if (pending == Owed::PredTiles && dft_paths(c)) {
     HIP_TRY(launch_field_solve_pred(f, c->d_pred, c->in.nmode, c->st));
-  } else if (pending == Owed::PredSums && c->field_solver == 0) {
+  } else if (pending == Owed::PredSums && dft_paths(c)) {
     HIP_TRY(launch_field_solve_pred_sums(f, c->pred_tab, c->d_pred, c->st));
   } else {
     if (pending == Owed::PredSums) HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, c->d_pred, nullptr, c->st));
@@ -419,7 +452,7 @@ static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
   if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
     if (int rc = fx_settle(c)) return rc;
   const bool multi = c->charge_sum == 0 && (c->lay.nranks > 1 || c->comm != nullptr);
-  const bool fused_xchg = multi && xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
+  const bool fused_xchg = multi && xchg_active(c) && dft_paths(c);  // exchange inside the solve's launch
   if (multi && !fused_xchg)
     if (int rc = reduce_charge(c)) return rc;
   Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
@@ -523,7 +556,7 @@ static bool diag_in_step(const pic1dp_ctx *c) {
 // describe E), few kept modes, and LDS for E0, Eh, the mode tables and the four accumulators
 // (kind 1 of the charge sum: no prediction -- two passes per step)
 static bool predict_capable(const pic1dp_ctx *c) {
-  return c->charge_sum == 0 && c->predict && c->pred_kind != 0 && c->d_pred && c->field_solver == 0 && step_recompute_ok(c);
+  return c->charge_sum == 0 && c->predict && c->pred_kind != 0 && c->d_pred && dft_paths(c) && step_recompute_ok(c);
 }
 static size_t pred_doubles(const pic1dp_ctx *c) {
   return c->pred_kind == 2 ? 8 * PRED_SUM_COPIES : static_cast<size_t>(c->in.nspecies) * (1 + 2 * c->in.nmode) * c->in.nx;
@@ -547,7 +580,7 @@ static void use_accumulators(pic1dp_ctx *c, int idx) {
 // gap and the field launch's start-up, 1-2 us of a step (the solve itself is a chain of dependent round trips either way).
 static bool fuse_capable(const pic1dp_ctx *c) {
   const bool multi = c->lay.nranks > 1 || c->comm != nullptr;
-  if (!(c->fuse_solve && !multi && c->pred_kind == 2 && c->in.nmode == 1 && c->field_solver == 0 && c->fa.npe <= 32 &&
+  if (!(c->fuse_solve && !multi && c->pred_kind == 2 && c->in.nmode == 1 && dft_paths(c) && c->fa.npe <= 32 &&
         predict_capable(c)))
     return false;
   // ... and serial forward sums that are short enough.  The solve costs inside a marker launch what it costs in its own: a
@@ -629,7 +662,7 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
   // several ranks, the six sums of one kept mode, the mode-filter solver: the packing of this rank's charge for the sum
   // over ranks rides in the tail of the last marker launch (RCCL: one all-reduce follows; exchange: posted at once)
   int tail_mode = 0, tail_species = -1;
-  if (tail_ok && pred && c->tail_on && c->pred_kind == 2 && c->in.nmode == 1 && c->field_solver == 0 &&
+  if (tail_ok && pred && c->tail_on && c->pred_kind == 2 && c->in.nmode == 1 && dft_paths(c) &&
       (c->lay.nranks > 1 || c->comm != nullptr)) {
     tail_mode = xchg_active(c) ? 2 : (c->comm != nullptr ? 1 : 0);
     for (int s = 0; s < c->in.nspecies; ++s)
@@ -820,8 +853,8 @@ static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = fal
   const bool multi = c->lay.nranks > 1 || c->comm != nullptr;
   if (c->pred_kind == 2) {
     if (f.chargeden == c->d_chargeden) c->cd_kept_mode_only = true;
-    if (defer && !multi && c->field_solver == 0 && f.tab_lds)  // the sums' combination, chargeden and the solve in the
-      return set_owed(c, Owed::PredSums);                       // launch of the solve_field that follows
+    if (defer && !multi && dft_paths(c) && f.tab_lds)  // the sums' combination, chargeden and the solve in the
+      return set_owed(c, Owed::PredSums);               // launch of the solve_field that follows
     if (!multi) {
       HIP_TRY(launch_pred_chargeden(f, c->pred_tab, c->d_pred, nullptr, c->st));
       return 0;
@@ -831,7 +864,7 @@ static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = fal
     HIP_TRY(launch_pred_chargeden(f, c->pred_tab, nullptr, c->d_charge, c->st));
     return 0;
   }
-  if (defer && !multi && c->field_solver == 0 && 2 * c->in.nmode <= 256)
+  if (defer && !multi && dft_paths(c) && 2 * c->in.nmode <= 256)
     return set_owed(c, Owed::PredTiles);  // all of it in the launch of the solve_field that follows
   HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
   if (multi)
@@ -905,10 +938,10 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
   if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
     if (int rc = fx_settle(c)) return rc;
   const bool multi = c->charge_sum == 0 && (c->lay.nranks > 1 || c->comm != nullptr);
-  const bool fused_xchg = multi && xchg_active(c) && c->field_solver == 0;  // exchange inside the solve's launch
+  const bool fused_xchg = multi && xchg_active(c) && dft_paths(c);  // exchange inside the solve's launch
   // RCCL path of a one-pass step: everything the two charge sums of the step need in one all-reduce
   const bool will_pack = pred && c->pred_version == c->state_version && multi && !fused_xchg && c->comm != nullptr &&
-                         !xchg_active(c) && c->field_solver == 0 && 2 * c->in.nmode <= 256 && Eout == c->d_E;
+                         !xchg_active(c) && dft_paths(c) && 2 * c->in.nmode <= 256 && Eout == c->d_E;
   const int tail_done = c->tail_done;  // what the marker launch's tail has done already (kernels.hpp StepTail)
   c->tail_done = 0;
   if (tail_done == 1 && !will_pack) return fail(PIC1DP_ERR_STATE, "internal: a packed charge nobody reduces");
@@ -942,7 +975,7 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
     c->fused_dirty = -1;
   }
   const bool pair = pred && c->pred_version == c->state_version && (!multi || fused_xchg || will_pack) &&
-                    c->field_solver == 0 && 2 * c->in.nmode <= 256 && Eout == c->d_E;
+                    dft_paths(c) && 2 * c->in.nmode <= 256 && Eout == c->d_E;
   if (pair) {
     // (cd_h: the tiles' scratch; with the six sums the kept mode's content of the half-step charge density -- what the call
     // sites adopt into field_chargeden when the host's next push(1), collect_charge, solve_field are served from this solve,
@@ -1007,7 +1040,7 @@ int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
         } else if (int rc = step_phase(c, false, c->d_Eh, false)) {
           return rc;
         } else {
-          c->eh_modes = c->field_solver == 0 ? 1 : 0;  // that solve left them in fa.mode_re / mode_im
+          c->eh_modes = dft_paths(c) ? 1 : 0;  // that solve left them in fa.mode_re / mode_im
         }
       }
       // may the NEXT step's launch take this step's solve?  Only if that step will be an ordinary predicted one (the

@@ -222,6 +222,13 @@ struct pic1dp_ctx {
                            // (PIC1DP_CARRY=0), 1 wherever -f0'/f0 bears an exp, 2 also two-stream2 between k_step_half / _full
   int step_mode = 0;       // 0 auto (recompute path when the LDS allows), 1 two fused sub-steps
   int field_solver = 0;    // 0 the reference's mode-filter DFT solve, 1 finite-difference tridiagonal (opt-in)
+  // how the mode-filter solve computes its DFT (pic1dp_hip_set_field_transform; kernels_fft.hip): 0 the dense tables, the
+  // reference's sums; 1 the FFT (plan built at the first switch).  Transform 1 runs none of the fused or predicted paths
+  // (capi_step.cpp dft_paths).
+  int field_transform = 0;
+  FftArgs fft{};
+  double *d_fft_tw = nullptr;
+  int *d_fft_idx = nullptr;
   // marker state (bytes) above which k_step_half / k_step_full stream non-temporally
   // The two kernels leave the caches to each other, so the pairs were compared inside
   // one process on the same arrays (tools/ab_nt.py, nx = 1024, half + full in ms):

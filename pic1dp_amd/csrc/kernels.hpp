@@ -455,6 +455,26 @@ hipError_t launch_chargeden(const FieldArgs &f, bool with_local, hipStream_t st)
 // launch_charge_local's work first in the same kernel (single-rank path)
 hipError_t launch_field_solve(const FieldArgs &f, bool with_local, bool from_chargeden,
                               hipStream_t st);
+// Transform 1 of the mode-filter solve (pic1dp_hip_set_field_transform; kernels_fft.hip): the DFT of
+// chargeden by a one-workgroup mixed-radix FFT in LDS instead of the dense tables.  Supported: nx = 2^a 3^b 5^c,
+// 2 <= nx <= FFT_MAX_NX, odd nx up to FFT_MAX_ODD_NX (two complex buffers of nx points in LDS).
+constexpr int FFT_MAX_NX = 8192, FFT_MAX_ODD_NX = 3375, FFT_MAX_PASSES = 16;
+struct FftArgs {
+  const double2 *tw;       // [nx] w_nx^k = e^{-2 pi i k / nx}, the angle reduced exactly on the host
+  const int *bin_start;    // [nx + 1] the kept modes of bin b (= m mod nx) are bin_mode[bin_start[b] .. bin_start[b + 1])
+  const int *bin_mode;     // [nmode] mode indices by bin, ascending within a bin
+  const int *mode_bin;     // [nmode] the bin of each kept mode
+  int n;                   // complex points transformed: nx / 2 (nx even: real packing) or nx
+  int npass;
+  int radix[FFT_MAX_PASSES];
+};
+bool fft_supported(int nx);
+// the plan of nx for the kept modes `modes`: radices into p, twiddles and the bins into device buffers (allocated when
+// null, synchronous copies)
+hipError_t fft_plan_upload(int nx, const int32_t *modes, int nmode, FftArgs &p, double **d_tw, int **d_idx);
+// launch_field_solve with the FFT: chargeden (unless from_chargeden), then one launch -- forward FFT, the kept modes, the
+// Hermitian spectrum of E, inverse FFT, E (+ field energy)
+hipError_t launch_field_fft(const FieldArgs &f, const FftArgs &p, bool with_local, bool from_chargeden, hipStream_t st);
 // opt-in alternative solve (all modes): finite-difference Poisson equation as a
 // tridiagonal system, parallel cyclic reduction in LDS; chargeden -> E (+ energy)
 hipError_t launch_field_fd(const double *chargeden, double *E, double *history, int nx, double lx,

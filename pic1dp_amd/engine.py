@@ -187,6 +187,11 @@ class Pic1dp:
         tridiagonal solve by parallel cyclic reduction (not in the reference)"""
         check(self.L.pic1dp_hip_set_field_solver(self._ctx, kind))
 
+    def set_field_transform(self, kind):
+        """how the mode-filter solve computes its DFT: 0 the direct partial DFT against dense tables (default, the
+        reference's sums); 1 an FFT (for many kept modes; nx = 2^a 3^b 5^c, see field_transform_supported)"""
+        check(self.L.pic1dp_hip_set_field_transform(self._ctx, int(kind)))
+
     def get_field_half(self):
         """field_electric between the two sub-steps of the last step()"""
         E = np.empty(self.inp.nx)
@@ -492,6 +497,13 @@ def charge_quantum(inp, ispecies=0):
     e = C.c_int32()
     check(_lib.load().pic1dp_hip_charge_quantum(C.byref(inp), int(ispecies), C.byref(e)))
     return e.value
+
+
+def field_transform_supported(nx, transform=1):
+    """does field transform `transform` handle a grid of nx cells?  (host only, no device)"""
+    ok = C.c_int32()
+    check(_lib.load().pic1dp_hip_field_transform_supported(int(nx), int(transform), C.byref(ok)))
+    return bool(ok.value)
 
 
 def device_count():

@@ -219,6 +219,19 @@ interface
     integer(c_int32_t), value :: kind
     integer(c_int) :: ierr
   end function pic1dp_hip_set_field_solver
+  function pic1dp_hip_set_field_transform(ctx, transform) bind(C, name="pic1dp_hip_set_field_transform") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: transform
+    integer(c_int) :: ierr
+  end function pic1dp_hip_set_field_transform
+  function pic1dp_hip_field_transform_supported(nx, transform, supported) &
+      bind(C, name="pic1dp_hip_field_transform_supported") result(ierr)
+    import
+    integer(c_int32_t), value :: nx, transform
+    integer(c_int32_t), intent(out) :: supported
+    integer(c_int) :: ierr
+  end function pic1dp_hip_field_transform_supported
   function pic1dp_hip_get_field_half(ctx, electric_half) bind(C, name="pic1dp_hip_get_field_half") result(ierr)
     import
     type(c_ptr), value :: ctx

@@ -59,6 +59,10 @@ call pic1dp_hip_check(pic1dp_hip_create(inp, lay, ctx), 'create')      ! particl
 ! chargeden, E and field energies do not depend on the order of the deposit's additions (the reference sums in FP64)
 call get_environment_variable('PIC1DP_CHARGE_SUM', buf, status=stat)
 if (stat == 0 .and. buf(1:5) == 'exact') call pic1dp_hip_check(pic1dp_hip_set_charge_sum(ctx, 1_c_int32_t), 'set_charge_sum')
+! PIC1DP_FIELD_TRANSFORM=fft (an option of this host program): the mode-filter solve's DFT by an FFT (transform 1 of
+! include/pic1dp_hip.h) -- for many kept modes; the default is the reference's direct partial DFT
+call get_environment_variable('PIC1DP_FIELD_TRANSFORM', buf, status=stat)
+if (stat == 0 .and. buf(1:3) == 'fft') call pic1dp_hip_check(pic1dp_hip_set_field_transform(ctx, 1_c_int32_t), 'set_field_transform')
 call get_environment_variable('PIC1DP_ALLREDUCE', buf, status=stat)
 use_rccl = (stat == 0 .and. buf(1:4) == 'rccl')
 if (use_rccl) then
