@@ -50,6 +50,12 @@ int pic1dp_probe_host_optimize(int32_t kind, int32_t typeremove, int32_t nx, int
 /* y[i] = exp(x[i]) as the marker kernels evaluate it (pexp; host arrays) */
 int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n);
 
+/* the prediction tiles' raise of a fixed-point bound (pic1dp_amd/csrc/device_fx.hpp fx_raise), as the end of n workgroups
+ * applies it: one device thread starts from *bound = bound0 and applies the events (noted[i], start[i]) in order -- noted:
+ * the workgroup's code (0 no marker met, 1 none within the bound, 2 + the bits of a float: the largest value met within it),
+ * start: the bound the workgroup started with.  *bound: the final value. */
+int pic1dp_probe_fx_raise(int32_t device, double bound0, const uint32_t *noted, const double *start, int64_t n, double *bound);
+
 /* one species of the input (src/pic1dp_input.F90:43-72) */
 typedef struct pic1dp_probe_species {
   int32_t iptcldist;

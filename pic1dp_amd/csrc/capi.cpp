@@ -704,9 +704,10 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   CHECK_CTX(c);
   HIP_TRY(hipSetDevice(c->device));
   if (int rc = materialize_cd(c)) return rc;  // deposits of the old markers are consumed, not mixed with the new ones
+  if (c->owed == Owed::AdoptHalfField)        // a half-step field waiting to be adopted: field_chargeden becomes the half-step
+    if (int rc = rebuild_half_step_chargeden(c)) return rc;  // charge density the eager collect_charge left (markers still there)
   HIP_TRY(hipStreamSynchronize(c->st));  // kernels of an earlier run may still be writing the arrays
-  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;  // a noted push of markers that are about to be replaced is
-                                                                         // void, and so is a half-step field waiting to be adopted
+  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;  // a noted push of markers that are about to be replaced is void
   c->state_version++;
   const pic1dp_input &in = c->in;
   const int npe = c->lay.npe, ns = in.nspecies;
@@ -808,6 +809,7 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
     double b[2] = {0.0, 0.0};
     fx_bounds_of(c->in, isp, p, w, np, b);
     HIP_TRY(hipMemcpy(S.fxb, b, sizeof b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(S.fxb + 2, 0, 2 * sizeof(double)));   // (the count of terms past the bounds starts over, as in particle_load)
   }
   if (c->nblk == 1) c->blk_np[isp][0] = np;
   c->rng_ready = false;  // the host's loader owns the random stream now
@@ -968,6 +970,7 @@ int pic1dp_hip_set_electric(pic1dp_ctx *c, const double *E) {
   CHECK_CTX(c);
   if (!E) return fail(PIC1DP_ERR_ARG, "null array");
   HIP_TRY(hipSetDevice(c->device));
+  if (int rc = settle_step_start_field(c)) return rc;   // (the kept modes stay the half step's, as after eager calls)
   if (int rc = settle_half_pair(c)) return rc;   // (d_E0 keeps the step-start field a noted push(1) saw)
   if (lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2)
     if (int rc = materialize(c)) return rc;
@@ -987,6 +990,7 @@ int pic1dp_hip_set_chargeden(pic1dp_ctx *c, const double *cd) {
   if (int rc = settle_half_pair(c)) return rc;
   if (c->owed == Owed::AdoptHalfField)
     if (int rc = set_owed(c, Owed::Nothing)) return rc;
+  c->cd_version++;
   HIP_TRY(hipStreamSynchronize(c->st));
   HIP_TRY(hipMemcpy(c->d_chargeden, cd, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
   c->cd_kept_mode_only = false;

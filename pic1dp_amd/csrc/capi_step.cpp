@@ -166,6 +166,7 @@ static int require_loaded_keep_lazy(pic1dp_ctx *c) {
   if (c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_local is waiting for charge_reduced");
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return fail(PIC1DP_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+  if (int rc = settle_step_start_field(c)) return rc;   // (a push or a step reads field_electric)
   return materialize_cd(c);
 }
 
@@ -224,7 +225,21 @@ int pic1dp_host::settle_half_pair(pic1dp_ctx *c) {
 }
 // for readers of the field only: nothing to do until the host has called solve_field for the half step -- until then
 // field_electric is the step-start field, which is what d_E holds
-int pic1dp_host::settle_field_view(pic1dp_ctx *c) { return solved_of(c->seq) ? settle_half_pair(c) : 0; }
+int pic1dp_host::settle_field_view(pic1dp_ctx *c) {
+  if (int rc = settle_step_start_field(c)) return rc;
+  return solved_of(c->seq) ? settle_half_pair(c) : 0;
+}
+// field_electric and its kept modes as the eager calls leave them after push(2), collect_charge of a pair-solved step: the
+// half-step field (the whole-step kernel read the step-start field from field_electric; d_Eh / d_mode_h hold the half step's)
+int pic1dp_host::settle_step_start_field(pic1dp_ctx *c) {
+  if (!c->e_step_start) return 0;
+  c->e_step_start = false;
+  const size_t nx = c->in.nx, nm = c->in.nmode;
+  HIP_TRY(hipMemcpyAsync(c->d_E, c->d_Eh, sizeof(double) * nx, hipMemcpyDeviceToDevice, c->st));
+  HIP_TRY(hipMemcpyAsync(c->fa.mode_re, c->d_mode_h, sizeof(double) * nm, hipMemcpyDeviceToDevice, c->st));
+  HIP_TRY(hipMemcpyAsync(c->fa.mode_im, c->d_mode_h + nm, sizeof(double) * nm, hipMemcpyDeviceToDevice, c->st));
+  return 0;
+}
 // field_electric and its kept modes <- the half-step field the pair solve left in d_Ehn / d_mode_h, and field_chargeden
 // <- the kept mode's content of the half-step charge density it left in d_cd_h (what collect_charge leaves there when it
 // is served from the six sums, Owed::PredSums): a solve_field that solves from field_chargeden again reproduces the half-step
@@ -242,6 +257,10 @@ int pic1dp_host::materialize(pic1dp_ctx *c) {
   if (int rc = settle_half_pair(c)) return rc;
   const int lz = lz_of(c->seq);
   if (lz == LZ_CLEAN) return 0;
+  // a half-step field waits to be adopted: it was solved from the half-step charge density, which leaves with the markers'
+  // half-step state -- that state is deposited for real on its way into memory (what the eager collect_charge left in
+  // field_chargeden), and the solve_field that follows solves from it (a step or substep in between overwrote d_Ehn / d_cd_h)
+  if (c->owed == Owed::AdoptHalfField) return rebuild_half_step_chargeden(c);
   if (int rc = set_seq(c, Seq::Clean)) return rc;
   if (lz == LZ_PUSH1) return enqueue_push(c, 1, false);           // the field has not changed since
   // LZ_HALF / LZ_PUSH2: push(1) saw d_E0; its deposit wrapped x
@@ -268,6 +287,7 @@ static int deposit_or_step(pic1dp_ctx *c) {
       std::swap(c->d_Eh, c->d_Ehn);
       c->eh_modes = 2;  // its kept mode: d_mode_h
       if (int rc = step_particles(c, true, c->d_E, c->d_Eh, diag, !diag)) return rc;
+      c->e_step_start = true;  // (field_electric: still the step-start field -- the solve_field that follows overwrites it)
       return set_seq(c, Seq::Clean);
     }
     // Eh = d_E: the kept modes describe it when the mode-filter solve wrote it last
@@ -282,6 +302,7 @@ static int deposit_or_step(pic1dp_ctx *c) {
 int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   CHECK_CTX(c);
   if (int rc = require_loaded_keep_lazy(c)) return rc;
+  c->cd_version++;
   // a whole-step kernel run for a noted push is booked under "push particle"
   // (step_particles); "collect charge" then covers the reduction and scaling only
   // after a noted push(1) whose charge the previous step's kernel has predicted (k_step_one): no
@@ -294,6 +315,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   if (c->seq == Seq::Push1 && c->call_pair && c->lazy_calls && c->lay.nranks == 1 && c->comm == nullptr && predict_capable(c) &&
       c->pred_kind == 2 && c->in.nmode == 1 && c->eh_version == c->state_version && c->eh_field_version == c->field_version) {
     c->cd_kept_mode_only = true;  // (field_chargeden is not the half step's: asking for it rebuilds, get_field)
+    c->adopt_cd_version = c->cd_version;
     return set_call_state(c, Seq::HalfPair, Owed::AdoptHalfField);  // what the solve_field that follows has to do: adopt the half-step field
   }
   if (c->seq == Seq::Push1 && pred_usable(c)) {
@@ -328,6 +350,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
 // d_E has been written: by the mode-filter solve (the kept modes describe it) or by something else
 void pic1dp_host::field_written(pic1dp_ctx *c, bool by_solve) {
   c->field_version++;
+  c->e_step_start = false;  // (every writer writes the whole of field_electric; set_electric settles the kept modes first)
   if (by_solve && c->field_solver == 0) c->modes_field_version = c->field_version;
 }
 
@@ -398,8 +421,10 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
     if (int rc = materialize(c)) return rc;
   Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
   FieldArgs f = c->fa;
-  const Owed pending = c->owed;  // what collect_charge left to this launch
+  Owed pending = c->owed;  // what collect_charge left to this launch
   if (int rc = set_owed(c, Owed::Nothing)) return rc;
+  if (pending == Owed::AdoptHalfField && c->adopt_cd_version != c->cd_version)  // (made for a charge density since overwritten:
+    pending = Owed::Nothing;                                                     // check_state refuses that state; a safety net)
   // One rank, behind the collect_charge of push(2) whose kernel has predicted the next half-step charge: BOTH fields in
   // one launch, as pic1dp_hip_step solves them -- the next step's push(1), collect_charge, solve_field then launch nothing
   // and a time step through the three call sites is two launches (round 5; three and a copy before)
@@ -440,6 +465,7 @@ int pic1dp_hip_push(pic1dp_ctx *c, int32_t irk) {
 
 static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
   c->cd_kept_mode_only = false;
+  c->cd_version++;
   if (irk == 2 && optimize_due_any(c)) {
     // src/pic1dp.F90:80-88: push, particle_optimize, collect_charge -- the pushed
     // state has to exist in memory for the host-side optimisation
@@ -1016,7 +1042,10 @@ int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
   CHECK_CTX(c);
   if (nsteps < 0) return fail(PIC1DP_ERR_ARG, "nsteps < 0");
   if (int rc = require_loaded(c)) return rc;
-  if (nsteps > 0) c->cd_kept_mode_only = false;  // every step ends with the deposit of the new state
+  if (nsteps > 0) {  // every step ends with the deposit of the new state
+    c->cd_kept_mode_only = false;
+    c->cd_version++;
+  }
   const bool recompute = step_recompute_ok(c);
   for (int it = 0; it < nsteps; ++it) {
     // a step in which a marker optimisation is due goes through the sub-steps
@@ -1102,6 +1131,10 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || (c->pred_kind == 2 && c->in.nmode == 1));
   INVARIANT(!pair_of(c->seq) || (c->call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
   INVARIANT(!c->cd_kept_mode_only || c->pred_kind == 2);
+  // an owed adoption is current: made for the field_chargeden the eager calls hold now (and, by kCallStateLegal, while the
+  // markers still stand at the half step)
+  INVARIANT(c->owed != Owed::AdoptHalfField || c->adopt_cd_version == c->cd_version);
+  INVARIANT(!c->e_step_start || (c->seq == Seq::Clean && c->eh_modes == 2));   // (the half-step field: d_Eh / d_mode_h)
   // whole-step path: nothing of a step() is left over between calls
   INVARIANT(!c->fused_pending);
   INVARIANT(c->fuse_args.on == 0);
@@ -1192,6 +1225,10 @@ int pic1dp_host::rebuild_half_step_chargeden(pic1dp_ctx *c) {
   if (c->lay.nranks > 1 || c->comm != nullptr) return 0;
   if (lz_of(c->seq) != LZ_HALF && lz_of(c->seq) != LZ_PUSH2) return 0;
   if (int rc = settle_half_pair(c)) return rc;
+  // the vector becomes the whole half-step charge density, and a solve from it is what the eager solve_field does: a half-step
+  // field owed for adoption is dropped (its copy of the kept mode's content would overwrite the whole vector, flag "full")
+  if (c->owed == Owed::AdoptHalfField)
+    if (int rc = set_owed(c, Owed::Nothing)) return rc;
   const bool push2_was_noted = lz_of(c->seq) == LZ_PUSH2;
   if (int rc = enqueue_push(c, 1, false, c->d_E0)) return rc;
   if (int rc = set_seq(c, Seq::Clean)) return rc;  // memory now holds the half-step state (x not yet wrapped): the deposit wraps and stores it
@@ -1248,6 +1285,7 @@ int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpy(c->d_charge, charge1, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
   c->charge_pending = false;
+  c->cd_version++;
   if (c->charge_pending_pred) {  // what came back are the summed prediction sums
     c->charge_pending_pred = false;
     c->cd_kept_mode_only = true;
@@ -1286,6 +1324,7 @@ int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *c, const int64_t *limbs) {
   const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
   HIP_TRY(hipMemcpy(c->d_fx, limbs, sizeof(int64_t) * n, hipMemcpyHostToDevice));
   c->charge_pending = false;
+  c->cd_version++;
   HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st));
   if (c->lazy_calls) return set_owed(c, Owed::SumScale);
   HIP_TRY(launch_chargeden(c->fa, true, c->st));

@@ -97,12 +97,15 @@ constexpr Seq push2_noted(Seq s) { return s == Seq::HalfPair ? Seq::Push2Pair : 
 // charge settles it first, materialize_cd).  PredTiles / PredSums: behind the collect_charge of a noted push(1) -- and
 // still owed after a look at the MARKERS has put the half-step state into memory (particles_download materialises the
 // markers, not the charge: Clean with a prediction owed; the fuzz campaign of round 6 found that one, 5 seeds in 4 500).
-// AdoptHalfField is set with HalfPair and outlives it when an inspection settles the pair before solve_field came (the
-// field is then adopted by copying); it ends with the solve_field of the half step, hence never with a Solved state.
+// AdoptHalfField is set with HalfPair and outlives it when a look at the field settles the pair before solve_field came
+// (the field is then adopted by copying); it ends with the solve_field of the half step, hence never with a Solved state.
+// It is made for the half-step charge density, so it never outlives the half step: whatever puts the markers into memory
+// while it is owed deposits that charge density for real instead (materialize -> rebuild_half_step_chargeden) -- never
+// Clean or Push1 -- and whatever writes field_chargeden drops it (cd_version, pic1dp_hip_check_state).
 constexpr bool kCallStateLegal[static_cast<int>(Seq::N)][static_cast<int>(Owed::N)] = {
     //                   Nothing Scale  SumScale PredTiles PredSums Adopt
-    /* Clean           */ {true, true,  true,    true,     true,    true},
-    /* Push1           */ {true, false, false,   false,    false,   true},
+    /* Clean           */ {true, true,  true,    true,     true,    false},
+    /* Push1           */ {true, false, false,   false,    false,   false},
     /* Half            */ {true, true,  true,    true,     true,    true},
     /* HalfPair        */ {false, false, false,  false,    false,   true},
     /* HalfPairSolved  */ {true, false, false,   false,    false,   false},
@@ -215,7 +218,16 @@ struct pic1dp_ctx {
   // holds there.  get_field rebuilds the full vector on one rank (rebuild_half_step_chargeden); cleared by
   // everything that writes field_chargeden.
   bool cd_kept_mode_only = false;
+  // field_chargeden as the eager calls leave it changes with every collect_charge, charge_reduced, set_chargeden, substep and
+  // step: cd_version counts those calls, adopt_cd_version is its value when the collect_charge set AdoptHalfField -- the
+  // adoption stands for a solve from THAT charge density and only holds while the two agree
+  uint64_t cd_version = 1, adopt_cd_version = 0;
   Seq seq = Seq::Clean;          // written by set_call_state only (capi_step.cpp)
+  // The collect_charge of a push(2) noted after a pair-solved half step (Push2PairSolved) runs the whole step with
+  // E0 = field_electric and leaves field_electric holding the STEP-START field, the kept modes too: the solve_field that
+  // follows overwrites both.  Everything that reads them before it first copies the half-step field (d_Eh / d_mode_h) in
+  // -- what the eager calls hold there (settle_step_start_field).
+  bool e_step_start = false;
   double *d_E0 = nullptr;        // field the noted push(1) saw
   double *d_rho_dummy = nullptr; // accumulator of a wrap-only deposit
   int carry = -1;          // whole-step kernels carry -f0'/f0 between them: -1 where measured to pay, 0 never
@@ -418,6 +430,7 @@ int set_seq(pic1dp_ctx *c, Seq seq);
 int set_owed(pic1dp_ctx *c, Owed owed);
 int settle_half_pair(pic1dp_ctx *c);      // call sites: the half-step field the pair solve left aside becomes field_electric (ctx.hpp half_pair)
 int settle_field_view(pic1dp_ctx *c);     // ... for readers of the field only
+int settle_step_start_field(pic1dp_ctx *c);  // field_electric <- the half-step field the second collect_charge left aside (e_step_start)
 int adopt_half_field(pic1dp_ctx *c);
 void optimize_release(pic1dp_ctx *c);     // the optimisation events' workers (streams, pinned and device staging), for destroy
 // ---- capi_optimize.cpp ----

@@ -12,6 +12,7 @@
 // in parallel; step_dispatch.cpp picks the instance.
 #include "device_diag.hpp"
 #include "device_field.hpp"
+#include "device_fx.hpp"
 #include "device_math.hpp"
 #include "device_xchg.hpp"
 #include "step_args.hpp"
@@ -317,7 +318,10 @@ __device__ __forceinline__ double pred_coef(double v, double w, double p, double
 //     THE MARKERS THAT WENT THE FIXED-POINT WAY: the population's growth moves them, an outlier never does (one marker of
 //     two-stream1 at v = 1e-9 would otherwise coarsen everybody's quantum by nine orders of magnitude, for good).  A
 //     workgroup that finds NOT ONE of its markers within a bound -- the whole population has jumped: a field set by the host
-//     -- raises that bound 256-fold per launch until the markers fit again;
+//     -- raises that bound to 256x what it was when THE WORKGROUP started, per launch until the markers fit again (not 256x
+//     the bound at its end: in an oversubscribed grid the raises of the workgroups that finished first would compound,
+//     256^k in one launch); every raise stays below 16x the smallest |value| that asked for it, so the bound stays below
+//     16x the largest value met (device_fx.hpp);
 //   * a term within 16x its bound (to be precise: below the cap the power-of-two scale leaves) is rounded ONCE to a power-of-two quantum chosen such that a workgroup's sums stay below
 //     2^61 (about 2^-41 of the bound at 2e5 markers per workgroup: 1e-13 of a cell's sum), the sums themselves are exact and
 //     independent of the atomics' order;
@@ -358,16 +362,7 @@ __device__ __forceinline__ void fx_note(unsigned *slot, float seen_f) {
     __hip_atomic_fetch_max(slot, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 }
-__device__ __forceinline__ void fx_raise(double *bound, unsigned noted) {
-  if (noted == 0u) return;
-  const double cur = __hip_atomic_load(bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  double want = 0.0;
-  if (noted >= 2u) want = static_cast<double>(__uint_as_float(noted - 2u)) * (1.0 + 0x1p-18);   // (rounded twice on the way: not below what was met)
-  else if (cur > 0.0) want = 256.0 * cur;                                                        // markers, and none of them within the bound
-  if (want > cur && want < 0x1p120)
-    __hip_atomic_fetch_max(reinterpret_cast<unsigned long long *>(bound), static_cast<unsigned long long>(__double_as_longlong(want)),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// (fx_raise, the bound's raise at the end of a workgroup: device_fx.hpp)
 
 template <int DIST, int MODE, int POW2, int NM>
 __device__ __forceinline__ double pred_one(const One &n, double p, int ix, double wl, const double *sAB, double *sP,
@@ -723,6 +718,7 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
   unsigned *sDraw = reinterpret_cast<unsigned *>(PRIV ? sP + NS * PT : sP + np1 * (nx + 2));  // the chunk counter of the drawn tail
   FxTiles fx{};
   fx.mx0 = fx.mx1 = -2.0f;
+  double fxb_start0 = 0.0, fxb_start1 = 0.0;   // the bounds this workgroup's tiles are summed against (fx_raise; wave-uniform)
   if constexpr (PRIV) {
     for (int k = 0; k < NS; ++k) sP[k * PT + threadIdx.x] = 0.0;
   } else {
@@ -735,8 +731,10 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
       sP[1] = __hip_atomic_load(a.fxb + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    fx.s0 = wave_uniform(fx_scale(16.0 * sP[0], a.fx_markers));
-    fx.s1 = wave_uniform(fx_scale(32.0 * sP[1], a.fx_markers));   // |A|, |B| <= 2 (tables 2 cos, -2 sin)
+    fxb_start0 = wave_uniform(sP[0]);
+    fxb_start1 = wave_uniform(sP[1]);
+    fx.s0 = wave_uniform(fx_scale(16.0 * fxb_start0, a.fx_markers));
+    fx.s1 = wave_uniform(fx_scale(32.0 * fxb_start1, a.fx_markers));   // |A|, |B| <= 2 (tables 2 cos, -2 sin)
     __syncthreads();
     for (int i = threadIdx.x; i < np1 * (nx + 2); i += blockDim.x) sP[i] = 0.0;
   }
@@ -869,8 +867,8 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
     }
   }
   if (threadIdx.x == 0) {   // the bounds follow the population (rarely an atomic: they only ever grow)
-    fx_raise(a.fxb, sDraw[1]);
-    fx_raise(a.fxb + 1, sDraw[2]);
+    fx_raise(a.fxb, sDraw[1], fxb_start0);
+    fx_raise(a.fxb + 1, sDraw[2], fxb_start1);
   }
   STAMP(a, 5);
 }

@@ -12,6 +12,7 @@
 
 #include "../../include/pic1dp_probe.h"
 #include "check_values.hpp"
+#include "device_fx.hpp"
 #include "device_math.hpp"
 
 namespace pic1dp {
@@ -198,6 +199,12 @@ __global__ void k_divc_check(double c, double rc, uint64_t seed, int64_t n, unsi
     const double q = div_const(a, c, rc, 1), b = a / c;
     if (__double_as_longlong(q) != __double_as_longlong(b)) atomicAdd(bad, 1ULL);
   }
+}
+
+// one thread applies n events (noted code, start bound) to one bound, in order: the raises of n workgroups as they finish
+__global__ void k_fx_raise_events(double *bound, const unsigned *noted, const double *start, int64_t n) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  for (int64_t i = 0; i < n; ++i) fx_raise(bound, noted[i], start[i]);
 }
 
 // the push's transcendental on its own (tests bound it against libm)
@@ -449,6 +456,26 @@ int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n) {
   PROBE_TRY(launch_exp_array(dx, dx + n, n, nullptr));
   PROBE_TRY(hipDeviceSynchronize());
   PROBE_TRY(hipMemcpy(y, dx + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pic1dp_probe_fx_raise(int32_t device, double bound0, const uint32_t *noted, const double *start, int64_t n, double *bound) {
+  if (!noted || !start || !bound || n < 0) return pfail("bad argument");
+  PROBE_TRY(hipSetDevice(device));
+  DevBuf d;
+  const size_t bytes = sizeof(double) * (1 + static_cast<size_t>(n)) + sizeof(unsigned) * static_cast<size_t>(n);
+  PROBE_TRY(hipMalloc(&d.p, bytes));
+  double *db = static_cast<double *>(d.p), *ds = db + 1;
+  unsigned *dn = reinterpret_cast<unsigned *>(ds + n);
+  PROBE_TRY(hipMemcpy(db, &bound0, sizeof(double), hipMemcpyHostToDevice));
+  if (n) {
+    PROBE_TRY(hipMemcpy(ds, start, sizeof(double) * n, hipMemcpyHostToDevice));
+    PROBE_TRY(hipMemcpy(dn, noted, sizeof(unsigned) * n, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_fx_raise_events, dim3(1), dim3(64), 0, nullptr, db, dn, ds, n);
+  PROBE_TRY(hipGetLastError());
+  PROBE_TRY(hipDeviceSynchronize());
+  PROBE_TRY(hipMemcpy(bound, db, sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 

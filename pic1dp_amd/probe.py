@@ -36,6 +36,7 @@ SIGNATURES = {
     "pic1dp_probe_host_optimize": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_int64,
                                    C.c_int64, _I64, _I64],
     "pic1dp_probe_exp": [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
+    "pic1dp_probe_fx_raise": [C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, _D],
     "pic1dp_probe_species_const": [_SP, _I32, _I32, _I32, _I32, _D],
     "pic1dp_probe_dlnf0": [C.c_int32, _SP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
 }
@@ -117,6 +118,22 @@ def device_exp(x, device=0):
     y = np.empty_like(x)
     _check(load().pic1dp_probe_exp(device, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size))
     return y
+
+
+def fx_raise(bound0, events, device=0):
+    """the prediction tiles' fixed-point bound after the raises of workgroups that finish in the given order: events is a
+    list of (noted code, start bound) -- code 0 no marker met, 1 none within the bound, 2 + the bits of the float32 value
+    met otherwise (fx_code); start: the bound the workgroup started with (device_fx.hpp fx_raise)"""
+    noted = np.ascontiguousarray([int(e[0]) for e in events], dtype=np.uint32)
+    start = np.ascontiguousarray([float(e[1]) for e in events], dtype=np.float64)
+    out = C.c_double()
+    _check(load().pic1dp_probe_fx_raise(device, float(bound0), noted.ctypes.data, start.ctypes.data, len(events), C.byref(out)))
+    return out.value
+
+
+def fx_code(value):
+    """the code a workgroup notes for the largest value it met within the bound (kernels_step.hip fx_note)"""
+    return int(np.float32(value).view(np.uint32)) + 2
 
 
 def species_const(sp):
