@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- particle-updates/sec of the PIC1D time-step hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: it sets up (on N > 1 including the rehearsal
+that picks the charge sum), warms up, times the K steps, writes --dump-outputs and
+prints the line.  Everything measured beside the headline -- the objects marked (--full)
+below, the roofline's measured denominators and traffic passes -- runs only with --full.
 
 Headline workload (BASELINE.json): configs[2] = bump-on-tail, 10^8 markers, 1024 grid
 cells, the configuration the metric is quoted on; it fits one GPU.  For N > 1 `value`
@@ -11,10 +16,10 @@ is the SAME 10^8 markers split over the N GPUs ("scaling": "strong" -- the metri
 "at 10^8 particles, 1/2/4/8 MI355X" and north_star's ">= 6x from 1 -> 8 GPUs" is a
 statement about exactly that curve), the per-GPU charge vector summed once per
 sub-step (RCCL all-reduce on the engine's stream, or the library's one-hop exchange);
-the weak reading (10^8 markers PER GPU) is measured in the same run and listed beside
-it (`weak_per_gpu`; --headline weak swaps the two).  The other GPU configurations of
-BASELINE.json are selectable, and the two multi-GPU ones are measured by the driver's
-plain command as well: `--gpus 4` adds a `configs3_c4` object, `--gpus 8` a
+with --full the weak reading (10^8 markers PER GPU) is measured in the same run and
+listed beside it (`weak_per_gpu`; --headline weak swaps the two).  The other GPU
+configurations of BASELINE.json are selectable, and with --full the two multi-GPU ones
+are measured as well: `--gpus 4` adds a `configs3_c4` object, `--gpus 8` a
 `configs4_c5` object (--extra-configs):
     c2  bump-on-tail, 10^7 markers per GPU, nx 256                      (weak)
     c4  two-stream (iptcldist 2, v0 = 3), 10^8 markers IN TOTAL, nx 512 (strong)
@@ -31,17 +36,22 @@ contract keys:
                      + 24 B written per marker for the second sub-step's kernel) / its
                      mean launch duration from HIP events on the engine's stream, vs
                      8 TB/s; the SURVEY 8(d) price of 80 B per update is reported as
-                     reference_priced_GBs, never as the fraction
-  weak_per_gpu     : N > 1: 10^8 markers PER GPU (the other reading of "at 10^8 particles,
-                     1/2/4/8 MI355X"), measured in the same run with the same charge sum
+                     reference_priced_GBs, never as the fraction.  (--full) adds the box's
+                     measured streaming rates and the traffic of two rocprofv3 passes
+  weak_per_gpu     : (--full) N > 1: 10^8 markers PER GPU (the other reading of "at 10^8
+                     particles, 1/2/4/8 MI355X"), measured in the same run with the same
+                     charge sum
   strong_1e8_total : 10^8 markers IN TOTAL split over the N GPUs -- `value` itself for
-                     N > 1 (kept as an object of its own for N = 1 and --headline weak)
-  configs3_c4 / configs4_c5 : BASELINE configs[3] (N = 4) / configs[4] (N = 8), 20 steps
-  exchange         : the same two workloads with the one-hop charge exchange instead of
-                     the RCCL all-reduce (N > 1)
-  attribution      : device time per step of the particle kernels, the charge sum and
-                     the field solve (the reference's timer ids, HIP events)
-  cpu_baseline     : the CPU oracle (line-faithful restatement of the reference,
+                     N > 1 and for N = 1 at the default sizes; a run of its own otherwise
+                     (--full)
+  configs3_c4 / configs4_c5 : (--full) BASELINE configs[3] (N = 4) / configs[4] (N = 8),
+                     20 steps
+  exchange         : (--full) the same two workloads with the one-hop charge exchange
+                     instead of the RCCL all-reduce (N > 1)
+  attribution      : (--full) device time per step of the particle kernels, the charge
+                     sum and the field solve (the reference's timer ids, HIP events)
+  drop_in_call_sites : (--full) the same K steps through the reference's three call sites
+  cpu_baseline     : (--full) the CPU oracle (line-faithful restatement of the reference,
                      "port") timed on this box's host cores on a bounded sample (N = 1)
 """
 import argparse
@@ -95,10 +105,14 @@ def parse():
     ap.add_argument("--no-strong", action="store_true")
     ap.add_argument("--headline", default="auto", choices=["auto", "strong", "weak"],
                     help="N > 1, config c3: which reading of 'at 10^8 particles, N GPUs' is `value` -- strong (10^8 in total, "
-                         "what north_star's >= 6x speed-up 1 -> 8 is a statement about; auto) or weak (10^8 per GPU); the "
-                         "other one is measured beside it")
+                         "what north_star's >= 6x speed-up 1 -> 8 is a statement about; auto) or weak (10^8 per GPU); with "
+                         "--full the other one is measured beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the roofline's streaming rates and traffic passes, "
+                         "attribution, the call sites, the CPU baseline, the other reading of 10^8 markers on N GPUs, the "
+                         "one-hop exchange beside RCCL and the extra configurations; off: the headline alone")
     ap.add_argument("--extra-configs", default="auto",
-                    help="BASELINE multi-GPU configurations measured beside the headline (20 steps each): auto = c4 when "
+                    help="(--full) BASELINE multi-GPU configurations measured beside the headline (20 steps each): auto = c4 when "
                          "N = 4 (configs[3]), c5 when N = 8 (configs[4]); a comma list insists (tests); none: nothing")
     ap.add_argument("--extra-particles", type=int, default=0,
                     help="(tests) marker count of the extra configurations: per GPU for c5, in total for c4")
@@ -116,9 +130,9 @@ def parse():
                          "(PIC1DP_LAZY_CALLS=0 in the environment: one kernel per call)")
     ap.add_argument("--step-mode", type=int, default=0, choices=[0, 1],
                     help="0: whole-step kernels (half-step state recomputed); 1: two fused sub-steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--no-traffic-pass", action="store_true",
-                    help="roofline.traffic from the committed profile constant instead of two rocprofv3 --pmc "
+                    help="(--full) roofline.traffic from the committed profile constant instead of two rocprofv3 --pmc "
                          "passes of this command run as child processes (N = 1 only)")
     ap.add_argument("--cpu-particles", type=int, default=10**7, help="markers of the CPU sample (BASELINE.md 3: C2)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target duration of the all-core CPU sample")
@@ -725,13 +739,15 @@ def main():
     _, np_local = eng.local_sizes()
     headline_kind = job.kind
 
+    # everything below that runs the GPU again, or the CPU baseline, is --full only: a plain run stops at the headline
+
     # the same work through the reference's own three call sites per sub-step (push,
     # collect_charge, solve_field -- src/pic1dp.F90:80-89), which the library serves lazily
     # with the same whole-step kernels; reported beside `value`, never instead of it
     calls_elapsed = None
-    if not a.unfused and not job.host_staged:
+    if a.full and not a.unfused and not job.host_staged:
         calls_elapsed = timed(job, a.steps, job.call_sites)
-    attr = attribution(job)
+    attr = attribution(job) if a.full else None
 
     # ---- the other reading of "10^8 markers, N GPUs" beside the headline: weak (10^8 per GPU) beside the strong headline
     # of N > 1, or strong (10^8 in total) beside a weak one (N = 1: same run; --headline weak; c2 / c5) ------
@@ -741,7 +757,7 @@ def main():
         if world == 1 and a.strong_total == total:
             strong = {"value": total * 2.0 * a.steps / elapsed, "ms_per_step": elapsed / a.steps * 1e3,
                       "same_run_as_headline": True}
-        else:
+        elif a.full:
             sjob = Job(a, other_key, pic1dp_amd.make_input(nparticle_max=other_total, **phys), rank, world, device,
                        dist, shared)
             if job.kind != sjob.kind:        # the two objects are measured with the same charge sum
@@ -760,18 +776,19 @@ def main():
                       "ms_per_step_min": min(s_blocks) / a.steps * 1e3, "ms_per_step_max": max(s_blocks) / a.steps * 1e3,
                       "particle_kernel_avg_ms": {k: v[0] / v[1] for k, v in stab.items() if v[1]},
                       "field_energy_end": s_energy, "attribution": attribution(sjob)}
-        s_tot = other_total if sjob is not None else total
-        strong.update({"unit": "updates/s", "scaling": "weak" if headline_strong else "strong", "particles_total": s_tot,
-                       "particles_per_gpu": s_tot // world, "allreduce": job.kind,
-                       "what": ("the headline physics with %g markers PER GPU on the %d GPUs (weak scaling)" % (s_tot // world, world))
-                               if headline_strong else
-                               ("the headline physics with %g markers IN TOTAL split over the %d GPU(s)" % (s_tot, world))})
+        if strong is not None:
+            s_tot = other_total if sjob is not None else total
+            strong.update({"unit": "updates/s", "scaling": "weak" if headline_strong else "strong", "particles_total": s_tot,
+                           "particles_per_gpu": s_tot // world, "allreduce": job.kind,
+                           "what": ("the headline physics with %g markers PER GPU on the %d GPUs (weak scaling)" % (s_tot // world, world))
+                                   if headline_strong else
+                                   ("the headline physics with %g markers IN TOTAL split over the %d GPU(s)" % (s_tot, world))})
 
     # ---- the one-hop exchange beside RCCL (measured LAST: a failed exchange leaves a run
     # that cannot go on, and everything else is already measured) -----------------------
     exchange = None
     primary = "rccl" if job.kind == "rccl" else "host"
-    if world > 1 and not job.kind.startswith("one-hop"):
+    if a.full and world > 1 and not job.kind.startswith("one-hop"):
         if job.have_p2p and (sjob is None or sjob.have_p2p):
             exchange = {}
             from pic1dp_amd import parallel
@@ -816,7 +833,7 @@ def main():
         else:
             exchange = {"unavailable": job.p2p_why or (sjob.p2p_why if sjob else None)}
 
-    # ---- BASELINE.json's own multi-GPU configurations, measured by the driver's plain command: configs[3] (two-stream,
+    # ---- BASELINE.json's own multi-GPU configurations, measured with --full: configs[3] (two-stream,
     # 10^8 markers in total, nx 512) when N = 4, configs[4] (Landau, 10^8 per GPU, nx 4096: "the scaling-curve run") when
     # N = 8 -- a short run each (three blocks of --extra-steps steps) with the headline's charge sum and the same attribution
     def measure_extra(name):
@@ -850,7 +867,9 @@ def main():
                            world, px["nx"])}
 
     extras = {}
-    if a.extra_configs == "auto":
+    if not a.full:
+        extra_names = []
+    elif a.extra_configs == "auto":
         extra_names = ["c4"] if world == 4 else (["c5"] if world == 8 else [])
     else:
         extra_names = [n for n in a.extra_configs.split(",") if n in CONFIGS]
@@ -916,7 +935,7 @@ def main():
         tkey = "k_step_one" if one_n else ("k_step_full" if full_n else "k_push")
         if sums:
             tkey = "k_step_sums"
-        if world == 1 and not a.no_traffic_pass and not a.unfused and a.step_mode == 0:
+        if a.full and world == 1 and not a.no_traffic_pass and not a.unfused and a.step_mode == 0:
             traffic, traffic_why = measure_traffic(a, tkey)
             if traffic is not None:
                 traffic_src = ("measured for this command in this run: two child processes, rocprofv3 --pmc FETCH_SIZE "
@@ -939,16 +958,18 @@ def main():
             except (OSError, ValueError):
                 pass
         # the box's own streaming rates (second denominator): plain copy and the
-        # dominant kernel's traffic shape (4 arrays read, 3 written)
-        from pic1dp_amd import probe       # libpic1dp_probe.so: measurement code, not part of the product library
-        probe_n = int(min(np_local, 10**8))
-        copy_gbs = max(probe.stream(1, 1, probe_n, 10, device=device) for _ in range(3))
-        shape_gbs = max(probe.stream(4, 3, probe_n, 10, device=device) for _ in range(3))
-        # the same traffic in the layout the markers are stored in (x | v | w | p tiles, three written back in
-        # place): what a kernel that did nothing but stream them would reach -- the denominator that does not
-        # depend on where the allocator puts seven separate arrays
-        tiled_ms = min(probe.layout(probe_n, 12, 10, device=device)[1] for _ in range(2))
-        tiled_gbs = 56.0 * (probe_n // 4096 * 4096) / (tiled_ms * 1e-3) / 1e9
+        # dominant kernel's traffic shape (4 arrays read, 3 written); --full only (null otherwise)
+        copy_gbs = shape_gbs = tiled_gbs = None
+        if a.full:
+            from pic1dp_amd import probe       # libpic1dp_probe.so: measurement code, not part of the product library
+            probe_n = int(min(np_local, 10**8))
+            copy_gbs = max(probe.stream(1, 1, probe_n, 10, device=device) for _ in range(3))
+            shape_gbs = max(probe.stream(4, 3, probe_n, 10, device=device) for _ in range(3))
+            # the same traffic in the layout the markers are stored in (x | v | w | p tiles, three written back in
+            # place): what a kernel that did nothing but stream them would reach -- the denominator that does not
+            # depend on where the allocator puts seven separate arrays
+            tiled_ms = min(probe.layout(probe_n, 12, 10, device=device)[1] for _ in range(2))
+            tiled_gbs = 56.0 * (probe_n // 4096 * 4096) / (tiled_ms * 1e-3) / 1e9
         # bytes the timed steps had to move: every launch of the three whole-step kernels at its own price
         step_bytes = None
         if full_n or one_n:
@@ -966,9 +987,10 @@ def main():
                           "device sync, max over ranks); kernel averages are over all blocks" % (repeats, a.steps),
             "scaling": "strong" if (strong_cfg or headline_strong) else "weak", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic" if not fake_engine else "NOT A MEASUREMENT: stand-in engine (%s), control-plane rehearsal" % fake_engine,
+            "full": a.full,
             "speedup_basis": (("value(N) / value(1) is the STRONG-scaling speed-up: the same %g markers in total on 1, 2, 4, 8 "
                                "GPUs -- the curve north_star's '>= 6x from 1 -> 8 GPUs' is judged on; the weak reading (%g "
-                               "markers per GPU) is weak_per_gpu, measured in this run with the same charge sum")
+                               "markers per GPU) is weak_per_gpu, measured with --full in the same run with the same charge sum")
                               % (total, (other_total or 0) // world)) if headline_strong else
                              ("one GPU: the strong and the weak reading of '10^8 markers on N GPUs' coincide" if world == 1 else
                               "value is %s-scaled (--headline / --config)" % ("strong" if strong_cfg else "weak")),
@@ -1068,7 +1090,7 @@ def main():
                         "solve_field, the three call sites of src/pic1dp.F90:80-89 (served lazily by the "
                         "whole-step kernels)" % a.steps,
             }
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.cpu_particles, 256, a.cpu_seconds)
         print(json.dumps(out), flush=True)
 

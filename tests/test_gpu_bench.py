@@ -49,12 +49,12 @@ CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per
 @pytest.mark.parametrize("config,nx,kernel,carry", [("c3", 256, "k_step_one<sums>", 0.0), ("c3", 1024, "k_step_one<sums>", 0.0),
                                                     ("c5", 4096, "k_step_sums", 0.0)])
 def test_bench_contract_line_small(config, nx, kernel, carry):
-    """the one JSON line of a default-form run (N = 1), without the traffic passes: contract keys, the roofline
+    """the one JSON line of a --full run (N = 1), without the traffic passes: contract keys, the roofline
     priced on the bytes the LIBRARY reports for the instantiation it launched (pic1dp_hip_kernel_bytes), and the
     same launch priced on the compulsory bytes alone (frac_compulsory)"""
     n = 2_000_000
     d = run_bench(["--config", config, "--particles", str(n), "--strong-total", str(n), "--nx", str(nx), "--steps", "5",
-                   "--warmup", "2", "--repeats", "5", "--no-cpu-baseline", "--no-traffic-pass"])
+                   "--warmup", "2", "--repeats", "5", "--full", "--no-cpu-baseline", "--no-traffic-pass"])
     for key in CONTRACT_KEYS:
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "f64"
@@ -97,7 +97,7 @@ def test_bench_measures_its_own_traffic():
         pytest.skip("rocprofv3 not installed")
     n = 8_000_000
     d = run_bench(["--particles", str(n), "--strong-total", str(n), "--nx", "256", "--steps", "5", "--warmup", "2",
-                   "--no-cpu-baseline"])
+                   "--full", "--no-cpu-baseline"])
     r = d["roofline"]
     if r["traffic"] is None or "measured for this command in this run" not in (r["traffic_source"] or ""):
         pytest.skip("the counter passes were not possible here: %s" % r["traffic_source"])
@@ -161,7 +161,7 @@ def test_bench_two_ranks_share_the_gpu(amd, config, particles, allreduce, self_l
     steps, warm, strong_total = 6, 2, 2_000_000
     d = run_bench(["--gpus", "2", "--config", config, "--particles", str(particles), "--nx", str(nx_small),
                    "--steps", str(steps), "--warmup", str(warm), "--strong-total", str(strong_total),
-                   "--allreduce", allreduce, "--no-cpu-baseline"], nproc=2, self_launch=self_launch)
+                   "--allreduce", allreduce, "--full", "--no-cpu-baseline"], nproc=2, self_launch=self_launch)
     strong_cfg = "total" in cfg
     # round 6: on several ranks the metric's own configuration (c3) is measured STRONG-scaled -- `value` is the 10^8 (here:
     # --strong-total) markers in total, what north_star's ">= 6x from 1 -> 8" is a statement about --, the weak reading
@@ -249,7 +249,7 @@ def test_bench_four_ranks_rehearsal_with_the_baseline_multi_gpu_configs(amd):
     b = bench_module()
     steps, particles, strong_total, xp, xsteps = 4, 500_000, 1_200_000, 400_000, 3
     d = run_bench(["--gpus", "4", "--particles", str(particles), "--nx", "128", "--steps", str(steps), "--warmup", "2",
-                   "--strong-total", str(strong_total), "--allreduce", "auto", "--rehearse-with-host", "--no-cpu-baseline",
+                   "--strong-total", str(strong_total), "--allreduce", "auto", "--rehearse-with-host", "--full", "--no-cpu-baseline",
                    "--extra-configs", "c4,c5", "--extra-particles", str(xp), "--extra-steps", str(xsteps)],
                   nproc=4, self_launch=True)
     assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["config"]["particles_total"] == strong_total
@@ -272,5 +272,5 @@ def test_bench_four_ranks_rehearsal_with_the_baseline_multi_gpu_configs(amd):
         assert abs(x["field_energy_end"] / e - 1.0) < 1e-10
     # without --extra-configs the rule is: c4 at N = 4, c5 at N = 8, nothing otherwise
     d2 = run_bench(["--gpus", "2", "--particles", "400000", "--nx", "128", "--steps", "3", "--warmup", "2", "--strong-total",
-                    "600000", "--allreduce", "p2p", "--no-cpu-baseline"], nproc=2, self_launch=True)
+                    "600000", "--allreduce", "p2p", "--full", "--no-cpu-baseline"], nproc=2, self_launch=True)
     assert not any(k.startswith("configs") for k in d2)

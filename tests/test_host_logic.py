@@ -460,7 +460,7 @@ def test_bench_control_plane_at_eight_ranks_with_a_stand_in_engine():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--repeats", "3",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -479,21 +479,21 @@ def test_bench_control_plane_at_eight_ranks_with_a_stand_in_engine():
         assert set(d["strong_1e8_total"]["by_charge_sum"]) == {"rccl", "one-hop exchange"}
     # and four ranks: configs[3]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--repeats", "3",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 4 and d["configs3_c4"]["particles_total"] == 10**8 and d["configs3_c4"]["scaling"] == "strong"
     assert "configs4_c5" not in d
 
 
-def _bench_with_stand_in_engine(args, cwd):
+def _bench_with_stand_in_engine(args, cwd, flags=("--no-cpu-baseline", "--no-traffic-pass")):
     import json
     import subprocess
     import sys
     env = dict(os.environ, PIC1DP_BENCH_ENGINE=os.path.join(ROOT, "tests", "fake_engine"), MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-traffic-pass"] + args,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(flags) + args,
                        cwd=str(cwd), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -545,3 +545,30 @@ def test_bench_steps_are_the_timed_steps_and_the_outputs_are_dumped(tmp_path):
                          ["%s_rank%d" % (k, r) for k in "xvpw" for r in (0, 1)])
     x = np.concatenate([np.load(str(tmp_path / "c" / ("x_rank%d.npy" % r))) for r in (0, 1)])
     assert np.array_equal(x, np.arange(1001) + float(after))
+
+
+def test_bench_plain_run_measures_the_headline_alone(tmp_path):
+    """A plain `bench.py --gpus N --steps K --warmup W` sets up, warms up, times the K steps and prints the line.  Nothing else
+    runs unless --full asks for it: no CPU baseline, traffic passes or streaming probes, call sites, attribution, second
+    workload, exchange beside the headline's sum or extra configuration.  On N > 1 the rehearsal that picks the headline's
+    charge sum is setup and stays.  Control plane only (tests/fake_engine)."""
+    n = 3_000_000
+    base = ["--particles", str(n), "--strong-total", str(n), "--nx", "64", "--steps", "5", "--warmup", "2"]
+    d = _bench_with_stand_in_engine(base, tmp_path, flags=())        # no --no-cpu-baseline, no --no-traffic-pass
+    assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0
+    assert "cpu_baseline" not in d and "drop_in_call_sites" not in d and d["attribution"] is None
+    r = d["roofline"]
+    assert r["traffic"] is None and r["measured_copy_GBs"] is None and r["measured_tiled_4read_3write_GBs"] is None
+    assert r["achieved"] > 0 and d["strong_1e8_total"]["same_run_as_headline"] is True
+    # the same command with --full: everything beside the headline, the headline itself measured alike
+    d = _bench_with_stand_in_engine(base + ["--full", "--cpu-particles", "20000", "--cpu-seconds", "0.2"], tmp_path,
+                                    flags=("--no-traffic-pass",))
+    assert d["full"] is True and d["steps"] == 5 and d["warmup"] == 2
+    assert d["cpu_baseline"]["value"] > 0 and d["drop_in_call_sites"]["value"] > 0
+    assert d["attribution"]["steps"] > 0 and d["roofline"]["measured_copy_GBs"] > 0
+    # several ranks: the strong headline with its rehearsed charge sum, nothing measured beside it
+    d = _bench_with_stand_in_engine(["--gpus", "4", "--particles", "500", "--strong-total", "1001", "--nx", "64", "--steps", "3",
+                                     "--warmup", "1"], tmp_path, flags=())
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["strong_1e8_total"]["same_run_as_headline"] is True
+    assert d["config"]["charge_sum_chosen_by"]["chosen"] in ("rccl", "p2p")
+    assert not [k for k in d if k in ("weak_per_gpu", "exchange", "cpu_baseline") or k.startswith("configs")]

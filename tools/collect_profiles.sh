@@ -15,7 +15,7 @@ export TMPDIR=/tmp
 cd /tmp
 
 echo "[1/4] default bench line" && date
-python3 "$R/bench.py" --config $CFG > "$OUT/bench_${CFG}_wholestep.json" 2> "$OUT/bench_${CFG}_wholestep.err"
+python3 "$R/bench.py" --config $CFG --full > "$OUT/bench_${CFG}_wholestep.json" 2> "$OUT/bench_${CFG}_wholestep.err"
 cat "$OUT/bench_${CFG}_wholestep.json"
 
 echo "[2/4] kernel trace + stats" && date

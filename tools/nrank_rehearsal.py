@@ -106,7 +106,7 @@ def main():
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c3", "--particles", str(n),
-               "--nx", str(a.nx), "--strong-total", str(2 * n), "--allreduce", "p2p", "--no-cpu-baseline",
+               "--nx", str(a.nx), "--strong-total", str(2 * n), "--allreduce", "p2p", "--full", "--no-cpu-baseline",
                "--steps", "100", "--warmup", "20"]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
