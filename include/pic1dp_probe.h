@@ -37,6 +37,11 @@ int pic1dp_probe_host_div_lx(double lx, int32_t nx, int64_t n, uint64_t seed, in
 /* a / divisor for a species constant (div_const), likewise */
 int pic1dp_probe_div_const(int32_t device, double divisor, int64_t n, uint64_t seed, int64_t *mismatches);
 int pic1dp_probe_host_div_const(double divisor, int64_t n, uint64_t seed, int64_t *mismatches);
+/* the diagnostics' divisions (diag_div: positions by lx, v + v_max by 2 v_max, an nx_opd x nv_opd grid's boundaries
+ * +- a few ulps, 0 and subnormal dividends included), likewise */
+int pic1dp_probe_diag_div(int32_t device, double lx, int32_t nxo, double vmax, int32_t nvo, int64_t n, uint64_t seed,
+                          int64_t *mismatches);
+int pic1dp_probe_host_diag_div(double lx, int32_t nxo, double vmax, int32_t nvo, int64_t n, uint64_t seed, int64_t *mismatches);
 
 /* The sequential walks of the GPU marker optimisation (pic1dp_amd/csrc/optimize.hpp plan_merge / plan_remove /
  * plan_split: one key per marker) against the routines on whole markers they restate (opt_merge / opt_remove /

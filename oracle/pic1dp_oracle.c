@@ -788,10 +788,17 @@ void orc_ptcldist(const orc_input *in, int64_t np, const double *x,
     double sv = (v[ip] + vmax) / (vmax * 2.0) * (double)(nvo - 1);
     int iv = (int)floor(sv);
     sv = 1.0 - (sv - (double)iv);
-    if (ix < 0 || ix >= nxo || iv < 0 || iv + 1 >= nvo) continue; /* safety */
+    /* x == lx (or x / lx rounding to 1): sx == 1, the periodic image of
+     * x = 0 (the deposit's fold); the reference would spill into the next row */
+    if (ix == nxo) ix = 0;
+    if (ix < 0 || ix >= nxo || iv < 0 || iv >= nvo) continue; /* safety */
+    /* iv == nvo - 1 only where sv came out as exactly nvo - 1: sv == 1 and the
+     * writes to row iv + 1 carry weight 0 (the reference's only out-of-range
+     * writes); the top row keeps the marker */
+    const int top = iv + 1 >= nvo;
     double pp = p[ip], pw = w ? w[ip] : 0.0;
     for (int pass = 0; pass < 2; pass++) {
-      int a = iv * nxo + ix, b = (iv + 1) * nxo + ix;
+      int a = iv * nxo + ix, b = (top ? iv : iv + 1) * nxo + ix;
       markr_xv[a] += sx * sv;
       total_xv[a] += sx * sv * pp;
       if (in->deltaf == 1) pertb_xv[a] += sx * sv * pw;
@@ -805,6 +812,7 @@ void orc_ptcldist(const orc_input *in, int64_t np, const double *x,
     markr_v[iv] += sv;
     total_v[iv] += sv * pp;
     if (in->deltaf == 1) pertb_v[iv] += sv * pw;
+    if (top) continue;
     markr_v[iv + 1] += (1.0 - sv);
     total_v[iv + 1] += (1.0 - sv) * pp;
     if (in->deltaf == 1) pertb_v[iv + 1] += (1.0 - sv) * pw;

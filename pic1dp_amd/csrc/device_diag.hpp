@@ -56,10 +56,12 @@ __device__ __forceinline__ void bin_add(double *p, double v) {
   }
 }
 
-// a / c for the constant c with rc = RN(1 / c): RN(a / c) by Markstein's construction (device_math.hpp div_const,
-// without its range test: the dividends here are positions in [0, lx] and v + v_max in (0, 2 v_max) -- normal numbers
-// or exact zeros, for which the five operations return the IEEE quotient)
+// a / c for the constant c with rc = RN(1 / c): RN(a / c) by Markstein's construction (device_math.hpp div_const).  The
+// dividends here are positions in [0, lx] and v + v_max in (0, 2 v_max); below 2^-500 (0 and subnormal positions: the
+// residuals underflow there and the five operations miss the IEEE quotient by an ulp, tests/test_gpu_diag_reference.py)
+// the hardware's division -- a branch no marker of a real run takes
 __device__ __forceinline__ double diag_div(double a, double c, double rc) {
+  if (!(a >= 0x1p-500)) return a / c;
   const double q0 = a * rc;
   const double r0 = fma(-c, q0, a);
   const double q1 = fma(r0, rc, q0);
@@ -85,20 +87,24 @@ __device__ __forceinline__ void ptcldist_one(double px, double pv, double pp, do
   double sx = px / dg.lx * static_cast<double>(nxo);
 #endif
   const double fx = floor(sx);
-  const int ix = static_cast<int>(fx);
+  int ix = static_cast<int>(fx);
   sx = 1.0 - (sx - fx);
+  if (ix == nxo) ix = 0;   // x == lx (or x / lx rounding to 1): sx == 1, the periodic image of x = 0 -- the deposit's fold
   const double av = pv + dg.vmax;
   double sv = (dg.vfast ? diag_div(av, dg.dv, dg.rdv) : av / dg.dv) * static_cast<double>(nvo - 1);  // :247
   const double fv = floor(sv);
   const int iv = static_cast<int>(fv);
   sv = 1.0 - (sv - fv);
-  // memory safety only (the reference would write out of bounds)
-  if (static_cast<unsigned>(ix) >= static_cast<unsigned>(nxo) || iv < 0 || iv + 1 >= nvo) return;
+  // memory safety only (NaN, positions outside [0, lx])
+  if (static_cast<unsigned>(ix) >= static_cast<unsigned>(nxo) || static_cast<unsigned>(iv) >= static_cast<unsigned>(nvo)) return;
+  // iv == nvo - 1 only where sv came out as exactly nvo - 1 (|v| < v_max): sv == 1, and the reference's writes to row
+  // iv + 1 carry weight 0 -- they go to row iv instead (adding zeros), the top row keeps the marker
+  const int ivu = iv + 1 < nvo ? iv + 1 : iv;
   const int ixr = ix + 1 > nxo - 1 ? 0 : ix + 1;        // :274-276
   const double sxr = 1.0 - sx, svu = 1.0 - sv;
   const int pl = b.template plane<LDS>();
   double *c00 = b.template bin<LDS>(iv * nxo + ix), *c10 = b.template bin<LDS>(iv * nxo + ixr);
-  double *c01 = b.template bin<LDS>((iv + 1) * nxo + ix), *c11 = b.template bin<LDS>((iv + 1) * nxo + ixr);
+  double *c01 = b.template bin<LDS>(ivu * nxo + ix), *c11 = b.template bin<LDS>(ivu * nxo + ixr);
   // the reference's products, in its order: (sx * sv), (sx * sv) * p, (sx * sv) * w, ...
   const double w00 = sx * sv, w01 = sx * svu, w10 = sxr * sv, w11 = sxr * svu;
   if constexpr (FX) {
@@ -137,9 +143,9 @@ __device__ __forceinline__ void ptcldist_one(double px, double pv, double pp, do
     bin_add<LDS>(&b.vv(0)[iv], sv);
     bin_add<LDS>(&b.vv(1)[iv], sv * pp);
     if constexpr (DELTAF) bin_add<LDS>(&b.vv(2)[iv], sv * pw);
-    bin_add<LDS>(&b.vv(0)[iv + 1], svu);
-    bin_add<LDS>(&b.vv(1)[iv + 1], svu * pp);
-    if constexpr (DELTAF) bin_add<LDS>(&b.vv(2)[iv + 1], svu * pw);
+    bin_add<LDS>(&b.vv(0)[ivu], svu);
+    bin_add<LDS>(&b.vv(1)[ivu], svu * pp);
+    if constexpr (DELTAF) bin_add<LDS>(&b.vv(2)[ivu], svu * pw);
   }
 }
 

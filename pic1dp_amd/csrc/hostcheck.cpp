@@ -43,6 +43,26 @@ int64_t host_div_check(double lx, int nx, uint64_t seed, int64_t n) {
   return bad;
 }
 
+// diag_div's algorithm (device_diag.hpp) with the host's FMA, on the operands of the diagnostics' two divisions
+int64_t host_diag_div_check(double lx, int nxo, double vmax, int nvo, uint64_t seed, int64_t n) {
+  const double rlx = 1.0 / lx, rdv = 1.0 / (vmax * 2.0);
+  int64_t bad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    double c;
+    const double a = diag_div_check_value(seed, i, lx, nxo, vmax, nvo, &c);
+    const double rc = c == lx ? rlx : rdv;
+    double q = a / c;
+    if (a >= 0x1p-500) {
+      const double q0 = a * rc;
+      const double q1 = fma(fma(-c, q0, a), rc, q0);
+      q = fma(fma(-c, q1, a), rc, q1);
+    }
+    const double b = a / c;
+    if (std::memcmp(&q, &b, 8) != 0) ++bad;
+  }
+  return bad;
+}
+
 // the histogram geometry of output_ptcldist with its two constant divisors prepared (kernels.hpp DistGeom)
 DistGeom make_dist_geom(double lx, double vmax, int nxo, int nvo) {
   DistGeom dg{};

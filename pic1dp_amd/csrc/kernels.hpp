@@ -561,6 +561,8 @@ int64_t host_div_check(double lx, int nx, uint64_t seed, int64_t n);
 int64_t host_optimize_check(const pic1dp_input &in, int kind, double threshold, uint64_t seed, int64_t np0, int64_t nalloc,
                             int64_t *np_after);
 int64_t host_divc_check(double c, uint64_t seed, int64_t n);
+// diag_div's (device_diag.hpp), on the operands of the diagnostics' divisions by lx and 2 v_max
+int64_t host_diag_div_check(double lx, int nxo, double vmax, int nvo, uint64_t seed, int64_t n);
 // cell index per marker and per-cell counts from (wrapped) x
 hipError_t launch_cell_indices(const double *x, int64_t np, const GridConst &g, int32_t *ix,
                                unsigned long long *count, hipStream_t st);

@@ -12,6 +12,7 @@
 
 #include "../../include/pic1dp_probe.h"
 #include "check_values.hpp"
+#include "device_diag.hpp"
 #include "device_fx.hpp"
 #include "device_math.hpp"
 
@@ -197,6 +198,17 @@ __global__ void k_divc_check(double c, double rc, uint64_t seed, int64_t n, unsi
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
     const double a = divc_check_value(seed, i);
     const double q = div_const(a, c, rc, 1), b = a / c;
+    if (__double_as_longlong(q) != __double_as_longlong(b)) atomicAdd(bad, 1ULL);
+  }
+}
+
+__global__ void k_diag_div_check(double lx, int nxo, double vmax, int nvo, uint64_t seed, int64_t n, unsigned long long *bad) {
+  const double rlx = 1.0 / lx, rdv = 1.0 / (vmax * 2.0);
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    double c;
+    const double a = diag_div_check_value(seed, i, lx, nxo, vmax, nvo, &c);
+    const double q = diag_div(a, c, c == lx ? rlx : rdv), b = a / c;
     if (__double_as_longlong(q) != __double_as_longlong(b)) atomicAdd(bad, 1ULL);
   }
 }
@@ -418,6 +430,29 @@ int pic1dp_probe_div_const(int32_t device, double divisor, int64_t n, uint64_t s
   unsigned long long h = 0;
   PROBE_TRY(hipMemcpy(&h, d.p, sizeof h, hipMemcpyDeviceToHost));
   *mismatches = static_cast<int64_t>(h);
+  return 0;
+}
+
+int pic1dp_probe_diag_div(int32_t device, double lx, int32_t nxo, double vmax, int32_t nvo, int64_t n, uint64_t seed,
+                          int64_t *mismatches) {
+  if (!mismatches || !(lx > 0.0) || !(vmax > 0.0) || nxo < 1 || nvo < 2 || n < 0) return pfail("bad argument");
+  PROBE_TRY(hipSetDevice(device));
+  DevBuf d;
+  PROBE_TRY(hipMalloc(&d.p, sizeof(unsigned long long)));
+  PROBE_TRY(hipMemset(d.p, 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(k_diag_div_check, dim3(2048), dim3(256), 0, nullptr, lx, nxo, vmax, nvo, seed, n,
+                     static_cast<unsigned long long *>(d.p));
+  PROBE_TRY(hipGetLastError());
+  PROBE_TRY(hipDeviceSynchronize());
+  unsigned long long h = 0;
+  PROBE_TRY(hipMemcpy(&h, d.p, sizeof h, hipMemcpyDeviceToHost));
+  *mismatches = static_cast<int64_t>(h);
+  return 0;
+}
+
+int pic1dp_probe_host_diag_div(double lx, int32_t nxo, double vmax, int32_t nvo, int64_t n, uint64_t seed, int64_t *mismatches) {
+  if (!mismatches || !(lx > 0.0) || !(vmax > 0.0) || nxo < 1 || nvo < 2 || n < 0) return pfail("bad argument");
+  *mismatches = host_diag_div_check(lx, nxo, vmax, nvo, seed, n);
   return 0;
 }
 

@@ -33,6 +33,8 @@ SIGNATURES = {
     "pic1dp_probe_host_div_lx": [C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
     "pic1dp_probe_div_const": [C.c_int32, C.c_double, C.c_int64, C.c_uint64, _I64],
     "pic1dp_probe_host_div_const": [C.c_double, C.c_int64, C.c_uint64, _I64],
+    "pic1dp_probe_diag_div": [C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
+    "pic1dp_probe_host_diag_div": [C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
     "pic1dp_probe_host_optimize": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_int64,
                                    C.c_int64, _I64, _I64],
     "pic1dp_probe_exp": [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
@@ -100,6 +102,16 @@ def div_lx_mismatches(lx, nx, n, seed, device=0, host=False):
         _check(L.pic1dp_probe_host_div_lx(lx, nx, n, seed, C.byref(m)))
     else:
         _check(L.pic1dp_probe_div_lx(device, lx, nx, n, seed, C.byref(m)))
+    return m.value
+
+
+def diag_div_mismatches(lx, nxo, vmax, nvo, n, seed, device=0, host=False):
+    m = C.c_int64(-1)
+    L = load()
+    if host:
+        _check(L.pic1dp_probe_host_diag_div(lx, nxo, vmax, nvo, n, seed, C.byref(m)))
+    else:
+        _check(L.pic1dp_probe_diag_div(device, lx, nxo, vmax, nvo, n, seed, C.byref(m)))
     return m.value
 
 
