@@ -1,10 +1,13 @@
 """ctypes face of the CPU oracle (oracle/pic1dp_oracle.c) and of the reference's
-own multirand module built into oracle/_ref/.
+own modules built into oracle/_ref/: multirand, and the hot path (load, deposit,
+push, field solve, marker optimisation) behind a serial PETSc stand-in, one
+library per configuration of oracle/ref_cases.json.
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg.  The product package (pic1dp_amd) never imports it.
 """
 import ctypes as C
+import json
 import os
 import subprocess
 
@@ -13,6 +16,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 REF_LIB_PATH = os.path.join(HERE, "_ref", "libmultirand_ref.so")
+REF_CASES_PATH = os.path.join(HERE, "ref_cases.json")
+REF_SRC = "/root/reference/src"
 
 MAX_SPECIES = 8
 MAX_MODES = 4096
@@ -89,7 +94,8 @@ def opt_defaults(d):
     return d
 
 
-def make_input(**kw):
+def input_values(**kw):
+    """the defaults with kw over them, every derived list filled in"""
     d = dict(DEFAULTS)
     for k in kw:
         if k not in d:
@@ -97,7 +103,11 @@ def make_input(**kw):
     d.update(kw)
     if d["species_nparticle_init"] is None:
         d["species_nparticle_init"] = [d["nparticle_max"]] * d["nspecies"]
-    opt_defaults(d)
+    return opt_defaults(d)
+
+
+def make_input(**kw):
+    d = input_values(**kw)
     inp = OrcInput()
     for name, _ in OrcInput._fields_:
         if name in ("pad0", "pad1"):
@@ -117,7 +127,8 @@ def build(force=False):
     if force or not os.path.exists(LIB_PATH) or (
             os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(HERE, "pic1dp_oracle.c"))):
         subprocess.check_call(["make", "-C", HERE, "all"], stdout=subprocess.DEVNULL)
-    elif not os.path.exists(REF_LIB_PATH) and os.path.exists("/root/reference/src/multirand.F90"):
+    elif os.path.exists(os.path.join(REF_SRC, "multirand.F90")) and not (
+            os.path.exists(REF_LIB_PATH) and all(os.path.exists(ref_lib_path(c)) for c in ref_case_names())):
         subprocess.check_call(["make", "-C", HERE, "ref"], stdout=subprocess.DEVNULL)
 
 
@@ -173,6 +184,7 @@ def lib():
         "orc_sim_step": (None, [P, C.c_int]),
         "orc_sim_itime": (C.c_int32, [P]),
         "orc_sim_time": (C.c_double, [P]),
+        "orc_sim_set_time": (None, [P, C.c_int32, C.c_double]),
         "orc_sim_field_energy": (C.c_double, [P]),
         "orc_sim_get_field": (None, [P, _dp, _dp, _dp, _dp]),
         "orc_sim_set_field": (None, [P, _dp]),
@@ -199,6 +211,12 @@ def lib():
         f.argtypes = args
     _lib = L
     return L
+
+
+class OrcMultirand(C.Structure):
+    """mirrors struct orc_multirand"""
+    _fields_ = [("seeds", C.c_uint64 * NSEED), ("iseed", C.c_int32), ("al_int", C.c_int32),
+                ("gaussian64buf_filled", C.c_int32), ("pad", C.c_int32), ("gaussian64buf", C.c_double)]
 
 
 class Multirand:
@@ -283,6 +301,252 @@ class RefMultirand:
         return a
 
 
+# --------------------------------------------------------------------------
+# the reference's own hot path (oracle/_ref/libpic1dp_ref_<case>.so)
+# --------------------------------------------------------------------------
+_ref_cases = None
+
+
+def _ref_case_file():
+    global _ref_cases
+    if _ref_cases is None:
+        with open(REF_CASES_PATH) as f:
+            _ref_cases = json.load(f)
+    return _ref_cases
+
+
+def ref_case_names():
+    """every configuration a library is built for: each case of ref_cases.json and its <case>_small variant"""
+    names = list(_ref_case_file()["cases"])
+    return names + [n + "_small" for n in names]
+
+
+def ref_case_kwargs(name):
+    """make_input keywords of a case (the same for the oracle and for the product)"""
+    f = _ref_case_file()
+    small = name.endswith("_small")
+    kw = dict(f["base"])
+    kw.update(f["cases"][name[:-len("_small")] if small else name])
+    fixture_n = kw.pop("fixture_nparticle_max", f["fixture_nparticle_max"])
+    if small:
+        kw["nparticle_max"] = fixture_n
+    frac = kw.pop("species_nparticle_init_frac", None)
+    if frac is not None:
+        kw["species_nparticle_init"] = [int(kw["nparticle_max"] * frac)] * kw.get("nspecies", 1)
+    return kw
+
+
+def ref_case_values(name):
+    d = input_values(**ref_case_kwargs(name))
+    assert d["multirand_seed_type"] == 1
+    return d
+
+
+def ref_lib_path(case):
+    return os.path.join(HERE, "_ref", "libpic1dp_ref_%s.so" % case)
+
+
+class RefUnavailable(RuntimeError):
+    """oracle/_ref holds no library for the case (no reference tree or no flang where it was built)"""
+
+
+class Ref:
+    """the reference's own modules for one case of ref_cases.json, with the verbs and accessors of Sim (one rank).
+    The modules keep their state at module level: one Ref per case and process, handed out by Ref.get()."""
+
+    _open = {}
+
+    @classmethod
+    def available(cls, case):
+        return os.path.exists(ref_lib_path(case))
+
+    @classmethod
+    def get(cls, case):
+        if case not in cls._open:
+            cls._open[case] = cls(case)
+        return cls._open[case]
+
+    def __init__(self, case):
+        if case in Ref._open:
+            raise RuntimeError("Ref(%r) exists in this process: use Ref.get" % case)
+        if not Ref.available(case):
+            raise RefUnavailable("no %s: build it with `make -C oracle ref` where the reference tree and flang are present"
+                                 % ref_lib_path(case))
+        L = C.CDLL(ref_lib_path(case))
+        i32 = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+        for name, res, args in (
+                ("ref_init", None, []), ("ref_sizes", None, [i32]), ("ref_load", None, []),
+                ("ref_compute_shape", None, []), ("ref_collect_charge", None, []), ("ref_solve_field", None, []),
+                ("ref_push", None, [C.c_int]), ("ref_optimize", C.c_int, [C.c_int]),
+                ("ref_dist_pertb_abs_v", None, [_dp]),
+                ("ref_get_array", None, [C.c_int, C.c_int, _dp, C.c_int64]),
+                ("ref_set_array", None, [C.c_int, C.c_int, _dp, C.c_int64]),
+                ("ref_get_np", C.c_int64, [C.c_int]), ("ref_set_np", None, [C.c_int, C.c_int64]),
+                ("ref_get_field", None, [C.c_int, _dp, C.c_int64]), ("ref_set_field", None, [C.c_int, _dp, C.c_int64]),
+                ("ref_field_table", None, [C.c_int, C.c_int, _dp]),
+                ("ref_get_time", None, [C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+                ("ref_set_time", None, [C.c_int32, C.c_double]), ("ref_advance_time", None, []),
+                ("ref_rng_ints", None, [_ip64, C.c_int64]),
+                ("ref_get_opt_index", None, [i32]), ("ref_set_opt_index", None, [i32]),
+                ("ref_gaussian_spare", None, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+                ("ref_exp_array", None, [_dp, _dp, C.c_int64, C.c_int]),
+                ("ref_cos_sin_array", None, [_dp, _dp, _dp, C.c_int64])):
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        self.L = L
+        self.case = case
+        self.kw = ref_case_kwargs(case)
+        self.inp = make_input(**self.kw)
+        L.ref_init()
+        sz = np.zeros(8, dtype=np.int32)
+        L.ref_sizes(sz)
+        self._opt0 = np.zeros(3, dtype=np.int32)
+        L.ref_get_opt_index(self._opt0)
+        self.nspecies, self.nx, self.nmode, self.nv, self.nalloc = (int(v) for v in sz[:5])
+        self.iptclshape = int(sz[6])
+        assert (self.nspecies, self.nx, self.nmode, self.nv, self.nalloc) == (
+            self.inp.nspecies, self.inp.nx, self.inp.nmode, self.inp.nv, self.inp.nparticle_max)
+        Ref._open[case] = self
+
+    def load(self):
+        """particle_load (re-initialises the random stream) at time zero"""
+        self.L.ref_set_time(0, 0.0)
+        self.L.ref_set_opt_index(self._opt0)
+        self.gaussian_spare(fresh=True)   # a program run starts without one
+        self.L.ref_load()
+        if self.iptclshape < 4:   # as the driver does right after the load
+            self.L.ref_compute_shape()
+        return 0
+
+    def opt_index(self):
+        """(imerge, iremove, isplit): the next event of each kind"""
+        a = np.zeros(3, dtype=np.int32)
+        self.L.ref_get_opt_index(a)
+        return tuple(int(v) for v in a)
+
+    def collect_charge(self):
+        """the shape arrays first where the driver fills them (iptclshape 3), then interaction_collect_charge"""
+        if self.iptclshape < 4:
+            self.L.ref_compute_shape()
+        self.L.ref_collect_charge()
+
+    def solve_field(self):
+        self.L.ref_solve_field()
+
+    def push(self, irk):
+        self.L.ref_push(irk)
+
+    def optimize(self, irk=2):
+        return bool(self.L.ref_optimize(irk))
+
+    def step(self, n=1):
+        """the driver's loop body: push, optimise, [shape,] collect, solve for both sub-steps, then the time update"""
+        for _ in range(n):
+            for irk in (1, 2):
+                self.push(irk)
+                self.optimize(irk)
+                self.collect_charge()
+                self.solve_field()
+            self.L.ref_advance_time()
+
+    @property
+    def itime(self):
+        return self._time()[0]
+
+    @property
+    def time(self):
+        return self._time()[1]
+
+    def _time(self):
+        it, t = C.c_int32(), C.c_double()
+        self.L.ref_get_time(C.byref(it), C.byref(t))
+        return it.value, t.value
+
+    def set_time(self, itime, time):
+        self.L.ref_set_time(itime, time)
+
+    def rank_np(self, rank=0, isp=0):
+        return int(self.L.ref_get_np(isp))
+
+    def set_rank_np(self, rank, np_valid, isp=0):
+        self.L.ref_set_np(isp, np_valid)
+
+    def rank_nalloc(self, rank=0):
+        return self.nalloc
+
+    def array(self, isp, which):
+        """a COPY of the whole marker array (tail slots included)"""
+        a = np.empty(self.nalloc)
+        self.L.ref_get_array(isp, ARR[which] if isinstance(which, str) else which, a, a.size)
+        return a
+
+    def set_array(self, isp, which, values):
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        assert a.size <= self.nalloc
+        self.L.ref_set_array(isp, ARR[which] if isinstance(which, str) else which, a, a.size)
+
+    def gather(self, which, isp=0):
+        return self.array(isp, which)[: self.rank_np(0, isp)]
+
+    def get_field(self):
+        """(E, chargeden, mode_re, mode_im) like Sim.get_field"""
+        out = []
+        for which, n in ((0, self.nx), (1, self.nx), (2, self.nmode), (3, self.nmode)):
+            a = np.empty(n)
+            self.L.ref_get_field(which, a, n)
+            out.append(a)
+        return tuple(out)
+
+    def set_field(self, E):
+        self.L.ref_set_field(0, np.ascontiguousarray(E, dtype=np.float64), self.nx)
+
+    def set_chargeden(self, rho):
+        self.L.ref_set_field(1, np.ascontiguousarray(rho, dtype=np.float64), self.nx)
+
+    def tables(self):
+        """(fourier_re, fourier_im, grad_inv) as field_init filled them: [nx, nmode], [nx, nmode], [nmode]"""
+        re, im = np.empty((self.nx, self.nmode)), np.empty((self.nx, self.nmode))
+        col = np.empty(self.nx)
+        for m in range(self.nmode):
+            self.L.ref_field_table(0, m, col)
+            re[:, m] = col
+            self.L.ref_field_table(1, m, col)
+            im[:, m] = col
+        g = np.empty(self.nmode)
+        self.L.ref_get_field(4, g, self.nmode)
+        return re, im, g
+
+    def dist_pertb_abs_v(self):
+        """particle_compute_dist_pertb_abs_v: [nspecies, nv]"""
+        out = np.empty((self.nspecies, self.nv))
+        self.L.ref_dist_pertb_abs_v(out)
+        return out
+
+    def rng_ints(self, n):
+        a = np.empty(n, dtype=np.int64)
+        self.L.ref_rng_ints(a, n)
+        return a
+
+    def gaussian_spare(self, fresh=False):
+        """(held, value) of the spare of the last Gaussian pair; fresh: drop it first"""
+        f, v = C.c_int32(), C.c_double()
+        self.L.ref_gaussian_spare(int(fresh), C.byref(f), C.byref(v))
+        return int(f.value), float(v.value)
+
+    def exp(self, x, vector=False):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.empty_like(x)
+        self.L.ref_exp_array(x, y, x.size, int(vector))
+        return y
+
+    def cos_sin(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        c, s = np.empty_like(x), np.empty_like(x)
+        self.L.ref_cos_sin_array(x, c, s, x.size)
+        return c, s
+
+
 class Field:
     def __init__(self, inp):
         self.inp = inp
@@ -360,6 +624,9 @@ class Sim:
     @property
     def time(self):
         return lib().orc_sim_time(self.s)
+
+    def set_time(self, itime, time):
+        lib().orc_sim_set_time(self.s, itime, time)
 
     def field_energy(self):
         return lib().orc_sim_field_energy(self.s)

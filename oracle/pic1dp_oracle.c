@@ -1265,6 +1265,10 @@ void orc_sim_set_rank_np(orc_sim *s, int rank, int isp, int64_t np) {
 
 int32_t orc_sim_itime(const orc_sim *s) { return s->itime; }
 double orc_sim_time(const orc_sim *s) { return s->time; }
+void orc_sim_set_time(orc_sim *s, int32_t itime, double time) {
+  s->itime = itime;
+  s->time = time;
+}
 double orc_sim_field_energy(const orc_sim *s) { return orc_field_energy(&s->in, s->E); }
 
 void orc_sim_get_field(const orc_sim *s, double *E, double *rho,

@@ -11,12 +11,11 @@
  *     (src/multirand.F90 compiled from /root/reference with flang by
  *     oracle/Makefile into oracle/_ref/) and against the reference's own KAT
  *     vectors (src/multirand.F90:396-425).
- *   - load / push / deposit / field-solve part: PARITY UNPINNED by reference
- *     outputs.  The reference cannot be built here (every hot-path file
- *     includes PETSc's finclude headers, PETSc is absent) and holds no golden
- *     vectors for these routines.  It is a restatement of
- *     the cited lines, cross-checked by the analytic field-solve identity and
- *     by linear growth rates against the Vlasov dispersion roots.
+ *   - load / push / deposit / field-solve / marker-optimisation part: PINNED
+ *     bit for bit, on one rank, against the reference's own sources compiled
+ *     behind the serial PETSc stand-in of oracle/petsc_standin (oracle/Makefile
+ *     target ref, tests/test_oracle_reference.py) and against the records of
+ *     those runs under tests/golden/.  Not pinned: the N-rank summation order.
  *
  * Arithmetic contract: plain IEEE double, no FMA contraction, no fast-math,
  * libm exp/sin/cos/fmod/floor/sqrt -- the reference is built "-O3" for generic
@@ -205,6 +204,7 @@ void orc_sim_push(orc_sim *s, int irk);
 void orc_sim_step(orc_sim *s, int nsteps);  /* nsteps x (irk=1,2) */
 int32_t orc_sim_itime(const orc_sim *s);
 double orc_sim_time(const orc_sim *s);
+void orc_sim_set_time(orc_sim *s, int32_t itime, double time);
 double orc_sim_field_energy(const orc_sim *s);
 void orc_sim_get_field(const orc_sim *s, double *E, double *rho,
                        double *mode_re, double *mode_im);
