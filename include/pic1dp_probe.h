@@ -75,6 +75,20 @@ int pic1dp_probe_species_const(const pic1dp_probe_species *sp, int32_t *pow2, in
  * reference's operation order, form 1 the one-exp form (iptcldist 2, 3) */
 int pic1dp_probe_dlnf0(int32_t device, const pic1dp_probe_species *sp, int32_t form, const double *v, double *y, int64_t n);
 
+/* The launch shape the product library picks for a marker kernel (pic1dp_amd/csrc/launch_policy.hpp), on the HOST: no GPU
+ * needed.  num_cu ... osub_req: the policy's view of the context; family: 0 sub-step kernels (with_E, with_rho, exact),
+ * 1 whole-step kernels (full, exact), 2 k_step_full<DIAG> (exact, nx_opd, nv_opd), 3 one-pass kernels (priv, pred_kind,
+ * nmode, exp_bearing: -f0'/f0 of the distribution bears an exp); fields a family does not name are ignored.
+ * shape = {threads, blocks, dynamic LDS bytes, resident workgroups (family 3; 0 otherwise)}; a shape whose LDS exceeds
+ * what a kernel may ask for is returned as it is.  Nonzero: null argument or unknown family (no message). */
+typedef struct pic1dp_probe_launch_query {
+  int32_t num_cu, threads_req, bpc_req, osub_req;
+  int32_t family, nx, nmode;
+  int64_t np;
+  int32_t full, exact, with_E, with_rho, priv, pred_kind, exp_bearing, nx_opd, nv_opd;
+} pic1dp_probe_launch_query;
+int pic1dp_probe_host_launch_shape(const pic1dp_probe_launch_query *q, int64_t shape[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,7 +161,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
         for (int i = 0; i < nv; ++i) h[i] = b == 0 ? local[i] : h[i] + local[i];
       }
     }
-    if (c->lay.nranks > 1 || c->comm) {
+    if (several_ranks(c)) {
       double *d = c->d_scratch;
       if (static_cast<size_t>(ns) * nv > static_cast<size_t>(kEnergyBlocks) * 3)
         return fail(PIC1DP_ERR_ARG, "nv too large for the reduction scratch");
@@ -422,7 +422,7 @@ static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
         for (int i = 0; i < nv; ++i) h[i] = b == 0 ? local[i] : h[i] + local[i];
       }
     }
-    if (c->lay.nranks > 1 || c->comm) {
+    if (several_ranks(c)) {
       double *d = c->d_scratch;
       if (static_cast<size_t>(ns) * nv > static_cast<size_t>(kEnergyBlocks) * 3)
         return fail(PIC1DP_ERR_ARG, "nv too large for the reduction scratch");

@@ -2,6 +2,7 @@
 // the error convention, the event spans, and the internal entry points one unit offers the others.
 //   capi.cpp           context, input, transfers, field access, timers and knobs
 //   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
+//   launch_policy.cpp  the marker kernels' launch shapes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
 //   capi_diag.cpp      diagnostics of output_all
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
@@ -20,6 +21,7 @@
 
 #include "../../include/pic1dp_hip.h"
 #include "kernels.hpp"
+#include "launch_policy.hpp"
 #include "loader.hpp"
 #include "multirand.hpp"
 #include "optimize.hpp"
@@ -51,8 +53,7 @@ constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf =
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int kEnergyBlocks = 1024;
-constexpr size_t kCuLds = 160 * 1024, kStaticLds = 1024;  // LDS of a CU; static LDS of a marker kernel (the exp table)
-// states of the lazy call sites (pic1dp_ctx::lz)
+constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
 // ---------------------------------------------------------------------------
 // The call sites' state (capi_step.cpp "lazy call sites").  Two variables, each an enum, and a table of
 // the pairs that can occur -- until round 6 this was lz, half_pair, half_solved and cd_lazy, 4 x 2 x 2 x 6 combinations of
@@ -205,13 +206,8 @@ struct pic1dp_ctx {
   // PIC1DP_CALL_PAIR=0: the three launches per step of rounds 2-4.
   int call_pair = 1;
   int64_t call_pair_skips = 0;   // solve_field calls of a half step served without a launch (kernel_stats 11)
-  // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step):
-  // 0 field_chargeden is current; 1 d_charge holds the summed charge1, its scaling is pending; 2 (one rank) the
-  // species accumulators hold the deposits, species sum and scaling pending; 3 (one rank, mode-filter solve, few
-  // modes) k_step_one's prediction accumulators hold the charge, combination with the kept modes, species sum and
-  // scaling pending; 4 (one rank, mode-filter solve) the six sums of the prediction are pending: the kept mode's
-  // content of chargeden follows from them.  materialize_cd() before anything else looks at charge, chargeden or the
-  // accumulators.
+  // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step): materialize_cd()
+  // before anything else looks at charge, chargeden or the accumulators.
   Owed owed = Owed::Nothing;
   // field_chargeden holds only the kept mode's content of the half-step charge density (collect_charge after a
   // noted push(1) served from the six sums, pred_kind 2): all solve_field looks at, but not what the reference
@@ -341,6 +337,12 @@ struct pic1dp_ctx {
 
 namespace pic1dp_host {
 
+// several ranks share the run: the layout says so, or a communicator exists
+inline bool several_ranks(const pic1dp_ctx *c) { return c->lay.nranks > 1 || c->comm != nullptr; }
+// ... and their charge is summed in FP64 (kind 0 of the charge sum; kind 1 sums exact integers in fx_settle, after which
+// the one-rank path runs)
+inline bool fp64_rank_sum(const pic1dp_ctx *c) { return c->charge_sum == 0 && several_ranks(c); }
+
 inline int ev_resolve(pic1dp_ctx *c) {
   if (c->ev_used == 0) return 0;
   HIP_TRY(hipStreamSynchronize(c->st));
@@ -416,7 +418,13 @@ int materialize(pic1dp_ctx *c);           // a noted push becomes memory
 int materialize_cd(pic1dp_ctx *c);        // what collect_charge left to the next solve_field becomes field_chargeden
 int rebuild_half_step_chargeden(pic1dp_ctx *c);  // the whole vector where only the kept mode's content was formed
 void field_written(pic1dp_ctx *c, bool by_solve);  // d_E changed: versions, what a noted push may still assume
-size_t step_lds_bytes(int nx, bool full, bool exact = false);  // dynamic LDS of a whole-step kernel (exact: kind 1's rho tile)
+int set_call_state(pic1dp_ctx *c, Seq seq, Owed owed);  // the one writer of the call sites' state: refuses pairs that cannot occur
+int set_seq(pic1dp_ctx *c, Seq seq);
+int set_owed(pic1dp_ctx *c, Owed owed);
+int settle_half_pair(pic1dp_ctx *c);      // call sites: the half-step field the pair solve left aside becomes field_electric (ctx.hpp half_pair)
+int settle_field_view(pic1dp_ctx *c);     // ... for readers of the field only
+int settle_step_start_field(pic1dp_ctx *c);  // field_electric <- the half-step field the second collect_charge left aside (e_step_start)
+int adopt_half_field(pic1dp_ctx *c);
 // ---- capi_comm.cpp ----
 int allreduce_charge(pic1dp_ctx *c);
 int allreduce_doubles(pic1dp_ctx *c, double *d, size_t n);
@@ -425,19 +433,12 @@ bool xchg_active(const pic1dp_ctx *c);
 XchgArgs next_xchg_args(pic1dp_ctx *c);
 int xchg_check(pic1dp_ctx *c);
 void comm_release(pic1dp_ctx *c);         // communicator and exchange mappings, for destroy
-int set_call_state(pic1dp_ctx *c, Seq seq, Owed owed);  // the one writer of the call sites' state: refuses pairs that cannot occur
-int set_seq(pic1dp_ctx *c, Seq seq);
-int set_owed(pic1dp_ctx *c, Owed owed);
-int settle_half_pair(pic1dp_ctx *c);      // call sites: the half-step field the pair solve left aside becomes field_electric (ctx.hpp half_pair)
-int settle_field_view(pic1dp_ctx *c);     // ... for readers of the field only
-int settle_step_start_field(pic1dp_ctx *c);  // field_electric <- the half-step field the second collect_charge left aside (e_step_start)
-int adopt_half_field(pic1dp_ctx *c);
-void optimize_release(pic1dp_ctx *c);     // the optimisation events' workers (streams, pinned and device staging), for destroy
+int xchg_vec(const pic1dp_ctx *c);      // vectors of nx doubles one exchange slot holds
 // ---- capi_optimize.cpp ----
 void optimize_due_at(const pic1dp_ctx *c, double time0, bool due[3]);  // which events a step starting at time0 fires
 void optimize_due(const pic1dp_ctx *c, bool due[3]);
 bool optimize_due_any(const pic1dp_ctx *c);
-int xchg_vec(const pic1dp_ctx *c);      // vectors of nx doubles one exchange slot holds
+void optimize_release(pic1dp_ctx *c);     // the optimisation events' workers (streams, pinned and device staging), for destroy
 // ---- exact_charge.cpp (kind 1 of the charge sum) ----
 FxArgs fx_args(const pic1dp_ctx *c, int isp);   // the marker kernels' exact accumulators of species isp (acc null in kind 0)
 int fx_settle(pic1dp_ctx *c);             // deposits -> summed over ranks -> the species accumulators (copy 0)

@@ -53,7 +53,7 @@ FxArgs fx_args(const pic1dp_ctx *c, int isp) {
 // one rank (k_charge_local / chargeden with the species sum): every rank forms the same doubles from the same integers.
 int fx_settle(pic1dp_ctx *c) {
   const int ns = c->in.nspecies, nx = c->in.nx;
-  if (c->lay.nranks > 1 || c->comm != nullptr) {
+  if (several_ranks(c)) {
     Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
     if (xchg_active(c)) {
       HIP_TRY(launch_fx_exchange(c->d_fx, ns, nx, next_xchg_args(c), c->st));

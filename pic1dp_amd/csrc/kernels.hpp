@@ -356,6 +356,13 @@ constexpr int PRED_MAX_MODES = PIC1DP_PRED_MAX_MODES;  // kept modes k_step_one'
 // pred_kind 2: the six sums (padded to 8) are kept in this many copies -- workgroup b of the marker kernel adds into
 // copy b % PRED_SUM_COPIES, the field kernels add the copies up: six addresses shared by all workgroups serialise
 constexpr int PRED_SUM_COPIES = 16;
+// dynamic LDS of the whole-step kernels k_step_half / k_step_full: E0 tile, Eh tile (full only), rho tile (exact: kind 1 of
+// the charge sum, two words per cell)
+inline size_t step_lds_bytes(int nx, bool full, bool exact = false) {
+  const size_t ne = static_cast<size_t>((nx + 2) & ~1);
+  return sizeof(double) * ((full ? 2 : 1) * ne + (exact ? 2 : 1) * ((static_cast<size_t>(nx) + 2) & ~static_cast<size_t>(1)) +
+                           2);  // (+ the drawn chunks' counter, 16-byte slot)
+}
 // dynamic LDS of k_step_sums: E0, A, B tiles (with guard cell), rho copies, reduction scratch
 inline size_t step_sums_lds_bytes(int nx) {
   const size_t ne = static_cast<size_t>((nx + 2) & ~1);

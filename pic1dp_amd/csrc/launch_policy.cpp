@@ -1,0 +1,126 @@
+// launch_policy.cpp -- launch shapes of the marker kernels (launch_policy.hpp): arithmetic only
+#include "launch_policy.hpp"
+
+#include <algorithm>
+
+namespace pic1dp {
+
+namespace {
+
+enum class Osub {
+  Never,    // the resident grid
+  IfAsked,  // a multiple of it only where PIC1DP_OSUB insists
+  Auto,     // ... or where the markers per workgroup allow it
+};
+
+// Grid of a marker kernel: `resident` workgroups fill the CUs; with a grid of exactly that size the kernel ends
+// when its slowest workgroup does, and the CUs do not all stream at the same rate.  A grid of several times that
+// size lets the CUs that finish early take more of the work (tools/ab_one_shapes.sh: k_step_one at 1e8 markers
+// 1.290 -> 1.238 ms with four times the resident workgroups) -- as long as a workgroup's share of the markers
+// dwarfs what it pays once (staging and flushing tiles of nx cells): about 48 markers per cell, at most x4.
+// Only where two workgroups share a CU (while one stages or flushes the other streams; alone on its CU a
+// workgroup's turn-over idles it: k_step_sums at nx 4096, 0.935 -> 1.004 ms with twice the grid), and not for
+// k_step_full, which measures 1-3 % slower that way (k_step_half 5 % faster; tools/ab_osub.sh).
+// PIC1DP_OSUB=n insists on a factor (1: the resident grid).
+int64_t oversubscribed(const LaunchPolicy &p, int nx, int64_t np, int64_t resident, Osub how) {
+  if (how == Osub::Never) return resident;
+  if (p.bpc_req > 0) return resident;  // a launch shape asked for by hand is taken literally
+  int64_t f = p.osub_req;
+  if (f <= 0 && how != Osub::Auto) return resident;
+  if (f <= 0) {
+    const int64_t per_wg = static_cast<int64_t>(48) * nx;
+    f = (np / per_wg + resident / 2) / std::max<int64_t>(resident, 1);
+  }
+  f = std::max<int64_t>(1, std::min<int64_t>(f, p.osub_req > 0 ? 64 : 4));
+  return resident * f;
+}
+
+// the tail of every shape: bpc workgroups on each CU are resident, the grid is that or a multiple of it, at most one
+// workgroup per `threads` marker pairs, at least one
+struct Grid {
+  int64_t resident;
+  int blocks;
+};
+Grid grid_of(const LaunchPolicy &p, int nx, int64_t np, int threads, int bpc, Osub how) {
+  const int64_t resident = static_cast<int64_t>(p.num_cu) * bpc;
+  const int64_t need = ((np >> 1) + threads - 1) / threads;
+  const int64_t blocks = std::max<int64_t>(1, std::min(oversubscribed(p, nx, np, resident, how), need));
+  return Grid{resident, static_cast<int>(blocks)};
+}
+
+// workgroups per CU of the sub-step and whole-step kernels: what the thread count suggests, what the LDS holds, what was
+// asked for by hand (within what the LDS holds)
+int workgroups_per_cu(const LaunchPolicy &p, int bpc, int by_lds) {
+  if (bpc > by_lds) bpc = by_lds;
+  if (p.bpc_req > 0) bpc = p.bpc_req < by_lds ? p.bpc_req : by_lds;
+  return bpc < 1 ? 1 : bpc;
+}
+
+}  // namespace
+
+LaunchCfg particle_launch(const LaunchPolicy &p, int nx, int64_t np, bool with_E, bool with_rho, bool exact) {
+  LaunchCfg lc{};
+  lc.lds = sizeof(double) * ((with_E ? static_cast<size_t>((nx + 2) & ~1) : 0) +
+                             (with_rho ? (exact ? 2 : 1) * (static_cast<size_t>(nx) + 1) : 0));  // + guard cell
+  int by_lds = lc.lds ? static_cast<int>(kCuLds / (lc.lds + kStaticLds)) : 8;
+  if (by_lds < 1) by_lds = 1;
+  int threads = p.threads_req > 0 ? p.threads_req : 512;
+  if (p.threads_req <= 0 && by_lds * threads < 2048) threads = 1024;
+  const int bpc = workgroups_per_cu(p, 2048 / threads, by_lds);
+  lc.threads = threads;
+  lc.blocks = grid_of(p, nx, np, threads, bpc, Osub::Never).blocks;
+  return lc;
+}
+
+LaunchCfg step_launch(const LaunchPolicy &p, int nx, int64_t np, bool full, bool exact) {
+  LaunchCfg lc{};
+  lc.lds = step_lds_bytes(nx, full, exact);
+  int by_lds = static_cast<int>(kCuLds / (lc.lds + kStaticLds));
+  if (by_lds < 1) by_lds = 1;
+  // two workgroups of 768 threads per CU (24 waves): measured inside one process
+  // (tools/ab_launch.py) best or within 1 % of best from 6.4e6 to 1e8 markers --
+  // fewer workgroups mean fewer LDS stagings and half as many global flush atomics
+  // as four workgroups of 512, which cost k_step_half 25 % at 6.4e6 and 15 % at 2e7
+  int threads = p.threads_req > 0 ? p.threads_req : 768;
+  if (p.threads_req <= 0 && by_lds < 2) threads = 1024;
+  const int bpc = workgroups_per_cu(p, p.threads_req > 0 ? 2048 / threads : (threads == 768 ? 2 : 1), by_lds);
+  lc.threads = threads;
+  lc.blocks = grid_of(p, nx, np, threads, bpc, !full && bpc >= 2 ? Osub::Auto : Osub::IfAsked).blocks;  // (not for k_step_full)
+  return lc;
+}
+
+LaunchCfg step_diag_launch(const LaunchPolicy &p, int nx, int64_t np, bool exact, int nx_opd, int nv_opd) {
+  LaunchCfg lc{};
+  lc.lds = step_lds_bytes(nx, true, exact) + step_diag_lds_bytes(nx, nx_opd, nv_opd);
+  lc.threads = 1024;
+  lc.blocks = grid_of(p, nx, np, lc.threads, 1, Osub::Never).blocks;
+  return lc;
+}
+
+PredLaunch pred_launch(const LaunchPolicy &p, int nx, int nmode, int64_t np, bool priv, int pred_kind, bool exp_bearing) {
+  LaunchCfg lc{};
+  lc.lds = priv ? step_one_private_lds_bytes(nx) : (pred_kind == 2 ? step_sums_lds_bytes(nx) : step_one_lds_bytes(nx, nmode));
+  bool two = 2 * (lc.lds + kStaticLds) <= kCuLds;  // both workgroups resident: each also holds the static exp table
+  int th2 = 768;
+  int th1 = 1024;
+  if (priv) {  // the private sums' slot stride is a compile-time constant: exactly that many threads
+    th2 = th1 = STEP_PRIVATE_THREADS;
+    if (STEP_PRIVATE_THREADS > 768) two = false;
+  }
+  if (pred_kind == 2 && !priv) {
+    // k_step_sums keeps its registers: four waves per SIMD with the exp-bearing distributions (one
+    // workgroup of 1024 per CU), eight with the others, which saturate the memory system with far fewer
+    // (tools/ab_sums_shapes.sh: 1e8 markers, Maxwellian, nx 4096: 512 x 1 0.925 ms, 1024 x 1 0.965 ms)
+    if (exp_bearing)
+      two = false;
+    else
+      th1 = 512;
+  }
+  lc.threads = p.threads_req > 0 ? p.threads_req : (two ? th2 : th1);
+  const int bpc = p.bpc_req > 0 ? p.bpc_req : (two ? 2 : 1);
+  const Grid g = grid_of(p, nx, np, lc.threads, bpc, bpc >= 2 ? Osub::Auto : Osub::IfAsked);
+  lc.blocks = g.blocks;
+  return PredLaunch{lc, g.resident};
+}
+
+}  // namespace pic1dp

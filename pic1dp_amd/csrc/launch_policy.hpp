@@ -1,0 +1,43 @@
+// launch_policy.hpp -- the launch shape of every marker kernel as a pure function of the device's size, the grid, the
+// marker count and three knobs.  No context, no HIP call: capi_step.cpp fills LaunchPolicy from the context and launches
+// what comes back; tests/test_launch_policy_host.py pins every shape on the host (include/pic1dp_probe.h).
+// The functions return a shape whose LDS exceeds PARTICLE_LDS_CAP as it is: the callers decide what to run instead.
+#pragma once
+#include "kernels.hpp"
+
+namespace pic1dp {
+
+constexpr size_t kCuLds = 160 * 1024, kStaticLds = 1024;  // LDS of a CU; static LDS of a marker kernel (the exp table)
+
+// what the policy needs from the context
+struct LaunchPolicy {
+  int num_cu;       // compute units of the device
+  int threads_req;  // pic1dp_hip_set_launch: threads per workgroup asked for by hand (0: the measured choice)
+  int bpc_req;      // ... and workgroups per CU (0: the measured choice)
+  int osub_req;     // PIC1DP_OSUB: grid size in units of the resident one (0: auto)
+};
+
+// a one-pass launch and the workgroups that fill the CUs (the grid is that, or a multiple: oversubscription)
+struct PredLaunch {
+  LaunchCfg lc;
+  int64_t resident;
+};
+
+// sub-step kernels (k_push, k_push<FUSED>, k_deposit): E tile and / or rho tile
+// exact: the rho tile of kind 1 of the charge sum (two words per cell)
+LaunchCfg particle_launch(const LaunchPolicy &p, int nx, int64_t np, bool with_E, bool with_rho, bool exact = false);
+// whole-step kernels k_step_half (full = false) and k_step_full
+LaunchCfg step_launch(const LaunchPolicy &p, int nx, int64_t np, bool full, bool exact);
+// k_step_full<DIAG>: one workgroup of 1024 threads per CU, grid tiles + the histograms of nx_opd x nv_opd cells in its LDS
+LaunchCfg step_diag_launch(const LaunchPolicy &p, int nx, int64_t np, bool exact, int nx_opd, int nv_opd);
+// the one-pass kernels: k_step_one (pred_kind 1, nmode kept modes), k_step_sums (pred_kind 2; exp_bearing: the
+// distribution's -f0'/f0 bears an exp) and k_step_one<PRIV> (priv)
+PredLaunch pred_launch(const LaunchPolicy &p, int nx, int nmode, int64_t np, bool priv, int pred_kind, bool exp_bearing);
+// may the prologue of this one-pass launch solve the previous step's field (kernels.hpp FusedSolve)?  It needs a first and
+// a last wave of its own (lean_forward_sums runs its chains in wave 0 while the last wave adds up the copies of the six
+// sums), and a grid within the resident one: EVERY workgroup runs the solve, an oversubscribed grid pays it per round
+inline bool fits_fused_solve(const PredLaunch &pl) {
+  return pl.lc.blocks <= pl.resident && pl.lc.threads >= 128 && pl.lc.threads % 64 == 0;
+}
+
+}  // namespace pic1dp

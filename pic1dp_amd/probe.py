@@ -20,6 +20,13 @@ class Species(C.Structure):
                 ("v0", C.c_double)]
 
 
+class LaunchQuery(C.Structure):
+    """struct pic1dp_probe_launch_query: what the launch policy sees of the context, a kernel family and its arguments"""
+    _fields_ = [(n, C.c_int32) for n in ("num_cu", "threads_req", "bpc_req", "osub_req", "family", "nx", "nmode")] + [
+        ("np", C.c_int64)] + [(n, C.c_int32) for n in ("full", "exact", "with_E", "with_rho", "priv", "pred_kind",
+                                                       "exp_bearing", "nx_opd", "nv_opd")]
+
+
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 _I32 = C.POINTER(C.c_int32)
@@ -41,6 +48,7 @@ SIGNATURES = {
     "pic1dp_probe_fx_raise": [C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, _D],
     "pic1dp_probe_species_const": [_SP, _I32, _I32, _I32, _I32, _D],
     "pic1dp_probe_dlnf0": [C.c_int32, _SP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
+    "pic1dp_probe_host_launch_shape": [C.POINTER(LaunchQuery), _I64],
 }
 
 _lib = None
@@ -172,3 +180,12 @@ def host_optimize_mismatches(kind, np_, nalloc, threshold, seed=1, typeremove=2,
     _check(load().pic1dp_probe_host_optimize(kind, typeremove, nx, nv, split_ngroup, threshold, seed, int(np_), int(nalloc),
                                              C.byref(m), C.byref(after)))
     return m.value, after.value
+
+
+def host_launch_shape(**query):
+    """(threads, blocks, LDS bytes, resident workgroups) the library's launch policy picks (csrc/launch_policy.hpp), on the
+    host; keywords: the fields of LaunchQuery (the others 0)"""
+    out = (C.c_int64 * 4)()
+    if load().pic1dp_probe_host_launch_shape(C.byref(LaunchQuery(**query)), out) != 0:
+        raise ValueError("pic1dp_probe_host_launch_shape: unknown family %r" % (query.get("family"),))
+    return tuple(out)
