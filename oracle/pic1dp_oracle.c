@@ -837,7 +837,9 @@ void orc_dist_pertb_abs_v(const orc_input *in, int64_t np, const double *v,
     int iv = (int)floor(sv);
     sv = 1.0 - (sv - (double)iv);
     hist[iv] = hist[iv] + sv * fabs(w[ip]);
-    hist[iv + 1] = hist[iv + 1] + (1.0 - sv) * fabs(w[ip]);
+    /* a velocity just below v_max can land on the last node exactly (sv rounds to nv - 1): the reference then adds
+     * (1 - 1) |w| = 0 one element past its array; that element does not exist here */
+    if (iv + 1 < nv) hist[iv + 1] = hist[iv + 1] + (1.0 - sv) * fabs(w[ip]);
   }
 }
 
@@ -852,15 +854,19 @@ static double hist_max(const orc_input *in, const double *hist) {
 static double df_at(const orc_input *in, const double *hist, double v, int *iv_out) {
   const int nv = in->nv;
   double sv = (v + in->v_max) / (in->v_max * 2.0) * (double)(nv - 1);
-  int iv = (int)floor(sv);
+  /* the branches are taken on the double: floor(sv, kpi) of a velocity far outside overflows the integer in the
+   * reference (undefined there); here such a marker takes the end value of its side */
+  const double fl = floor(sv);
+  int iv;
   double df;
-  if (iv < 0) {
+  if (fl < 0.0) {
     iv = 0;
     df = hist[iv];
-  } else if (iv >= nv - 1) {
+  } else if (fl >= (double)(nv - 1)) {
     iv = nv - 1;
     df = hist[iv];
   } else {
+    iv = (int)fl;
     sv = 1.0 - (sv - (double)iv);
     df = hist[iv] * sv + hist[iv + 1] * (1.0 - sv);
   }

@@ -20,15 +20,17 @@ struct VGrid {
   double at(double v, int &cell) const {
     const int last = in.nv - 1;
     const double pos = (v + in.v_max) / (in.v_max * 2.0) * static_cast<double>(last);
-    const int c = static_cast<int>(std::floor(pos));
-    if (c < 0) {
+    const double fl = std::floor(pos);
+    // (the comparison on the double, as kernels_opt.hip opt_df: a velocity far outside must not overflow the conversion)
+    if (fl < 0.0) {
       cell = 0;
       return hist[0];
     }
-    if (c >= last) {
+    if (fl >= static_cast<double>(last)) {
       cell = last;
       return hist[last];
     }
+    const int c = static_cast<int>(fl);
     cell = c;
     const double left = 1.0 - (pos - static_cast<double>(c));
     return hist[c] * left + hist[c + 1] * (1.0 - left);
@@ -61,7 +63,9 @@ void opt_histogram(const pic1dp_input &in, int64_t np, const double *v, const do
     const double left = 1.0 - (pos - static_cast<double>(c));
     const double a = std::fabs(w[k]);
     hist[c] = hist[c] + left * a;
-    hist[c + 1] = hist[c + 1] + (1.0 - left) * a;
+    // a velocity just below v_max can land on the last node exactly (pos rounds to nv - 1): its right-hand share is
+    // (1 - 1) a = 0 and has no bin (the device path's dump bin, kernels_opt.hip k_opt_hist_items)
+    if (c + 1 < in.nv) hist[c + 1] = hist[c + 1] + (1.0 - left) * a;
   }
 }
 

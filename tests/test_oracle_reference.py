@@ -24,7 +24,7 @@ def live(oracle, case):
 
 def test_cases_cover_the_shared_distributions(oracle_mod):
     """the cases the comparison is made for: the seven shared distributions, linear, full-f, two species, three kept
-    modes on an odd grid, the shape arrays, and merge + remove (both types) + split events"""
+    modes on an odd grid, the shape arrays, and merge + remove (both types) + split events, with one and two species"""
     from conftest import DIST_CASES
     for name, kw in DIST_CASES:
         got = oracle_mod.ref_case_kwargs(name)
@@ -36,6 +36,10 @@ def test_cases_cover_the_shared_distributions(oracle_mod):
     assert v("shape3")["iptclshape"] == 3
     assert v("optimize")["nmerge"] and v("optimize")["nremove"] and v("optimize")["nsplit"]
     assert {v("optimize")["typeremove"], v("optimize_threshold")["typeremove"]} == {1, 2}
+    two = v("optimize_two_species")
+    assert two["nspecies"] == 2 and two["species_charge"] == [-1.0, 1.0] and two["species_mass"] == [1.0, 4.0]
+    assert two["nmerge"] and two["nremove"] and two["nsplit"] and two["typeremove"] == 2 and two["iptcldist"] == 0
+    assert two["tmerge"][0] == two["tremove"][0] == two["tsplit"][0] == 0.3
     for name in CASES:
         assert v(name + "_small")["nparticle_max"] <= 4096
 
