@@ -89,6 +89,14 @@ typedef struct pic1dp_probe_launch_query {
 } pic1dp_probe_launch_query;
 int pic1dp_probe_host_launch_shape(const pic1dp_probe_launch_query *q, int64_t shape[4]);
 
+/* The dynamic LDS and the workgroup size of a one-workgroup field launch (pic1dp_amd/csrc/field_lds.hpp: the layout the
+ * kernel itself takes its pointers from), on the HOST: no GPU needed.  family 0: k_field_solve and its _pred, _pred_sums,
+ * _xchg siblings (nx, nmode, tab_lds); family 1: what launch_field_solve_pair runs for (nx, nmode, npe, tab_lds, with_xchg:
+ * the one-hop exchange inside the launch, pred_kind 1 tiles / 2 sums).  out = {bytes, threads, kernel: 0 k_field_solve...,
+ * 1 k_field_solve_pair, 2 k_field_solve_pair1, 3 k_field_solve_pair_sums1}.  Nonzero: null argument or unknown family. */
+int pic1dp_probe_host_field_lds(int32_t family, int32_t nx, int32_t nmode, int32_t npe, int32_t tab_lds, int32_t with_xchg,
+                                int32_t pred_kind, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

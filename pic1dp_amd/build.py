@@ -35,7 +35,7 @@ PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_st
 PROBE_UNITS = [("probe.hip", [], "probe"), ("optcheck.cpp", [], "optcheck"), ("policy_probe.cpp", [], "policy_probe")]
 PROBE_SHARED = ["species", "hostcheck", "optimize", "multirand", "launch_policy"]      # objects of the product the probe library links as well
 HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "loader.hpp",
-           "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "launch_policy.hpp",
+           "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "launch_policy.hpp", "field_lds.hpp",
            os.path.join("..", "..", "include", "pic1dp_hip.h"), os.path.join("..", "..", "include", "pic1dp_probe.h")]
 
 # -ffp-contract=off : products and sums round separately, like the reference's

@@ -1,6 +1,9 @@
-// device_field.hpp -- the pieces of the mode-filter solve (src/pic1dp_field.F90:218-257) that more than one
-// translation unit runs: the field kernels (kernels_field.hip) and the whole-step marker kernels whose prologue
-// solves the field of the previous step itself (kernels_step.hip, FUSED).  Same functions, hence the same bits.
+// device_field.hpp -- every stage of the grid side that more than one kernel runs, each written ONCE: the species sum of
+// the charge and its scaling, the consuming reads of the prediction accumulators, the mode-filter solve
+// (src/pic1dp_field.F90:218-257) from its serial forward sums to the scaling of a kept mode, the one-mode inverse and the
+// field energy.  Called by the field kernels (kernels_field.hip, kernels_fft.hip) and by the whole-step marker kernels
+// whose prologue solves the field of the previous step itself (kernels_step.hip, FUSED).  Same functions, hence the same
+// bits: the reference's lines are cited here, at the one function that restates them.
 #pragma once
 #include "device_math.hpp"
 
@@ -21,7 +24,95 @@ __device__ __forceinline__ double chargeden_from(const FieldArgs &f, double char
   return cd;
 }
 
+// ---- the charge of one grid point from the species accumulators ----
+// charge2(:) = charge2(:) + charge1(:)*Z over species, from 0 (src/pic1dp_interaction.F90:81,126-127); charge1 of a
+// species: copy 0 first, then the copies the workgroups flushed into, ascending.  The order is part of the result.
+__device__ __forceinline__ double charge_local_read(const FieldArgs &f, int ix) {
+  const int nx = f.nx;
+  double c2 = 0.0;
+  for (int s = 0; s < f.nspecies; ++s) {
+    const double *r = f.rho_sp + static_cast<size_t>(s) * nx + ix;
+    double c1 = *r;
+    for (int g = 1; g < f.rho_copies; ++g) c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
+    c2 = c2 + c1 * f.Z[s];
+  }
+  return c2;
+}
+// the accumulators are consumed: zero for the next deposit
+__device__ __forceinline__ void charge_local_zero(const FieldArgs &f, int ix) {
+  const int nx = f.nx;
+  for (int s = 0; s < f.nspecies; ++s) {
+    double *r = f.rho_sp + static_cast<size_t>(s) * nx + ix;
+    for (int g = 0; g < f.rho_copies; ++g) r[static_cast<size_t>(g) * f.rho_stride] = 0.0;
+  }
+}
+__device__ __forceinline__ double charge_local_one(const FieldArgs &f, int ix) {
+  const double c2 = charge_local_read(f, ix);
+  charge_local_zero(f, ix);
+  f.charge[ix] = c2;
+  return c2;
+}
+
+// ---- prediction as tiles (k_step_one): pred = [nspecies][1 + 2 nm_pred][nx] slices R0, RA_m, RB_m, consumed (re-zeroed) ----
+// this rank's charge2 of the next step's first sub-step at grid point ix,
+//   charge2_h = sum_s Z_s * (R0_s + sum_m re_m RA_sm + im_m RB_sm),   re / im = the kept modes of the field the markers
+// were just advanced to
+__device__ __forceinline__ double pred_combine_take(const FieldArgs &f, double *pred, int nm_pred, int ix, const double *re,
+                                                    const double *im) {
+  const int nx = f.nx, np1 = 1 + 2 * nm_pred;
+  double c2 = 0.0;
+  for (int s = 0; s < f.nspecies; ++s) {
+    double *r = pred + static_cast<size_t>(s) * np1 * nx + ix;
+    double c1 = r[0];
+    r[0] = 0.0;
+    for (int m = 0; m < nm_pred; ++m) {
+      double *ra = r + static_cast<size_t>(1 + m) * nx, *rb = r + static_cast<size_t>(1 + nm_pred + m) * nx;
+      c1 = c1 + re[m] * *ra;
+      c1 = c1 + im[m] * *rb;
+      *ra = 0.0;
+      *rb = 0.0;
+    }
+    c2 = c2 + c1 * f.Z[s];
+  }
+  return c2;
+}
+// slice k (of np1) summed over species with Z, for a sum over ranks BEFORE the combination with the kept modes (it is
+// linear, so the species sum and the sum over ranks commute with it)
+__device__ __forceinline__ double pred_pack_take(const FieldArgs &f, double *pred, int np1, int k, int ix) {
+  double c2 = 0.0;
+  for (int s = 0; s < f.nspecies; ++s) {
+    double *r = pred + (static_cast<size_t>(s) * np1 + k) * f.nx + ix;
+    c2 = c2 + *r * f.Z[s];
+    *r = 0.0;
+  }
+  return c2;
+}
+
+// ---- kind 1 of the charge sum (kernels.hpp FxArgs): the exact accumulators [nspecies][2][nx] (hi row, lo row) ----
+// element k of [nspecies][nx]: the carry of the low limb moves into the high one
+__device__ __forceinline__ void fx_normalise_one(long long *acc, int nx, int k) {
+  long long *hi = acc + static_cast<size_t>(k / nx) * 2 * nx + k % nx, *lo = hi + nx;
+  const unsigned long long l = static_cast<unsigned long long>(*lo);
+  *hi = *hi + static_cast<long long>(l >> 32);
+  *lo = static_cast<long long>(l & 0xffffffffull);
+}
+
 // ---- prediction as six sums (k_step_sums) ----
+// The six sums arrive in PRED_SUM_COPIES copies (kernels.hpp: workgroup b of the marker kernel adds into copy
+// b % PRED_SUM_COPIES -- six addresses shared by every workgroup serialise their atomics at the L2 when the
+// workgroups finish together: 29 us of a 140 us kernel at 1e7 markers).  Sum k over the copies, in copy order, all
+// loads in flight at once; the copies are re-zeroed (consumed).
+__device__ __forceinline__ double pred_sum_take(double *pred, int k) {
+  double t[PRED_SUM_COPIES];
+#pragma unroll
+  for (int c = 0; c < PRED_SUM_COPIES; ++c) t[c] = pred[c * 8 + k];
+#pragma unroll
+  for (int c = 0; c < PRED_SUM_COPIES; ++c) pred[c * 8 + k] = 0.0;
+  double acc = t[0];
+#pragma unroll
+  for (int c = 1; c < PRED_SUM_COPIES; ++c) acc = acc + t[c];
+  return acc;
+}
 // The forward sums sum_c fre[c] cd_h[c], sum_c fim[c] cd_h[c] of the NEXT first sub-step's charge density
 // from the six sums K (summed over species with Z, and over ranks) and the kept mode (re, im) of the field the
 // markers were just advanced to (derivation at k_step_sums); PredTab: what the host knows of the tables
@@ -32,6 +123,52 @@ __device__ __forceinline__ void pred_forward_sums(const FieldArgs &f, const Pred
     for (int s = 0; s < f.nspecies; ++s) off = off + f.Z[s] * f.n0[s];  // chargeden -= Z n0, :142-148
   acc_c = 0.5 * (K[0] + re * K[1] + im * K[2]) * f.dnx / f.lx - off * pt.sum_fre;
   acc_s = 0.5 * (K[3] + re * K[4] + im * K[5]) * f.dnx / f.lx - off * pt.sum_fim;
+}
+
+// the kept mode's content of that charge density, cd[c] = alpha fre[c] + beta fim[c] with sum fre cd = acc_c, sum fim cd =
+// acc_s (the Gram matrix of the two tables: PredTab), from which the ordinary solve reproduces the predicted Eh to rounding
+__device__ __forceinline__ void pred_cd_coeffs(const PredTab &pt, double ac, double as, double &alpha, double &beta) {
+  const double det = pt.g11 * pt.g22 - pt.g12 * pt.g12;
+  alpha = (ac * pt.g22 - as * pt.g12) / det;
+  beta = (as * pt.g11 - ac * pt.g12) / det;
+}
+
+// ---- from a forward sum to a kept mode, and back to the grid ----
+// src/pic1dp_field.F90:234/:239 VecScale by -1/nx resp. 1/nx, then :243-247 times 1/k (ginv = grad_inv of the mode).
+// use_cos: the sum over the cos table, which gives mode_im; otherwise the -sin table's, which gives mode_re
+__device__ __forceinline__ double mode_scale(const FieldArgs &f, bool use_cos, double acc, double ginv) {
+  return use_cos ? acc * f.sc_im * ginv : acc * f.sc_re * ginv;
+}
+// ... stored as kept mode m of nm: into sMode = [re(nm) | im(nm)] and, where to_memory, into f.mode_re / f.mode_im.  (nm from
+// the caller, who has it in a register or as a constant: this runs right behind the serial sums, on the critical path of a
+// latency-bound launch, where a fresh scalar load of f.nmode costs the pair kernels a microsecond)
+__device__ __forceinline__ void mode_store(const FieldArgs &f, double *sMode, int nm, int m, bool use_cos, double acc, double ginv,
+                                           bool to_memory = true) {
+  if (use_cos) {
+    const double im = mode_scale(f, true, acc, ginv);
+    sMode[nm + m] = im;
+    if (to_memory) f.mode_im[m] = im;
+  } else {
+    const double re = mode_scale(f, false, acc, ginv);
+    sMode[m] = re;
+    if (to_memory) f.mode_re[m] = re;
+  }
+}
+// inverse of ONE kept mode at a grid point, E = 2*(Fre*mode_re + Fim*mode_im), :251-256: from zero, every product rounded
+__device__ __forceinline__ double inverse_one_mode(double tr, double ti, double re, double im) {
+  double s = 0.0;
+  s = s + tr * re;
+  s = s + ti * im;
+  return s * 2.0;
+}
+// int E^2 dx from every thread's share e2 of sum E^2, as src/pic1dp_output.F90:120-124 forms it (the norm, squared again).
+// Called by EVERY thread of the workgroup (block_sum meets at barriers); sScr: [16]
+__device__ __forceinline__ void field_energy_store(double e2, double *sScr, double lx, double dnx, double *out) {
+  const double tot = block_sum(e2, sScr);
+  if (threadIdx.x == 0) {
+    const double nrm = sqrt(tot);
+    *out = nrm * nrm * lx / dnx;
+  }
 }
 
 // sum of prod[0..nx) in ascending order, one lane, bit-identical to the sequential loop.

@@ -423,7 +423,7 @@ struct PairArgs {
 };
 // doubles k_charge_pack writes / one exchange of a one-pass step carries per rank:
 // kind 1: charge2 + the 1 + 2 nmode Z-weighted prediction slices; kind 2: charge2 + the six sums (padded to 8)
-inline size_t pack_doubles(int nx, int nmode, int kind) {
+constexpr size_t pack_doubles(int nx, int nmode, int kind) {  // (constexpr: host and device, field_lds.hpp)
   return kind == 2 ? static_cast<size_t>(nx) + 8 : static_cast<size_t>(2 + 2 * nmode) * nx;
 }
 // this rank's charge2 and prediction packed for one all-reduce (accumulators re-zeroed)

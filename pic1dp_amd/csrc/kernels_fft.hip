@@ -6,6 +6,7 @@
 // nx even: the nx real points are packed into n = nx / 2 complex ones, z[j] = rho[2j] + i rho[2j+1], and untangled after
 // the transform (and the other way round for E); nx odd: n = nx complex points with zero imaginary parts.  One launch:
 // forward FFT, kept-mode pick and scaling, the Hermitian spectrum of E, inverse FFT, E, int E^2 dx.
+#include "device_field.hpp"
 #include "device_math.hpp"
 
 #include <cmath>
@@ -137,11 +138,11 @@ __device__ __forceinline__ double2 spectrum_bin(const FftArgs &p, const double2 
   return x;
 }
 
-// kept mode m as the direct solve scales it (kernels_field.hip solve_body): R = Re X, I = Im X of its bin,
-// mode_re = I sc_re grad_inv, mode_im = R sc_im grad_inv -- as (re, im)
+// kept mode m as the direct solve scales it (device_field.hpp mode_scale): R = Re X, I = Im X of its bin,
+// mode_re from I, mode_im from R -- as (re, im)
 __device__ __forceinline__ double2 kept_mode(const FieldArgs &f, const FftArgs &p, const double2 *Zc, int m) {
   const double2 x = spectrum_bin(p, Zc, f.nx, p.mode_bin[m]);
-  return double2{x.y * f.sc_re * f.grad_inv[m], x.x * f.sc_im * f.grad_inv[m]};
+  return double2{mode_scale(f, false, x.y, f.grad_inv[m]), mode_scale(f, true, x.x, f.grad_inv[m])};
 }
 
 // bin k (< nx) of the Hermitian spectrum of E = 2 sum_m (re_m cos - im_m sin)(2 pi m ix / nx) = sum_k S[k] e^{+2 pi i k ix / nx}:
@@ -204,13 +205,7 @@ __global__ void __launch_bounds__(FFT_THREADS) k_field_fft(const FieldArgs f, co
       e2 += y.x * y.x;
     }
   }
-  if (f.history) {  // int E^2 dx, src/pic1dp_output.F90:120-124 (as k_field_energy)
-    const double tot = block_sum(e2, sScr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(tot);
-      *f.history = nrm * nrm * f.lx / f.dnx;
-    }
-  }
+  if (f.history) field_energy_store(e2, sScr, f.lx, f.dnx, f.history);
 }
 
 size_t fft_lds_bytes(int n) { return 2 * sizeof(double2) * static_cast<size_t>(fft_pad(n - 1) + 1) + 16 * sizeof(double); }

@@ -1,7 +1,10 @@
 // kernels_field.hip -- the grid side of the hot path: species sum and scaling of the charge, the mode-filter
 // partial-DFT solve (src/pic1dp_field.F90:218-257) in its one-workgroup and wide forms, the paired solves of a
 // one-pass step, the one-hop charge exchange, the opt-in finite-difference solver.  gfx950, wave64.
+// The kernels here are what runs in which order and what stays in flight; the stages they share are device_field.hpp's,
+// and the dynamic LDS of the solves is field_lds.hpp's, for the kernel and for its launcher alike.
 #include "device_field.hpp"
+#include "field_lds.hpp"
 #include "device_math.hpp"
 #include "device_xchg.hpp"
 
@@ -13,25 +16,6 @@ namespace pic1dp {
 // field kernels (nx <= a few thousand: one workgroup, latency-bound, tiny)
 // ---------------------------------------------------------------------------
 namespace {
-
-constexpr int FIELD_THREADS = 256;
-// charge2(:) = charge2(:) + charge1(:)*Z over species, from 0
-// (src/pic1dp_interaction.F90:81,126-127); accumulators are re-zeroed
-__device__ __forceinline__ double charge_local_one(const FieldArgs &f, int ix) {
-  double c2 = 0.0;
-  for (int s = 0; s < f.nspecies; ++s) {
-    double *r = f.rho_sp + static_cast<size_t>(s) * f.nx + ix;
-    double c1 = *r;
-    *r = 0.0;
-    for (int g = 1; g < f.rho_copies; ++g) {  // the copies the workgroups flushed into
-      c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
-      r[static_cast<size_t>(g) * f.rho_stride] = 0.0;
-    }
-    c2 = c2 + c1 * f.Z[s];
-  }
-  f.charge[ix] = c2;
-  return c2;
-}
 
 __global__ void __launch_bounds__(FIELD_THREADS) k_charge_local(const FieldArgs f) {
   for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) charge_local_one(f, ix);
@@ -46,12 +30,7 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_chargeden(const FieldArgs f) 
 // ---- kind 1 of the charge sum (kernels.hpp FxArgs): the exact accumulators [nspecies][2][nx] (hi row, lo row) ----
 __global__ void __launch_bounds__(FIELD_THREADS) k_fx_normalise(long long *acc, int nspecies, int nx) {
   const int n = nspecies * nx;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
-    long long *hi = acc + static_cast<size_t>(k / nx) * 2 * nx + k % nx, *lo = hi + nx;
-    const unsigned long long l = static_cast<unsigned long long>(*lo);
-    *hi = *hi + static_cast<long long>(l >> 32);
-    *lo = static_cast<long long>(l & 0xffffffffull);
-  }
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) fx_normalise_one(acc, nx, k);
 }
 // rho_sp copy 0 <- each species' total as the nearest double times 2^e_s (exact); acc re-zeroed.  From here on the FP64
 // path runs as in kind 0: charge_local_one, chargeden_from, the solve.
@@ -71,86 +50,44 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_fx_to_rho(long long *acc, dou
 // the packet over the ranks of the one-hop exchange: normalised, posted into every rank's slot, added up (one workgroup)
 __global__ void __launch_bounds__(FIELD_THREADS) k_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs x) {
   const int n = 2 * nspecies * nx;
-  for (int k = threadIdx.x; k < nspecies * nx; k += blockDim.x) {
-    long long *hi = acc + static_cast<size_t>(k / nx) * 2 * nx + k % nx, *lo = hi + nx;
-    const unsigned long long l = static_cast<unsigned long long>(*lo);
-    *hi = *hi + static_cast<long long>(l >> 32);
-    *lo = static_cast<long long>(l & 0xffffffffull);
-  }
+  for (int k = threadIdx.x; k < nspecies * nx; k += blockDim.x) fx_normalise_one(acc, nx, k);
   __syncthreads();
   exchange_post(x, reinterpret_cast<const double *>(acc), n);
   exchange_wait_sum_i64(x, acc, n);
 }
 
-// k_step_one's prediction turned into this rank's charge2 of the next step's first sub-step:
-//   charge2_h = sum_s Z_s * (R0_s + sum_m re_m RA_sm + im_m RB_sm),   re / im = the kept modes of the
-// field the markers were just advanced to.  The accumulators are consumed (re-zeroed).  The caller
+// k_step_one's prediction turned into this rank's charge2 of the next step's first sub-step (pred_combine_take, with
+// the kept modes of the field as it is).  The accumulators are consumed (re-zeroed).  The caller
 // reduces f.charge over ranks and scales it (k_chargeden<false>) like any other charge2.
 __global__ void __launch_bounds__(FIELD_THREADS) k_pred_combine(const FieldArgs f, double *pred, int nm_pred) {
-  const int nx = f.nx, np1 = 1 + 2 * nm_pred;
-  for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
-    double c2 = 0.0;
-    for (int s = 0; s < f.nspecies; ++s) {
-      double *r = pred + static_cast<size_t>(s) * np1 * nx + ix;
-      double c1 = r[0];
-      r[0] = 0.0;
-      for (int m = 0; m < nm_pred; ++m) {
-        double *ra = r + static_cast<size_t>(1 + m) * nx, *rb = r + static_cast<size_t>(1 + nm_pred + m) * nx;
-        c1 = c1 + f.mode_re[m] * *ra;
-        c1 = c1 + f.mode_im[m] * *rb;
-        *ra = 0.0;
-        *rb = 0.0;
-      }
-      c2 = c2 + c1 * f.Z[s];
-    }
-    f.charge[ix] = c2;
-  }
+  for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x)
+    f.charge[ix] = pred_combine_take(f, pred, nm_pred, ix, f.mode_re, f.mode_im);
 }
 
 // RCCL path of a one-pass step: everything this rank contributes to the two charge sums of the step,
 // packed for ONE all-reduce: pack[0] = charge2 of the new state, pack[1 + k] = sum_s Z_s * (R0, RA_m, RB_m)_s
-// (the combination with the kept modes is linear, so the species sum and the sum over ranks commute with it).
-__global__ void __launch_bounds__(FIELD_THREADS) k_charge_pack(const FieldArgs f, double *pred, int nm_pred, double *pack) {
-  const int nx = f.nx, np1 = 1 + 2 * nm_pred;
+// (pred_pack_take).
+// v: [1 + np1][nx], memory or LDS
+__device__ __forceinline__ void charge_pack_fill(const FieldArgs &f, double *pred, int np1, double *v) {
+  const int nx = f.nx;
   for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
-    pack[ix] = charge_local_one(f, ix);
-    for (int k = 0; k < np1; ++k) {
-      double c2 = 0.0;
-      for (int s = 0; s < f.nspecies; ++s) {
-        double *r = pred + (static_cast<size_t>(s) * np1 + k) * nx + ix;
-        c2 = c2 + *r * f.Z[s];
-        *r = 0.0;
-      }
-      pack[static_cast<size_t>(1 + k) * nx + ix] = c2;
-    }
+    v[ix] = charge_local_one(f, ix);
+    for (int k = 0; k < np1; ++k) v[static_cast<size_t>(1 + k) * nx + ix] = pred_pack_take(f, pred, np1, k, ix);
   }
 }
-
-// The six sums arrive in PRED_SUM_COPIES copies (kernels.hpp: workgroup b of the marker kernel adds into copy
-// b % PRED_SUM_COPIES -- six addresses shared by every workgroup serialise their atomics at the L2 when the
-// workgroups finish together: 29 us of a 140 us kernel at 1e7 markers).  Sum k over the copies, in copy order, all
-// loads in flight at once; the copies are re-zeroed (consumed).
-__device__ __forceinline__ double pred_sum_take(double *pred, int k) {
-  double t[PRED_SUM_COPIES];
-#pragma unroll
-  for (int c = 0; c < PRED_SUM_COPIES; ++c) t[c] = pred[c * 8 + k];
-#pragma unroll
-  for (int c = 0; c < PRED_SUM_COPIES; ++c) pred[c * 8 + k] = 0.0;
-  double acc = t[0];
-#pragma unroll
-  for (int c = 1; c < PRED_SUM_COPIES; ++c) acc = acc + t[c];
-  return acc;
+__global__ void __launch_bounds__(FIELD_THREADS) k_charge_pack(const FieldArgs f, double *pred, int nm_pred, double *pack) {
+  charge_pack_fill(f, pred, 1 + 2 * nm_pred, pack);
 }
 
 // Call-site path: collect_charge after a noted push(1).  The host will call solve_field next, which works
-// from field_chargeden -- so chargeden gets the kept mode's content of the half-step charge density,
-//     cd[c] = alpha fre[c] + beta fim[c]   with   sum fre cd = acc_c,  sum fim cd = acc_s,
+// from field_chargeden -- so chargeden gets the kept mode's content of the half-step charge density (pred_cd_coeffs),
 // from which the ordinary solve reproduces the predicted Eh (to rounding).  What the filter drops is absent
 // from this chargeden; nothing in the reference driver reads chargeden between the sub-steps.
 // One rank: pred = this rank's copies of the six sums (consumed), K null.  Several ranks: pred null, K the six sums
-// already summed over ranks.
-__global__ void __launch_bounds__(FIELD_THREADS) k_pred_chargeden(const FieldArgs f, const PredTab pt, double *pred,
-                                                                 const double *K) {
+// already summed over ranks.  sCD: null, or an LDS copy of the chargeden.  Meets at barriers; behind the last one
+// nobody reads f.mode_re / f.mode_im any more (only thread 0 did).
+__device__ __forceinline__ void pred_chargeden_fill(const FieldArgs &f, const PredTab &pt, double *pred, const double *K,
+                                                    double *sCD) {
   __shared__ double sab[2];
   __shared__ double sK[8];
   if (threadIdx.x < 8) sK[threadIdx.x] = pred ? pred_sum_take(pred, threadIdx.x) : K[threadIdx.x];
@@ -158,18 +95,20 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_pred_chargeden(const FieldArg
   if (threadIdx.x == 0) {
     double ac, as;
     pred_forward_sums(f, pt, sK, f.mode_re[0], f.mode_im[0], ac, as);
-    const double det = pt.g11 * pt.g22 - pt.g12 * pt.g12;
-    sab[0] = (ac * pt.g22 - as * pt.g12) / det;
-    sab[1] = (as * pt.g11 - ac * pt.g12) / det;
+    pred_cd_coeffs(pt, ac, as, sab[0], sab[1]);
   }
   __syncthreads();
   const double alpha = sab[0], beta = sab[1];
-  for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) f.chargeden[ix] = alpha * f.fre[ix] + beta * f.fim[ix];
+  for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) {
+    const double cd = alpha * f.fre[ix] + beta * f.fim[ix];
+    f.chargeden[ix] = cd;
+    if (sCD) sCD[ix] = cd;
+  }
 }
-
-// k_pred_chargeden and the mode-filter solve in one launch (call sites, one rank: collect_charge after a noted
-// push(1) leaves both to the solve_field that follows)
-__global__ void __launch_bounds__(FIELD_THREADS) k_field_solve_pred_sums(const FieldArgs f, const PredTab pt, double *pred);
+__global__ void __launch_bounds__(FIELD_THREADS) k_pred_chargeden(const FieldArgs f, const PredTab pt, double *pred,
+                                                                 const double *K) {
+  pred_chargeden_fill(f, pt, pred, K, nullptr);
+}
 
 // this rank's six sums into the head of f.charge (rest zero) for a reduction over ranks (call-site path)
 __global__ void __launch_bounds__(FIELD_THREADS) k_pred_to_charge(const FieldArgs f, double *pred) {
@@ -207,13 +146,8 @@ __device__ __forceinline__ void solve_fill_chargeden(const FieldArgs &f, double 
       if (ix < nx) {
         if constexpr (FROM_CD) {
           c[u] = f.chargeden[ix];
-        } else if constexpr (WITH_LOCAL) {  // src/pic1dp_interaction.F90:126-127
-          for (int sp = 0; sp < f.nspecies; ++sp) {
-            const double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
-            double c1 = *r;
-            for (int g = 1; g < f.rho_copies; ++g) c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
-            c[u] = c[u] + c1 * f.Z[sp];
-          }
+        } else if constexpr (WITH_LOCAL) {
+          c[u] = charge_local_read(f, ix);
         } else {
           c[u] = f.charge[ix];
         }
@@ -226,9 +160,7 @@ __device__ __forceinline__ void solve_fill_chargeden(const FieldArgs &f, double 
         double cd = c[u];
         if constexpr (!FROM_CD) {
           if constexpr (WITH_LOCAL) {
-            for (int sp = 0; sp < f.nspecies; ++sp)
-              for (int g = 0; g < f.rho_copies; ++g)
-                f.rho_sp[static_cast<size_t>(g) * f.rho_stride + static_cast<size_t>(sp) * nx + ix] = 0.0;
+            charge_local_zero(f, ix);
             f.charge[ix] = c[u];
           }
           cd = chargeden_from(f, c[u]);
@@ -245,8 +177,8 @@ __device__ __forceinline__ void solve_fill_chargeden(const FieldArgs &f, double 
 // Only for a field that has no reference order to keep: the half-step field predicted by k_step_one, whose
 // charge already differs from a marker-by-marker deposit by rounding (0.6 us instead of 5.8 us at nx = 1024).
 template <bool TREE = false>
-__device__ __forceinline__ void solve_body(const FieldArgs &f, double *sCD, double *sMode, double *sScr,
-                                           double *sTab) {
+__device__ __forceinline__ void solve_body(const FieldArgs &f, double *lds, const SolveLds &L) {
+  double *sCD = lds + L.cd, *sMode = lds + L.mode, *sScr = lds + L.scr, *sTab = lds + L.tab;
   const int nx = f.nx, nm = f.nmode;
   constexpr int U = 4;
   if constexpr (TREE) {
@@ -257,17 +189,7 @@ __device__ __forceinline__ void solve_body(const FieldArgs &f, double *sCD, doub
       double part = 0.0;
       for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) part = part + tab[ix] * sCD[ix];
       const double acc = block_sum(part, sScr);
-      if (threadIdx.x == 0) {
-        if (use_cos) {
-          const double im = acc * f.sc_im * f.grad_inv[m];
-          sMode[nm + m] = im;
-          f.mode_im[m] = im;
-        } else {
-          const double re = acc * f.sc_re * f.grad_inv[m];
-          sMode[m] = re;
-          f.mode_re[m] = re;
-        }
-      }
+      if (threadIdx.x == 0) mode_store(f, sMode, nm, m, use_cos, acc, f.grad_inv[m]);
     }
     __syncthreads();
   } else {
@@ -344,21 +266,12 @@ __device__ __forceinline__ void solve_body(const FieldArgs &f, double *sCD, doub
       }
       for (; ix < nx; ++ix) acc = acc + tab[ix] * sCD[ix];
     }
-    // :234/:239 VecScale by -1/nx resp. 1/nx, then :243-247 times 1/k
-    if (use_cos) {
-      const double im = acc * f.sc_im * f.grad_inv[m];
-      sMode[nm + m] = im;
-      f.mode_im[m] = im;
-    } else {
-      const double re = acc * f.sc_re * f.grad_inv[m];
-      sMode[m] = re;
-      f.mode_re[m] = re;
-    }
+    mode_store(f, sMode, nm, m, use_cos, acc, f.grad_inv[m]);
   }
   __syncthreads();
   }  // !TREE
 
-  // inverse: E = 2*(Fre*mode_re + Fim*mode_im), :251-256 (mode order: inverse_row)
+  // inverse (inverse_one_mode; several modes, in the row's order: inverse_row)
   double e2 = 0.0;
   if (nm == 1) {  // the usual case: both table reads of four grid points in flight together
     for (int base = threadIdx.x; base < nx; base += U * FIELD_THREADS) {
@@ -373,10 +286,7 @@ __device__ __forceinline__ void solve_body(const FieldArgs &f, double *sCD, doub
       for (int u = 0; u < U; ++u) {
         const int ix = base + u * FIELD_THREADS;
         if (ix < nx) {
-          double s = 0.0;
-          s = s + tr[u] * sMode[0];
-          s = s + ti[u] * sMode[1];
-          const double e = s * 2.0;
+          const double e = inverse_one_mode(tr[u], ti[u], sMode[0], sMode[1]);
           f.E[ix] = e;
           e2 += e * e;
         }
@@ -389,25 +299,17 @@ __device__ __forceinline__ void solve_body(const FieldArgs &f, double *sCD, doub
       e2 += e * e;
     }
   }
-  if (f.history) {  // int E^2 dx, src/pic1dp_output.F90:120-124
-    const double tot = block_sum(e2, sScr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(tot);
-      *f.history = nrm * nrm * f.lx / f.dnx;
-    }
-  }
+  if (f.history) field_energy_store(e2, sScr, f.lx, f.dnx, f.history);
 }
 
 template <bool WITH_LOCAL, bool FROM_CD>
 __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve(const FieldArgs f) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sCD = reinterpret_cast<double *>(smem);       // [nx]
-  double *sMode = sCD + f.nx;                           // [2*nmode]: re then im
-  double *sScr = sMode + 2 * f.nmode;                   // [16]
-  double *sTab = sScr + 16;                             // [2][nmode][nx] when tab_lds
-  solve_fill_chargeden<WITH_LOCAL, FROM_CD>(f, sCD);
+  double *lds = reinterpret_cast<double *>(smem);
+  const SolveLds L(f.nx, f.nmode, f.tab_lds);
+  solve_fill_chargeden<WITH_LOCAL, FROM_CD>(f, lds + L.cd);
   __syncthreads();
-  solve_body(f, sCD, sMode, sScr, sTab);
+  solve_body(f, lds, L);
 }
 
 // Call sites, one rank: collect_charge after a noted push(1) whose charge k_step_one has predicted, and the
@@ -415,61 +317,28 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve(const FieldArgs f
 // scaling, the solve.  The prediction accumulators are consumed.
 __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve_pred(const FieldArgs f, double *pred, int nm_pred) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sCD = reinterpret_cast<double *>(smem);
-  double *sMode = sCD + f.nx;
-  double *sScr = sMode + 2 * f.nmode;
-  double *sTab = sScr + 16;
-  const int nx = f.nx, np1 = 1 + 2 * nm_pred;
-  for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
-    double c2 = 0.0;
-    for (int s = 0; s < f.nspecies; ++s) {
-      double *r = pred + static_cast<size_t>(s) * np1 * nx + ix;
-      double c1 = r[0];
-      r[0] = 0.0;
-      for (int m = 0; m < nm_pred; ++m) {
-        double *ra = r + static_cast<size_t>(1 + m) * nx, *rb = r + static_cast<size_t>(1 + nm_pred + m) * nx;
-        c1 = c1 + f.mode_re[m] * *ra;
-        c1 = c1 + f.mode_im[m] * *rb;
-        *ra = 0.0;
-        *rb = 0.0;
-      }
-      c2 = c2 + c1 * f.Z[s];
-    }
+  double *lds = reinterpret_cast<double *>(smem);
+  const SolveLds L(f.nx, f.nmode, f.tab_lds);
+  for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) {
+    const double c2 = pred_combine_take(f, pred, nm_pred, ix, f.mode_re, f.mode_im);
     f.charge[ix] = c2;
     const double cd = chargeden_from(f, c2);
     f.chargeden[ix] = cd;
-    sCD[ix] = cd;
+    lds[L.cd + ix] = cd;
   }
   __syncthreads();  // every thread has read mode_re / mode_im before solve_body overwrites them
-  solve_body(f, sCD, sMode, sScr, sTab);
+  solve_body(f, lds, L);
 }
 
+// k_pred_chargeden and the mode-filter solve in one launch (call sites, one rank: collect_charge after a noted
+// push(1) leaves both to the solve_field that follows)
 __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve_pred_sums(const FieldArgs f, const PredTab pt, double *pred) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sCD = reinterpret_cast<double *>(smem);
-  double *sMode = sCD + f.nx;
-  double *sScr = sMode + 2 * f.nmode;
-  double *sTab = sScr + 16;
-  __shared__ double sab[2];
-  __shared__ double sK[8];
-  if (threadIdx.x < 8) sK[threadIdx.x] = pred_sum_take(pred, threadIdx.x);
+  double *lds = reinterpret_cast<double *>(smem);
+  const SolveLds L(f.nx, f.nmode, f.tab_lds);
+  pred_chargeden_fill(f, pt, pred, nullptr, lds + L.cd);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double ac, as;
-    pred_forward_sums(f, pt, sK, f.mode_re[0], f.mode_im[0], ac, as);
-    const double det = pt.g11 * pt.g22 - pt.g12 * pt.g12;
-    sab[0] = (ac * pt.g22 - as * pt.g12) / det;
-    sab[1] = (as * pt.g11 - ac * pt.g12) / det;
-  }
-  __syncthreads();  // (every thread is past its reads of mode_re / mode_im before solve_body overwrites them: only thread 0 read)
-  const double alpha = sab[0], beta = sab[1];
-  for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) {
-    const double cd = alpha * f.fre[ix] + beta * f.fim[ix];
-    f.chargeden[ix] = cd;
-    sCD[ix] = cd;
-  }
-  __syncthreads();
-  solve_body(f, sCD, sMode, sScr, sTab);
+  solve_body(f, lds, L);
 }
 
 // ---------------------------------------------------------------------------
@@ -526,10 +395,9 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_charge_exchange(const FieldAr
 // local charge -> exchange -> chargeden -> solve: one launch per sub-step
 __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve_xchg(const FieldArgs f, const XchgArgs x) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sCD = reinterpret_cast<double *>(smem);
-  double *sMode = sCD + f.nx;
-  double *sScr = sMode + 2 * f.nmode;
-  double *sTab = sScr + 16;
+  double *lds = reinterpret_cast<double *>(smem);
+  const SolveLds L(f.nx, f.nmode, f.tab_lds);
+  double *sCD = lds + L.cd;
   exchange_charge(f, x, sCD);
   for (int ix = threadIdx.x; ix < f.nx; ix += blockDim.x) {  // own elements again
     const double cd = chargeden_from(f, sCD[ix]);
@@ -537,7 +405,7 @@ __global__ void __launch_bounds__(FIELD_THREADS) k_field_solve_xchg(const FieldA
     sCD[ix] = cd;
   }
   __syncthreads();
-  solve_body(f, sCD, sMode, sScr, sTab);
+  solve_body(f, lds, L);
 }
 
 // One launch for both fields of the one-pass-per-step scheme (k_step_one): the field of the new
@@ -551,27 +419,15 @@ template <int SRC>
 __global__ void __launch_bounds__(FIELD_THREADS)
 k_field_solve_pair(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sCD = reinterpret_cast<double *>(smem);
-  double *sMode = sCD + f.nx;
-  double *sScr = sMode + 2 * f.nmode;
-  double *sTab = sScr + 16;
+  double *lds = reinterpret_cast<double *>(smem);
   const int nx = f.nx, nm = f.nmode, np1 = 1 + 2 * nm;
+  const SolveLds L = SolveLds::pair(nx, nm, f.tab_lds, SRC == 1);
+  double *sCD = lds + L.cd, *sMode = lds + L.mode;
   // SRC 1: [charge2 | Z-weighted prediction slices] of this rank, then of all ranks, behind the solve's tiles
-  double *sV = sTab + (f.tab_lds ? 2 * static_cast<size_t>(nm) * nx : 0);
+  double *sV = lds + L.vec;
   const double *pk = pa.pack;  // SRC 2: the same slices, all-reduced in memory
   if constexpr (SRC == 1) {
-    for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
-      sV[ix] = charge_local_one(f, ix);
-      for (int k = 0; k < np1; ++k) {
-        double c2 = 0.0;
-        for (int s = 0; s < f.nspecies; ++s) {
-          double *r = pa.pred + (static_cast<size_t>(s) * np1 + k) * nx + ix;
-          c2 = c2 + *r * f.Z[s];
-          *r = 0.0;
-        }
-        sV[static_cast<size_t>(1 + k) * nx + ix] = c2;
-      }
-    }
+    charge_pack_fill(f, pa.pred, np1, sV);
     // element i of the packed vector belongs to thread i % blockDim; with nx a multiple of blockDim that is
     // the thread that wrote it -- otherwise meet first
     __syncthreads();
@@ -591,7 +447,7 @@ k_field_solve_pair(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
     solve_fill_chargeden<true, false>(f, sCD);
   }
   __syncthreads();
-  solve_body(f, sCD, sMode, sScr, sTab);
+  solve_body(f, lds, L);
   __syncthreads();  // E, mode_re/im (also in sMode) are final; sCD and sTab are free again
   for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
     double c2 = 0.0;
@@ -603,19 +459,7 @@ k_field_solve_pair(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
         c2 = c2 + sMode[nm + m] * r[static_cast<size_t>(1 + nm + m) * nx];
       }
     } else {
-      for (int s = 0; s < f.nspecies; ++s) {
-        double *r = pa.pred + static_cast<size_t>(s) * np1 * nx + ix;
-        double c1 = r[0];
-        r[0] = 0.0;
-        for (int m = 0; m < nm; ++m) {
-          double *ra = r + static_cast<size_t>(1 + m) * nx, *rb = r + static_cast<size_t>(1 + nm + m) * nx;
-          c1 = c1 + sMode[m] * *ra;
-          c1 = c1 + sMode[nm + m] * *rb;
-          *ra = 0.0;
-          *rb = 0.0;
-        }
-        c2 = c2 + c1 * f.Z[s];
-      }
+      c2 = pred_combine_take(f, pa.pred, nm, ix, sMode, sMode + nm);
     }
     const double cd = chargeden_from(f, c2);
     pa.cd_h[ix] = cd;
@@ -627,7 +471,7 @@ k_field_solve_pair(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
   g.mode_re = pa.mode_h;
   g.mode_im = pa.mode_h + nm;
   g.history = nullptr;
-  solve_body<true>(g, sCD, sMode, sScr, sTab);
+  solve_body<true>(g, lds, L);
 }
 
 // k_field_solve_pair for the usual case -- ONE kept mode, tables that fit the LDS -- with everything that does
@@ -645,29 +489,14 @@ __global__ void __launch_bounds__(FIELD_THREADS)
 k_field_solve_pair1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nx = f.nx;
-  const int ne = (nx + 1) & ~1;
-  double *sPc = reinterpret_cast<double *>(smem);  // [ne] fre * chargeden   (16-byte aligned rows for the chain)
-  double *sPs = sPc + ne;                           // [ne] fim * chargeden
-  double *sW = sPs + ne;                            // [FIELD_THREADS / 64][6] wave partials of the six sums
-  double *sMode = sW + (FIELD_THREADS / 64) * 6;    // re, im, then the six sums of the workgroup
-  double *sScr = sMode + 8;                         // [16]
-  double *sPart = sScr + 16;                        // [2 npe] partial chains of the npe-rank order
-  double *sV = sPart + ((2 * f.npe + 1) & ~1);      // SRC 1: [charge2 | R0 | RA | RB] of this rank, then of all
-  const double *pk = pa.pack;                       // SRC 2: the same, all-reduced in memory
+  double *lds = reinterpret_cast<double *>(smem);
+  const LeanPairLds L = LeanPairLds::pair1(nx, f.npe, SRC == 1);
+  double *sPc = lds + L.pc, *sPs = lds + L.ps, *sW = lds + L.w, *sMode = lds + L.mode, *sScr = lds + L.scr, *sPart = lds + L.part;
+  double *sV = lds + L.vec;    // SRC 1: [charge2 | R0 | RA | RB] of this rank, then of all
+  const double *pk = pa.pack;  // SRC 2: the same, all-reduced in memory
   const size_t np1 = 3;
   if constexpr (SRC == 1) {
-    for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
-      sV[ix] = charge_local_one(f, ix);
-      for (size_t k = 0; k < np1; ++k) {
-        double c2 = 0.0;
-        for (int sp = 0; sp < f.nspecies; ++sp) {
-          double *r = pa.pred + (static_cast<size_t>(sp) * np1 + k) * nx + ix;
-          c2 = c2 + *r * f.Z[sp];
-          *r = 0.0;
-        }
-        sV[(1 + k) * nx + ix] = c2;
-      }
-    }
+    charge_pack_fill(f, pa.pred, 3, sV);
     __syncthreads();
     exchange_vectors(x1, sV, 4 * nx);
     __syncthreads();
@@ -695,8 +524,10 @@ k_field_solve_pair1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
           ra[u] = pk[2 * static_cast<size_t>(nx) + ix];
           rb[u] = pk[3 * static_cast<size_t>(nx) + ix];
         } else {
-          for (int sp = 0; sp < f.nspecies; ++sp) {  // src/pic1dp_interaction.F90:126-127
-            double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
+          // charge_local_read's sum in a form of its own, in ONE species loop with the slices: two loops are two dependent
+          // round trips to memory per grid point (+0.9 us per launch, profiles/r11/field_refactor_ab_speed.log)
+          for (int sp = 0; sp < f.nspecies; ++sp) {
+            const double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
             double c1 = *r;
             for (int g = 1; g < f.rho_copies; ++g) c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
             c[u] = c[u] + c1 * f.Z[sp];
@@ -713,9 +544,8 @@ k_field_solve_pair1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
       const int ix = base + u * FIELD_THREADS;
       if (ix < nx) {
         if constexpr (SRC == 0) {  // accumulators consumed: zero for the next kernels
+          charge_local_zero(f, ix);
           for (int sp = 0; sp < f.nspecies; ++sp) {
-            double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
-            for (int g = 0; g < f.rho_copies; ++g) r[static_cast<size_t>(g) * f.rho_stride] = 0.0;
             double *q = pa.pred + static_cast<size_t>(sp) * np1 * nx + ix;
             q[0] = 0.0;
             q[nx] = 0.0;
@@ -757,22 +587,14 @@ k_field_solve_pair1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
         sMode[2 + k] = t;
       }
     });
-    if (threadIdx.x == 0) {
-      const double im = acc * f.sc_im * ginv;
-      sMode[1] = im;
-      f.mode_im[0] = im;
-    } else if (threadIdx.x == 1) {
-      const double re = acc * f.sc_re * ginv;
-      sMode[0] = re;
-      f.mode_re[0] = re;
-    }
+    if (threadIdx.x < 2) mode_store(f, sMode, 1, 0, threadIdx.x == 0, acc, ginv);
   }
   __syncthreads();
   // the kept mode of the next step's half-step field (every thread for itself), both inverse transforms (:251-257)
   double e2 = 0.0;
   const double re = sMode[0], im = sMode[1];
   const double ac = sMode[2] + re * sMode[3] + im * sMode[4], as = sMode[5] + re * sMode[6] + im * sMode[7];
-  const double im_h = ac * f.sc_im * ginv, re_h = as * f.sc_re * ginv;
+  const double im_h = mode_scale(f, true, ac, ginv), re_h = mode_scale(f, false, as, ginv);
   if (threadIdx.x == 0) {
     pa.mode_h[0] = re_h;
     pa.mode_h[1] = im_h;
@@ -791,26 +613,14 @@ k_field_solve_pair1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
     for (int u = 0; u < U; ++u) {
       const int ix = base + u * FIELD_THREADS;
       if (ix < nx) {
-        double a = 0.0;
-        a = a + tr[u] * re;
-        a = a + ti[u] * im;
-        const double e = a * 2.0;
+        const double e = inverse_one_mode(tr[u], ti[u], re, im);
         f.E[ix] = e;
         e2 += e * e;
-        double b = 0.0;
-        b = b + tr[u] * re_h;
-        b = b + ti[u] * im_h;
-        pa.E_h[ix] = b * 2.0;
+        pa.E_h[ix] = inverse_one_mode(tr[u], ti[u], re_h, im_h);
       }
     }
   }
-  if (f.history) {  // int E^2 dx, src/pic1dp_output.F90:120-124
-    const double tot = block_sum(e2, sScr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(tot);
-      *f.history = nrm * nrm * f.lx / f.dnx;
-    }
-  }
+  if (f.history) field_energy_store(e2, sScr, f.lx, f.dnx, f.history);
 }
 
 // The pair solve for the six-sum prediction (k_step_one<PRIV>, k_step_sums; one kept mode): the field of the new state
@@ -827,13 +637,10 @@ __global__ void __launch_bounds__(1024)
 k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nx = f.nx;
-  const int ne = (nx + 1) & ~1;
-  double *sPc = reinterpret_cast<double *>(smem);  // [ne] fre * chargeden
-  double *sPs = sPc + ne;                           // [ne] fim * chargeden
-  double *sMode = sPs + ne;                         // re, im, then the six sums
-  double *sScr = sMode + 8;                         // [16]
-  double *sPart = sScr + 16;                        // [2 npe] partial chains of the npe-rank order
-  double *sV = sPart + ((2 * f.npe + 1) & ~1);      // SRC 1: [charge2 | six sums | pad]
+  double *lds = reinterpret_cast<double *>(smem);
+  const LeanPairLds L = LeanPairLds::sums1(nx, f.npe, SRC == 1);
+  double *sPc = lds + L.pc, *sPs = lds + L.ps, *sMode = lds + L.mode, *sScr = lds + L.scr, *sPart = lds + L.part;
+  double *sV = lds + L.vec;  // SRC 1: [charge2 | six sums | pad]
   const double *pk = pa.pack;
   if constexpr (SRC == 1) {
     if (!pa.posted) {  // (posted: the marker launch's tail has formed and stored this rank's vector, StepTail mode 2)
@@ -861,12 +668,7 @@ k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa
         if constexpr (SRC != 0) {
           c[u] = pk[ix];
         } else {
-          for (int sp = 0; sp < f.nspecies; ++sp) {  // src/pic1dp_interaction.F90:126-127
-            const double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
-            double c1 = *r;
-            for (int g = 1; g < f.rho_copies; ++g) c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
-            c[u] = c[u] + c1 * f.Z[sp];
-          }
+          c[u] = charge_local_read(f, ix);
         }
       }
     }
@@ -874,11 +676,7 @@ k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa
     for (int u = 0; u < U; ++u) {
       const int ix = base + u * T;
       if (ix < nx) {
-        if constexpr (SRC == 0)
-          for (int sp = 0; sp < f.nspecies; ++sp) {
-            double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
-            for (int g = 0; g < f.rho_copies; ++g) r[static_cast<size_t>(g) * f.rho_stride] = 0.0;
-          }
+        if constexpr (SRC == 0) charge_local_zero(f, ix);
         f.charge[ix] = c[u];
         const double cd = chargeden_from(f, c[u]);  // :138-148
         f.chargeden[ix] = cd;
@@ -900,21 +698,13 @@ k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa
         }
       }
     });
-    if (threadIdx.x == 0) {
-      const double im = acc * f.sc_im * ginv;
-      sMode[1] = im;
-      f.mode_im[0] = im;
-    } else if (threadIdx.x == 1) {
-      const double re = acc * f.sc_re * ginv;
-      sMode[0] = re;
-      f.mode_re[0] = re;
-    }
+    if (threadIdx.x < 2) mode_store(f, sMode, 1, 0, threadIdx.x == 0, acc, ginv);
   }
   __syncthreads();
   const double re = sMode[0], im = sMode[1];
   double ac, as;
   pred_forward_sums(f, pa.pt, sMode + 2, re, im, ac, as);
-  const double im_h = ac * f.sc_im * ginv, re_h = as * f.sc_re * ginv;  // :234, :239, :243-247
+  const double im_h = mode_scale(f, true, ac, ginv), re_h = mode_scale(f, false, as, ginv);
   if (threadIdx.x == 0) {
     pa.mode_h[0] = re_h;
     pa.mode_h[1] = im_h;
@@ -922,11 +712,7 @@ k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa
   // call sites: the kept mode's content of the half-step charge density, as k_pred_chargeden forms it -- what
   // field_chargeden has to hold once the host has called solve_field for the half step (adopt_half_field)
   double alpha = 0.0, beta = 0.0;
-  if (pa.cd_h) {
-    const double det = pa.pt.g11 * pa.pt.g22 - pa.pt.g12 * pa.pt.g12;
-    alpha = (ac * pa.pt.g22 - as * pa.pt.g12) / det;
-    beta = (as * pa.pt.g11 - ac * pa.pt.g12) / det;
-  }
+  if (pa.cd_h) pred_cd_coeffs(pa.pt, ac, as, alpha, beta);
   double e2 = 0.0;
   const bool one_trip = nx <= U * T;
   for (int base = threadIdx.x; base < nx; base += U * T) {
@@ -941,28 +727,16 @@ k_field_solve_pair_sums1(const FieldArgs f, const XchgArgs x1, const PairArgs pa
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int ix = base + u * T;
-      if (ix < nx) {  // both inverse transforms, :251-257
-        double a = 0.0;
-        a = a + tr[u] * re;
-        a = a + ti[u] * im;
-        const double e = a * 2.0;
+      if (ix < nx) {  // both inverse transforms
+        const double e = inverse_one_mode(tr[u], ti[u], re, im);
         f.E[ix] = e;
         e2 += e * e;
-        double b = 0.0;
-        b = b + tr[u] * re_h;
-        b = b + ti[u] * im_h;
-        pa.E_h[ix] = b * 2.0;
+        pa.E_h[ix] = inverse_one_mode(tr[u], ti[u], re_h, im_h);
         if (pa.cd_h) pa.cd_h[ix] = alpha * tr[u] + beta * ti[u];
       }
     }
   }
-  if (f.history) {  // int E^2 dx, src/pic1dp_output.F90:120-124
-    const double tot = block_sum(e2, sScr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(tot);
-      *f.history = nrm * nrm * f.lx / f.dnx;
-    }
-  }
+  if (f.history) field_energy_store(e2, sScr, f.lx, f.dnx, f.history);
 }
 
 // Many kept modes (2*nmode > FIELD_THREADS, up to the full spectrum nmode = nx/2,
@@ -997,10 +771,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) k_field_modes_wide(const FieldAr
     for (int k = 0; k < 8; ++k) acc = acc + t[k] * sCD[ix + k];
   }
   for (; ix < nx; ++ix) acc = acc + tab[ix] * sCD[ix];
-  if (use_cos)
-    f.mode_im[m] = acc * f.sc_im * f.grad_inv[m];
-  else
-    f.mode_re[m] = acc * f.sc_re * f.grad_inv[m];
+  (use_cos ? f.mode_im : f.mode_re)[m] = mode_scale(f, use_cos, acc, f.grad_inv[m]);
 }
 
 // inverse: one grid point per thread, serial over the modes in the row's order (inverse_row, :251-256)
@@ -1023,11 +794,7 @@ k_field_energy(const double *E, int nx, double lx, double dnx, double *out) {
   __shared__ double scr[16];
   double e2 = 0.0;
   for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) e2 += E[ix] * E[ix];
-  const double tot = block_sum(e2, scr);
-  if (threadIdx.x == 0) {
-    const double nrm = sqrt(tot);
-    *out = nrm * nrm * lx / dnx;
-  }
+  field_energy_store(e2, scr, lx, dnx, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1109,13 +876,7 @@ k_field_fd(const double *chargeden, double *E, double *history, int nx, double l
     E[i] = e;
     e2 += e * e;
   }
-  if (history) {
-    const double t2 = block_sum(e2, scr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(t2);
-      *history = nrm * nrm * lx / dnx;
-    }
-  }
+  if (history) field_energy_store(e2, scr, lx, dnx, history);
 }
 
 }  // namespace
@@ -1136,6 +897,14 @@ hipError_t launch_chain_selftest(const double *v, int nrows, int n, double *out,
   const size_t lds = sizeof(double) * nrows * ((n + 1) & ~1);
   return launch_kernel(k_chain_selftest, dim3(1), dim3(64), lds, st, v, nrows, n, out);
 }
+
+namespace {
+// one workgroup of FIELD_THREADS: most launches of this file
+template <typename K, typename... Args>
+hipError_t launch_one(K kern, size_t lds, hipStream_t st, const Args &...args) {
+  return launch_kernel(kern, dim3(1), dim3(FIELD_THREADS), lds, st, args...);
+}
+}  // namespace
 
 hipError_t launch_field_fd(const double *chargeden, double *E, double *history, int nx, double lx,
                            double dnx, hipStream_t st) {
@@ -1160,26 +929,17 @@ hipError_t launch_fx_to_rho(long long *acc, double *rho_sp, int nspecies, int nx
 
 hipError_t launch_fx_exchange(long long *acc, int nspecies, int nx, const XchgArgs &x, hipStream_t st) {
   if (2 * nspecies * nx > x.vstride) return hipErrorInvalidValue;  // (the slots are sized for it: capi_comm.cpp xchg_vec)
-  return launch_kernel(k_fx_exchange, dim3(1), dim3(FIELD_THREADS), 0, st, acc, nspecies, nx, x);
+  return launch_one(k_fx_exchange, 0, st, acc, nspecies, nx, x);
 }
 
 hipError_t launch_charge_local(const FieldArgs &f, hipStream_t st) {
-  return launch_kernel(k_charge_local, dim3(1), dim3(FIELD_THREADS), 0, st, f);
+  return launch_one(k_charge_local, 0, st, f);
 }
 
 hipError_t launch_chargeden(const FieldArgs &f, bool with_local, hipStream_t st) {
-  if (with_local) return launch_kernel(k_chargeden<true>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
-  return launch_kernel(k_chargeden<false>, dim3(1), dim3(FIELD_THREADS), 0, st, f);
+  if (with_local) return launch_one(k_chargeden<true>, 0, st, f);
+  return launch_one(k_chargeden<false>, 0, st, f);
 }
-
-namespace {
-// dynamic LDS of the one-workgroup mode-filter solves (k_field_solve and its siblings): the grid vector, the modes,
-// scratch, and the tables where they fit (FieldArgs::tab_lds)
-size_t solve_lds_bytes(const FieldArgs &f) {
-  return sizeof(double) * (static_cast<size_t>(f.nx) + 2 * f.nmode + 16 +
-                           (f.tab_lds ? 2 * static_cast<size_t>(f.nmode) * f.nx : 0));
-}
-}  // namespace
 
 hipError_t launch_field_solve(const FieldArgs &f, bool with_local, bool from_chargeden,
                               hipStream_t st) {
@@ -1192,21 +952,21 @@ hipError_t launch_field_solve(const FieldArgs &f, bool with_local, bool from_cha
       e = launch_kernel(k_field_inverse_wide, dim3((f.nx + WIDE_THREADS - 1) / WIDE_THREADS), dim3(WIDE_THREADS),
                         sizeof(double) * 2 * f.nmode, st, f);
     if (e == hipSuccess && f.history)
-      e = launch_kernel(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, f.E, f.nx, f.lx, f.dnx, f.history);
+      e = launch_one(k_field_energy, 0, st, f.E, f.nx, f.lx, f.dnx, f.history);
     return e;
   }
-  const size_t lds = solve_lds_bytes(f);
-  if (from_chargeden) return launch_kernel(k_field_solve<false, true>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
-  if (with_local) return launch_kernel(k_field_solve<true, false>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
-  return launch_kernel(k_field_solve<false, false>, dim3(1), dim3(FIELD_THREADS), lds, st, f);
+  const size_t lds = solve_launch(f.nx, f.nmode, f.tab_lds).bytes;
+  if (from_chargeden) return launch_one(k_field_solve<false, true>, lds, st, f);
+  if (with_local) return launch_one(k_field_solve<true, false>, lds, st, f);
+  return launch_one(k_field_solve<false, false>, lds, st, f);
 }
 
 hipError_t launch_pred_combine(const FieldArgs &f, double *pred, int nm_pred, hipStream_t st) {
-  return launch_kernel(k_pred_combine, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred);
+  return launch_one(k_pred_combine, 0, st, f, pred, nm_pred);
 }
 
 hipError_t launch_charge_exchange(const FieldArgs &f, const XchgArgs &x, hipStream_t st) {
-  return launch_kernel(k_charge_exchange, dim3(1), dim3(FIELD_THREADS), sizeof(double) * f.nx, st, f, x);
+  return launch_one(k_charge_exchange, sizeof(double) * f.nx, st, f, x);
 }
 
 hipError_t launch_field_solve_xchg(const FieldArgs &f, const XchgArgs &x, hipStream_t st) {
@@ -1215,7 +975,7 @@ hipError_t launch_field_solve_xchg(const FieldArgs &f, const XchgArgs &x, hipStr
     if (e != hipSuccess) return e;
     return launch_field_solve(f, false, false, st);
   }
-  return launch_kernel(k_field_solve_xchg, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, x);
+  return launch_one(k_field_solve_xchg, solve_launch(f.nx, f.nmode, f.tab_lds).bytes, st, f, x);
 }
 
 hipError_t launch_field_solve_pair(const FieldArgs &f, const PairArgs &pa, const XchgArgs *x1, hipStream_t st) {
@@ -1228,57 +988,51 @@ hipError_t launch_field_solve_pair(const FieldArgs &f, const PairArgs &pa, const
     if (pa.pack) return launch(std::integral_constant<int, 2>{});
     return launch(std::integral_constant<int, 0>{});
   };
-  const size_t ne = (static_cast<size_t>(f.nx) + 1) & ~static_cast<size_t>(1);
-  const size_t npe2 = (2 * static_cast<size_t>(f.npe) + 1) & ~static_cast<size_t>(1);
-  if (pa.kind != 2 && f.nmode == 1 && f.tab_lds) {  // the lean kernel of the usual case
-    const size_t lds =
-        sizeof(double) * (2 * ne + (FIELD_THREADS / 64) * 6 + 8 + 16 + npe2 + (x1 ? 4 * static_cast<size_t>(f.nx) : 0));
-    return by_src([&](auto SRC) {
-      return launch_kernel(k_field_solve_pair1<SRC>, dim3(1), dim3(FIELD_THREADS), lds, st, f, x, pa);
-    });
+  const FieldLaunch fl = pair_launch(f.nx, f.nmode, f.npe, f.tab_lds, x1 != nullptr, pa.kind);
+  switch (fl.family) {
+    case FIELD_PAIR1:
+      return by_src([&](auto SRC) {
+        return launch_kernel(k_field_solve_pair1<SRC>, dim3(1), dim3(fl.threads), fl.bytes, st, f, x, pa);
+      });
+    case FIELD_PAIR_SUMS1:
+      if (f.nmode != 1) return hipErrorInvalidValue;
+      return by_src([&](auto SRC) {
+        return launch_kernel(k_field_solve_pair_sums1<SRC>, dim3(1), dim3(fl.threads), fl.bytes, st, f, x, pa);
+      });
+    default:
+      return by_src([&](auto SRC) {
+        return launch_kernel(k_field_solve_pair<SRC>, dim3(1), dim3(fl.threads), fl.bytes, st, f, x, pa);
+      });
   }
-  if (pa.kind == 2) {  // the six sums of ONE kept mode
-    if (f.nmode != 1) return hipErrorInvalidValue;
-    const size_t lds = sizeof(double) * (2 * ne + 8 + 16 + npe2 + (x1 ? pack_doubles(f.nx, 1, 2) : 0));
-    const int threads = f.nx > 2048 ? 1024 : (f.nx > 1024 ? 512 : FIELD_THREADS);
-    return by_src([&](auto SRC) {
-      return launch_kernel(k_field_solve_pair_sums1<SRC>, dim3(1), dim3(threads), lds, st, f, x, pa);
-    });
-  }
-  // (x1: + the packed vector)
-  const size_t lds = solve_lds_bytes(f) + (x1 ? sizeof(double) * (2 + 2 * static_cast<size_t>(f.nmode)) * f.nx : 0);
-  return by_src([&](auto SRC) {
-    return launch_kernel(k_field_solve_pair<SRC>, dim3(1), dim3(FIELD_THREADS), lds, st, f, x, pa);
-  });
 }
 
 hipError_t launch_field_solve_pred(const FieldArgs &f, double *pred, int nm_pred, hipStream_t st) {
   if (2 * f.nmode > FIELD_THREADS) return hipErrorInvalidValue;
-  return launch_kernel(k_field_solve_pred, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, pred, nm_pred);
+  return launch_one(k_field_solve_pred, solve_launch(f.nx, f.nmode, f.tab_lds).bytes, st, f, pred, nm_pred);
 }
 
 hipError_t launch_field_solve_pred_sums(const FieldArgs &f, const PredTab &pt, double *pred, hipStream_t st) {
   if (f.nmode != 1) return hipErrorInvalidValue;
-  return launch_kernel(k_field_solve_pred_sums, dim3(1), dim3(FIELD_THREADS), solve_lds_bytes(f), st, f, pt, pred);
+  return launch_one(k_field_solve_pred_sums, solve_launch(f.nx, f.nmode, f.tab_lds).bytes, st, f, pt, pred);
 }
 
 hipError_t launch_charge_pack(const FieldArgs &f, double *pred, int nm_pred, int kind, double *pack, hipStream_t st) {
-  if (kind == 2) return launch_kernel(k_charge_pack_sums, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, pack);
-  return launch_kernel(k_charge_pack, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred, nm_pred, pack);
+  if (kind == 2) return launch_one(k_charge_pack_sums, 0, st, f, pred, pack);
+  return launch_one(k_charge_pack, 0, st, f, pred, nm_pred, pack);
 }
 
 hipError_t launch_pred_chargeden(const FieldArgs &f, const PredTab &pt, double *pred, const double *K, hipStream_t st) {
   if (f.nmode != 1) return hipErrorInvalidValue;
-  return launch_kernel(k_pred_chargeden, dim3(1), dim3(FIELD_THREADS), 0, st, f, pt, pred, K);
+  return launch_one(k_pred_chargeden, 0, st, f, pt, pred, K);
 }
 
 hipError_t launch_pred_to_charge(const FieldArgs &f, double *pred, hipStream_t st) {
-  return launch_kernel(k_pred_to_charge, dim3(1), dim3(FIELD_THREADS), 0, st, f, pred);
+  return launch_one(k_pred_to_charge, 0, st, f, pred);
 }
 
 hipError_t launch_field_energy(const double *E, int nx, double lx, double dnx, double *out,
                                hipStream_t st) {
-  return launch_kernel(k_field_energy, dim3(1), dim3(FIELD_THREADS), 0, st, E, nx, lx, dnx, out);
+  return launch_one(k_field_energy, 0, st, E, nx, lx, dnx, out);
 }
 
 }  // namespace pic1dp

@@ -494,14 +494,16 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
   const bool lead = blockIdx.x == 0;
   double *sPc = sE0, *sPs = sX;
   for (int ix = threadIdx.x; ix < nx; ix += blockDim.x) {
+    // charge_local_read's sum in a form of its own: through the shared function the allocator gives the FUSED kernels two
+    // to three VGPRs more (profiles/r11/kernel_resources_before_after.log); with this form they are the parent's to the register
     double c2 = 0.0;
-    for (int sp = 0; sp < f.nspecies; ++sp) {  // src/pic1dp_interaction.F90:126-127
+    for (int sp = 0; sp < f.nspecies; ++sp) {  // (zeroed below, by workgroup 0 alone)
       const double *r = f.rho_sp + static_cast<size_t>(sp) * nx + ix;
       double c1 = *r;
       for (int g = 1; g < f.rho_copies; ++g) c1 = c1 + r[static_cast<size_t>(g) * f.rho_stride];
       c2 = c2 + c1 * f.Z[sp];
     }
-    const double cd = chargeden_from(f, c2);  // :138-148
+    const double cd = chargeden_from(f, c2);
     if (lead) {
       f.charge[ix] = c2;
       f.chargeden[ix] = cd;
@@ -523,6 +525,8 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
     const double acc = lean_forward_sums<FUSED_CHAIN_W>(f, sPc, sPs, sPart, [&]() {
       const int k = static_cast<int>(threadIdx.x) - (static_cast<int>(blockDim.x) - 64);
       if (k >= 0 && k < 6) {
+        // (pred_sum_take's additions, kept in a form of their own: every workgroup reads the copies, so nothing is zeroed
+        // here, and eight loads in flight instead of sixteen keep the kernel inside its 80 VGPRs)
         double a = 0.0;
         static_assert(PRED_SUM_COPIES % 8 == 0, "eight copies in flight at a time");
         for (int c0 = 0; c0 < PRED_SUM_COPIES; c0 += 8) {
@@ -535,15 +539,7 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
         sMode[2 + k] = a;
       }
     });
-    if (threadIdx.x == 0) {
-      const double im = acc * f.sc_im * ginv;
-      sMode[1] = im;
-      if (lead) f.mode_im[0] = im;
-    } else if (threadIdx.x == 1) {
-      const double re = acc * f.sc_re * ginv;
-      sMode[0] = re;
-      if (lead) f.mode_re[0] = re;
-    }
+    if (threadIdx.x < 2) mode_store(f, sMode, 1, 0, threadIdx.x == 0, acc, ginv, lead);
   }
   __syncthreads();
   STAMP_SOLVE(stamps, 3);
@@ -551,8 +547,8 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
   double ac, as;
   pred_forward_sums(f, fs.pt, sMode + 2, re, im, ac, as);
   STAMP_SOLVE(stamps, 4);
-  im_h = ac * f.sc_im * ginv;  // :234, :239, :243-247
-  re_h = as * f.sc_re * ginv;
+  im_h = mode_scale(f, true, ac, ginv);
+  re_h = mode_scale(f, false, as, ginv);
   if (lead && threadIdx.x == 0) {
     fs.mode_h[0] = re_h;
     fs.mode_h[1] = im_h;
@@ -562,14 +558,7 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
     double tA, tB;
     tab.get(ix, tA, tB);
     const double tr = 0.5 * tA, ti = 0.5 * tB;  // fre, fim: bit for bit
-    double a = 0.0;
-    a = a + tr * re;
-    a = a + ti * im;
-    const double e = a * 2.0;
-    double b = 0.0;
-    b = b + tr * re_h;
-    b = b + ti * im_h;
-    const double eh = b * 2.0;
+    const double e = inverse_one_mode(tr, ti, re, im), eh = inverse_one_mode(tr, ti, re_h, im_h);
     sE0[ix] = e;
     if constexpr (TILE_EH) sX[ix] = eh;
     if (ix == 0) {  // the guard cell behind the last one
@@ -582,13 +571,7 @@ __device__ __forceinline__ void fused_solve(const FusedSolve &fs, const TAB &tab
       fs.E_h[ix] = eh;
     }
   }
-  if (lead && f.history) {  // int E^2 dx, src/pic1dp_output.F90:120-124
-    const double tot = block_sum(e2, sScr);
-    if (threadIdx.x == 0) {
-      const double nrm = sqrt(tot);
-      *f.history = nrm * nrm * f.lx / f.dnx;
-    }
-  }
+  if (lead && f.history) field_energy_store(e2, sScr, f.lx, f.dnx, f.history);
 }
 
 // PRIV: the prediction of ONE kept mode as six sums instead of three tiles (the algebra of k_step_sums below: the

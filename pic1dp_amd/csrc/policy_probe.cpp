@@ -1,6 +1,8 @@
-// policy_probe.cpp -- the launch policy (launch_policy.hpp) behind the C ABI of the probe library, for the host test that
-// pins every shape (tests/test_launch_policy_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// policy_probe.cpp -- the launch policy (launch_policy.hpp) and the LDS layouts of the field kernels (field_lds.hpp) behind
+// the C ABI of the probe library, for the host tests that pin every shape (tests/test_launch_policy_host.py,
+// tests/test_field_lds_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include "../../include/pic1dp_probe.h"
+#include "field_lds.hpp"
 #include "launch_policy.hpp"
 
 using namespace pic1dp;
@@ -20,5 +22,20 @@ extern "C" int pic1dp_probe_host_launch_shape(const pic1dp_probe_launch_query *q
   shape[1] = pl.lc.blocks;
   shape[2] = static_cast<int64_t>(pl.lc.lds);
   shape[3] = pl.resident;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_field_lds(int32_t family, int32_t nx, int32_t nmode, int32_t npe, int32_t tab_lds,
+                                           int32_t with_xchg, int32_t pred_kind, int64_t out[3]) {
+  if (!out) return 1;
+  FieldLaunch fl{};
+  switch (family) {
+    case 0: fl = solve_launch(nx, nmode, tab_lds != 0); break;
+    case 1: fl = pair_launch(nx, nmode, npe, tab_lds != 0, with_xchg != 0, pred_kind); break;
+    default: return 1;
+  }
+  out[0] = static_cast<int64_t>(fl.bytes);
+  out[1] = fl.threads;
+  out[2] = fl.family;
   return 0;
 }

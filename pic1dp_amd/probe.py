@@ -49,6 +49,7 @@ SIGNATURES = {
     "pic1dp_probe_species_const": [_SP, _I32, _I32, _I32, _I32, _D],
     "pic1dp_probe_dlnf0": [C.c_int32, _SP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
     "pic1dp_probe_host_launch_shape": [C.POINTER(LaunchQuery), _I64],
+    "pic1dp_probe_host_field_lds": [C.c_int32] * 7 + [_I64],
 }
 
 _lib = None
@@ -188,4 +189,13 @@ def host_launch_shape(**query):
     out = (C.c_int64 * 4)()
     if load().pic1dp_probe_host_launch_shape(C.byref(LaunchQuery(**query)), out) != 0:
         raise ValueError("pic1dp_probe_host_launch_shape: unknown family %r" % (query.get("family"),))
+    return tuple(out)
+
+
+def host_field_lds(family, nx, nmode=1, npe=1, tab_lds=1, with_xchg=0, pred_kind=1):
+    """(dynamic LDS bytes, threads, kernel) of a one-workgroup field launch (csrc/field_lds.hpp), on the host; family 0 the
+    plain solves, 1 launch_field_solve_pair; kernel: 0 k_field_solve..., 1 k_field_solve_pair, 2 _pair1, 3 _pair_sums1"""
+    out = (C.c_int64 * 3)()
+    if load().pic1dp_probe_host_field_lds(family, nx, nmode, npe, tab_lds, with_xchg, pred_kind, out) != 0:
+        raise ValueError("pic1dp_probe_host_field_lds: unknown family %r" % (family,))
     return tuple(out)

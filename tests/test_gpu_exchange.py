@@ -32,17 +32,24 @@ def run_ranks(tmp_path, nproc, kw, steps, mode, port, timeout_ms="60000", per=1)
     return [np.load(out + ".rank%d.npz" % k) for k in range(nproc * per)]
 
 
-@pytest.mark.parametrize("nproc,mode,kind,nx", [(2, "step", 1, 128), (3, "step", 1, 128), (2, "calls", 1, 128),
-                                                (3, "step", 2, 128), (2, "calls", 2, 128),
-                                                (2, "step", 1, 2048), (2, "step", 2, 4096)],
-                         ids=["2-step", "3-step", "2-calls", "3-step-sums", "2-calls-sums", "2-step-nx2048", "2-step-sums-nx4096"])
-def test_exchange_ranks_share_the_gpu(amd, tmp_path, monkeypatch, nproc, mode, kind, nx):
+@pytest.mark.parametrize("nproc,mode,kind,nx,modes", [(2, "step", 1, 128, None), (3, "step", 1, 128, None), (2, "calls", 1, 128, None),
+                                                      (3, "step", 2, 128, None), (2, "calls", 2, 128, None),
+                                                      (2, "step", 1, 2048, None), (2, "step", 2, 4096, None),
+                                                      (2, "step", 1, 64, [1, 2]), (2, "step", 1, 63, [1, 2])],
+                         ids=["2-step", "3-step", "2-calls", "3-step-sums", "2-calls-sums", "2-step-nx2048", "2-step-sums-nx4096",
+                              "2-step-two-modes", "2-step-two-modes-nx63"])
+def test_exchange_ranks_share_the_gpu(amd, tmp_path, monkeypatch, nproc, mode, kind, nx, modes):
     """kind 2: the one-pass prediction travels as six sums behind charge2 (k_step_sums, the large-grid kernel,
-    insisted on at the small grid); the large grids: the paired solve's exchange vector beyond 64 KiB of LDS"""
+    insisted on at the small grid); the large grids: the paired solve's exchange vector beyond 64 KiB of LDS; two kept
+    modes: the generic paired solve with the exchange inside (k_field_solve_pair<1>), its packed vector behind the tables
+    on an even and on an odd grid, 4096 markers per rank"""
     kw = dict(nparticle_max=600_000, nx=nx)
     steps = 12
+    if modes:
+        kw.update(nparticle_max=4096 * nproc, nmode=len(modes), modes=modes)
+        steps = 10
     monkeypatch.setenv("PIC1DP_PRED_KIND", str(kind))
-    ranks = run_ranks(tmp_path, nproc, kw, steps, mode, 29541 + nproc + 10 * kind + (nx > 128) * 20)
+    ranks = run_ranks(tmp_path, nproc, kw, steps, mode, 29541 + nproc + 10 * kind + (nx > 128) * 20 + (40 + nx % 2 if modes else 0))
     # every rank holds the same field, bit for bit
     for r in ranks[1:]:
         assert np.array_equal(r["E"], ranks[0]["E"])

@@ -728,15 +728,18 @@ def test_split_phase_charge_time_loop(amd):
     assert b.kernel_stats(1)[1] == 0 and b.kernel_stats(4)[1] + b.kernel_stats(6)[1] == 3
 
 
-@pytest.mark.parametrize("kind,nx", [(1, 64), (2, 64), (1, 2048), (2, 4096)], ids=["tiles", "sums", "tiles-nx2048", "sums-nx4096"])
-def test_rccl_allreduce_path_single_rank(oracle_mod, amd, monkeypatch, kind, nx):
+@pytest.mark.parametrize("kind,nx,modes", [(1, 64, None), (2, 64, None), (1, 2048, None), (2, 4096, None), (1, 64, [1, 2]),
+                                           (1, 63, [1, 2])],
+                         ids=["tiles", "sums", "tiles-nx2048", "sums-nx4096", "tiles-two-modes", "tiles-two-modes-nx63"])
+def test_rccl_allreduce_path_single_rank(oracle_mod, amd, monkeypatch, kind, nx, modes):
     """a 1-rank RCCL communicator: exercises the run-time RCCL binding, the
     unique-id hand-off and the split kernels (charge_local -> ncclAllReduce on
     the engine's stream -> field solve; in a one-pass step: pack -> ONE
     ncclAllReduce -> the paired solve, with the prediction as tiles or as six
-    sums) that N > 1 uses"""
+    sums) that N > 1 uses; two kept modes: the generic paired solve from the pack (k_field_solve_pair<2>)"""
     monkeypatch.setenv("PIC1DP_PRED_KIND", str(kind))
-    sim, eng = pair(oracle_mod, amd, nparticle_max=100000, nx=nx)
+    kw = dict(nmode=len(modes), modes=modes) if modes else {}
+    sim, eng = pair(oracle_mod, amd, nparticle_max=100000, nx=nx, **kw)
     assert eng.predict_kind() == kind
     uid = eng.comm_unique_id()
     assert len(uid) == 128 and any(uid)
