@@ -467,7 +467,8 @@ int pic1dp_hip_charge_reduced(pic1dp_ctx *ctx, const double *charge1);
  *   - Only between time steps (nothing noted or owed, no charge_local pending): PIC1DP_ERR_STATE otherwise.  All ranks
  *     switch at the same point of the run.  Back to 0 restores kind 0's paths.
  *   - Kind 1 predicts nothing: step mode 0 runs two passes per step (pic1dp_hip_predict_kind reports 0 while it is
- *     set), and the diagnostics of output_all are taken in their own pass with their own summation (not exact).
+ *     set), and the diagnostics of output_all are taken in their own pass with their own summation (exact on
+ *     request as well: pic1dp_hip_set_diag_sum below).
  *   - A contribution of 2^62 quanta or more (a weight ~2^10 past the input's bound) is not summed: it is counted
  *     (kernel_stats which = 14) and the next synchronising call returns PIC1DP_ERR_ARG naming the species.
  *   - charge_local / charge_reduced return PIC1DP_ERR_STATE in kind 1 (a sum of doubles cannot be exact).
@@ -482,6 +483,47 @@ int pic1dp_hip_charge_quantum(const pic1dp_input *in, int32_t ispecies, int32_t 
  * charge_reduced_exact <- the same array summed element by element over the ranks (lo need not be normalised). */
 int pic1dp_hip_charge_local_exact(pic1dp_ctx *ctx, int64_t *limbs);
 int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *ctx, const int64_t *limbs);
+
+/* ---- exact sums for the diagnostics of output_all (opt-in) -----------------
+ * set_diag_sum(kind): 0 the pass as it was (FP64 sums, or fixed point scaled per pass; default), 1 exact.  In kind 1
+ * energy_sums, output_scalars, ptcldist(finish = 0 / 1) and output_all are fixed by the input and the markers alone:
+ * they do not depend on launch shape, storage order of the markers, split over ranks or API path.
+ *   Terms.  Per species the float64 products of the pass, in the reference's order: for a marker with |v| < v_max the
+ *     four corner weights sx sv, sx (1 - sv), (1 - sx) sv, (1 - sx)(1 - sv), each times 1, p and w (planes markr,
+ *     total, pertb; full-f: no pertb terms), with the two edge rules of DESIGN 2.1; for every marker slot the kinetic
+ *     sums count (the tail slots included) v v, (v v) p, (v v) w.
+ *   Quanta.  Every term t becomes n = rint(t 2^-e), one rounding to nearest even; the integers are summed exactly -- in
+ *     registers, in the LDS, across workgroups and across ranks --, every bin's total is converted to double once
+ *     (round to nearest even) and multiplied by 2^e.  From that double on the finish runs as in kind 0.
+ *   v histograms.  The exact integer sums over ix of the (x, v) planes' bins, on every path.
+ *   diag_quanta: the six e of a species -- markr, total, pertb, sum v^2, sum v^2 p, sum v^2 w -- from the input alone
+ *     (no device): with kb = ceil(log2 B_s) (B_s: charge_quantum's bound) and kv = ceil(log2 v_max^2),
+ *     -40, kb - 40, kb - 40, kv - 52, kv + kb - 52, kv + kb - 52.
+ *   A histogram term of 2^44 quanta or more, a kinetic term of 2^62 or more (|p|, |w| 2^4 past the bound; |v| beyond
+ *     32 v_max), or a NaN is not summed: it is counted (kernel_stats which = 15) and every call that hands out
+ *     diagnostics of that pass returns PIC1DP_ERR_ARG naming the species and the plane, until the markers change.
+ *   - Only between time steps, as set_charge_sum (PIC1DP_ERR_STATE otherwise); independent of the charge sum's kind.
+ *     The switch drops the cached diagnostics.
+ *   - Kind 1 always takes the diagnostics in their own pass: set_output_fusion is ignored while it is set, and the
+ *     one-pass prediction survives an output_all as it does in kind 0.
+ *   - With an RCCL communicator output_scalars, ptcldist(finish = 1) and output_all sum the limbs over the ranks as
+ *     int64.  A host that owns the reduction takes
+ *       diag_limbs_len -> n = 6 nx_opd nv_opd + 6
+ *       diag_local_exact -> limbs[n] of a species: [3 planes][2][nx_opd nv_opd] (hi row, lo row, as charge_local_exact:
+ *         a bin's total is hi 2^32 + lo quanta) then [3 sums][2] (hi, lo),
+ *     sums them element by element over the ranks (lo need not be normalised) and hands them to
+ *       diag_convert_exact -> sums[3] as energy_sums and dist[3 nx_opd nv_opd + 3 nv_opd] as ptcldist(finish = 0)
+ *         return them (either may be NULL); ptcldist_finish and output_scalars_from take over from there.
+ *     diag_convert is the same conversion from the input alone (no context, no device).
+ *   diag_quantise: n = rint(term 2^-log2_quantum) as the pass forms it (kinetic = 0: limit 2^44; 1: 2^62), or
+ *     PIC1DP_ERR_ARG for a term the pass would not sum.  Host only. */
+int pic1dp_hip_set_diag_sum(pic1dp_ctx *ctx, int32_t kind);
+int pic1dp_hip_diag_quanta(const pic1dp_input *in, int32_t ispecies, int32_t log2_quantum[6]);
+int pic1dp_hip_diag_quantise(double term, int32_t log2_quantum, int32_t kinetic, int64_t *n);
+int pic1dp_hip_diag_limbs_len(pic1dp_ctx *ctx, int64_t *n);
+int pic1dp_hip_diag_local_exact(pic1dp_ctx *ctx, int32_t ispecies, int64_t *limbs);
+int pic1dp_hip_diag_convert_exact(pic1dp_ctx *ctx, int32_t ispecies, const int64_t *limbs, double sums[3], double *dist);
+int pic1dp_hip_diag_convert(const pic1dp_input *in, int32_t ispecies, const int64_t *limbs, double sums[3], double *dist);
 
 /* ---- multi-GPU: RCCL communicator (replaces MPI_Allreduce at
  * src/pic1dp_interaction.F90:132) ------------------------------------------
@@ -584,7 +626,9 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * were added in doubles straight into the global accumulators -- rare by design, a count that grows with every
  * step says the bounds have lost the population; *ms = the first species' bound on |q| as it stands (waits for the stream);
  * which = 14: *launches = contributions of the exact charge sum (set_charge_sum(1)) beyond 2^62 quanta so far, which
- * were not summed (each batch is reported once as PIC1DP_ERR_ARG), *ms = 0 (waits for the stream) */
+ * were not summed (each batch is reported once as PIC1DP_ERR_ARG), *ms = 0 (waits for the stream)
+ * which = 15: *launches = terms the passes of the exact diagnostics sum (set_diag_sum(1)) did not sum so far (counted
+ * when a pass's results are first handed out), *ms = 0 */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

@@ -129,6 +129,13 @@ SIGNATURES = {
     "pic1dp_hip_charge_quantum": [_INP, C.c_int32, C.POINTER(C.c_int32)],
     "pic1dp_hip_charge_local_exact": [_P, _P],
     "pic1dp_hip_charge_reduced_exact": [_P, _P],
+    "pic1dp_hip_set_diag_sum": [_P, C.c_int32],
+    "pic1dp_hip_diag_quanta": [_INP, C.c_int32, C.POINTER(C.c_int32)],
+    "pic1dp_hip_diag_quantise": [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_diag_limbs_len": [_P, C.POINTER(C.c_int64)],
+    "pic1dp_hip_diag_local_exact": [_P, C.c_int32, _P],
+    "pic1dp_hip_diag_convert_exact": [_P, C.c_int32, _P, _P, _P],
+    "pic1dp_hip_diag_convert": [_INP, C.c_int32, _P, _P, _P],
     "pic1dp_hip_comm_unique_id": [_P],
     "pic1dp_hip_comm_init": [_P, _P],
     "pic1dp_hip_comm_available": [],

@@ -597,6 +597,7 @@ int pic1dp_hip_destroy(pic1dp_ctx *c) {
   comm_release(c);
   optimize_release(c);
   fx_release(c);
+  dfx_release(c);
   for (auto &S : c->sp) {
     (void)hipFree(S.slab[0]);
     (void)hipFree(S.slab[1]);
@@ -1118,7 +1119,12 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 14) return fail(PIC1DP_ERR_ARG, "which must be 0..14");
+  if (which < 0 || which > 15) return fail(PIC1DP_ERR_ARG, "which must be 0..15");
+  if (which == 15) {  // kind 1 of the diagnostics sum: terms its passes did not sum so far (reported as PIC1DP_ERR_ARG)
+    if (launches) *launches = c->dfx_rejected;
+    if (ms) *ms = 0.0;
+    return PIC1DP_OK;
+  }
   if (which == 14) {  // kind 1 of the charge sum: contributions beyond 2^62 quanta so far (not summed; reported as PIC1DP_ERR_ARG)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->st));

@@ -144,6 +144,109 @@ int ensure_diag(pic1dp_ctx *c, int isp) {
 }
 
 
+// ---------------------------------------------------------------------------
+// kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum; kernels.hpp DiagFxArgs)
+// ---------------------------------------------------------------------------
+void dfx_release(pic1dp_ctx *c) {
+  (void)hipFree(c->d_dfx);
+  c->d_dfx = nullptr;
+}
+
+static const char *const kDfxNames[6] = {"markr", "total", "pertb", "sum v^2", "sum v^2 p", "sum v^2 w"};
+
+// the exact pass over species isp into its slot of d_dfx: the markers' histograms and kinetic terms, then the tail
+// slots' kinetic terms (the reference sums the whole local vector; slots beyond np live in set 0)
+static int run_diag_pass_exact(pic1dp_ctx *c, int isp) {
+  const pic1dp_input &in = c->in;
+  Species &S = c->sp[isp];
+  const PSet &A = S.set[c->cur];
+  const size_t words = diag_fx_words(in.nx_opd, in.nv_opd);
+  DiagFxArgs a{};
+  a.acc = c->d_dfx + words * isp;
+  for (int k = 0; k < 6; ++k) a.inv_q[k] = std::ldexp(1.0, -c->dfx_e[isp][k]);
+  HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(long long) * words, c->st));
+  if (S.np > 0)
+    HIP_TRY(launch_ptcldist_exact(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, a, c->num_cu, c->dyn_tail, c->st));
+  HIP_TRY(launch_energy_sums_exact(S.set[0].v, S.p, in.deltaf ? S.set[0].w : nullptr, S.np, S.nalloc - S.np, a,
+                                   in.nx_opd * in.nv_opd, c->st));
+  c->diag_passes++;
+  return 0;
+}
+
+// Species isp's limbs and its counters of terms not summed on the host (out: diag_fx_words), from the cached pass or
+// a new one: this rank's, or (reduced, with a communicator) the limbs summed over the ranks as int64.  A pass that left
+// terms out is an error for every call it serves, until the markers change.
+static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long long> &out) {
+  const pic1dp_input &in = c->in;
+  if (int rc = diag_buffers(c)) return rc;
+  const size_t words = diag_fx_words(in.nx_opd, in.nv_opd), limbs = diag_fx_limbs(in.nx_opd, in.nv_opd);
+  if (!c->d_dfx) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_dfx), sizeof(long long) * words * (in.nspecies + 1)));
+  if (c->diag_version[isp] != c->state_version) {
+    if (int rc = run_diag_pass_exact(c, isp)) return rc;
+    c->diag_pending[isp] = 1;
+    c->diag_version[isp] = c->state_version;
+  }
+  const long long *src = c->d_dfx + words * isp;
+  if (reduced && c->comm) {  // reduce a copy: the cached local limbs stay local
+    long long *red = c->d_dfx + words * in.nspecies;
+    HIP_TRY(hipMemcpyAsync(red, src, sizeof(long long) * words, hipMemcpyDeviceToDevice, c->st));
+    ncclResult_t r = rccl().AllReduce(red, red, limbs, ncclInt64, ncclSum, c->comm, c->st);
+    if (r != ncclSuccess) return fail(PIC1DP_ERR_COMM, "ncclAllReduce: %s", rccl().GetErrorString(r));
+    src = red;
+  } else if (reduced && c->lay.nranks > 1) {
+    return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: take diag_local_exact and reduce the limbs on the host");
+  }
+  out.resize(words);
+  HIP_TRY(hipMemcpyAsync(out.data(), src, sizeof(long long) * words, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  const long long *rej = out.data() + limbs;
+  if (c->diag_pending[isp]) {
+    for (int k = 0; k < 6; ++k) c->dfx_rejected += rej[k];
+    c->diag_pending[isp] = 0;
+  }
+  for (int k = 0; k < 6; ++k)
+    if (rej[k] != 0)
+      return fail(PIC1DP_ERR_ARG,
+                  "exact diagnostics sum: %lld term(s) of species %d, plane %s, lay beyond 2^%d quanta of 2^%d (|p|, |w| or |v| far "
+                  "past the bounds the input gives) and were not summed; the diagnostics are incomplete",
+                  rej[k], isp, kDfxNames[k], k < 3 ? 44 : 62, c->dfx_e[isp][k]);
+  return 0;
+}
+
+// limbs -> the raw sums of the pass: every bin's total converted once (fx_limbs_to_double) and times 2^e; the v
+// histograms are the integer row sums over ix of the planes.  dist: [3 nxv + 3 nv_opd] as ptcldist(finish = 0), or null
+static void dfx_convert(const pic1dp_input &in, const int32_t e[6], const long long *limbs, double *sums, double *dist) {
+  const int nxo = in.nx_opd, nvo = in.nv_opd;
+  const size_t nxv = static_cast<size_t>(nxo) * nvo;
+  for (int k = 0; k < 3 && dist; ++k) {
+    const long long *hi = limbs + 2 * k * nxv, *lo = hi + nxv;
+    const double q = std::ldexp(1.0, e[k]);
+    for (size_t i = 0; i < nxv; ++i) dist[k * nxv + i] = fx_limbs_to_double(hi[i], static_cast<unsigned long long>(lo[i])) * q;
+    for (int iv = 0; iv < nvo; ++iv) {
+      long long H = 0;
+      unsigned long long L = 0;   // (each bin normalised first: the row's lo sum stays below nx_opd 2^32)
+      for (int ix = 0; ix < nxo; ++ix) {
+        const unsigned long long l = static_cast<unsigned long long>(lo[static_cast<size_t>(iv) * nxo + ix]);
+        H += hi[static_cast<size_t>(iv) * nxo + ix] + static_cast<long long>(l >> 32);
+        L += l & 0xffffffffull;
+      }
+      dist[3 * nxv + static_cast<size_t>(k) * nvo + iv] = fx_limbs_to_double(H, L) * q;
+    }
+  }
+  for (int k = 0; k < 3 && sums; ++k)
+    sums[k] = fx_limbs_to_double(limbs[6 * nxv + 2 * k], static_cast<unsigned long long>(limbs[6 * nxv + 2 * k + 1])) *
+              std::ldexp(1.0, e[3 + k]);
+}
+
+// what the calls of kind 1 serve from: the raw kinetic sums and / or histograms of species isp
+static int dfx_serve(pic1dp_ctx *c, int isp, bool reduced, double *sums, double *dist) {
+  std::vector<long long> limbs;
+  if (int rc = dfx_limbs_host(c, isp, reduced, limbs)) return rc;
+  dfx_convert(c->in, c->dfx_e[isp], limbs.data(), sums, dist);
+  return 0;
+}
+
+
 }  // namespace pic1dp_host
 
 extern "C" {
@@ -152,8 +255,12 @@ int pic1dp_hip_energy_sums(pic1dp_ctx *c, int32_t isp, double out[3]) {
   CHECK_CTX(c);
   if (isp < 0 || isp >= c->in.nspecies || !out) return fail(PIC1DP_ERR_ARG, "bad argument");
   if (int rc = require_loaded(c)) return rc;
-  if (int rc = ensure_diag(c, isp)) return rc;
-  for (int k = 0; k < 3; ++k) out[k] = c->diag_sums[3 * static_cast<size_t>(isp) + k];
+  if (c->diag_sum == 1) {
+    if (int rc = dfx_serve(c, isp, false, out, nullptr)) return rc;
+  } else {
+    if (int rc = ensure_diag(c, isp)) return rc;
+    for (int k = 0; k < 3; ++k) out[k] = c->diag_sums[3 * static_cast<size_t>(isp) + k];
+  }
   if (!c->in.deltaf) out[2] = out[1];
   return 0;
 }
@@ -166,6 +273,14 @@ int pic1dp_hip_output_scalars(pic1dp_ctx *c, double *out, int32_t n) {
   const int ns = c->in.nspecies;
   if (!out || n != 2 + 3 * ns) return fail(PIC1DP_ERR_ARG, "out must hold 2 + 3*nspecies doubles");
   std::vector<double> sums(3 * ns);
+  if (c->diag_sum == 1) {  // the limbs summed over the ranks as integers, then converted: every rank forms the same doubles
+    if (int rc = require_loaded(c)) return rc;
+    for (int s = 0; s < ns; ++s) {
+      if (int rc = dfx_serve(c, s, c->comm != nullptr, &sums[3 * s], nullptr)) return rc;
+      if (!c->in.deltaf) sums[3 * s + 2] = sums[3 * s + 1];
+    }
+    return pic1dp_hip_output_scalars_from(c, sums.data(), out, n);
+  }
   for (int s = 0; s < ns; ++s)
     if (int rc = pic1dp_hip_energy_sums(c, s, &sums[3 * s])) return rc;
   if (c->comm) {  // VecSum's scalar all-reduce
@@ -268,8 +383,21 @@ int pic1dp_hip_ptcldist(pic1dp_ctx *c, int32_t isp, int32_t finish, double *mark
   if (int rc = require_loaded(c)) return rc;
   const pic1dp_input &in = c->in;
   const int nxo = in.nx_opd, nvo = in.nv_opd;
-  if (int rc = ensure_diag(c, isp)) return rc;
   const size_t nxv = static_cast<size_t>(nxo) * nvo, ntot = 3 * nxv + 3 * nvo;
+  if (c->diag_sum == 1) {
+    if (finish && !c->comm && c->lay.nranks > 1)
+      return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: take diag_local_exact and reduce the limbs on the host");
+    std::vector<double> raw(ntot);
+    if (int rc = dfx_serve(c, isp, finish && c->comm, nullptr, raw.data())) return rc;
+    double *mxv = raw.data(), *txv = mxv + nxv, *pxv = txv + nxv, *mv = pxv + nxv, *tv = mv + nvo, *pv = tv + nvo;
+    if (finish) finish_ptcldist(in, isp, mxv, txv, pxv, mv, tv, pv);
+    const double *src[6] = {mxv, txv, pxv, mv, tv, pv};
+    double *dst[6] = {markr_xv, total_xv, pertb_xv, markr_v, total_v, pertb_v};
+    for (int k = 0; k < 6; ++k)
+      if (dst[k]) std::memcpy(dst[k], src[k], sizeof(double) * (k < 3 ? nxv : static_cast<size_t>(nvo)));
+    return 0;
+  }
+  if (int rc = ensure_diag(c, isp)) return rc;
   const double *hist = c->d_dist + ntot * isp;
   if (finish && c->comm) {  // reduce a copy: the cached local histograms stay local
     double *red = c->d_dist + ntot * in.nspecies;
@@ -319,7 +447,7 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
   const int ns = in.nspecies;
   if (!scalars || nscal != 2 + 3 * ns) return fail(PIC1DP_ERR_ARG, "scalars must hold 2 + 3*nspecies doubles");
   const size_t nx = in.nx, nm = in.nmode, ntot = dist_len(in), nxv = static_cast<size_t>(in.nx_opd) * in.nv_opd;
-  if (c->comm || c->lay.nranks > 1) {
+  if (c->comm || c->lay.nranks > 1 || c->diag_sum == 1) {  // (kind 1 of the diagnostics sum: served by the separate calls)
     if (int rc = pic1dp_hip_output_scalars(c, scalars, nscal)) return rc;
     if (int rc = pic1dp_hip_get_field(c, E, cd, re, im)) return rc;
     for (int s = 0; s < ns && dist; ++s) {
@@ -464,6 +592,83 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
     std::memcpy(dist + ntot * s, d, sizeof(double) * ntot);
   }
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// kind 1 of the diagnostics sum: the switch, the quanta, the split phase
+// ---------------------------------------------------------------------------
+int pic1dp_hip_diag_quanta(const pic1dp_input *in, int32_t ispecies, int32_t log2_quantum[6]) {
+  if (!in || !log2_quantum) return fail(PIC1DP_ERR_ARG, "null argument");
+  int32_t e = 0;
+  if (int rc = pic1dp_hip_charge_quantum(in, ispecies, &e)) return rc;
+  const int kb = e + 52;  // |p|, |w| <= 2^kb
+  const double v2 = in->v_max * in->v_max;
+  if (!(v2 > 0.0) || !std::isfinite(v2)) return fail(PIC1DP_ERR_ARG, "v_max must be positive and finite");
+  int kv = 0;
+  const double f = std::frexp(v2, &kv);  // ceil(log2 v_max^2) = kv, or kv - 1 for a power of two
+  if (f == 0.5) kv -= 1;
+  log2_quantum[0] = -40;
+  log2_quantum[1] = log2_quantum[2] = kb - 40;
+  log2_quantum[3] = kv - 52;
+  log2_quantum[4] = log2_quantum[5] = kv + kb - 52;
+  return 0;
+}
+
+int pic1dp_hip_diag_quantise(double term, int32_t log2_quantum, int32_t kinetic, int64_t *n) {
+  if (!n) return fail(PIC1DP_ERR_ARG, "null argument");
+  long long q = 0;
+  if (!diag_fx_quantise(term, std::ldexp(1.0, -log2_quantum), kinetic ? FX_LIMIT : DIAG_FX_LIMIT, &q))
+    return fail(PIC1DP_ERR_ARG, "a term of 2^%d quanta or more is not summed", kinetic ? 62 : 44);
+  *n = q;
+  return 0;
+}
+
+int pic1dp_hip_set_diag_sum(pic1dp_ctx *c, int32_t kind) {
+  CHECK_CTX(c);
+  if (kind != 0 && kind != 1) return fail(PIC1DP_ERR_ARG, "diagnostics sum must be 0 (FP64 and per-pass fixed point) or 1 (exact)");
+  if (c->seq != Seq::Clean || c->owed != Owed::Nothing || c->charge_pending || c->fused_pending)
+    return fail(PIC1DP_ERR_STATE, "set_diag_sum while a push, a charge or a solve is pending: call it between time steps");
+  if (kind == 1)
+    for (int s = 0; s < c->in.nspecies; ++s)
+      if (int rc = pic1dp_hip_diag_quanta(&c->in, s, c->dfx_e[s])) return rc;
+  // the cached diagnostics belong to the other kind
+  for (size_t s = 0; s < c->diag_version.size(); ++s) c->diag_version[s] = 0, c->diag_pending[s] = 0;
+  c->diag_sum = kind;
+  return 0;
+}
+
+int pic1dp_hip_diag_limbs_len(pic1dp_ctx *c, int64_t *n) {
+  CHECK_CTX(c);
+  if (!n) return fail(PIC1DP_ERR_ARG, "null argument");
+  *n = static_cast<int64_t>(diag_fx_limbs(c->in.nx_opd, c->in.nv_opd));
+  return 0;
+}
+
+int pic1dp_hip_diag_local_exact(pic1dp_ctx *c, int32_t isp, int64_t *limbs) {
+  CHECK_CTX(c);
+  if (isp < 0 || isp >= c->in.nspecies || !limbs) return fail(PIC1DP_ERR_ARG, "bad argument");
+  if (c->diag_sum != 1) return fail(PIC1DP_ERR_STATE, "diag_local_exact needs set_diag_sum(1)");
+  if (int rc = require_loaded(c)) return rc;
+  std::vector<long long> w;
+  if (int rc = dfx_limbs_host(c, isp, false, w)) return rc;
+  std::memcpy(limbs, w.data(), sizeof(int64_t) * diag_fx_limbs(c->in.nx_opd, c->in.nv_opd));
+  return 0;
+}
+
+int pic1dp_hip_diag_convert(const pic1dp_input *in, int32_t isp, const int64_t *limbs, double sums[3], double *dist) {
+  if (!in || !limbs) return fail(PIC1DP_ERR_ARG, "null argument");
+  int32_t e[6];
+  if (int rc = pic1dp_hip_diag_quanta(in, isp, e)) return rc;
+  if (in->nx_opd < 1 || in->nv_opd < 2) return fail(PIC1DP_ERR_ARG, "nx_opd >= 1 and nv_opd >= 2 required");
+  static_assert(sizeof(long long) == sizeof(int64_t), "limbs are 64-bit");
+  dfx_convert(*in, e, reinterpret_cast<const long long *>(limbs), sums, dist);
+  if (sums && !in->deltaf) sums[2] = sums[1];
+  return 0;
+}
+
+int pic1dp_hip_diag_convert_exact(pic1dp_ctx *c, int32_t isp, const int64_t *limbs, double sums[3], double *dist) {
+  CHECK_CTX(c);
+  return pic1dp_hip_diag_convert(&c->in, isp, limbs, sums, dist);
 }
 
 }  // extern "C"

@@ -67,9 +67,9 @@ static size_t pred_doubles(const pic1dp_ctx *c) {
 // output pays a first-sub-step pass again (k_step_half): 10 steps + output_all at 1e8 markers 10.57 ms against 9.5 for
 // ten plain steps --, whereas k_step_one followed by the diagnostics' own pass (k_ptcldist: it changes no marker, the
 // prediction stays valid) costs that pass alone (profiles/r05/experiments/diag_bench.log).
-// (kind 1 of the charge sum: never -- the diagnostics keep their own pass and summation)
+// (kind 1 of the charge sum or of the diagnostics sum: never -- the diagnostics keep their own pass and summation)
 static bool diag_in_step(const pic1dp_ctx *c) {
-  return c->charge_sum == 0 && (c->fuse_output == 2 || (c->fuse_output == 1 && !predict_capable(c)));
+  return c->charge_sum == 0 && c->diag_sum == 0 && (c->fuse_output == 2 || (c->fuse_output == 1 && !predict_capable(c)));
 }
 
 // the accumulator set the marker kernels deposit into from now on (d_rho_all / d_pred_all hold three)

@@ -311,6 +311,13 @@ struct pic1dp_ctx {
   unsigned long long fx_ovf_seen[8] = {0};   // ... of which the host has reported
   int fx_e[8] = {0};                         // e_s of the quantum 2^e_s
   double fx_q[8] = {0}, fx_inv_q[8] = {0};   // 2^e_s, 2^-e_s
+  // kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum, capi_diag.cpp; kernels.hpp DiagFxArgs): output_all's
+  // diagnostics from exact integer sums, always in their own pass (no k_step_full<DIAG> while it is set); independent of
+  // charge_sum.  The cached pass of a species is d_dfx's slot, valid while diag_version says so.
+  int diag_sum = 0;
+  long long *d_dfx = nullptr;                // [nspecies + 1][diag_fx_words]: per species, + the copy summed over ranks
+  int dfx_e[8][6] = {{0}};                   // the six log2 quanta per species (pic1dp_hip_diag_quanta)
+  int64_t dfx_rejected = 0;                  // terms the exact passes did not sum so far (kernel_stats 15)
   // launch
   int threads_req = 0, bpc_req = 0;
   // timing
@@ -450,5 +457,6 @@ int diag_max_blocks(const pic1dp_ctx *c);
 const DistGeom &dist_geom(pic1dp_ctx *c);
 int pinned(pic1dp_ctx *c, size_t ndoubles, double **out);   // the context's pinned staging with room for ndoubles
 size_t dist_len(const pic1dp_input &in);
+void dfx_release(pic1dp_ctx *c);
 
 }  // namespace pic1dp_host

@@ -224,5 +224,141 @@ __device__ __forceinline__ void ptcldist_finish(const DistGeom &dg, const DistBi
   }
 }
 
+// ---------------------------------------------------------------------------
+// Kind 1 of the diagnostics sum (kernels.hpp DiagFxArgs): the same terms, each rounded once to whole
+// quanta, summed as integers.  A workgroup's LDS copy (LDS = true) holds ONE signed 64-bit word per bin, the three
+// planes interleaved as above; terms stay below 2^44 quanta and a bin receives at most 4 * 2^17 of them between two
+// flushes, so the word stays below 2^63.  The flush splits every word into (hi, lo 32 bits) and adds the two into
+// the global rows with non-returning integer atomics.  LDS = false adds a term's limbs straight into the global rows.
+// The v histograms are not accumulated at all: they are the integer row sums of the planes, formed by the host.
+// ---------------------------------------------------------------------------
+struct DistBinsFx {
+  unsigned long long *s;     // LDS: [nxv][3]
+  unsigned long long *acc;   // global: DiagFxArgs::acc
+  int nxv;
+};
+struct KinFx {
+  unsigned long long lo[3] = {0ull, 0ull, 0ull}, hi[3] = {0ull, 0ull, 0ull};   // two-limb sums of this thread
+};
+__device__ __forceinline__ void glb_add_u64(unsigned long long *p, unsigned long long v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long *dfx_rejected(const DistBinsFx &b, int k) {
+  return b.acc + 6 * static_cast<size_t>(b.nxv) + 6 + k;
+}
+template <bool LDS>
+__device__ __forceinline__ void dfx_bin_add(const DistBinsFx &b, int k, int cell, double term, double inv_q) {
+  const double t = __builtin_rint(term * inv_q);   // term 2^-e is exact: ONE rounding, to nearest even
+  if (!(fabs(t) < DIAG_FX_LIMIT)) {                // (NaN too) not summed: counted, reported by the host
+    glb_add_u64(dfx_rejected(b, k), 1ull);
+    return;
+  }
+  // the integer t as two's complement (|t| < 2^44: the sum with 1.5 * 2^52 is exact, its low bits are t)
+  const unsigned long long n = static_cast<unsigned long long>(__double_as_longlong(t + 6755399441055744.0)) - 0x4338000000000000ull;
+  if constexpr (LDS) {
+    __hip_atomic_fetch_add(&b.s[3 * cell + k], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else {
+    const unsigned long long lo = n & 0xffffffffull;
+    const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(n) >> 32);
+    if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
+    if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+  }
+}
+__device__ __forceinline__ void dfx_kin_add(KinFx &s, const DistBinsFx &b, int k, double term, double inv_q) {
+  long long n;
+  if (!diag_fx_quantise(term, inv_q, FX_LIMIT, &n)) {
+    glb_add_u64(dfx_rejected(b, 3 + k), 1ull);
+    return;
+  }
+  s.lo[k] += static_cast<unsigned long long>(n) & 0xffffffffull;
+  s.hi[k] += static_cast<unsigned long long>(n >> 32);
+}
+// the kinetic terms of one marker slot (src/pic1dp_output.F90:126-151)
+template <bool DELTAF>
+__device__ __forceinline__ void kinetic_one_exact(double pv, double pp, double pw, const DistBinsFx &b, KinFx &sm,
+                                                  const DiagFxArgs &a) {
+  const double v2 = pv * pv;
+  dfx_kin_add(sm, b, 0, v2, a.inv_q[3]);
+  dfx_kin_add(sm, b, 1, v2 * pp, a.inv_q[4]);
+  if constexpr (DELTAF) dfx_kin_add(sm, b, 2, v2 * pw, a.inv_q[5]);
+}
+// ptcldist_one with exact sums: the cells, the weights and the products are formed as there
+template <bool LDS, bool DELTAF>
+__device__ __forceinline__ void ptcldist_one_exact(double px, double pv, double pp, double pw, const DistGeom &dg,
+                                                   const DistBinsFx &b, KinFx &sm, const DiagFxArgs &a) {
+  const int nxo = dg.nxo, nvo = dg.nvo;
+  kinetic_one_exact<DELTAF>(pv, pp, pw, b, sm, a);
+  if (fabs(pv) >= dg.vmax) return;                      // :241
+#if PIC1DP_FAST_DIV
+  double sx = diag_div(px, dg.lx, dg.rlx) * static_cast<double>(nxo);    // :243
+#else
+  double sx = px / dg.lx * static_cast<double>(nxo);
+#endif
+  const double fx = floor(sx);
+  int ix = static_cast<int>(fx);
+  sx = 1.0 - (sx - fx);
+  if (ix == nxo) ix = 0;
+  const double av = pv + dg.vmax;
+  double sv = (dg.vfast ? diag_div(av, dg.dv, dg.rdv) : av / dg.dv) * static_cast<double>(nvo - 1);  // :247
+  const double fv = floor(sv);
+  const int iv = static_cast<int>(fv);
+  sv = 1.0 - (sv - fv);
+  if (static_cast<unsigned>(ix) >= static_cast<unsigned>(nxo) || static_cast<unsigned>(iv) >= static_cast<unsigned>(nvo)) return;
+  const int ivu = iv + 1 < nvo ? iv + 1 : iv;
+  const int ixr = ix + 1 > nxo - 1 ? 0 : ix + 1;
+  const double sxr = 1.0 - sx, svu = 1.0 - sv;
+  const int cell[4] = {iv * nxo + ix, ivu * nxo + ix, iv * nxo + ixr, ivu * nxo + ixr};
+  const double wt[4] = {sx * sv, sx * svu, sxr * sv, sxr * svu};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    dfx_bin_add<LDS>(b, 0, cell[c], wt[c], a.inv_q[0]);
+    dfx_bin_add<LDS>(b, 1, cell[c], wt[c] * pp, a.inv_q[1]);
+    if constexpr (DELTAF) dfx_bin_add<LDS>(b, 2, cell[c], wt[c] * pw, a.inv_q[2]);
+  }
+}
+// the workgroup's LDS copy into the global rows, zeroed on the way; the caller puts barriers around it
+__device__ __forceinline__ void dfx_flush(const DistBinsFx &b) {
+  const int n = 3 * b.nxv;
+  const int rot = static_cast<int>((static_cast<long long>(blockIdx.x) * n) / gridDim.x);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    int j = i + rot;                                    // j: plane k, cell -- the order of the global rows
+    if (j >= n) j -= n;
+    const int k = j / b.nxv, cell = j - k * b.nxv;
+    const unsigned long long w = b.s[3 * cell + k];
+    if (w == 0ull) continue;
+    b.s[3 * cell + k] = 0ull;
+    const unsigned long long lo = w & 0xffffffffull;
+    const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(w) >> 32);
+    if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
+    if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+  }
+}
+// the threads' two-limb kinetic sums over the workgroup (integers: any order), then one pair of global atomics per sum;
+// sK: six zeroed LDS words
+__device__ __forceinline__ void dfx_kin_finish(const KinFx &sm, const DistBinsFx &b, unsigned long long *sK) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    unsigned long long lo = sm.lo[k], hi = sm.hi[k];
+    for (int off = 32; off > 0; off >>= 1) {
+      lo += __shfl_down(lo, off, 64);
+      hi += __shfl_down(hi, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      if (lo) __hip_atomic_fetch_add(&sK[2 * k + 1], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (hi) __hip_atomic_fetch_add(&sK[2 * k], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {   // (hi, lo) of sum k at acc[6 nxv + 2 k], + 1; lo is below 2^32 per term, 2^64 for 2^32 terms
+    unsigned long long w = sK[threadIdx.x];
+    if (threadIdx.x & 1) {  // the carry of lo goes with hi: the stored lo stays below 2^32 per workgroup
+      w &= 0xffffffffull;
+    } else {
+      w += sK[threadIdx.x + 1] >> 32;
+    }
+    if (w) glb_add_u64(b.acc + 6 * static_cast<size_t>(b.nxv) + threadIdx.x, w);
+  }
+}
+
 }  // namespace
 }  // namespace pic1dp

@@ -520,6 +520,36 @@ hipError_t launch_ptcldist(const double *x, const double *v, const double *p, co
                            int64_t np, const DistGeom &dg, bool deltaf, double bound_p, double bound_w,
                            double *out, double *partial, int num_cu, int dyn_tail, hipStream_t st, bool *fixed_point);
 int ptcldist_blocks(int64_t np, int nxo, int nvo, int num_cu);
+
+// Kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum): every term of the pass -- the corner weights
+// times 1, p, w of the (x, v) histograms, and v^2, v^2 p, v^2 w of the kinetic sums -- is rounded once to a whole number
+// n = rint(t 2^-e) of quanta 2^e (six per species, from the input alone: pic1dp_hip_diag_quanta) and the integers are
+// summed exactly.  acc: [3 planes][2][nx_opd nv_opd] (hi row, lo row, as FxArgs) | [3 sums][2] (hi, lo) |
+// [6] terms that were not summed (plane 0..2: 2^44 quanta or more, sum 0..2: 2^62 or more) | [2] padding.
+struct DiagFxArgs {
+  long long *acc;
+  double inv_q[6];   // 2^-e: markr, total, pertb, sum v^2, sum v^2 p, sum v^2 w
+};
+constexpr double DIAG_FX_LIMIT = 0x1p44;   // a histogram term of this many quanta or more is not summed
+constexpr int DIAG_FX_WINDOW_TRIPS = 32;   // a workgroup flushes its LDS copy after this many trips of 2 x 1024 markers
+inline size_t diag_fx_limbs(int nxo, int nvo) { return 6 * static_cast<size_t>(nxo) * nvo + 6; }
+inline size_t diag_fx_words(int nxo, int nvo) { return diag_fx_limbs(nxo, nvo) + 8; }
+// n = rint(t 2^-e) of a term, one rounding to nearest even (t 2^-e itself is exact); false: |n| >= limit or NaN
+__host__ __device__ inline bool diag_fx_quantise(double term, double inv_q, double limit, long long *n) {
+  const double t = __builtin_rint(term * inv_q);
+  if (!(__builtin_fabs(t) < limit)) return false;
+  *n = static_cast<long long>(t);
+  return true;
+}
+// the exact pass over markers [0, np) of a species: histograms and kinetic sums into a.acc (accumulated)
+hipError_t launch_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np,
+                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, int num_cu, int dyn_tail,
+                                 hipStream_t st);
+// ... and the kinetic sums of the tail slots [i0, i0 + n) into the same accumulators
+hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
+                                    const DiagFxArgs &a, int nxv, hipStream_t st);
+int ptcldist_exact_blocks(int64_t np, int num_cu);
+bool ptcldist_exact_lds(int nxo, int nvo);
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

@@ -202,6 +202,147 @@ hipError_t launch_ptcldist(const double *x, const double *v, const double *p, co
   return deltaf ? go(k_ptcldist<false, true, false, false>) : go(k_ptcldist<false, false, false, false>);
 }
 
+// ---------------------------------------------------------------------------
+// kind 1 of the diagnostics sum: the exact pass (kernels.hpp DiagFxArgs, device_diag.hpp)
+// ---------------------------------------------------------------------------
+namespace {
+
+// k_ptcldist's loop -- marker pairs, the next trip's loads in flight, the drawn tail, the NT switch -- with integer sums:
+// no max |p|, max |w| or overflow bookkeeping and no repeat pass (the quanta come from the input), the kinetic sums
+// reduced over the workgroup as integers.  LDS: the workgroup's copy is flushed every DIAG_FX_WINDOW_TRIPS dealt trips
+// and once at the end; the drawn rows are capped one below that, and the odd marker falls into the first window, so a
+// word sees fewer than 2^17 markers = 2^19 terms of less than 2^44 quanta between two flushes.  The dealt trips are the
+// same number for every thread of the workgroup, so the barriers around a flush inside the loop are met by all.
+template <bool LDS, bool DELTAF, bool NT>
+__global__ void __launch_bounds__(1024)
+k_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const DistGeom dg,
+                 const DiagFxArgs a, int dyn_tail) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nxv = dg.nxo * dg.nvo;
+  unsigned long long *sK = reinterpret_cast<unsigned long long *>(smem);   // [6] kinetic sums, then the drawn chunks' counter
+  unsigned *sDraw = reinterpret_cast<unsigned *>(sK + 6);
+  const DistBinsFx b{sK + 8, reinterpret_cast<unsigned long long *>(a.acc), nxv};
+  if constexpr (LDS)
+    for (int i = threadIdx.x; i < 3 * nxv; i += blockDim.x) b.s[i] = 0ull;
+  if (threadIdx.x < 6) sK[threadIdx.x] = 0ull;
+  if (threadIdx.x == 0) *sDraw = 0u;
+  __syncthreads();
+  const int64_t npair = np >> 1;
+  const double2 *x2 = reinterpret_cast<const double2 *>(x), *v2 = reinterpret_cast<const double2 *>(v);
+  const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
+  KinFx sm;
+  if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t i = tidx(np - 1);
+    ptcldist_one_exact<LDS, DELTAF>(x[i], v[i], p[i], DELTAF ? w[i] : 0.0, dg, b, sm, a);
+  }
+  PairRows rows = pair_rows(npair, dyn_tail);
+  {
+    const int waves = static_cast<int>(blockDim.x >> 6);
+    const int extra = rows.drawn_total / waves - (DIAG_FX_WINDOW_TRIPS - 1);
+    if (extra > 0) {
+      rows.dealt += extra;
+      rows.drawn_total -= extra * waves;
+    }
+  }
+  int k = 0;
+  int64_t j = rows.first + threadIdx.x;
+  bool have = rows.dealt > 0 || draw_chunk(rows, sDraw, j);
+  double2 X = make_double2(0.0, 0.0), V = X, P = X, W = X;
+  if (have && j < npair) {
+    const int64_t o = tidx2(j);
+    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
+    if constexpr (DELTAF) W = ld2t<NT>(w2 + o);
+  }
+  while (have) {
+    int64_t jn = j + rows.stride;
+    bool have_n = true;
+    if (++k >= rows.dealt) have_n = draw_chunk(rows, sDraw, jn);
+    double2 Xn = make_double2(0.0, 0.0), Vn = Xn, Pn = Xn, Wn = Xn;
+    if (have_n && jn < npair) {  // the next trip's loads are under way while this trip's atomics run
+      const int64_t o = tidx2(jn);
+      Xn = ld2t<NT>(x2 + o), Vn = ld2t<NT>(v2 + o), Pn = ld2t<NT>(p2 + o);
+      if constexpr (DELTAF) Wn = ld2t<NT>(w2 + o);
+    }
+    if (j < npair) {
+      ptcldist_one_exact<LDS, DELTAF>(X.x, V.x, P.x, W.x, dg, b, sm, a);
+      ptcldist_one_exact<LDS, DELTAF>(X.y, V.y, P.y, W.y, dg, b, sm, a);
+    }
+    if constexpr (LDS) {
+      if (k <= rows.dealt && (k & (DIAG_FX_WINDOW_TRIPS - 1)) == 0) {   // (k: dealt trips done -- uniform over the workgroup)
+        __syncthreads();
+        dfx_flush(b);
+        __syncthreads();
+      }
+    }
+    X = Xn, V = Vn, P = Pn, W = Wn;
+    j = jn;
+    have = have_n;
+  }
+  dfx_kin_finish(sm, b, sK);
+  if constexpr (LDS) {
+    __syncthreads();
+    dfx_flush(b);
+  }
+}
+
+// the tail slots' kinetic terms into the same accumulators
+template <bool DELTAF>
+__global__ void __launch_bounds__(256)
+k_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n, int nxv, const DiagFxArgs a) {
+  __shared__ unsigned long long sK[6];
+  const DistBinsFx b{nullptr, reinterpret_cast<unsigned long long *>(a.acc), nxv};
+  if (threadIdx.x < 6) sK[threadIdx.x] = 0ull;
+  __syncthreads();
+  KinFx sm;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; k < n; k += stride) {
+    const int64_t i = tidx(i0 + k);
+    kinetic_one_exact<DELTAF>(v[i], p[i], DELTAF ? w[i] : 0.0, b, sm, a);
+  }
+  dfx_kin_finish(sm, b, sK);
+}
+
+}  // namespace
+
+// one 64-bit word per bin and plane in the workgroup's LDS copy, + the kinetic words and the drawn chunks' counter
+bool ptcldist_exact_lds(int nxo, int nvo) {
+  return sizeof(long long) * (3 * static_cast<size_t>(nxo) * nvo + 8) <= 150 * 1024;
+}
+// A workgroup's flush costs what a few trips cost (two global atomics per non-zero bin), so a workgroup gets at least
+// 2^17 markers (64 trips) before a second one is started; never more workgroups than CUs (one copy per CU fits).
+int ptcldist_exact_blocks(int64_t np, int num_cu) {
+  int64_t blocks = np >> 17;
+  if (blocks > num_cu) blocks = num_cu;
+  if (blocks < 1) blocks = 1;
+  return static_cast<int>(blocks);
+}
+
+hipError_t launch_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np,
+                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, int num_cu, int dyn_tail,
+                                 hipStream_t st) {
+  const bool lds = ptcldist_exact_lds(dg.nxo, dg.nvo);
+  const size_t bytes = sizeof(long long) * ((lds ? 3 * static_cast<size_t>(dg.nxo) * dg.nvo : 0) + 8);
+  const int blocks = ptcldist_exact_blocks(np, num_cu);
+  const bool nt = 32.0 * static_cast<double>(np) > 288.0 * 1048576.0;   // as launch_ptcldist
+  auto go = [&](auto kern) {
+    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(1024), bytes, st, x, v, p, w, np, dg, a, dyn_tail);
+  };
+  if (lds) {
+    if (nt) return deltaf ? go(k_ptcldist_exact<true, true, true>) : go(k_ptcldist_exact<true, false, true>);
+    return deltaf ? go(k_ptcldist_exact<true, true, false>) : go(k_ptcldist_exact<true, false, false>);
+  }
+  if (nt) return deltaf ? go(k_ptcldist_exact<false, true, true>) : go(k_ptcldist_exact<false, false, true>);
+  return deltaf ? go(k_ptcldist_exact<false, true, false>) : go(k_ptcldist_exact<false, false, false>);
+}
+
+hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
+                                    const DiagFxArgs &a, int nxv, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int blocks = static_cast<int>(std::min<int64_t>(1024, (n + 255) / 256));
+  if (w) return launch_kernel(k_energy_sums_exact<true>, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, nxv, a);
+  return launch_kernel(k_energy_sums_exact<false>, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, nxv, a);
+}
+
 namespace {
 __global__ void __launch_bounds__(256) k_pack_record(const PackArgs a, double *out) {
   const int seg = blockIdx.y;

@@ -378,6 +378,40 @@ class Pic1dp:
             raise ValueError("limbs must have nspecies * 2 * nx entries")
         check(self.L.pic1dp_hip_charge_reduced_exact(self._ctx, _ptr(a)))
 
+    # -- exact diagnostics sum (kind 1, include/pic1dp_hip.h) ---------------------------
+    def set_diag_sum(self, kind):
+        """0: the diagnostics pass as it was (default); 1: exact -- every term of the histograms and kinetic sums
+        rounded once to whole quanta (diag_quanta) and summed as integers, so energy_sums, output_scalars, ptcldist
+        and output_all do not depend on the order of the sums.  Only between time steps."""
+        check(self.L.pic1dp_hip_set_diag_sum(self._ctx, int(kind)))
+
+    def diag_quanta(self, ispecies=0):
+        """the six log2 quanta of species ispecies (markr, total, pertb, sum v^2, sum v^2 p, sum v^2 w)"""
+        return diag_quanta(self.inp, ispecies)
+
+    def diag_limbs_len(self):
+        n = C.c_int64()
+        check(self.L.pic1dp_hip_diag_limbs_len(self._ctx, C.byref(n)))
+        return n.value
+
+    def diag_local_exact(self, ispecies=0):
+        """kind 1 split phase: this rank's exact diagnostics sums of a species as int64 limbs, [3 planes][2][nx_opd
+        nv_opd] (hi, lo) then [3 sums][2]; to be summed element by element over the ranks and handed to
+        diag_convert_exact"""
+        out = np.empty(self.diag_limbs_len(), dtype=np.int64)
+        check(self.L.pic1dp_hip_diag_local_exact(self._ctx, int(ispecies), _ptr(out)))
+        return out
+
+    def diag_convert_exact(self, limbs, ispecies=0):
+        """(sums, raw): the rank-summed limbs as energy_sums and ptcldist(finish=False) return them"""
+        a = np.ascontiguousarray(limbs, dtype=np.int64)
+        if a.size != self.diag_limbs_len():
+            raise ValueError("limbs must have 6 * nx_opd * nv_opd + 6 entries")
+        nxv, nvo = self.inp.nx_opd * self.inp.nv_opd, self.inp.nv_opd
+        sums, dist = np.empty(3), np.empty(3 * nxv + 3 * nvo)
+        check(self.L.pic1dp_hip_diag_convert_exact(self._ctx, int(ispecies), _ptr(a), _ptr(sums), _ptr(dist)))
+        return sums, _split_dist(dist, nxv, nvo)
+
     # -- RCCL ------------------------------------------------------------------------
     def comm_unique_id(self):
         buf = (C.c_ubyte * _lib.COMM_ID_BYTES)()
@@ -497,6 +531,41 @@ def charge_quantum(inp, ispecies=0):
     e = C.c_int32()
     check(_lib.load().pic1dp_hip_charge_quantum(C.byref(inp), int(ispecies), C.byref(e)))
     return e.value
+
+
+_DIST_NAMES = ("markr_xv", "total_xv", "pertb_xv", "markr_v", "total_v", "pertb_v")
+
+
+def _split_dist(dist, nxv, nvo):
+    parts = [dist[0:nxv], dist[nxv:2 * nxv], dist[2 * nxv:3 * nxv], dist[3 * nxv:3 * nxv + nvo],
+             dist[3 * nxv + nvo:3 * nxv + 2 * nvo], dist[3 * nxv + 2 * nvo:]]
+    return dict(zip(_DIST_NAMES, parts))
+
+
+def diag_quanta(inp, ispecies=0):
+    """the six log2 quanta of the exact diagnostics sum of a species -- markr, total, pertb, sum v^2, sum v^2 p,
+    sum v^2 w -- from the input alone (no device)"""
+    e = (C.c_int32 * 6)()
+    check(_lib.load().pic1dp_hip_diag_quanta(C.byref(inp), int(ispecies), e))
+    return list(e)
+
+
+def diag_quantise(term, log2_quantum, kinetic=False):
+    """n = rint(term 2^-log2_quantum) as the exact diagnostics pass forms it; Pic1dpError for a term it would not sum"""
+    n = C.c_int64()
+    check(_lib.load().pic1dp_hip_diag_quantise(float(term), int(log2_quantum), int(bool(kinetic)), C.byref(n)))
+    return n.value
+
+
+def diag_convert(inp, limbs, ispecies=0):
+    """(sums, raw) from a species' limbs summed over the ranks, from the input alone (no context, no device)"""
+    a = np.ascontiguousarray(limbs, dtype=np.int64)
+    nxv, nvo = inp.nx_opd * inp.nv_opd, inp.nv_opd
+    if a.size != 6 * nxv + 6:
+        raise ValueError("limbs must have 6 * nx_opd * nv_opd + 6 entries")
+    sums, dist = np.empty(3), np.empty(3 * nxv + 3 * nvo)
+    check(_lib.load().pic1dp_hip_diag_convert(C.byref(inp), int(ispecies), _ptr(a), _ptr(sums), _ptr(dist)))
+    return sums, _split_dist(dist, nxv, nvo)
 
 
 def field_transform_supported(nx, transform=1):

@@ -13,6 +13,7 @@ integer(c_int32_t), parameter :: vec_file_classid = 1211214
 ! way to the host) and the file writes; the counterpart of the reference's global_iwt_output timer
 logical :: output_profile = .false.
 real(c_double) :: output_lib_s = 0.0_c_double, output_write_s = 0.0_c_double
+logical :: output_exact = .false.   ! PIC1DP_DIAG_SUM=exact: several ranks reduce the diagnostics as int64 limbs
 integer :: output_records = 0
 ! A record is assembled in memory as big-endian 8-byte words (every item of it is one: a float64, or a Vec's two int32 of
 ! header) and written with ONE native write: through the Fortran runtime's convert='big_endian' the same bytes cost 0.12 ms
@@ -107,7 +108,9 @@ subroutine output_all(ctx, inp, verbosity)
   integer(c_int32_t), intent(in) :: verbosity
   real(c_double) :: scal(2 + 3 * inp%nspecies), sums(3 * inp%nspecies)
   real(c_double) :: e(inp%nx), cd(inp%nx), re(inp%nmode), im(inp%nmode)
-  real(c_double), allocatable :: mxv(:), txv(:), pxv(:), mv(:), tv(:), pv(:), dist(:)
+  real(c_double), allocatable :: mxv(:), txv(:), pxv(:), mv(:), tv(:), pv(:), dist(:), raw(:, :)
+  integer(c_int64_t), allocatable :: limbs(:)
+  integer(c_int64_t) :: nlimbs
   integer(c_int32_t) :: s, itime
   real(c_double) :: time, progress(2)
   character :: cprogress
@@ -135,10 +138,23 @@ subroutine output_all(ctx, inp, verbosity)
   else
   allocate (mxv(nxv), txv(nxv), pxv(nxv), mv(inp%nv_opd), tv(inp%nv_opd), pv(inp%nv_opd))
   ! VecSum over ranks (src/pic1dp_output.F90:126-151): local sums, reduced to rank 0, finished there
+  if (output_exact) then
+    ! the exact diagnostics sum: every species' limbs summed over the ranks as integers, converted on rank 0
+    ntot = 3 * nxv + 3 * inp%nv_opd
+    call pic1dp_hip_check(pic1dp_hip_diag_limbs_len(ctx, nlimbs), 'diag_limbs_len')
+    allocate (limbs(nlimbs), raw(ntot, inp%nspecies))
+    do s = 0, inp%nspecies - 1
+      call pic1dp_hip_check(pic1dp_hip_diag_local_exact(ctx, s, limbs), 'diag_local_exact')
+      call ranks_reduce_int64_to_root(limbs, int(nlimbs))
+      if (ranks_rank == 0) call pic1dp_hip_check(pic1dp_hip_diag_convert_exact(ctx, s, limbs, sums(3 * s + 1 : 3 * s + 3), &
+        raw(:, s + 1)), 'diag_convert_exact')
+    end do
+  else
   do s = 0, inp%nspecies - 1
     call pic1dp_hip_check(pic1dp_hip_energy_sums(ctx, s, sums(3 * s + 1 : 3 * s + 3)), 'energy_sums')
   end do
   call ranks_reduce_to_root(sums, 3 * inp%nspecies)
+  end if
   if (ranks_rank == 0) call pic1dp_hip_check(pic1dp_hip_output_scalars_from(ctx, sums, scal, &
     int(size(scal), c_int32_t)), 'output_scalars_from')
   if (ranks_rank == 0) then
@@ -155,6 +171,16 @@ subroutine output_all(ctx, inp, verbosity)
   end if
   do s = 0, inp%nspecies - 1
     ! MPI_Reduce of the six histograms to rank 0 (:333-356), which scales and writes them
+    if (output_exact) then
+      if (ranks_rank == 0) then
+        mxv = raw(1 : nxv, s + 1)
+        txv = raw(nxv + 1 : 2 * nxv, s + 1)
+        pxv = raw(2 * nxv + 1 : 3 * nxv, s + 1)
+        mv = raw(3 * nxv + 1 : 3 * nxv + inp%nv_opd, s + 1)
+        tv = raw(3 * nxv + inp%nv_opd + 1 : 3 * nxv + 2 * inp%nv_opd, s + 1)
+        pv = raw(3 * nxv + 2 * inp%nv_opd + 1 : ntot, s + 1)
+      end if
+    else
     call pic1dp_hip_check(pic1dp_hip_ptcldist(ctx, s, 0_c_int32_t, mxv, txv, pxv, mv, tv, pv), 'ptcldist')
     call ranks_reduce_to_root(mxv, nxv)
     call ranks_reduce_to_root(txv, nxv)
@@ -162,6 +188,7 @@ subroutine output_all(ctx, inp, verbosity)
     call ranks_reduce_to_root(mv, int(inp%nv_opd))
     call ranks_reduce_to_root(tv, int(inp%nv_opd))
     call ranks_reduce_to_root(pv, int(inp%nv_opd))
+    end if
     if (ranks_rank == 0) call pic1dp_hip_check(pic1dp_hip_ptcldist_finish(ctx, s, mxv, txv, pxv, mv, tv, pv), &
       'ptcldist_finish')
     if (ranks_rank /= 0) cycle

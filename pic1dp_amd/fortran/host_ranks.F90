@@ -6,6 +6,7 @@
 !   ranks_allgather_handles  <->  MPI_Allgather of the 64-byte exchange handles (INTEGRATION.md section 4)
 !   ranks_bcast_bytes        <->  MPI_Bcast of RCCL's 128-byte unique id from rank 0 (PIC1DP_ALLREDUCE=rccl)
 !   ranks_reduce_to_root     <->  MPI_Reduce(..., MPI_SUM, 0, ...) of the diagnostics (src/pic1dp_output.F90:333-356)
+!   ranks_reduce_int64_to_root: the same of MPI_INT64_T (the exact diagnostics sum's limbs)
 ! The charge sum of the hot path (MPI_Allreduce, src/pic1dp_interaction.F90:130-135) does NOT go through files:
 ! it is the library's one-hop exchange between the GPUs.  With MPI in the image these two routines are the two
 ! MPI calls named above and nothing else changes.
@@ -149,6 +150,29 @@ subroutine ranks_reduce_to_root(a, n)
     rc = c_unlink(trim(ranks_file('reduce', ranks_seq, q))//c_null_char)
   end do
 end subroutine ranks_reduce_to_root
+
+! MPI_Reduce(a, a, n, MPI_INT64_T, MPI_SUM, 0): the limbs of the exact diagnostics sum (pic1dp_hip_diag_local_exact)
+subroutine ranks_reduce_int64_to_root(a, n)
+  integer(c_int64_t), intent(inout), target :: a(*)
+  integer, intent(in) :: n
+  integer(c_int64_t), allocatable, target :: other(:)
+  integer(c_signed_char), pointer :: raw(:)
+  integer :: q, rc
+  if (ranks_size == 1) return
+  ranks_seq = ranks_seq + 1
+  if (ranks_rank /= 0) then
+    call c_f_pointer(c_loc(a), raw, [8 * n])
+    call ranks_publish(ranks_file('reduce', ranks_seq, ranks_rank), raw, 8 * n)
+    return
+  end if
+  allocate (other(n))
+  call c_f_pointer(c_loc(other), raw, [8 * n])
+  do q = 1, ranks_size - 1
+    call ranks_fetch(ranks_file('reduce', ranks_seq, q), raw, 8 * n)
+    a(1 : n) = a(1 : n) + other(1 : n)
+    rc = c_unlink(trim(ranks_file('reduce', ranks_seq, q))//c_null_char)
+  end do
+end subroutine ranks_reduce_int64_to_root
 
 ! the end of a run that went well: this rank's gather files go (the reduce files went as they were read)
 subroutine ranks_finalize()

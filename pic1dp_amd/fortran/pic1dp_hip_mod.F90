@@ -427,6 +427,56 @@ interface
     integer(c_int64_t), intent(in) :: limbs(*)
     integer(c_int) :: ierr
   end function pic1dp_hip_charge_reduced_exact
+  function pic1dp_hip_set_diag_sum(ctx, kind) bind(C, name="pic1dp_hip_set_diag_sum") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: kind
+    integer(c_int) :: ierr
+  end function pic1dp_hip_set_diag_sum
+  function pic1dp_hip_diag_quanta(inp, ispecies, log2_quantum) bind(C, name="pic1dp_hip_diag_quanta") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), intent(out) :: log2_quantum(6)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_quanta
+  function pic1dp_hip_diag_limbs_len(ctx, n) bind(C, name="pic1dp_hip_diag_limbs_len") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_limbs_len
+  function pic1dp_hip_diag_local_exact(ctx, ispecies, limbs) bind(C, name="pic1dp_hip_diag_local_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), intent(out) :: limbs(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_local_exact
+  function pic1dp_hip_diag_convert_exact(ctx, ispecies, limbs, sums, dist) bind(C, name="pic1dp_hip_diag_convert_exact") &
+      result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), intent(in) :: limbs(*)
+    real(c_double), intent(out) :: sums(3), dist(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_convert_exact
+  function pic1dp_hip_diag_convert(inp, ispecies, limbs, sums, dist) bind(C, name="pic1dp_hip_diag_convert") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), intent(in) :: limbs(*)
+    real(c_double), intent(out) :: sums(3), dist(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_convert
+  function pic1dp_hip_diag_quantise(term, log2_quantum, kinetic, n) bind(C, name="pic1dp_hip_diag_quantise") result(ierr)
+    import
+    real(c_double), value :: term
+    integer(c_int32_t), value :: log2_quantum, kinetic
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_diag_quantise
   function pic1dp_hip_comm_unique_id(id) bind(C, name="pic1dp_hip_comm_unique_id") result(ierr)
     import
     integer(c_signed_char), intent(inout) :: id(*)

@@ -59,6 +59,11 @@ call pic1dp_hip_check(pic1dp_hip_create(inp, lay, ctx), 'create')      ! particl
 ! chargeden, E and field energies do not depend on the order of the deposit's additions (the reference sums in FP64)
 call get_environment_variable('PIC1DP_CHARGE_SUM', buf, status=stat)
 if (stat == 0 .and. buf(1:5) == 'exact') call pic1dp_hip_check(pic1dp_hip_set_charge_sum(ctx, 1_c_int32_t), 'set_charge_sum')
+! PIC1DP_DIAG_SUM=exact (an option of this host program): the exact diagnostics sum of include/pic1dp_hip.h -- the
+! records of pic1dp.out then do not depend on the order of the diagnostics' additions or on the split over ranks
+call get_environment_variable('PIC1DP_DIAG_SUM', buf, status=stat)
+output_exact = (stat == 0 .and. buf(1:5) == 'exact')
+if (output_exact) call pic1dp_hip_check(pic1dp_hip_set_diag_sum(ctx, 1_c_int32_t), 'set_diag_sum')
 ! PIC1DP_FIELD_TRANSFORM=fft (an option of this host program): the mode-filter solve's DFT by an FFT (transform 1 of
 ! include/pic1dp_hip.h) -- for many kept modes; the default is the reference's direct partial DFT
 call get_environment_variable('PIC1DP_FIELD_TRANSFORM', buf, status=stat)
