@@ -97,6 +97,16 @@ int pic1dp_probe_host_launch_shape(const pic1dp_probe_launch_query *q, int64_t s
 int pic1dp_probe_host_field_lds(int32_t family, int32_t nx, int32_t nmode, int32_t npe, int32_t tab_lds, int32_t with_xchg,
                                 int32_t pred_kind, int64_t out[3]);
 
+/* The launch shape of a diagnostics pass of output_all (launch_policy.hpp diag_launch), on the HOST: kind 0 k_ptcldist,
+ * 1 k_ptcldist_exact.  out = {blocks, threads, histograms in the LDS (1) or straight into memory (0), dynamic LDS bytes,
+ * non-temporal loads, workgroups that sum ntail tail slots}.  Nonzero: null argument or unknown kind. */
+int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t nx_opd, int32_t nv_opd, int32_t num_cu, int64_t ntail,
+                                  int64_t out[6]);
+/* The scales of a fixed-point diagnostics pass (kernels.hpp make_dist_scale), on the HOST: out = {1 fixed point / 0 double
+ * sums, log2 of the scale of the planes markr, total, pertb}. */
+int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w, int32_t threads,
+                                 int32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

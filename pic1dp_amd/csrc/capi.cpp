@@ -386,6 +386,7 @@ int pic1dp_hip_create(const pic1dp_input *in, const pic1dp_layout *layout, pic1d
   // particle storage: valid markers of the owned blocks packed first, block
   // tails (allocated but unloaded slots) behind them
   c->sp.resize(ns);
+  c->diag.resize(ns);
   int64_t nalloc = 0;
   for (int b = 0; b < c->nblk; ++b) nalloc += block_alloc(in->nparticle_max, c->blk0 + b, npe);
   // species charge accumulators in gcopies copies: workgroup b adds its LDS tile into copy b % gcopies,
@@ -765,8 +766,7 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
     HIP_TRY(hipMemset(c->sp[s].fxb + 2, 0, 2 * sizeof(double)));   // (the count of terms past the bounds starts over)
   }
   c->rng_ready = true;
-  std::fill(c->diag_max_p.begin(), c->diag_max_p.end(), 0.0);  // (new markers: the fixed-point diagnostics' bounds are void)
-  std::fill(c->diag_max_w.begin(), c->diag_max_w.end(), 0.0);
+  diag_void_bounds(c);  // (new markers)
   c->cur = 0;
   c->loaded = true;
   c->itime = 0;
@@ -814,8 +814,7 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
   }
   if (c->nblk == 1) c->blk_np[isp][0] = np;
   c->rng_ready = false;  // the host's loader owns the random stream now
-  std::fill(c->diag_max_p.begin(), c->diag_max_p.end(), 0.0);
-  std::fill(c->diag_max_w.begin(), c->diag_max_w.end(), 0.0);
+  diag_void_bounds(c);
   c->loaded = true;
   return 0;
 }

@@ -42,107 +42,141 @@ int diag_buffers(pic1dp_ctx *c) {
   const pic1dp_input &in = c->in;
   const int ns = in.nspecies;
   if (in.nx_opd < 1 || in.nv_opd < 2) return fail(PIC1DP_ERR_ARG, "nx_opd >= 1 and nv_opd >= 2 required");
-  if (c->diag_version.empty()) {
-    c->diag_version.assign(ns, 0);
-    c->diag_sums.assign(3 * static_cast<size_t>(ns), 0.0);
-    c->diag_pending.assign(ns, 0);
-    c->diag_blocks.assign(ns, 0);
-    c->diag_stride.assign(ns, 3);
-    c->diag_max_p.assign(ns, 0.0);
-    c->diag_max_w.assign(ns, 0.0);
-    c->diag_fixed.assign(ns, 0);
-  }
   if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, sizeof(double) * dist_len(in) * (ns + 1)));
-  if (!c->d_diag_part) HIP_TRY(hipMalloc(&c->d_diag_part, sizeof(double) * 6 * diag_max_blocks(c) * ns));
+  if (!c->d_diag_part) HIP_TRY(hipMalloc(&c->d_diag_part, sizeof(double) * DIAG_PART * diag_max_blocks(c) * ns));
   return 0;
 }
 
+double *diag_part_dev(const pic1dp_ctx *c, int isp) { return c->d_diag_part + static_cast<size_t>(DIAG_PART) * diag_max_blocks(c) * isp; }
+
+void diag_void_bounds(pic1dp_ctx *c) {
+  for (DiagSpecies &D : c->diag) D.max_p = D.max_w = 0.0;
+}
+
+// may species isp's next pass sum its histograms in fixed point (device_diag.hpp DistScale), and within which bounds: its
+// max |p|, max |w| of the pass before with a margin (p changes with load / upload / events only, w by a few per cent a record)
+bool diag_fx_bounds(const pic1dp_ctx *c, int isp, double *bound_p, double *bound_w) {
+  const DiagSpecies &D = c->diag[isp];
+  if (!(c->diag_fx && D.max_p > 0.0 && (c->in.deltaf != 1 || D.max_w > 0.0))) return false;
+  *bound_p = 2.0 * D.max_p;
+  *bound_w = c->diag_fx_margin_w * D.max_w;
+  return true;
+}
+
+// a pass over species isp's markers as they are now is enqueued: what the collector has to know, and the counters
+// (launched: in a launch of its own, k_ptcldist or k_ptcldist_exact -- not k_step_full<DIAG>)
+void diag_note_pass(pic1dp_ctx *c, int isp, int blocks, bool fixed, bool launched) {
+  DiagSpecies &D = c->diag[isp];
+  D.blocks = blocks, D.fixed = fixed, D.pending = true, D.version = c->state_version;
+  if (launched) c->diag_passes++;
+  if (fixed) c->diag_fx_passes++;
+}
+
 // the diagnostics' own pass over species isp (k_ptcldist) into its cached histograms; fixed: 64-bit fixed-point sums where
-// the species' max |p|, max |w| are known from the pass before (with a margin: p changes with load / upload / events only,
-// w grows by a few per cent between two records), else -- and whenever `fixed` is false -- double sums
-static int run_diag_pass(pic1dp_ctx *c, int isp, bool fixed, bool *was_fixed) {
+// diag_fx_bounds allows them, else -- and whenever `fixed` is false -- double sums
+static int run_diag_pass(pic1dp_ctx *c, int isp, bool fixed) {
   const pic1dp_input &in = c->in;
   Species &S = c->sp[isp];
   const PSet &A = S.set[c->cur];
   const size_t ntot = dist_len(in);
   double *hist = c->d_dist + ntot * isp;
-  double *part_dev = c->d_diag_part + static_cast<size_t>(6) * diag_max_blocks(c) * isp;
   HIP_TRY(hipMemsetAsync(hist, 0, sizeof(double) * ntot, c->st));
-  c->diag_blocks[isp] = 0;
-  c->diag_stride[isp] = 6;
-  *was_fixed = false;
-  c->diag_fixed[isp] = 0;
-  if (S.np <= 0) return 0;
-  double bp = 0.0, bw = 0.0;
-  if (fixed && c->diag_fx && c->diag_max_p[isp] > 0.0 && (in.deltaf != 1 || c->diag_max_w[isp] > 0.0)) {
-    bp = 2.0 * c->diag_max_p[isp];
-    bw = c->diag_fx_margin_w * c->diag_max_w[isp];
+  int blocks = 0;
+  bool was_fixed = false;
+  if (S.np > 0) {
+    double bp = 0.0, bw = 0.0;
+    if (fixed) (void)diag_fx_bounds(c, isp, &bp, &bw);
+    const DiagLaunch dl = diag_launch(0, S.np, in.nx_opd, in.nv_opd, c->num_cu);
+    blocks = dl.blocks;
+    HIP_TRY(launch_ptcldist(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, bp, bw, hist, diag_part_dev(c, isp), dl, c->dyn_tail,
+                            c->st, &was_fixed));
   }
-  c->diag_blocks[isp] = ptcldist_blocks(S.np, in.nx_opd, in.nv_opd, c->num_cu);
-  HIP_TRY(launch_ptcldist(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, bp, bw, hist, part_dev, c->num_cu, c->dyn_tail, c->st,
-                          was_fixed));
-  c->diag_passes++;
-  if (*was_fixed) c->diag_fx_passes++;
-  c->diag_fixed[isp] = *was_fixed;
+  diag_note_pass(c, isp, blocks, was_fixed, S.np > 0);
   return 0;
 }
 
-int ensure_diag(pic1dp_ctx *c, int isp) {
-  const pic1dp_input &in = c->in;
-  if (int rc = diag_buffers(c)) return rc;
-  Species &S = c->sp[isp];
-  double *part_dev = c->d_diag_part + static_cast<size_t>(6) * diag_max_blocks(c) * isp;
-  bool was_fixed = false;
-  if (c->diag_version[isp] != c->state_version) {  // no pass has seen these markers yet: run one
-    if (int rc = run_diag_pass(c, isp, true, &was_fixed)) return rc;
-    c->diag_pending[isp] = 1;
-    c->diag_version[isp] = c->state_version;
+// a pass of kind 0 if nothing has seen these markers yet
+static int diag_refresh(pic1dp_ctx *c, int isp) {
+  return c->diag[isp].version == c->state_version ? 0 : run_diag_pass(c, isp, true);
+}
+
+// Where a species' results lie in the pinned staging: the pass's partial sums [diag_max_blocks][DIAG_PART], the tail
+// slots' [kEnergyBlocks][3], the histograms [dist_len] (output_all only)
+struct DiagSlots {
+  double *part, *tail, *hist;
+  static size_t len(const pic1dp_ctx *c, bool with_hist) {
+    return static_cast<size_t>(DIAG_PART) * diag_max_blocks(c) + 3 * static_cast<size_t>(kEnergyBlocks) + (with_hist ? dist_len(c->in) : 0);
   }
-  if (!c->diag_pending[isp]) return 0;
-  was_fixed = c->diag_fixed[isp] != 0;  // (the pending pass: the one just run, or k_step_full<DIAG> inside a step)
-  // collect: partial kinetic sums of the pass (k_ptcldist, or k_step_full's DIAG variant), workgroup order
-  double *sums = &c->diag_sums[3 * static_cast<size_t>(isp)];
-  // the pass's partial sums and those of the tail slots (the reference sums the whole local vector, VecSum; slots beyond
-  // np live in set 0) through the pinned staging: both transfers enqueued, ONE wait
-  const int64_t ntail = S.nalloc - S.np;
-  const int tb = ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const int blocks = c->diag_blocks[isp], stride = c->diag_stride[isp];
-    sums[0] = sums[1] = sums[2] = 0.0;
-    double *part = nullptr;
-    if (int rc = pinned(c, static_cast<size_t>(stride) * blocks + 3 * static_cast<size_t>(tb) + 8, &part)) return rc;
-    if (blocks > 0) HIP_TRY(hipMemcpyAsync(part, part_dev, sizeof(double) * blocks * stride, hipMemcpyDeviceToHost, c->st));
-    if (tb > 0) {
-      HIP_TRY(launch_energy_sums(S.set[0].v, S.p, in.deltaf ? S.set[0].w : nullptr, S.np, ntail, c->d_scratch, tb,
-                                 c->st));
-      HIP_TRY(hipMemcpyAsync(part + static_cast<size_t>(stride) * blocks, c->d_scratch, sizeof(double) * tb * 3,
-                             hipMemcpyDeviceToHost, c->st));
-    }
-    if (blocks + tb > 0) HIP_TRY(hipStreamSynchronize(c->st));
+  DiagSlots(const pic1dp_ctx *c, double *base)
+      : part(base), tail(part + static_cast<size_t>(DIAG_PART) * diag_max_blocks(c)), hist(tail + 3 * static_cast<size_t>(kEnergyBlocks)) {}
+};
+
+// workgroups that sum the tail slots of species isp's pending pass (the reference sums the whole local vector, VecSum;
+// slots beyond np live in set 0)
+static int diag_tail_blocks(const pic1dp_ctx *c, int isp) {
+  return c->diag[isp].pending ? tail_sum_blocks(c->sp[isp].nalloc - c->sp[isp].np) : 0;
+}
+// ... enqueued: their partial sums through d_scratch into the species' slot
+static int enqueue_tail_sums(pic1dp_ctx *c, int isp, const DiagSlots &to) {
+  const Species &S = c->sp[isp];
+  const int tb = diag_tail_blocks(c, isp);
+  if (tb == 0) return 0;
+  HIP_TRY(launch_energy_sums(S.set[0].v, S.p, c->in.deltaf ? S.set[0].w : nullptr, S.np, S.nalloc - S.np, c->d_scratch, tb, c->st));
+  HIP_TRY(hipMemcpyAsync(to.tail, c->d_scratch, sizeof(double) * tb * 3, hipMemcpyDeviceToHost, c->st));
+  return 0;
+}
+
+// The collector: species isp's pending pass (its own, or k_step_full<DIAG> inside a step) from its slots, once they have
+// arrived: the kinetic sums in workgroup order, then the tail slots'; the maxima the next pass may scale with.  A
+// fixed-point pass skipped every marker beyond its bounds: the species once more in doubles (rare), into THIS species'
+// slots only -- the rest of the buffer may still be unread --; the tail sums are the ones already there.
+static int diag_collect(pic1dp_ctx *c, int isp, const DiagSlots &at, bool with_hist) {
+  DiagSpecies &D = c->diag[isp];
+  if (!D.pending) return 0;
+  const int tb = diag_tail_blocks(c, isp);
+  for (;;) {
+    D.sums[0] = D.sums[1] = D.sums[2] = 0.0;
     double maxp = 0.0, maxw = 0.0, over = 0.0;
-    for (int b = 0; b < blocks; ++b) {
-      for (int k = 0; k < 3; ++k) sums[k] += part[b * stride + k];
-      if (stride >= 6) {
-        maxp = std::max(maxp, part[b * stride + 3]);
-        maxw = std::max(maxw, part[b * stride + 4]);
-        over = std::max(over, part[b * stride + 5]);
-      }
+    for (int b = 0; b < D.blocks; ++b) {
+      const double *q = at.part + static_cast<size_t>(b) * DIAG_PART;
+      for (int k = 0; k < 3; ++k) D.sums[k] += q[k];
+      maxp = std::max(maxp, q[3]);
+      maxw = std::max(maxw, q[4]);
+      over = std::max(over, q[5]);
     }
     for (int b = 0; b < tb; ++b)
-      for (int k = 0; k < 3; ++k) sums[k] += part[static_cast<size_t>(stride) * blocks + b * 3 + k];
-    if (stride >= 6 && blocks > 0) {  // what the next pass of this species may scale its fixed-point sums with
-      c->diag_max_p[isp] = maxp;
-      c->diag_max_w[isp] = maxw;
-    }
-    if (!(was_fixed && over > 0.0)) break;
-    // a marker beyond the bounds the fixed-point pass was scaled for (it skipped that marker): once more, in doubles
-    c->diag_fx_repeats++;
-    if (int rc = run_diag_pass(c, isp, false, &was_fixed)) return rc;
+      for (int k = 0; k < 3; ++k) D.sums[k] += at.tail[b * 3 + k];
+    if (D.blocks > 0) D.max_p = maxp, D.max_w = maxw;
+    if (!(D.fixed && over > 0.0)) break;
+    c->diag_fx_repeats++;   // (the repeat is no fixed-point pass: the next round ends the loop)
+    if (int rc = run_diag_pass(c, isp, false)) return rc;
+    if (D.blocks > diag_max_blocks(c)) return fail(PIC1DP_ERR_STATE, "diagnostics: more partial sums than their slot holds");
+    if (D.blocks > 0)
+      HIP_TRY(hipMemcpyAsync(at.part, diag_part_dev(c, isp), sizeof(double) * DIAG_PART * D.blocks, hipMemcpyDeviceToHost, c->st));
+    if (with_hist)
+      HIP_TRY(hipMemcpyAsync(at.hist, c->d_dist + dist_len(c->in) * isp, sizeof(double) * dist_len(c->in), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
   }
-  c->diag_pending[isp] = 0;
+  D.pending = false;
   return 0;
 }
 
+// species isp's kinetic sums (DiagSpecies::sums) and cached histograms (d_dist) belong to the markers as they are: both
+// transfers through the pinned staging enqueued, ONE wait
+int ensure_diag(pic1dp_ctx *c, int isp) {
+  if (int rc = diag_buffers(c)) return rc;
+  if (int rc = diag_refresh(c, isp)) return rc;
+  const DiagSpecies &D = c->diag[isp];
+  if (!D.pending) return 0;
+  double *h = nullptr;
+  if (int rc = pinned(c, DiagSlots::len(c, false), &h)) return rc;
+  const DiagSlots at(c, h);
+  if (D.blocks > 0)
+    HIP_TRY(hipMemcpyAsync(at.part, diag_part_dev(c, isp), sizeof(double) * DIAG_PART * D.blocks, hipMemcpyDeviceToHost, c->st));
+  if (int rc = enqueue_tail_sums(c, isp, at)) return rc;
+  if (D.blocks + diag_tail_blocks(c, isp) > 0) HIP_TRY(hipStreamSynchronize(c->st));
+  return diag_collect(c, isp, at, false);
+}
 
 // ---------------------------------------------------------------------------
 // kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum; kernels.hpp DiagFxArgs)
@@ -166,11 +200,17 @@ static int run_diag_pass_exact(pic1dp_ctx *c, int isp) {
   for (int k = 0; k < 6; ++k) a.inv_q[k] = std::ldexp(1.0, -c->dfx_e[isp][k]);
   HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(long long) * words, c->st));
   if (S.np > 0)
-    HIP_TRY(launch_ptcldist_exact(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, a, c->num_cu, c->dyn_tail, c->st));
+    HIP_TRY(launch_ptcldist_exact(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, a,
+                                  diag_launch(1, S.np, in.nx_opd, in.nv_opd, c->num_cu), c->dyn_tail, c->st));
   HIP_TRY(launch_energy_sums_exact(S.set[0].v, S.p, in.deltaf ? S.set[0].w : nullptr, S.np, S.nalloc - S.np, a,
                                    in.nx_opd * in.nv_opd, c->st));
-  c->diag_passes++;
+  diag_note_pass(c, isp, 0, false, true);
   return 0;
+}
+
+// a pass of kind 1 if nothing has seen these markers yet
+static int dfx_refresh(pic1dp_ctx *c, int isp) {
+  return c->diag[isp].version == c->state_version ? 0 : run_diag_pass_exact(c, isp);
 }
 
 // Species isp's limbs and its counters of terms not summed on the host (out: diag_fx_words), from the cached pass or
@@ -181,11 +221,7 @@ static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long
   if (int rc = diag_buffers(c)) return rc;
   const size_t words = diag_fx_words(in.nx_opd, in.nv_opd), limbs = diag_fx_limbs(in.nx_opd, in.nv_opd);
   if (!c->d_dfx) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_dfx), sizeof(long long) * words * (in.nspecies + 1)));
-  if (c->diag_version[isp] != c->state_version) {
-    if (int rc = run_diag_pass_exact(c, isp)) return rc;
-    c->diag_pending[isp] = 1;
-    c->diag_version[isp] = c->state_version;
-  }
+  if (int rc = dfx_refresh(c, isp)) return rc;
   const long long *src = c->d_dfx + words * isp;
   if (reduced && c->comm) {  // reduce a copy: the cached local limbs stay local
     long long *red = c->d_dfx + words * in.nspecies;
@@ -200,9 +236,9 @@ static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long
   HIP_TRY(hipMemcpyAsync(out.data(), src, sizeof(long long) * words, hipMemcpyDeviceToHost, c->st));
   HIP_TRY(hipStreamSynchronize(c->st));
   const long long *rej = out.data() + limbs;
-  if (c->diag_pending[isp]) {
+  if (c->diag[isp].pending) {
     for (int k = 0; k < 6; ++k) c->dfx_rejected += rej[k];
-    c->diag_pending[isp] = 0;
+    c->diag[isp].pending = false;
   }
   for (int k = 0; k < 6; ++k)
     if (rej[k] != 0)
@@ -259,7 +295,7 @@ int pic1dp_hip_energy_sums(pic1dp_ctx *c, int32_t isp, double out[3]) {
     if (int rc = dfx_serve(c, isp, false, out, nullptr)) return rc;
   } else {
     if (int rc = ensure_diag(c, isp)) return rc;
-    for (int k = 0; k < 3; ++k) out[k] = c->diag_sums[3 * static_cast<size_t>(isp) + k];
+    for (int k = 0; k < 3; ++k) out[k] = c->diag[isp].sums[k];
   }
   if (!c->in.deltaf) out[2] = out[1];
   return 0;
@@ -376,52 +412,53 @@ static void finish_ptcldist(const pic1dp_input &in, int isp, double *mxv, double
   }
 }
 
+// the six arrays of a raw [3 nx_opd nv_opd + 3 nv_opd] block: markr_xv, total_xv, pertb_xv, markr_v, total_v, pertb_v
+static void dist_split(const pic1dp_input &in, double *raw, double *a[6]) {
+  const size_t nxv = static_cast<size_t>(in.nx_opd) * in.nv_opd;
+  for (int k = 0; k < 6; ++k) a[k] = raw + (k < 3 ? k * nxv : 3 * nxv + (k - 3) * static_cast<size_t>(in.nv_opd));
+}
+static void finish_ptcldist(const pic1dp_input &in, int isp, double *raw) {
+  double *a[6];
+  dist_split(in, raw, a);
+  finish_ptcldist(in, isp, a[0], a[1], a[2], a[3], a[4], a[5]);
+}
+
 int pic1dp_hip_ptcldist(pic1dp_ctx *c, int32_t isp, int32_t finish, double *markr_xv, double *total_xv,
                         double *pertb_xv, double *markr_v, double *total_v, double *pertb_v) {
   CHECK_CTX(c);
   if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "bad species index");
   if (int rc = require_loaded(c)) return rc;
   const pic1dp_input &in = c->in;
-  const int nxo = in.nx_opd, nvo = in.nv_opd;
-  const size_t nxv = static_cast<size_t>(nxo) * nvo, ntot = 3 * nxv + 3 * nvo;
+  const size_t ntot = dist_len(in);
+  // either kind: the raw block of the species on the host, summed over the ranks where the caller wants it finished
+  double *raw = nullptr;
+  std::vector<double> converted;
   if (c->diag_sum == 1) {
     if (finish && !c->comm && c->lay.nranks > 1)
       return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: take diag_local_exact and reduce the limbs on the host");
-    std::vector<double> raw(ntot);
-    if (int rc = dfx_serve(c, isp, finish && c->comm, nullptr, raw.data())) return rc;
-    double *mxv = raw.data(), *txv = mxv + nxv, *pxv = txv + nxv, *mv = pxv + nxv, *tv = mv + nvo, *pv = tv + nvo;
-    if (finish) finish_ptcldist(in, isp, mxv, txv, pxv, mv, tv, pv);
-    const double *src[6] = {mxv, txv, pxv, mv, tv, pv};
-    double *dst[6] = {markr_xv, total_xv, pertb_xv, markr_v, total_v, pertb_v};
-    for (int k = 0; k < 6; ++k)
-      if (dst[k]) std::memcpy(dst[k], src[k], sizeof(double) * (k < 3 ? nxv : static_cast<size_t>(nvo)));
-    return 0;
+    converted.resize(ntot);
+    raw = converted.data();
+    if (int rc = dfx_serve(c, isp, finish && c->comm, nullptr, raw)) return rc;
+  } else {
+    if (int rc = ensure_diag(c, isp)) return rc;
+    const double *hist = c->d_dist + ntot * isp;
+    if (finish && c->comm) {  // reduce a copy: the cached local histograms stay local
+      double *red = c->d_dist + ntot * in.nspecies;
+      HIP_TRY(hipMemcpyAsync(red, hist, sizeof(double) * ntot, hipMemcpyDeviceToDevice, c->st));
+      if (int rc = allreduce_doubles(c, red, ntot)) return rc;
+      hist = red;
+    } else if (finish && c->lay.nranks > 1) {
+      return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: take finish = 0 and reduce the local sums on the host");
+    }
+    if (int rc = pinned(c, ntot, &raw)) return rc;
+    HIP_TRY(hipMemcpyAsync(raw, hist, sizeof(double) * ntot, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
   }
-  if (int rc = ensure_diag(c, isp)) return rc;
-  const double *hist = c->d_dist + ntot * isp;
-  if (finish && c->comm) {  // reduce a copy: the cached local histograms stay local
-    double *red = c->d_dist + ntot * in.nspecies;
-    HIP_TRY(hipMemcpyAsync(red, hist, sizeof(double) * ntot, hipMemcpyDeviceToDevice, c->st));
-    if (int rc = allreduce_doubles(c, red, ntot)) return rc;
-    hist = red;
-  } else if (finish && c->lay.nranks > 1) {
-    return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: take finish = 0 and reduce the local sums on the host");
-  }
-  double *h = nullptr;
-  if (int rc = pinned(c, ntot, &h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h, hist, sizeof(double) * ntot, hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  double *mxv = h, *txv = mxv + nxv, *pxv = txv + nxv, *mv = pxv + nxv, *tv = mv + nvo, *pv = tv + nvo;
-  if (finish) finish_ptcldist(in, isp, mxv, txv, pxv, mv, tv, pv);
-  auto give = [&](double *dst, const double *src, size_t n) {
-    if (dst) std::memcpy(dst, src, sizeof(double) * n);
-  };
-  give(markr_xv, mxv, nxv);
-  give(total_xv, txv, nxv);
-  give(pertb_xv, pxv, nxv);
-  give(markr_v, mv, nvo);
-  give(total_v, tv, nvo);
-  give(pertb_v, pv, nvo);
+  if (finish) finish_ptcldist(in, isp, raw);
+  double *src[6], *dst[6] = {markr_xv, total_xv, pertb_xv, markr_v, total_v, pertb_v};
+  dist_split(in, raw, src);
+  for (int k = 0; k < 6; ++k)
+    if (dst[k]) std::memcpy(dst[k], src[k], sizeof(double) * (k < 3 ? static_cast<size_t>(in.nx_opd) * in.nv_opd : static_cast<size_t>(in.nv_opd)));
   return 0;
 }
 
@@ -435,6 +472,78 @@ int pic1dp_hip_ptcldist_finish(pic1dp_ctx *c, int32_t isp, double *markr_xv, dou
 }
 
 
+// output_all's pinned record: [E | cd | re | im | energy + pad], then per species its DiagSlots with the histograms
+struct RecordLayout {
+  size_t nx, nm, cd, re, im, energy, species, per_species, total;   // (E at 0)
+  explicit RecordLayout(const pic1dp_ctx *c)
+      : nx(c->in.nx), nm(c->in.nmode), cd(nx), re(2 * nx), im(re + nm), energy(im + nm), species(energy + 8),
+        per_species(DiagSlots::len(c, true)), total(species + per_species * c->in.nspecies) {}
+  DiagSlots slots(const pic1dp_ctx *c, double *h, int s) const { return DiagSlots(c, h + species + per_species * s); }
+};
+
+// output_all, enqueued: the passes of the species nothing has seen yet, int E^2 dx, the record gathered on the device and
+// sent in ONE transfer (every small copy of its own costs the stream ~10 us), the tail slots' sums behind it
+static int enqueue_record(pic1dp_ctx *c, const RecordLayout &L, double *h, bool with_hist) {
+  const int ns = c->in.nspecies;
+  const size_t ntot = dist_len(c->in);
+  for (int s = 0; s < ns; ++s)
+    if (int rc = diag_refresh(c, s)) return rc;
+  double *slot = c->d_scratch + kEnergyBlocks * 3;
+  HIP_TRY(launch_field_energy(c->d_E, c->in.nx, c->in.lx, static_cast<double>(c->in.nx), slot, c->st));
+  if (c->d_rec_doubles < L.total) {
+    if (c->d_rec) HIP_TRY(hipFree(c->d_rec));
+    c->d_rec = nullptr, c->d_rec_doubles = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_rec), sizeof(double) * L.total));
+    c->d_rec_doubles = L.total;
+  }
+  PackArgs pk{};
+  auto seg = [&pk](const double *src, size_t dst, size_t n) {
+    if (n == 0) return;
+    pk.src[pk.count] = src, pk.dst[pk.count] = static_cast<unsigned>(dst), pk.n[pk.count] = static_cast<unsigned>(n);
+    pk.count++;
+  };
+  seg(c->d_E, 0, L.nx);
+  seg(c->d_chargeden, L.cd, L.nx);
+  seg(c->d_mode_re, L.re, L.nm);
+  seg(c->d_mode_im, L.im, L.nm);
+  seg(slot, L.energy, 1);
+  for (int s = 0; s < ns; ++s) {
+    const DiagSlots at = L.slots(c, h, s);
+    if (c->diag[s].pending) seg(diag_part_dev(c, s), at.part - h, static_cast<size_t>(DIAG_PART) * c->diag[s].blocks);
+    if (with_hist) seg(c->d_dist + ntot * s, at.hist - h, ntot);
+  }
+  HIP_TRY(launch_pack_record(pk, c->d_rec, c->st));
+  HIP_TRY(hipMemcpyAsync(h, c->d_rec, sizeof(double) * L.total, hipMemcpyDeviceToHost, c->st));
+  for (int s = 0; s < ns; ++s)  // (unloaded or emptied slots)
+    if (int rc = enqueue_tail_sums(c, s, L.slots(c, h, s))) return rc;
+  return 0;
+}
+
+// output_all, settled: the record has arrived -- the species' passes collected, the scalars formed, everything handed out
+static int settle_record(pic1dp_ctx *c, const RecordLayout &L, double *h, double *scalars, double *E, double *cd, double *re,
+                         double *im, double *dist) {
+  const pic1dp_input &in = c->in;
+  const int ns = in.nspecies;
+  const size_t ntot = dist_len(in);
+  std::vector<double> sums(3 * static_cast<size_t>(ns));
+  for (int s = 0; s < ns; ++s) {
+    if (int rc = diag_collect(c, s, L.slots(c, h, s), dist != nullptr)) return rc;
+    for (int k = 0; k < 3; ++k) sums[3 * s + k] = c->diag[s].sums[k];
+    if (!in.deltaf) sums[3 * s + 2] = sums[3 * s + 1];
+  }
+  fill_scalars(c, sums.data(), h[L.energy], scalars);
+  if (E) std::memcpy(E, h, sizeof(double) * L.nx);
+  if (cd) std::memcpy(cd, h + L.cd, sizeof(double) * L.nx);
+  if (re) std::memcpy(re, h + L.re, sizeof(double) * L.nm);
+  if (im) std::memcpy(im, h + L.im, sizeof(double) * L.nm);
+  for (int s = 0; s < ns && dist; ++s) {
+    double *d = L.slots(c, h, s).hist;
+    finish_ptcldist(in, s, d);
+    std::memcpy(dist + ntot * s, d, sizeof(double) * ntot);
+  }
+  return 0;
+}
+
 // Everything output_all writes (src/pic1dp_output.F90:100-189, 196-477) in ONE call and one wait: the diagnostics passes of
 // all species, int E^2 dx, and every transfer to the host enqueued behind them on the engine's stream through the pinned
 // staging (the separate calls wait three times and more per record: 0.16 ms of host time that is most of what a record
@@ -446,15 +555,13 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
   const pic1dp_input &in = c->in;
   const int ns = in.nspecies;
   if (!scalars || nscal != 2 + 3 * ns) return fail(PIC1DP_ERR_ARG, "scalars must hold 2 + 3*nspecies doubles");
-  const size_t nx = in.nx, nm = in.nmode, ntot = dist_len(in), nxv = static_cast<size_t>(in.nx_opd) * in.nv_opd;
   if (c->comm || c->lay.nranks > 1 || c->diag_sum == 1) {  // (kind 1 of the diagnostics sum: served by the separate calls)
     if (int rc = pic1dp_hip_output_scalars(c, scalars, nscal)) return rc;
     if (int rc = pic1dp_hip_get_field(c, E, cd, re, im)) return rc;
     for (int s = 0; s < ns && dist; ++s) {
-      double *d = dist + ntot * s;
-      if (int rc = pic1dp_hip_ptcldist(c, s, 1, d, d + nxv, d + 2 * nxv, d + 3 * nxv, d + 3 * nxv + in.nv_opd,
-                                       d + 3 * nxv + 2 * in.nv_opd))
-        return rc;
+      double *d[6];
+      dist_split(in, dist + dist_len(in) * s, d);
+      if (int rc = pic1dp_hip_ptcldist(c, s, 1, d[0], d[1], d[2], d[3], d[4], d[5])) return rc;
     }
     return 0;
   }
@@ -464,134 +571,13 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
   if (cd && c->cd_kept_mode_only)
     if (int rc = rebuild_half_step_chargeden(c)) return rc;
   if (int rc = diag_buffers(c)) return rc;
-  // the pinned record: [E | cd | re | im | energy + pad] then per species [partial sums | tail sums | histograms]
-  std::vector<size_t> off_part(ns), off_tail(ns), off_hist(ns);
-  std::vector<int> tb(ns, 0);
-  std::vector<char> fixed(ns, 0);
-  size_t off = 2 * nx + 2 * nm + 8;
-  for (int s = 0; s < ns; ++s) {  // launch what has not seen these markers yet
-    if (c->diag_version[s] != c->state_version) {
-      bool was_fixed = false;
-      if (int rc = run_diag_pass(c, s, true, &was_fixed)) return rc;
-      c->diag_pending[s] = 1;
-      c->diag_version[s] = c->state_version;
-    }
-    fixed[s] = c->diag_pending[s] && c->diag_fixed[s];  // (the pass just run, or k_step_full<DIAG> inside the step before)
-    const int64_t ntail = c->sp[s].nalloc - c->sp[s].np;
-    tb[s] = c->diag_pending[s] && ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
-    off_part[s] = off;
-    off += static_cast<size_t>(6) * diag_max_blocks(c);
-    off_tail[s] = off;
-    off += static_cast<size_t>(3) * kEnergyBlocks;
-    off_hist[s] = off;
-    off += ntot;
-  }
+  const RecordLayout L(c);
   double *h = nullptr;
-  if (int rc = pinned(c, off, &h)) return rc;
-  double *slot = c->d_scratch + kEnergyBlocks * 3;
-  HIP_TRY(launch_field_energy(c->d_E, in.nx, in.lx, static_cast<double>(in.nx), slot, c->st));
-  // the record is gathered on the device and crosses in ONE transfer (every small copy of its own costs the stream ~10 us)
-  if (c->d_rec_doubles < off) {
-    if (c->d_rec) HIP_TRY(hipFree(c->d_rec));
-    c->d_rec = nullptr, c->d_rec_doubles = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_rec), sizeof(double) * off));
-    c->d_rec_doubles = off;
-  }
-  PackArgs pk{};
-  auto seg = [&pk](const double *src, size_t dst, size_t n) {
-    if (n == 0) return;
-    pk.src[pk.count] = src, pk.dst[pk.count] = static_cast<unsigned>(dst), pk.n[pk.count] = static_cast<unsigned>(n);
-    pk.count++;
-  };
-  seg(c->d_E, 0, nx);
-  seg(c->d_chargeden, nx, nx);
-  seg(c->d_mode_re, 2 * nx, nm);
-  seg(c->d_mode_im, 2 * nx + nm, nm);
-  seg(slot, 2 * nx + 2 * nm, 1);
-  size_t used = 2 * nx + 2 * nm + 8;
-  bool tails = false;
-  for (int s = 0; s < ns; ++s) {
-    if (c->diag_pending[s]) {
-      const int blocks = c->diag_blocks[s], stride = c->diag_stride[s];
-      seg(c->d_diag_part + static_cast<size_t>(6) * diag_max_blocks(c) * s, off_part[s], static_cast<size_t>(blocks) * stride);
-      if (tb[s] > 0) tails = true;
-    }
-    if (dist) seg(c->d_dist + ntot * s, off_hist[s], ntot);
-    used = off_hist[s] + ntot;
-  }
-  HIP_TRY(launch_pack_record(pk, c->d_rec, c->st));
-  HIP_TRY(hipMemcpyAsync(h, c->d_rec, sizeof(double) * used, hipMemcpyDeviceToHost, c->st));
-  if (tails) {  // (unloaded or emptied slots: the reference sums the whole local vector (VecSum); slots beyond np live in set 0)
-    for (int s = 0; s < ns; ++s) {
-      Species &S = c->sp[s];
-      if (!(c->diag_pending[s] && tb[s] > 0)) continue;
-      HIP_TRY(launch_energy_sums(S.set[0].v, S.p, in.deltaf ? S.set[0].w : nullptr, S.np, S.nalloc - S.np, c->d_scratch,
-                                 tb[s], c->st));
-      HIP_TRY(hipMemcpyAsync(h + off_tail[s], c->d_scratch, sizeof(double) * tb[s] * 3, hipMemcpyDeviceToHost, c->st));
-    }
-  }
+  if (int rc = pinned(c, L.total, &h)) return rc;
+  if (int rc = enqueue_record(c, L, h, dist != nullptr)) return rc;
   HIP_TRY(hipStreamSynchronize(c->st));
   if (int rc = xchg_check(c)) return rc;
-  // a species' kinetic sums from its slots of the record (the pass's per-workgroup partial sums, then the tail slots'), and
-  // whether the pass saw a marker beyond its fixed-point bounds
-  auto fold = [&](int s) -> bool {
-    double *acc = &c->diag_sums[3 * static_cast<size_t>(s)];
-    const int blocks = c->diag_blocks[s], stride = c->diag_stride[s];
-    const double *part = h + off_part[s], *tail = h + off_tail[s];
-    acc[0] = acc[1] = acc[2] = 0.0;
-    double maxp = 0.0, maxw = 0.0, over = 0.0;
-    for (int b = 0; b < blocks; ++b) {
-      for (int k = 0; k < 3; ++k) acc[k] += part[b * stride + k];
-      if (stride >= 6) {
-        maxp = std::max(maxp, part[b * stride + 3]);
-        maxw = std::max(maxw, part[b * stride + 4]);
-        over = std::max(over, part[b * stride + 5]);
-      }
-    }
-    for (int b = 0; b < tb[s]; ++b)
-      for (int k = 0; k < 3; ++k) acc[k] += tail[b * 3 + k];
-    if (stride >= 6 && blocks > 0) {
-      c->diag_max_p[s] = maxp;
-      c->diag_max_w[s] = maxw;
-    }
-    return over > 0.0;
-  };
-  std::vector<double> sums(3 * static_cast<size_t>(ns));
-  for (int s = 0; s < ns; ++s) {
-    if (c->diag_pending[s]) {
-      if (fold(s) && fixed[s]) {
-        // a marker beyond the fixed-point bounds: this species once more, in doubles (rare).  The repeat's partial sums and
-        // histograms go into THIS species' slots of the record -- everything else in it (the fields, the other species) is
-        // still to be read (the repeat used to stage through the start of the same buffer); the tail slots' sums
-        // are the ones already there
-        c->diag_fx_repeats++;
-        bool was_fixed = false;
-        if (int rc = run_diag_pass(c, s, false, &was_fixed)) return rc;
-        const size_t npart = static_cast<size_t>(c->diag_blocks[s]) * c->diag_stride[s];
-        if (npart > static_cast<size_t>(6) * diag_max_blocks(c)) return fail(PIC1DP_ERR_STATE, "diagnostics: more partial sums than their slot holds");
-        if (npart > 0)
-          HIP_TRY(hipMemcpyAsync(h + off_part[s], c->d_diag_part + static_cast<size_t>(6) * diag_max_blocks(c) * s, sizeof(double) * npart,
-                                 hipMemcpyDeviceToHost, c->st));
-        if (dist) HIP_TRY(hipMemcpyAsync(h + off_hist[s], c->d_dist + ntot * s, sizeof(double) * ntot, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-        (void)fold(s);
-      }
-      c->diag_pending[s] = 0;
-    }
-    for (int k = 0; k < 3; ++k) sums[3 * s + k] = c->diag_sums[3 * static_cast<size_t>(s) + k];
-    if (!in.deltaf) sums[3 * s + 2] = sums[3 * s + 1];
-  }
-  fill_scalars(c, sums.data(), h[2 * nx + 2 * nm], scalars);
-  if (E) std::memcpy(E, h, sizeof(double) * nx);
-  if (cd) std::memcpy(cd, h + nx, sizeof(double) * nx);
-  if (re) std::memcpy(re, h + 2 * nx, sizeof(double) * nm);
-  if (im) std::memcpy(im, h + 2 * nx + nm, sizeof(double) * nm);
-  for (int s = 0; s < ns && dist; ++s) {
-    double *d = h + off_hist[s];
-    finish_ptcldist(in, s, d, d + nxv, d + 2 * nxv, d + 3 * nxv, d + 3 * nxv + in.nv_opd, d + 3 * nxv + 2 * in.nv_opd);
-    std::memcpy(dist + ntot * s, d, sizeof(double) * ntot);
-  }
-  return 0;
+  return settle_record(c, L, h, scalars, E, cd, re, im, dist);
 }
 
 // ---------------------------------------------------------------------------
@@ -632,7 +618,7 @@ int pic1dp_hip_set_diag_sum(pic1dp_ctx *c, int32_t kind) {
     for (int s = 0; s < c->in.nspecies; ++s)
       if (int rc = pic1dp_hip_diag_quanta(&c->in, s, c->dfx_e[s])) return rc;
   // the cached diagnostics belong to the other kind
-  for (size_t s = 0; s < c->diag_version.size(); ++s) c->diag_version[s] = 0, c->diag_pending[s] = 0;
+  for (DiagSpecies &D : c->diag) D.version = 0, D.pending = false;
   c->diag_sum = kind;
   return 0;
 }

@@ -334,21 +334,14 @@ static int wire_diag(pic1dp_ctx *c, int s, StepArgsDev &a, LaunchCfg &lc) {
   const size_t ntot = dist_len(c->in);
   a.dg = dist_geom(c);
   a.dist_out = c->d_dist + ntot * s;
-  a.dist_partial = c->d_diag_part + static_cast<size_t>(6) * diag_max_blocks(c) * s;
+  a.dist_partial = diag_part_dev(c, s);
   HIP_TRY(hipMemsetAsync(a.dist_out, 0, sizeof(double) * ntot, c->st));
   lc = step_diag_launch(policy_of(c), c->in.nx, a.np, c->charge_sum == 1, c->in.nx_opd, c->in.nv_opd);
-  c->diag_blocks[s] = lc.blocks;
-  c->diag_stride[s] = 6;       // the kinetic sums, max |p|, max |w|, the fixed-point pass's overflow flag
-  // the histograms as 64-bit fixed-point sums where the species' max |p|, max |w| are known from the pass before (as the
-  // diagnostics' own pass does, capi_diag.cpp run_diag_pass; a marker beyond them: the collector repeats in doubles)
-  a.diag_fx = 0;
-  if (c->diag_fx && c->diag_max_p[s] > 0.0 && (c->in.deltaf != 1 || c->diag_max_w[s] > 0.0))
-    a.diag_fx = make_dist_scale(a.np, lc.blocks, c->in.deltaf == 1, 2.0 * c->diag_max_p[s],
-                                c->diag_fx_margin_w * c->diag_max_w[s], &a.dscale, lc.threads) ? 1 : 0;
-  c->diag_fixed[s] = a.diag_fx != 0;
-  if (a.diag_fx) c->diag_fx_passes++;
-  c->diag_pending[s] = 1;
-  c->diag_version[s] = c->state_version;  // the caller has bumped it for this step already
+  // the histograms as 64-bit fixed-point sums where the diagnostics' own pass would take them so (capi_diag.cpp
+  // diag_fx_bounds; a marker beyond the bounds: the collector repeats in doubles)
+  double bp = 0.0, bw = 0.0;
+  a.diag_fx = diag_fx_bounds(c, s, &bp, &bw) && make_dist_scale(a.np, lc.blocks, c->in.deltaf == 1, bp, bw, &a.dscale, lc.threads) ? 1 : 0;
+  diag_note_pass(c, s, lc.blocks, a.diag_fx != 0, false);  // (the caller has bumped state_version for this step already)
   return 0;
 }
 
@@ -1240,7 +1233,7 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT(c->modes_field_version <= c->field_version);
   INVARIANT(c->eh_modes >= 0 && c->eh_modes <= 2);
   for (int s = 0; s < c->in.nspecies; ++s) {
-    if (static_cast<size_t>(s) < c->diag_version.size()) INVARIANT(c->diag_version[s] <= c->state_version);  // (sized by the first diagnostics call)
+    INVARIANT(c->diag[s].version <= c->state_version);
     INVARIANT(c->sp[s].t2_version <= c->state_version);
   }
   INVARIANT(!c->charge_pending_pred || c->charge_pending);

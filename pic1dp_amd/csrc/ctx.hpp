@@ -2,7 +2,7 @@
 // the error convention, the event spans, and the internal entry points one unit offers the others.
 //   capi.cpp           context, input, transfers, field access, timers and knobs
 //   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
-//   launch_policy.cpp  the marker kernels' launch shapes (launch_policy.hpp: no context, no HIP call)
+//   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
 //   capi_diag.cpp      diagnostics of output_all
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
@@ -52,7 +52,6 @@ constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf =
               kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
-constexpr int kEnergyBlocks = 1024;
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
 // ---------------------------------------------------------------------------
 // The call sites' state (capi_step.cpp "lazy call sites").  Two variables, each an enum, and a table of
@@ -126,6 +125,17 @@ struct Species {
   double *fxb = nullptr;  // device [2]: bounds on |q| and |c| of this species' markers for the prediction tiles' fixed-point
                           // sums (kernels_step.hip FxTiles): seeded from the markers the host loads, raised by the kernels
   SpeciesConst sc{};
+};
+
+// Marker diagnostics of output_all, per species: one fused pass (histograms + kinetic sums; a launch of its own, or inside
+// k_step_full<DIAG>), collected once and kept until the markers change (capi_diag.cpp)
+struct DiagSpecies {
+  uint64_t version = 0;               // state_version the cached results belong to
+  double sums[3] = {0.0, 0.0, 0.0};   // the kinetic sums
+  bool pending = false;               // a pass ran, its partial sums are still on the device
+  int blocks = 0;                     // workgroups of that pass
+  bool fixed = false;                 // ... which summed its histograms in 64-bit fixed point (device_diag.hpp DistScale)
+  double max_p = 0.0, max_w = 0.0;    // max |p|, |w| as the last pass saw them: the next pass's scales (0: unknown -- doubles)
 };
 
 struct EvPair {
@@ -254,17 +264,9 @@ struct pic1dp_ctx {
   // marker diagnostics of output_all: one fused pass per species (histograms +
   // kinetic sums), kept until the markers change
   uint64_t state_version = 1;              // bumped by everything that writes marker arrays
-  std::vector<uint64_t> diag_version;      // [nspecies] version the cached results belong to
-  std::vector<double> diag_sums;           // [nspecies][3]
-  double *d_diag_part = nullptr;           // [nspecies][3 * diag_max_blocks] per-workgroup partial sums of the pass
-  std::vector<char> diag_pending;          // [nspecies] a pass ran, its partial sums are still on the device
-  std::vector<int> diag_blocks;            // [nspecies] workgroups of that pass
-  std::vector<int> diag_stride;            // [nspecies] doubles per workgroup in its partial sums: 3 (k_step_full<DIAG>) or 6 (k_ptcldist)
-  // k_ptcldist with 64-bit fixed-point histogram sums (device_diag.hpp DistScale): max |p| and max |w| of the species as
-  // the last pass saw them (0: unknown -- the next pass sums in doubles and finds out); PIC1DP_DIAG_FX=0: always doubles
-  std::vector<double> diag_max_p, diag_max_w;
-  std::vector<char> diag_fixed;            // [nspecies] the pending pass summed its histograms in fixed point (an overflow: once more in doubles)
-  std::vector<uint64_t> diag_max_p_version;   // state_version-independent stamp: p changes with load / upload / events only
+  std::vector<DiagSpecies> diag;           // [nspecies]
+  double *d_diag_part = nullptr;           // [nspecies][diag_max_blocks][DIAG_PART] per-workgroup partial sums of the pass
+  // (PIC1DP_DIAG_FX=0: the histograms always as double sums)
   int diag_fx = 1;
   double diag_fx_margin_w = 16.0;   // bound on |w| = this x the last pass's max |w| (PIC1DP_DIAG_FX_MARGIN: tests)
   int64_t diag_fx_passes = 0, diag_fx_repeats = 0;   // fixed-point passes so far; passes repeated in doubles after an overflow
@@ -313,7 +315,7 @@ struct pic1dp_ctx {
   double fx_q[8] = {0}, fx_inv_q[8] = {0};   // 2^e_s, 2^-e_s
   // kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum, capi_diag.cpp; kernels.hpp DiagFxArgs): output_all's
   // diagnostics from exact integer sums, always in their own pass (no k_step_full<DIAG> while it is set); independent of
-  // charge_sum.  The cached pass of a species is d_dfx's slot, valid while diag_version says so.
+  // charge_sum.  The cached pass of a species is d_dfx's slot, valid while DiagSpecies::version says so.
   int diag_sum = 0;
   long long *d_dfx = nullptr;                // [nspecies + 1][diag_fx_words]: per species, + the copy summed over ranks
   int dfx_e[8][6] = {{0}};                   // the six log2 quanta per species (pic1dp_hip_diag_quanta)
@@ -454,6 +456,10 @@ void fx_release(pic1dp_ctx *c);
 // ---- capi_diag.cpp ----
 int diag_buffers(pic1dp_ctx *c);
 int diag_max_blocks(const pic1dp_ctx *c);
+double *diag_part_dev(const pic1dp_ctx *c, int isp);   // species isp's slice of d_diag_part
+void diag_void_bounds(pic1dp_ctx *c);                   // new or changed p, w: the fixed-point passes' bounds are void
+bool diag_fx_bounds(const pic1dp_ctx *c, int isp, double *bound_p, double *bound_w);  // may the next pass sum in fixed point?
+void diag_note_pass(pic1dp_ctx *c, int isp, int blocks, bool fixed, bool launched);   // a pass is enqueued
 const DistGeom &dist_geom(pic1dp_ctx *c);
 int pinned(pic1dp_ctx *c, size_t ndoubles, double **out);   // the context's pinned staging with room for ndoubles
 size_t dist_len(const pic1dp_input &in);

@@ -1,5 +1,6 @@
-// device_diag.hpp -- the per-marker part and the finish of output_all's diagnostics, shared by k_ptcldist
-// (kernels_diag.hip) and the DIAG variant of k_step_full (kernels_step.hip)
+// device_diag.hpp -- output_all's diagnostics on the device: what the FP64 kind and the exact kind add per marker
+// (ptcldist_one, with the cell stencil in its own text; ptcldist_one_exact on dist_stencil) and their finishes.  Shared by
+// k_ptcldist, k_ptcldist_exact (kernels_diag.hip) and the DIAG variant of k_step_full (kernels_step.hip)
 #pragma once
 #include "device_math.hpp"
 
@@ -69,6 +70,46 @@ __device__ __forceinline__ double diag_div(double a, double c, double rc) {
   return fma(r1, rc, q1);
 }
 
+// The four cells a marker adds to and their bilinear weights (src/pic1dp_output.F90:239-315), in the reference's
+// operation order; false: no bins for this marker.  Cells are iv * nx_opd + ix: c00 = (ix, iv), c01 = (ix, iv + 1),
+// c10 = (ix + 1, iv), c11 = (ix + 1, iv + 1).
+struct DistStencil {
+  int c00, c01, c10, c11;
+  double w00, w01, w10, w11;
+};
+__device__ __forceinline__ bool dist_stencil(double px, double pv, const DistGeom &dg, DistStencil &s) {
+  const int nxo = dg.nxo, nvo = dg.nvo;
+  if (fabs(pv) >= dg.vmax) return false;                // :241
+#if PIC1DP_FAST_DIV
+  double sx = diag_div(px, dg.lx, dg.rlx) * static_cast<double>(nxo);    // :243
+#else
+  double sx = px / dg.lx * static_cast<double>(nxo);
+#endif
+  const double fx = floor(sx);
+  int ix = static_cast<int>(fx);
+  sx = 1.0 - (sx - fx);
+  if (ix == nxo) ix = 0;   // x == lx (or x / lx rounding to 1): sx == 1, the periodic image of x = 0 -- the deposit's fold
+  const double av = pv + dg.vmax;
+  double sv = (dg.vfast ? diag_div(av, dg.dv, dg.rdv) : av / dg.dv) * static_cast<double>(nvo - 1);  // :247
+  const double fv = floor(sv);
+  const int iv = static_cast<int>(fv);
+  sv = 1.0 - (sv - fv);
+  // memory safety only (NaN, positions outside [0, lx])
+  if (static_cast<unsigned>(ix) >= static_cast<unsigned>(nxo) || static_cast<unsigned>(iv) >= static_cast<unsigned>(nvo)) return false;
+  // iv == nvo - 1 only where sv came out as exactly nvo - 1 (|v| < v_max): sv == 1, and the reference's writes to row
+  // iv + 1 carry weight 0 -- they go to row iv instead (adding zeros), the top row keeps the marker
+  const int ivu = iv + 1 < nvo ? iv + 1 : iv;
+  const int ixr = ix + 1 > nxo - 1 ? 0 : ix + 1;        // :274-276
+  const double sxr = 1.0 - sx, svu = 1.0 - sv;
+  s.c00 = iv * nxo + ix, s.c10 = iv * nxo + ixr, s.c01 = ivu * nxo + ix, s.c11 = ivu * nxo + ixr;
+  // the reference's products, in its order: (sx * sv), (sx * sv) * p, (sx * sv) * w, ...
+  s.w00 = sx * sv, s.w01 = sx * svu, s.w10 = sxr * sv, s.w11 = sxr * svu;
+  return true;
+}
+
+// ptcldist_one keeps its own text of the stencil (the same lines as dist_stencil): it is the per-marker part of
+// k_step_full<DIAG>, which sits at its register budget, and taking the cells from dist_stencil's struct moved VGPRs and SGPR
+// spills of its instantiations in four of the six distributions (profiles/r15/kernel_resources_before_after.log)
 template <bool LDS, bool DELTAF, bool FX = false>
 __device__ __forceinline__ void ptcldist_one(double px, double pv, double pp, double pw, const DistGeom &dg,
                                              const DistBins &b, DistSums &sm, const DistScale *scale = nullptr) {
@@ -149,7 +190,6 @@ __device__ __forceinline__ void ptcldist_one(double px, double pv, double pp, do
   }
 }
 
-
 // per-workgroup partial kinetic sums, v histograms as row sums, flush of the LDS copy
 // maximum over the workgroup (valid on thread 0); the values are >= 0
 __device__ __forceinline__ double block_max(double v, double *scratch) {
@@ -164,9 +204,8 @@ __device__ __forceinline__ double block_max(double v, double *scratch) {
   return t;
 }
 
-// PSTRIDE: doubles per workgroup in `partial` -- 3 (the kinetic sums; k_step_full<DIAG>) or 6 (+ max |p|, max |w|, the
-// overflow flag; k_ptcldist)
-template <bool LDS, bool DELTAF, bool FX = false, int PSTRIDE = 3>
+// partial: [workgroups][DIAG_PART] = the kinetic sums, max |p|, max |w|, the overflow flag
+template <bool LDS, bool DELTAF, bool FX = false>
 __device__ __forceinline__ void ptcldist_finish(const DistGeom &dg, const DistBins &b, const DistSums &sm, double *scr,
                                                 double *out, double *partial, const DistScale *fx = nullptr) {
   const int nxo = dg.nxo, nvo = dg.nvo, nxv = nxo * nvo, ntot = 3 * nxv + 3 * nvo;
@@ -175,19 +214,17 @@ __device__ __forceinline__ void ptcldist_finish(const DistGeom &dg, const DistBi
     const double t1 = block_sum(sm.s1, scr);
     const double t2 = block_sum(sm.s2, scr);
     if (threadIdx.x == 0) {
-      partial[blockIdx.x * PSTRIDE + 0] = t0;
-      partial[blockIdx.x * PSTRIDE + 1] = t1;
-      partial[blockIdx.x * PSTRIDE + 2] = t2;
+      partial[blockIdx.x * DIAG_PART + 0] = t0;
+      partial[blockIdx.x * DIAG_PART + 1] = t1;
+      partial[blockIdx.x * DIAG_PART + 2] = t2;
     }
-    if constexpr (PSTRIDE >= 6) {
-      const double mp = block_max(sm.maxp, scr);
-      const double mw = block_max(sm.maxw, scr);
-      const double ov = block_max(sm.over ? 1.0 : 0.0, scr);
-      if (threadIdx.x == 0) {
-        partial[blockIdx.x * PSTRIDE + 3] = mp;
-        partial[blockIdx.x * PSTRIDE + 4] = mw;
-        partial[blockIdx.x * PSTRIDE + 5] = ov;
-      }
+    const double mp = block_max(sm.maxp, scr);
+    const double mw = block_max(sm.maxw, scr);
+    const double ov = block_max(sm.over ? 1.0 : 0.0, scr);
+    if (threadIdx.x == 0) {
+      partial[blockIdx.x * DIAG_PART + 3] = mp;
+      partial[blockIdx.x * DIAG_PART + 4] = mw;
+      partial[blockIdx.x * DIAG_PART + 5] = ov;
     }
   }
   if constexpr (LDS) {
@@ -246,6 +283,13 @@ __device__ __forceinline__ void glb_add_u64(unsigned long long *p, unsigned long
 __device__ __forceinline__ unsigned long long *dfx_rejected(const DistBinsFx &b, int k) {
   return b.acc + 6 * static_cast<size_t>(b.nxv) + 6 + k;
 }
+// a 64-bit word of plane k, cell into the global (hi, lo 32 bits) rows
+__device__ __forceinline__ void dfx_limbs_add(const DistBinsFx &b, int k, int cell, unsigned long long w) {
+  const unsigned long long lo = w & 0xffffffffull;
+  const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(w) >> 32);
+  if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
+  if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+}
 template <bool LDS>
 __device__ __forceinline__ void dfx_bin_add(const DistBinsFx &b, int k, int cell, double term, double inv_q) {
   const double t = __builtin_rint(term * inv_q);   // term 2^-e is exact: ONE rounding, to nearest even
@@ -258,10 +302,7 @@ __device__ __forceinline__ void dfx_bin_add(const DistBinsFx &b, int k, int cell
   if constexpr (LDS) {
     __hip_atomic_fetch_add(&b.s[3 * cell + k], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   } else {
-    const unsigned long long lo = n & 0xffffffffull;
-    const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(n) >> 32);
-    if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
-    if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+    dfx_limbs_add(b, k, cell, n);
   }
 }
 __device__ __forceinline__ void dfx_kin_add(KinFx &s, const DistBinsFx &b, int k, double term, double inv_q) {
@@ -282,33 +323,15 @@ __device__ __forceinline__ void kinetic_one_exact(double pv, double pp, double p
   dfx_kin_add(sm, b, 1, v2 * pp, a.inv_q[4]);
   if constexpr (DELTAF) dfx_kin_add(sm, b, 2, v2 * pw, a.inv_q[5]);
 }
-// ptcldist_one with exact sums: the cells, the weights and the products are formed as there
+// ptcldist_one with exact sums
 template <bool LDS, bool DELTAF>
 __device__ __forceinline__ void ptcldist_one_exact(double px, double pv, double pp, double pw, const DistGeom &dg,
                                                    const DistBinsFx &b, KinFx &sm, const DiagFxArgs &a) {
-  const int nxo = dg.nxo, nvo = dg.nvo;
   kinetic_one_exact<DELTAF>(pv, pp, pw, b, sm, a);
-  if (fabs(pv) >= dg.vmax) return;                      // :241
-#if PIC1DP_FAST_DIV
-  double sx = diag_div(px, dg.lx, dg.rlx) * static_cast<double>(nxo);    // :243
-#else
-  double sx = px / dg.lx * static_cast<double>(nxo);
-#endif
-  const double fx = floor(sx);
-  int ix = static_cast<int>(fx);
-  sx = 1.0 - (sx - fx);
-  if (ix == nxo) ix = 0;
-  const double av = pv + dg.vmax;
-  double sv = (dg.vfast ? diag_div(av, dg.dv, dg.rdv) : av / dg.dv) * static_cast<double>(nvo - 1);  // :247
-  const double fv = floor(sv);
-  const int iv = static_cast<int>(fv);
-  sv = 1.0 - (sv - fv);
-  if (static_cast<unsigned>(ix) >= static_cast<unsigned>(nxo) || static_cast<unsigned>(iv) >= static_cast<unsigned>(nvo)) return;
-  const int ivu = iv + 1 < nvo ? iv + 1 : iv;
-  const int ixr = ix + 1 > nxo - 1 ? 0 : ix + 1;
-  const double sxr = 1.0 - sx, svu = 1.0 - sv;
-  const int cell[4] = {iv * nxo + ix, ivu * nxo + ix, iv * nxo + ixr, ivu * nxo + ixr};
-  const double wt[4] = {sx * sv, sx * svu, sxr * sv, sxr * svu};
+  DistStencil t;
+  if (!dist_stencil(px, pv, dg, t)) return;
+  const int cell[4] = {t.c00, t.c01, t.c10, t.c11};
+  const double wt[4] = {t.w00, t.w01, t.w10, t.w11};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     dfx_bin_add<LDS>(b, 0, cell[c], wt[c], a.inv_q[0]);
@@ -327,10 +350,7 @@ __device__ __forceinline__ void dfx_flush(const DistBinsFx &b) {
     const unsigned long long w = b.s[3 * cell + k];
     if (w == 0ull) continue;
     b.s[3 * cell + k] = 0ull;
-    const unsigned long long lo = w & 0xffffffffull;
-    const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(w) >> 32);
-    if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
-    if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+    dfx_limbs_add(b, k, cell, w);
   }
 }
 // the threads' two-limb kinetic sums over the workgroup (integers: any order), then one pair of global atomics per sum;

@@ -189,8 +189,18 @@ struct DistScale {
   double bound[3];  // |q_k| the scale allows
 };
 // the scales for a pass of `blocks` workgroups over np markers whose |p|, |w| stay below bound_p, bound_w (<= 0: unknown);
-// false: no fixed-point pass possible (sum in doubles)
+// false: no fixed-point pass possible (sum in doubles).  (launch_policy.cpp: host arithmetic)
 bool make_dist_scale(int64_t np, int blocks, bool deltaf, double bound_p, double bound_w, DistScale *fx, int threads = 1024);
+// doubles per workgroup in the partial sums of a diagnostics pass (k_ptcldist, k_step_full<DIAG>): the kinetic sums,
+// max |p|, max |w|, the fixed-point pass's overflow flag
+constexpr int DIAG_PART = 6;
+// launch shape of a diagnostics pass (launch_policy.hpp diag_launch)
+struct DiagLaunch {
+  int blocks, threads;
+  bool lds;       // the histograms as a copy per workgroup in its LDS; false: straight into memory
+  size_t bytes;   // dynamic LDS
+  bool nt;        // non-temporal marker loads
+};
 
 // dynamic LDS any kernel may ask for: 160 KiB per CU minus 1 KiB, the most static LDS a kernel that asks for more than
 // 64 KiB holds (the particle kernels' exp table; k_field_fd: 144 B)
@@ -513,13 +523,12 @@ hipError_t launch_tile_gather(const double *arr, int64_t i0, double *dst, int64_
 hipError_t launch_tile_copy(double *dst, const double *src, int64_t n, hipStream_t st);
 // raw (x,v) and v histograms of output_ptcldist into out =
 // [markr_xv | total_xv | pertb_xv | markr_v | total_v | pertb_v] (accumulated)
-// In the same pass: partial[blocks][6] = per-workgroup sums of v^2, v^2 p, v^2 w over all np markers, max |p|, max |w|,
-// and whether a marker exceeded the bounds of a fixed-point pass; blocks = ptcldist_blocks(...).
+// In the same pass: partial[dl.blocks][DIAG_PART] = per-workgroup sums of v^2, v^2 p, v^2 w over all np markers, max |p|,
+// max |w|, and whether a marker exceeded the bounds of a fixed-point pass; dl = diag_launch(0, ...).
 // bound_p, bound_w > 0: the (x, v) histograms as 64-bit fixed-point sums in the LDS (device_diag.hpp DistScale)
-hipError_t launch_ptcldist(const double *x, const double *v, const double *p, const double *w,
-                           int64_t np, const DistGeom &dg, bool deltaf, double bound_p, double bound_w,
-                           double *out, double *partial, int num_cu, int dyn_tail, hipStream_t st, bool *fixed_point);
-int ptcldist_blocks(int64_t np, int nxo, int nvo, int num_cu);
+hipError_t launch_ptcldist(const double *x, const double *v, const double *p, const double *w, int64_t np, const DistGeom &dg,
+                           bool deltaf, double bound_p, double bound_w, double *out, double *partial, const DiagLaunch &dl,
+                           int dyn_tail, hipStream_t st, bool *fixed_point);
 
 // Kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum): every term of the pass -- the corner weights
 // times 1, p, w of the (x, v) histograms, and v^2, v^2 p, v^2 w of the kinetic sums -- is rounded once to a whole number
@@ -541,15 +550,14 @@ __host__ __device__ inline bool diag_fx_quantise(double term, double inv_q, doub
   *n = static_cast<long long>(t);
   return true;
 }
-// the exact pass over markers [0, np) of a species: histograms and kinetic sums into a.acc (accumulated)
+// the exact pass over markers [0, np) of a species: histograms and kinetic sums into a.acc (accumulated);
+// dl = diag_launch(1, ...)
 hipError_t launch_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np,
-                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, int num_cu, int dyn_tail,
+                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, const DiagLaunch &dl, int dyn_tail,
                                  hipStream_t st);
 // ... and the kinetic sums of the tail slots [i0, i0 + n) into the same accumulators
 hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
                                     const DiagFxArgs &a, int nxv, hipStream_t st);
-int ptcldist_exact_blocks(int64_t np, int num_cu);
-bool ptcldist_exact_lds(int nxo, int nvo);
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

@@ -1,11 +1,13 @@
-// kernels_diag.hip -- off the timed path: the fused diagnostics pass of output_all (k_ptcldist), kinetic sums of
-// tail slots, cell indices per marker (parity tests), and the copies between contiguous host-side buffers and the
-// tiled marker slabs.  gfx950, wave64.
+// kernels_diag.hip -- off the timed path: the diagnostics passes of output_all (k_ptcldist and k_ptcldist_exact around one
+// pair sweep; their launch shapes: launch_policy.cpp diag_launch), kinetic sums of tail slots, cell indices per marker
+// (parity tests), and the copies between contiguous host-side buffers and the tiled marker slabs.  gfx950, wave64.
 #include "device_diag.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "device_math.hpp"
+#include "launch_policy.hpp"
 
 namespace pic1dp {
 
@@ -55,6 +57,45 @@ k_cell_indices(const double *x, int64_t np, const GridConst g, int32_t *ixo,
 
 namespace {
 
+// A workgroup's rows of marker pairs (device_math.hpp pair_rows), the last dyn_tail / 16 of them drawn chunk by chunk by
+// its waves: with one workgroup of sixteen waves per CU, the waves that are done would idle a quarter of the CU each.
+// Pairs as double2 (the marker kernels' access shape), the NEXT trip's loads issued before this trip's work, non-temporal
+// loads where NT says so (round 5, below).  one(x, v, p, w) per marker; after_trip(k) once per trip, k the trips done.
+template <bool DELTAF, bool NT, class One, class After>
+__device__ __forceinline__ void pair_sweep(const double *x, const double *v, const double *p, const double *w, int64_t npair,
+                                           const PairRows &rows, unsigned *sDraw, One &&one, After &&after_trip) {
+  const double2 *x2 = reinterpret_cast<const double2 *>(x), *v2 = reinterpret_cast<const double2 *>(v);
+  const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
+  int k = 0;
+  int64_t j = rows.first + threadIdx.x;
+  bool have = rows.dealt > 0 || draw_chunk(rows, sDraw, j);
+  double2 X = make_double2(0.0, 0.0), V = X, P = X, W = X;
+  if (have && j < npair) {
+    const int64_t o = tidx2(j);
+    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
+    if constexpr (DELTAF) W = ld2t<NT>(w2 + o);
+  }
+  while (have) {
+    int64_t jn = j + rows.stride;
+    bool have_n = true;
+    if (++k >= rows.dealt) have_n = draw_chunk(rows, sDraw, jn);
+    double2 Xn = make_double2(0.0, 0.0), Vn = Xn, Pn = Xn, Wn = Xn;
+    if (have_n && jn < npair) {  // the next trip's loads are under way while this trip's atomics run
+      const int64_t o = tidx2(jn);
+      Xn = ld2t<NT>(x2 + o), Vn = ld2t<NT>(v2 + o), Pn = ld2t<NT>(p2 + o);
+      if constexpr (DELTAF) Wn = ld2t<NT>(w2 + o);
+    }
+    if (j < npair) {
+      one(X.x, V.x, P.x, W.x);
+      one(X.y, V.y, P.y, W.y);
+    }
+    after_trip(k);
+    X = Xn, V = Vn, P = Pn, W = Wn;
+    j = jn;
+    have = have_n;
+  }
+}
+
 // One pass over a species for everything output_all needs from the markers:
 // * the (x,v) and v histograms of output_ptcldist, src/pic1dp_output.F90:239-315:
 //   4-point bilinear weights on an nx_opd x nv_opd grid, markers with
@@ -92,114 +133,45 @@ k_ptcldist(const double *x, const double *v, const double *p, const double *w, i
     for (int i = threadIdx.x; i < ntot; i += blockDim.x) b.h[i] = 0.0;
   if (threadIdx.x == 0) *sDraw = 0u;
   __syncthreads();
-  const int64_t npair = np >> 1;
-  const double2 *x2 = reinterpret_cast<const double2 *>(x), *v2 = reinterpret_cast<const double2 *>(v);
-  const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
   DistSums sm;
-  // the workgroup's rows of pairs, the last dyn_tail / 16 of them drawn chunk by chunk by its waves (device_math.hpp
-  // pair_rows): with one workgroup of sixteen waves per CU, the waves that are done would idle a quarter of the CU each
-  const PairRows rows = pair_rows(npair, dyn_tail);
-  int k = 0;
-  int64_t j = rows.first + threadIdx.x;
-  bool have = rows.dealt > 0 || draw_chunk(rows, sDraw, j);
-  double2 X = make_double2(0.0, 0.0), V = X, P = X, W = X;
-  if (have && j < npair) {
-    const int64_t o = tidx2(j);
-    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
-    if constexpr (DELTAF) W = ld2t<NT>(w2 + o);
-  }
-  while (have) {
-    int64_t jn = j + rows.stride;
-    bool have_n = true;
-    if (++k >= rows.dealt) have_n = draw_chunk(rows, sDraw, jn);
-    double2 Xn = make_double2(0.0, 0.0), Vn = Xn, Pn = Xn, Wn = Xn;
-    if (have_n && jn < npair) {  // the next trip's loads are under way while this trip's atomics run
-      const int64_t o = tidx2(jn);
-      Xn = ld2t<NT>(x2 + o), Vn = ld2t<NT>(v2 + o), Pn = ld2t<NT>(p2 + o);
-      if constexpr (DELTAF) Wn = ld2t<NT>(w2 + o);
-    }
-    if (j < npair) {
-      ptcldist_one<LDS, DELTAF, FX>(X.x, V.x, P.x, W.x, dg, b, sm, &fx);
-      ptcldist_one<LDS, DELTAF, FX>(X.y, V.y, P.y, W.y, dg, b, sm, &fx);
-    }
-    X = Xn, V = Vn, P = Pn, W = Wn;
-    j = jn;
-    have = have_n;
-  }
-  if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  auto one = [&](double px, double pv, double pp, double pw) { ptcldist_one<LDS, DELTAF, FX>(px, pv, pp, pw, dg, b, sm, &fx); };
+  pair_sweep<DELTAF, NT>(x, v, p, w, np >> 1, pair_rows(np >> 1, dyn_tail), sDraw, one, [](int) {});
+  if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // (after the pairs: the FP64 kinetic sums depend on the order)
     const int64_t i = tidx(np - 1);
-    ptcldist_one<LDS, DELTAF, FX>(x[i], v[i], p[i], DELTAF ? w[i] : 0.0, dg, b, sm, &fx);
+    one(x[i], v[i], p[i], DELTAF ? w[i] : 0.0);
   }
-  ptcldist_finish<LDS, DELTAF, FX, 6>(dg, b, sm, scr, out, partial, &fx);
+  ptcldist_finish<LDS, DELTAF, FX>(dg, b, sm, scr, out, partial, &fx);
+}
+
+// run-time bools as compile-time arguments: f(std::bool_constant...), one per bool
+template <class F>
+hipError_t with_bools(F &&f) {
+  return f();
+}
+template <class F, class... Bools>
+hipError_t with_bools(F &&f, bool first, Bools... rest) {
+  auto next = [&](auto B) { return with_bools([&](auto... r) { return f(B, r...); }, rest...); };
+  return first ? next(std::true_type{}) : next(std::false_type{});
 }
 
 }  // namespace
 
-int ptcldist_blocks(int64_t np, int nxo, int nvo, int num_cu) {
-  const size_t bytes = sizeof(double) * (3 * static_cast<size_t>(nxo) * nvo + 3 * static_cast<size_t>(nvo));
-  const bool lds = bytes <= 150 * 1024;
-  int64_t blocks = lds ? num_cu : static_cast<int64_t>(num_cu) * 2;
-  const int64_t need = ((np >> 1) + 1023) / 1024;
-  if (blocks > need) blocks = need;
-  if (blocks < 1) blocks = 1;
-  return static_cast<int>(blocks);
-}
-
-// fixed-point sums: a workgroup adds at most its share of the markers into one bin; weights <= 1
-bool make_dist_scale(int64_t np, int blocks, bool deltaf, double bound_p, double bound_w, DistScale *out, int threads) {
-  DistScale fx{};
-  bool use_fx = blocks > 0 && bound_p > 0.0 && (!deltaf || bound_w > 0.0) && std::isfinite(bound_p) && std::isfinite(bound_w);
-  if (use_fx) {
-    const double th = static_cast<double>(threads);
-    const double per_wg = 2.0 * th * std::ceil(static_cast<double>((np >> 1) + 1) / (static_cast<double>(blocks) * th)) + 2.0;
-    const int e_n = static_cast<int>(std::ceil(std::log2(per_wg))) + 1;  // 2^e_n > the terms a bin can receive
-    const double bounds[3] = {1.0, bound_p, deltaf ? bound_w : 1.0};
-    for (int k = 0; k < 3; ++k) {
-      int eb;
-      (void)std::frexp(bounds[k], &eb);               // bounds[k] < 2^eb
-      const int mag = std::min(62 - e_n, 50);         // |term * 2^e| < 2^mag: below 2^51 for to_fixed, and the sums below 2^62
-      const int e = mag - eb;
-      if (e < -900 || e > 900) use_fx = false;        // (a bound no scale can serve)
-      fx.sc[k] = std::ldexp(1.0, e);
-      fx.inv[k] = std::ldexp(1.0, -e);
-      fx.bound[k] = std::ldexp(1.0, eb);
-    }
-  }
-  *out = fx;
-  return use_fx;
-}
-
 // bound_p / bound_w: max |p|, max |w| the markers are known not to exceed (with the caller's margin), or <= 0: unknown --
-// the pass then sums in doubles.  partial: [blocks][6] = the kinetic sums, max |p|, max |w|, overflow flag per workgroup
-hipError_t launch_ptcldist(const double *x, const double *v, const double *p, const double *w,
-                           int64_t np, const DistGeom &dg, bool deltaf, double bound_p, double bound_w,
-                           double *out, double *partial, int num_cu, int dyn_tail, hipStream_t st, bool *fixed_point) {
-  const int nxo = dg.nxo, nvo = dg.nvo;
-  const size_t hist = sizeof(double) * (3 * static_cast<size_t>(nxo) * nvo + 3 * static_cast<size_t>(nvo));
-  const bool lds = hist <= 150 * 1024;
-  const size_t bytes = (lds ? hist : 0) + 18 * sizeof(double);  // + block_sum scratch + the drawn chunks' counter
-  const int threads = 1024;
-  const int blocks = ptcldist_blocks(np, nxo, nvo, num_cu);
-  // x, v, p, w against the 256 MiB Infinity Cache: beyond it the pass streams (PIC1DP_DIAG_NT=0 / 1 insists)
-  bool nt = 32.0 * static_cast<double>(np) > 288.0 * 1048576.0;
+// the pass then sums in doubles.  partial: [blocks][DIAG_PART] = the kinetic sums, max |p|, max |w|, overflow flag per workgroup
+hipError_t launch_ptcldist(const double *x, const double *v, const double *p, const double *w, int64_t np, const DistGeom &dg,
+                           bool deltaf, double bound_p, double bound_w, double *out, double *partial, const DiagLaunch &dl,
+                           int dyn_tail, hipStream_t st, bool *fixed_point) {
+  bool nt = dl.nt;   // (PIC1DP_DIAG_NT=0 / 1 insists)
   if (const char *e = tuning_env("PIC1DP_DIAG_NT")) nt = std::atoi(e) != 0;
   DistScale fx{};
-  const bool use_fx = lds && make_dist_scale(np, blocks, deltaf, bound_p, bound_w, &fx);
+  const bool use_fx = dl.lds && make_dist_scale(np, dl.blocks, deltaf, bound_p, bound_w, &fx, dl.threads);
   if (fixed_point) *fixed_point = use_fx;
-  auto go = [&](auto kern) {
-    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(threads), bytes, st, x, v, p, w, np, dg, out, partial,
-                         fx, dyn_tail);
-  };
-  if (use_fx) {
-    if (nt) return deltaf ? go(k_ptcldist<true, true, true, true>) : go(k_ptcldist<true, false, true, true>);
-    return deltaf ? go(k_ptcldist<true, true, false, true>) : go(k_ptcldist<true, false, false, true>);
-  }
-  if (lds) {
-    if (nt) return deltaf ? go(k_ptcldist<true, true, true, false>) : go(k_ptcldist<true, false, true, false>);
-    return deltaf ? go(k_ptcldist<true, true, false, false>) : go(k_ptcldist<true, false, false, false>);
-  }
-  if (nt) return deltaf ? go(k_ptcldist<false, true, true, false>) : go(k_ptcldist<false, false, true, false>);
-  return deltaf ? go(k_ptcldist<false, true, false, false>) : go(k_ptcldist<false, false, false, false>);
+  return with_bools(
+      [&](auto LDS, auto DELTAF, auto NT, auto FX) {
+        return launch_kernel(k_ptcldist<LDS, DELTAF, NT, LDS && FX>, dim3(static_cast<unsigned>(dl.blocks)), dim3(dl.threads),
+                             dl.bytes, st, x, v, p, w, np, dg, out, partial, fx, dyn_tail);
+      },
+      dl.lds, deltaf, nt, use_fx);
 }
 
 // ---------------------------------------------------------------------------
@@ -207,12 +179,12 @@ hipError_t launch_ptcldist(const double *x, const double *v, const double *p, co
 // ---------------------------------------------------------------------------
 namespace {
 
-// k_ptcldist's loop -- marker pairs, the next trip's loads in flight, the drawn tail, the NT switch -- with integer sums:
-// no max |p|, max |w| or overflow bookkeeping and no repeat pass (the quanta come from the input), the kinetic sums
-// reduced over the workgroup as integers.  LDS: the workgroup's copy is flushed every DIAG_FX_WINDOW_TRIPS dealt trips
-// and once at the end; the drawn rows are capped one below that, and the odd marker falls into the first window, so a
-// word sees fewer than 2^17 markers = 2^19 terms of less than 2^44 quanta between two flushes.  The dealt trips are the
-// same number for every thread of the workgroup, so the barriers around a flush inside the loop are met by all.
+// The sweep of k_ptcldist with integer sums: no max |p|, max |w| or overflow bookkeeping and no repeat pass (the quanta
+// come from the input), the kinetic sums reduced over the workgroup as integers.  LDS: the workgroup's copy is flushed
+// every DIAG_FX_WINDOW_TRIPS dealt trips and once at the end; the drawn rows are capped one below that, and the odd marker
+// falls into the first window, so a word sees fewer than 2^17 markers = 2^19 terms of less than 2^44 quanta between two
+// flushes.  The dealt trips are the same number for every thread of the workgroup, so the barriers around a flush inside
+// the sweep are met by all.
 template <bool LDS, bool DELTAF, bool NT>
 __global__ void __launch_bounds__(1024)
 k_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const DistGeom dg,
@@ -227,15 +199,13 @@ k_ptcldist_exact(const double *x, const double *v, const double *p, const double
   if (threadIdx.x < 6) sK[threadIdx.x] = 0ull;
   if (threadIdx.x == 0) *sDraw = 0u;
   __syncthreads();
-  const int64_t npair = np >> 1;
-  const double2 *x2 = reinterpret_cast<const double2 *>(x), *v2 = reinterpret_cast<const double2 *>(v);
-  const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
   KinFx sm;
-  if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  auto one = [&](double px, double pv, double pp, double pw) { ptcldist_one_exact<LDS, DELTAF>(px, pv, pp, pw, dg, b, sm, a); };
+  if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // (before the pairs: inside the first window)
     const int64_t i = tidx(np - 1);
-    ptcldist_one_exact<LDS, DELTAF>(x[i], v[i], p[i], DELTAF ? w[i] : 0.0, dg, b, sm, a);
+    one(x[i], v[i], p[i], DELTAF ? w[i] : 0.0);
   }
-  PairRows rows = pair_rows(npair, dyn_tail);
+  PairRows rows = pair_rows(np >> 1, dyn_tail);
   {
     const int waves = static_cast<int>(blockDim.x >> 6);
     const int extra = rows.drawn_total / waves - (DIAG_FX_WINDOW_TRIPS - 1);
@@ -244,29 +214,7 @@ k_ptcldist_exact(const double *x, const double *v, const double *p, const double
       rows.drawn_total -= extra * waves;
     }
   }
-  int k = 0;
-  int64_t j = rows.first + threadIdx.x;
-  bool have = rows.dealt > 0 || draw_chunk(rows, sDraw, j);
-  double2 X = make_double2(0.0, 0.0), V = X, P = X, W = X;
-  if (have && j < npair) {
-    const int64_t o = tidx2(j);
-    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
-    if constexpr (DELTAF) W = ld2t<NT>(w2 + o);
-  }
-  while (have) {
-    int64_t jn = j + rows.stride;
-    bool have_n = true;
-    if (++k >= rows.dealt) have_n = draw_chunk(rows, sDraw, jn);
-    double2 Xn = make_double2(0.0, 0.0), Vn = Xn, Pn = Xn, Wn = Xn;
-    if (have_n && jn < npair) {  // the next trip's loads are under way while this trip's atomics run
-      const int64_t o = tidx2(jn);
-      Xn = ld2t<NT>(x2 + o), Vn = ld2t<NT>(v2 + o), Pn = ld2t<NT>(p2 + o);
-      if constexpr (DELTAF) Wn = ld2t<NT>(w2 + o);
-    }
-    if (j < npair) {
-      ptcldist_one_exact<LDS, DELTAF>(X.x, V.x, P.x, W.x, dg, b, sm, a);
-      ptcldist_one_exact<LDS, DELTAF>(X.y, V.y, P.y, W.y, dg, b, sm, a);
-    }
+  pair_sweep<DELTAF, NT>(x, v, p, w, np >> 1, rows, sDraw, one, [&](int k) {
     if constexpr (LDS) {
       if (k <= rows.dealt && (k & (DIAG_FX_WINDOW_TRIPS - 1)) == 0) {   // (k: dealt trips done -- uniform over the workgroup)
         __syncthreads();
@@ -274,10 +222,7 @@ k_ptcldist_exact(const double *x, const double *v, const double *p, const double
         __syncthreads();
       }
     }
-    X = Xn, V = Vn, P = Pn, W = Wn;
-    j = jn;
-    have = have_n;
-  }
+  });
   dfx_kin_finish(sm, b, sK);
   if constexpr (LDS) {
     __syncthreads();
@@ -304,41 +249,21 @@ k_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i
 
 }  // namespace
 
-// one 64-bit word per bin and plane in the workgroup's LDS copy, + the kinetic words and the drawn chunks' counter
-bool ptcldist_exact_lds(int nxo, int nvo) {
-  return sizeof(long long) * (3 * static_cast<size_t>(nxo) * nvo + 8) <= 150 * 1024;
-}
-// A workgroup's flush costs what a few trips cost (two global atomics per non-zero bin), so a workgroup gets at least
-// 2^17 markers (64 trips) before a second one is started; never more workgroups than CUs (one copy per CU fits).
-int ptcldist_exact_blocks(int64_t np, int num_cu) {
-  int64_t blocks = np >> 17;
-  if (blocks > num_cu) blocks = num_cu;
-  if (blocks < 1) blocks = 1;
-  return static_cast<int>(blocks);
-}
-
 hipError_t launch_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np,
-                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, int num_cu, int dyn_tail,
+                                 const DistGeom &dg, bool deltaf, const DiagFxArgs &a, const DiagLaunch &dl, int dyn_tail,
                                  hipStream_t st) {
-  const bool lds = ptcldist_exact_lds(dg.nxo, dg.nvo);
-  const size_t bytes = sizeof(long long) * ((lds ? 3 * static_cast<size_t>(dg.nxo) * dg.nvo : 0) + 8);
-  const int blocks = ptcldist_exact_blocks(np, num_cu);
-  const bool nt = 32.0 * static_cast<double>(np) > 288.0 * 1048576.0;   // as launch_ptcldist
-  auto go = [&](auto kern) {
-    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(1024), bytes, st, x, v, p, w, np, dg, a, dyn_tail);
-  };
-  if (lds) {
-    if (nt) return deltaf ? go(k_ptcldist_exact<true, true, true>) : go(k_ptcldist_exact<true, false, true>);
-    return deltaf ? go(k_ptcldist_exact<true, true, false>) : go(k_ptcldist_exact<true, false, false>);
-  }
-  if (nt) return deltaf ? go(k_ptcldist_exact<false, true, true>) : go(k_ptcldist_exact<false, false, true>);
-  return deltaf ? go(k_ptcldist_exact<false, true, false>) : go(k_ptcldist_exact<false, false, false>);
+  return with_bools(
+      [&](auto LDS, auto DELTAF, auto NT) {
+        return launch_kernel(k_ptcldist_exact<LDS, DELTAF, NT>, dim3(static_cast<unsigned>(dl.blocks)), dim3(dl.threads),
+                             dl.bytes, st, x, v, p, w, np, dg, a, dyn_tail);
+      },
+      dl.lds, deltaf, dl.nt);
 }
 
 hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
                                     const DiagFxArgs &a, int nxv, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  const int blocks = static_cast<int>(std::min<int64_t>(1024, (n + 255) / 256));
+  const int blocks = tail_sum_blocks(n);
+  if (blocks == 0) return hipSuccess;
   if (w) return launch_kernel(k_energy_sums_exact<true>, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, nxv, a);
   return launch_kernel(k_energy_sums_exact<false>, dim3(blocks), dim3(256), 0, st, v, p, w, i0, n, nxv, a);
 }

@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(1024) k_step_full(const StepArgsDev a) {
     flush_rho_fx(reinterpret_cast<const unsigned long long *>(sR0), a.fx, a.g);
   else
     flush_rho(sR0, a.rho, a.g);
-  if constexpr (DIAG) ptcldist_finish<true, HAS_W, FX, 6>(a.dg, bins, sums, sH + ntot, a.dist_out, a.dist_partial, &a.dscale);
+  if constexpr (DIAG) ptcldist_finish<true, HAS_W, FX>(a.dg, bins, sums, sH + ntot, a.dist_out, a.dist_partial, &a.dscale);
 }
 
 // ---------------------------------------------------------------------------

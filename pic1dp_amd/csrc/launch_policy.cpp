@@ -1,7 +1,8 @@
-// launch_policy.cpp -- launch shapes of the marker kernels (launch_policy.hpp): arithmetic only
+// launch_policy.cpp -- launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp): arithmetic only
 #include "launch_policy.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace pic1dp {
 
@@ -121,6 +122,57 @@ PredLaunch pred_launch(const LaunchPolicy &p, int nx, int nmode, int64_t np, boo
   const Grid g = grid_of(p, nx, np, lc.threads, bpc, bpc >= 2 ? Osub::Auto : Osub::IfAsked);
   lc.blocks = g.blocks;
   return PredLaunch{lc, g.resident};
+}
+
+DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu) {
+  const size_t nxv = static_cast<size_t>(nxo) * nvo;
+  DiagLaunch d{};
+  d.threads = 1024;
+  // x, v, p, w against the 256 MiB Infinity Cache: beyond it the pass streams
+  d.nt = 32.0 * static_cast<double>(np) > 288.0 * 1048576.0;
+  int64_t blocks;
+  if (kind == 1) {
+    d.lds = sizeof(long long) * (3 * nxv + 8) <= kDiagLdsCap;
+    d.bytes = sizeof(long long) * ((d.lds ? 3 * nxv : 0) + 8);
+    // A workgroup's flush costs what a few trips cost (two global atomics per non-zero bin), so a workgroup gets at least
+    // 2^17 markers (64 trips) before a second one is started; never more workgroups than CUs (one copy per CU fits).
+    blocks = std::min<int64_t>(np >> 17, num_cu);
+  } else {
+    const size_t hist = sizeof(double) * (3 * nxv + 3 * static_cast<size_t>(nvo));
+    d.lds = hist <= kDiagLdsCap;
+    d.bytes = (d.lds ? hist : 0) + 18 * sizeof(double);
+    blocks = std::min<int64_t>(d.lds ? num_cu : static_cast<int64_t>(num_cu) * 2, ((np >> 1) + 1023) / 1024);
+  }
+  d.blocks = static_cast<int>(std::max<int64_t>(blocks, 1));
+  return d;
+}
+
+int tail_sum_blocks(int64_t ntail) {
+  return ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
+}
+
+// fixed-point sums: a workgroup adds at most its share of the markers into one bin; weights <= 1
+bool make_dist_scale(int64_t np, int blocks, bool deltaf, double bound_p, double bound_w, DistScale *out, int threads) {
+  DistScale fx{};
+  bool use_fx = blocks > 0 && bound_p > 0.0 && (!deltaf || bound_w > 0.0) && std::isfinite(bound_p) && std::isfinite(bound_w);
+  if (use_fx) {
+    const double th = static_cast<double>(threads);
+    const double per_wg = 2.0 * th * std::ceil(static_cast<double>((np >> 1) + 1) / (static_cast<double>(blocks) * th)) + 2.0;
+    const int e_n = static_cast<int>(std::ceil(std::log2(per_wg))) + 1;  // 2^e_n > the terms a bin can receive
+    const double bounds[3] = {1.0, bound_p, deltaf ? bound_w : 1.0};
+    for (int k = 0; k < 3; ++k) {
+      int eb;
+      (void)std::frexp(bounds[k], &eb);               // bounds[k] < 2^eb
+      const int mag = std::min(62 - e_n, 50);         // |term * 2^e| < 2^mag: below 2^51 for to_fixed, and the sums below 2^62
+      const int e = mag - eb;
+      if (e < -900 || e > 900) use_fx = false;        // (a bound no scale can serve)
+      fx.sc[k] = std::ldexp(1.0, e);
+      fx.inv[k] = std::ldexp(1.0, -e);
+      fx.bound[k] = std::ldexp(1.0, eb);
+    }
+  }
+  *out = fx;
+  return use_fx;
 }
 
 }  // namespace pic1dp

@@ -1,6 +1,7 @@
 // launch_policy.hpp -- the launch shape of every marker kernel as a pure function of the device's size, the grid, the
 // marker count and three knobs.  No context, no HIP call: capi_step.cpp fills LaunchPolicy from the context and launches
-// what comes back; tests/test_launch_policy_host.py pins every shape on the host (include/pic1dp_probe.h).
+// what comes back; tests/test_launch_policy_host.py pins every shape on the host (include/pic1dp_probe.h).  The
+// diagnostics passes of output_all have theirs here too (diag_launch; tests/test_diag_launch_host.py).
 // The functions return a shape whose LDS exceeds PARTICLE_LDS_CAP as it is: the callers decide what to run instead.
 #pragma once
 #include "kernels.hpp"
@@ -39,5 +40,14 @@ PredLaunch pred_launch(const LaunchPolicy &p, int nx, int nmode, int64_t np, boo
 inline bool fits_fused_solve(const PredLaunch &pl) {
   return pl.lc.blocks <= pl.resident && pl.lc.threads >= 128 && pl.lc.threads % 64 == 0;
 }
+
+// ---- the diagnostics passes of output_all (kernels_diag.hip) ----
+constexpr size_t kDiagLdsCap = 150 * 1024;  // a workgroup's LDS copy of the histograms: one workgroup of 1024 threads per CU
+constexpr int kEnergyBlocks = 1024;         // most workgroups a pass over tail slots gets
+// kind 0: k_ptcldist, the workgroup's copy [3 nxo nvo + 3 nvo] doubles + block_sum scratch and the drawn chunks' counter;
+// kind 1: k_ptcldist_exact, one 64-bit word per bin and plane + the kinetic words and the counter
+DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu);
+// workgroups of 256 threads for the kinetic sums of ntail tail slots (0: none)
+int tail_sum_blocks(int64_t ntail);
 
 }  // namespace pic1dp

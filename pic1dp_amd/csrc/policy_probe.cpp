@@ -1,6 +1,8 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp) and the LDS layouts of the field kernels (field_lds.hpp) behind
 // the C ABI of the probe library, for the host tests that pin every shape (tests/test_launch_policy_host.py,
-// tests/test_field_lds_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_field_lds_host.py, tests/test_diag_launch_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+#include <cmath>
+
 #include "../../include/pic1dp_probe.h"
 #include "field_lds.hpp"
 #include "launch_policy.hpp"
@@ -37,5 +39,27 @@ extern "C" int pic1dp_probe_host_field_lds(int32_t family, int32_t nx, int32_t n
   out[0] = static_cast<int64_t>(fl.bytes);
   out[1] = fl.threads;
   out[2] = fl.family;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t nx_opd, int32_t nv_opd, int32_t num_cu,
+                                             int64_t ntail, int64_t out[6]) {
+  if (!out || (kind != 0 && kind != 1)) return 1;
+  const DiagLaunch d = diag_launch(kind, np, nx_opd, nv_opd, num_cu);
+  out[0] = d.blocks;
+  out[1] = d.threads;
+  out[2] = d.lds;
+  out[3] = static_cast<int64_t>(d.bytes);
+  out[4] = d.nt;
+  out[5] = tail_sum_blocks(ntail);
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w,
+                                            int32_t threads, int32_t out[4]) {
+  if (!out) return 1;
+  DistScale fx{};
+  out[0] = make_dist_scale(np, blocks, deltaf != 0, bound_p, bound_w, &fx, threads);
+  for (int k = 0; k < 3; ++k) out[1 + k] = fx.sc[k] > 0.0 ? std::ilogb(fx.sc[k]) : 0;
   return 0;
 }

@@ -50,6 +50,8 @@ SIGNATURES = {
     "pic1dp_probe_dlnf0": [C.c_int32, _SP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
     "pic1dp_probe_host_launch_shape": [C.POINTER(LaunchQuery), _I64],
     "pic1dp_probe_host_field_lds": [C.c_int32] * 7 + [_I64],
+    "pic1dp_probe_host_diag_launch": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _I64],
+    "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
 }
 
 _lib = None
@@ -198,4 +200,22 @@ def host_field_lds(family, nx, nmode=1, npe=1, tab_lds=1, with_xchg=0, pred_kind
     out = (C.c_int64 * 3)()
     if load().pic1dp_probe_host_field_lds(family, nx, nmode, npe, tab_lds, with_xchg, pred_kind, out) != 0:
         raise ValueError("pic1dp_probe_host_field_lds: unknown family %r" % (family,))
+    return tuple(out)
+
+
+def host_diag_launch(kind, np_, nx_opd, nv_opd, num_cu, ntail=0):
+    """(blocks, threads, LDS copy or not, dynamic LDS bytes, NT, tail-slot workgroups) of a diagnostics pass of output_all
+    (csrc/launch_policy.hpp diag_launch), on the host; kind 0 k_ptcldist, 1 k_ptcldist_exact"""
+    out = (C.c_int64 * 6)()
+    if load().pic1dp_probe_host_diag_launch(kind, int(np_), nx_opd, nv_opd, num_cu, int(ntail), out) != 0:
+        raise ValueError("pic1dp_probe_host_diag_launch: unknown kind %r" % (kind,))
+    return tuple(out)
+
+
+def host_dist_scale(np_, blocks, deltaf, bound_p, bound_w, threads=1024):
+    """(fixed point or not, log2 scale of markr, total, pertb) a fixed-point diagnostics pass would use
+    (csrc/kernels.hpp make_dist_scale), on the host"""
+    out = (C.c_int32 * 4)()
+    if load().pic1dp_probe_host_dist_scale(int(np_), blocks, deltaf, bound_p, bound_w, threads, out) != 0:
+        raise ValueError("pic1dp_probe_host_dist_scale")
     return tuple(out)

@@ -205,9 +205,9 @@ def double_bound(plane, workgroups, extra=0):
 
 
 def dist_quanta(np_markers, num_cu, deltaf, bound_p, bound_w, threads=1024):
-    """2^e of the three planes' fixed-point sums: make_dist_scale (kernels_diag.hip) restated, for the launch of
-    ptcldist_blocks (LDS path: min(num_cu, the workgroups the markers fill)).  bound_p / bound_w: the bounds the pass was
-    scaled for (2 max |p|, margin x max |w| of the pass before: capi_diag.cpp run_diag_pass)"""
+    """2^e of the three planes' fixed-point sums: make_dist_scale (launch_policy.cpp) restated, for the launch of
+    diag_launch there (LDS path: min(num_cu, the workgroups the markers fill)).  bound_p / bound_w: the bounds the pass was
+    scaled for (2 max |p|, margin x max |w| of the pass before: capi_diag.cpp diag_fx_bounds)"""
     need = ((np_markers >> 1) + 1023) // 1024
     blocks = max(1, min(num_cu, need))
     per_wg = 2.0 * threads * math.ceil(((np_markers >> 1) + 1) / (blocks * threads)) + 2.0

@@ -317,3 +317,34 @@ def test_scale_two_species_of_unequal_counts(scale):
     assert scale["np"] == [N_SCALE, (1 << 22) + 5]
     assert 32.0 * scale["np"][1] <= 288.0 * 1048576.0
     two_passes(scale["eng"], scale, "(e) two species", True)
+
+
+def test_two_species_overflow_repeats_through_the_separate_calls(amd, monkeypatch):
+    """(h) the repeat in doubles as energy_sums / ptcldist reach it (the collector's other caller: output_all has
+    test_output_all_record_survives_a_fixed_point_repeat), two species of 4097 and 2049 markers (one workgroup each, an
+    odd last marker), 16 x 16 bins, PIC1DP_DIAG_FX_MARGIN=0.5: each species' second pass overflows its bound on |w| and
+    is repeated; the repeat of one species leaves the other's cached sums and histograms alone"""
+    monkeypatch.setenv("PIC1DP_DIAG_FX_MARGIN", "0.5")
+    counts = [4097, 2049]
+    inp = amd.make_input(nparticle_max=counts[0], nx=64, nx_opd=16, nv_opd=16,
+                         **dict(SCALE_INPUTS["two_species"], species_nparticle_init=counts))
+    with amd.Pic1dp(inp) as eng:
+        eng.particle_load()
+        g = [eng.particles_download(s) for s in range(2)]
+        sizes = [eng.local_sizes(s) for s in range(2)]
+        assert [npv for _, npv in sizes] == counts
+        refs = [species_reference(g[s], sizes[s][0], counts[s], inp) for s in range(2)]
+        ones = [one_marker(g[s], inp, counts[s] - 1) for s in range(2)]
+        for s in range(2):
+            compare(eng.ptcldist(s, finish=False), refs[s], inp, None, "(h) species %d pass 1" % s, ones[s])
+        assert eng.kernel_stats(12) == (0.0, 0)
+        eng.interaction_collect_charge()
+        e0 = eng.energy_sums(0)                          # species 0: the overflow met by energy_sums
+        assert eng.kernel_stats(12) == (1.0, 1)
+        raw1 = eng.ptcldist(1, finish=False)             # species 1: by ptcldist
+        assert eng.kernel_stats(12) == (2.0, 2)          # two fixed-point passes, each repeated in doubles
+        raw0 = eng.ptcldist(0, finish=False)             # (cached: no further pass)
+        assert eng.kernel_stats(12) == (2.0, 2) and np.array_equal(eng.energy_sums(0), e0)
+        compare(raw0, refs[0], inp, None, "(h) species 0 pass 2 (repeated in doubles)", ones[0])
+        compare(raw1, refs[1], inp, None, "(h) species 1 pass 2 (repeated in doubles)", ones[1])
+        check_sums(eng, refs, "(h)")

@@ -29,5 +29,6 @@ for b, d in zip(blocks, dem):
     d = d.replace("pic1dp::(anonymous namespace)::", "").replace("void ", "")
     d = re.sub(r"\(.*", "", d)
     if flt in d:
-        print("%-60s VGPR %3d  SGPR %3d  scratch %4d  waves/SIMD %d  spill %d" % (
-            d[:60], g("VGPRs"), g("TotalSGPRs"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"), g("VGPRs Spill")))
+        print("%-60s VGPR %3d  SGPR %3d  scratch %4d  waves/SIMD %d  spill %d  SGPR spill %d" % (
+            d[:60], g("VGPRs"), g("TotalSGPRs"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"), g("VGPRs Spill"),
+            g("SGPRs Spill")))
