@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "pic1dp_hip.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -106,6 +108,21 @@ int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t nx_opd, int3
  * sums, log2 of the scale of the planes markr, total, pertb}. */
 int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w, int32_t threads,
                                  int32_t out[4]);
+
+/* What pic1dp_hip_create decides before its first allocation (pic1dp_amd/csrc/context_plan.hpp plan_context), on the HOST,
+ * for an input, a layout and the three requests of the settings that bear on it (0: none): PIC1DP_PRED_KIND,
+ * PIC1DP_RHO_GLOBAL_COPIES as given (refused like settings_from_env refuses it), PIC1DP_FIELD_ONE_RANK_ORDER.  The input is taken as it is (not validated).
+ * out (cap words, at least 16 + nspecies + nblk (1 + nspecies)) = {npe, nblk, blk0, nalloc, imerge, iremove, isplit,
+ * gcopies, gstride, rho_set_doubles, pred_kind, pred_private, pred_set_doubles, pack_doubles, tab_lds, the field's npe,
+ * np[nspecies], blk_alloc[nblk], blk_np[nspecies][nblk]}; sc = {sc_re, sc_im}.  Nonzero: null argument, nspecies or
+ * nranks out of range, cap too small. */
+int pic1dp_probe_host_context_plan(const pic1dp_input *in, const pic1dp_layout *lay, int32_t pred_kind_req, int32_t gcopies_req,
+                                   int32_t one_rank_order, int64_t *out, int64_t cap, double sc[2]);
+/* The settings a context created now would take from the environment (pic1dp_amd/csrc/settings.hpp settings_from_env):
+ * iv = {fuse_solve, tail_on, call_pair, lazy_calls, predict, carry, osub_req, dyn_tail, dyn_tail_full, diag_fx,
+ * pred_kind_req, chain_mfma_req, gcopies_req, field_one_rank_order, chain_selftest_verbose}, dv = {nt_threshold_half,
+ * nt_threshold_full, diag_fx_margin_w}. */
+int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]);
 
 #ifdef __cplusplus
 }

@@ -78,7 +78,7 @@ namespace pic1dp_host {
 int ensure_second_set(pic1dp_ctx *c) {
   for (Species &S : c->sp) {
     if (S.slab[1]) continue;
-    HIP_TRY(hipMalloc(&S.slab[1], sizeof(double) * static_cast<size_t>(slab_doubles(S.nalloc + 2))));
+    HIP_TRY(c->mem.alloc(&S.slab[1], static_cast<size_t>(slab_doubles(S.nalloc + 2))));
     const int64_t as = slab_array_stride(S.nalloc + 2);
     S.set[1].x = S.slab[1];
     S.set[1].v = c->in.linear == 1 ? S.set[0].v : S.slab[1] + as;      // v is never pushed in a linear run
@@ -310,232 +310,112 @@ static int chain_selftest(pic1dp_ctx *c) {
   if (std::memcmp(got[0], want, sizeof(double) * kr) != 0) return -2;
   const bool a_ok = std::memcmp(got[0] + 16, want, sizeof(double) * kr) == 0;
   const bool b_ok = std::memcmp(got[1] + 16, want + kr, sizeof(double) * kr) == 0;
-  if (const char *dbg = tuning_env("PIC1DP_CHAIN_SELFTEST_VERBOSE"))
-    if (std::atoi(dbg) != 0)
-      std::fprintf(stderr, "pic1dp: chain self-test: matrix unit set A %s, set B (cancellation, subnormals) %s; one-lane chain set B %s\n",
-                   a_ok ? "identical" : "DIFFERS", b_ok ? "identical" : "DIFFERS",
-                   std::memcmp(got[1], want + kr, sizeof(double) * kr) == 0 ? "identical" : "DIFFERS");
+  if (c->cfg.chain_selftest_verbose)
+    std::fprintf(stderr, "pic1dp: chain self-test: matrix unit set A %s, set B (cancellation, subnormals) %s; one-lane chain set B %s\n",
+                 a_ok ? "identical" : "DIFFERS", b_ok ? "identical" : "DIFFERS",
+                 std::memcmp(got[1], want + kr, sizeof(double) * kr) == 0 ? "identical" : "DIFFERS");
   return a_ok && b_ok ? 1 : 0;
 }
 
-int pic1dp_hip_create(const pic1dp_input *in, const pic1dp_layout *layout, pic1dp_ctx **out) {
-  if (!in || !layout || !out) return fail(PIC1DP_ERR_ARG, "null argument");
-  *out = nullptr;
-  if (int rc = validate(*in, *layout)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(PIC1DP_ERR_NODEVICE, "no HIP device visible: this engine has no CPU path");
-  }
-  pic1dp_ctx *c = new pic1dp_ctx();
-  c->in = *in;
-  c->lay = *layout;
-  if (c->lay.npe <= 0) c->lay.npe = c->lay.nranks;
-  c->device = layout->device >= 0 ? layout->device : layout->rank % ndev;
-  if (c->device >= ndev) {
-    delete c;
-    return fail(PIC1DP_ERR_ARG, "device %d not present (%d visible)", layout->device, ndev);
-  }
-#define HIP_TRY_C(expr)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      int rc_ = fail(PIC1DP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-      pic1dp_hip_destroy(c);                                                             \
-      return rc_;                                                                        \
-    }                                                                                    \
-  } while (0)
-  HIP_TRY_C(hipSetDevice(c->device));
+// settings -> plan -> tables -> allocate -> self-test.  A step that fails returns at once: destroy() releases what the
+// context's owner has recorded by then.
+static int create_filled(pic1dp_ctx *c) {
+  const pic1dp_input &in = c->in;
+  c->cfg = settings_from_env();
+  c->plan = plan_context(in, c->lay, c->cfg);
+  const ContextPlan &P = c->plan;
+  c->lay.npe = P.npe;
+  HIP_TRY(hipSetDevice(c->device));
   hipDeviceProp_t prop;
-  HIP_TRY_C(hipGetDeviceProperties(&prop, c->device));
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    std::string arch = prop.gcnArchName;
-    pic1dp_hip_destroy(c);
-    return fail(PIC1DP_ERR_NODEVICE, "device arch %s: the kernels are built for gfx950 only", arch.c_str());
-  }
+  HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(PIC1DP_ERR_NODEVICE, "device arch %s: the kernels are built for gfx950 only", prop.gcnArchName);
   c->num_cu = prop.multiProcessorCount;
-  HIP_TRY_C(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
 
-  const int npe = c->lay.npe;
-  c->nblk = npe / c->lay.nranks;
-  c->blk0 = c->lay.rank * c->nblk;
-  c->blk_alloc.resize(c->nblk);
-  c->blk_np.assign(in->nspecies, std::vector<int64_t>(c->nblk, 0));
-  for (int b = 0; b < c->nblk; ++b) {
-    c->blk_alloc[b] = block_alloc(in->nparticle_max, c->blk0 + b, npe);
-    for (int s = 0; s < in->nspecies; ++s) c->blk_np[s][b] = block_np(*in, s, c->blk0 + b, npe);
-  }
-  c->blk_rng.resize(c->nblk);
-  // particle_init, src/pic1dp_particle.F90:73-87
-  c->imerge = in->nmerge > 0 ? 1 : 0;
-  c->iremove = in->nremove > 0 ? 1 : 0;
-  c->isplit = in->nsplit > 0 ? 1 : 0;
-  const int nx = in->nx, nm = in->nmode, ns = in->nspecies;
-  c->grid.lx = in->lx;
+  const int nx = in.nx, nm = in.nmode, ns = in.nspecies;
+  c->blk_np = P.blk_np;
+  c->blk_rng.resize(P.nblk);
+  c->imerge = P.imerge, c->iremove = P.iremove, c->isplit = P.isplit;
+  c->grid.lx = in.lx;
   c->grid.dnx = static_cast<double>(nx);
-  c->grid.dt_full = in->dt;
+  c->grid.dt_full = in.dt;
   c->grid.nx = nx;
-  c->grid.rlx = 1.0 / in->lx;
-  if (const char *e = tuning_env("PIC1DP_OSUB")) c->osub_req = std::max(0, std::atoi(e));
-  if (const char *e = tuning_env("PIC1DP_DYN_TAIL")) c->dyn_tail = c->dyn_tail_full = std::max(0, std::min(16, std::atoi(e)));
-  if (const char *e = tuning_env("PIC1DP_DYN_TAIL_FULL")) c->dyn_tail_full = std::max(0, std::min(16, std::atoi(e)));
-  if (const char *e = tuning_env("PIC1DP_NT_THRESHOLD_MB"))
-    c->nt_threshold_half = c->nt_threshold_full = std::atof(e) * 1048576.0;
-  if (const char *e = tuning_env("PIC1DP_NT_THRESHOLD_FULL_MB")) c->nt_threshold_full = std::atof(e) * 1048576.0;
-
-  // particle storage: valid markers of the owned blocks packed first, block
-  // tails (allocated but unloaded slots) behind them
+  c->grid.rlx = 1.0 / in.lx;
+  c->grid.gcopies = P.gcopies;
+  c->grid.gstride = P.gstride;
   c->sp.resize(ns);
   c->diag.resize(ns);
-  int64_t nalloc = 0;
-  for (int b = 0; b < c->nblk; ++b) nalloc += block_alloc(in->nparticle_max, c->blk0 + b, npe);
-  // species charge accumulators in gcopies copies: workgroup b adds its LDS tile into copy b % gcopies,
-  // so an address receives 1/gcopies of the flush atomics; the field kernels add the copies up.
-  // Measured (tools/fresh_and_flush.sh): the flush into ONE copy costs 4.8 % of a step at 6.4e6
-  // markers / nx 192, 1.5 % at 1e7 / 256, 0.9 % at 1e8 / 1024.  Eight copies (tools/ab_global_copies.sh)
-  // win back 2 % of the step at nx 192, nothing at nx 256, and LOSE 4 % at 1.25e7 markers / nx 1024: the
-  // one-workgroup field kernel then reads and re-zeroes 8 x nx words on the critical path.  So: eight
-  // copies for small grids only.  PIC1DP_RHO_GLOBAL_COPIES overrides.
-  c->grid.gcopies = nx <= 256 ? 8 : 1;
-  if (const char *e = tuning_env("PIC1DP_RHO_GLOBAL_COPIES")) {
-    const int k = std::atoi(e);
-    if (k >= 1 && k <= 64 && (k & (k - 1)) == 0) c->grid.gcopies = k;
-  }
-  c->grid.gstride = ns * nx;
-  const size_t rho_doubles = static_cast<size_t>(c->grid.gcopies) * ns * nx;
-  c->rho_set_doubles = rho_doubles;
-  HIP_TRY_C(hipMalloc(&c->d_rho_all, sizeof(double) * 3 * rho_doubles));
-  HIP_TRY_C(hipMemsetAsync(c->d_rho_all, 0, sizeof(double) * 3 * rho_doubles, c->st));
+  // field storage and the operators of field_init (src/pic1dp_field.F90:158-210),
+  // evaluated on the host with libm like the reference, stored mode-major
+  const ModeTables tab = mode_tables(in, P.pred_kind);
+  c->pred_tab = tab.pred_tab;
+
+  // The allocations, in the order and of the sizes they have always had: where the allocator puts the buffers moves the
+  // marker kernels (kernels.hpp "Marker storage"), so this sequence is not to be tidied.
+  DeviceMem &M = c->mem;
+  HIP_TRY(M.alloc(&c->d_rho_all, 3 * P.rho_set_doubles));
+  HIP_TRY(hipMemsetAsync(c->d_rho_all, 0, sizeof(double) * 3 * P.rho_set_doubles, c->st));
   c->d_rho_sp = c->d_rho_all;
-  if (const char *e = std::getenv("PIC1DP_FUSE_SOLVE")) c->fuse_solve = std::max(0, std::min(2, std::atoi(e)));
-  if (const char *e = std::getenv("PIC1DP_TAIL")) c->tail_on = std::atoi(e) != 0;
-  if (const char *e = std::getenv("PIC1DP_CALL_PAIR")) c->call_pair = std::atoi(e) != 0;
-  if (const char *e = std::getenv("PIC1DP_DIAG_FX")) c->diag_fx = std::atoi(e) != 0;
-  if (const char *e = std::getenv("PIC1DP_DIAG_FX_MARGIN")) c->diag_fx_margin_w = std::atof(e);
-  HIP_TRY_C(hipMalloc(reinterpret_cast<void **>(&c->d_ticket), 64));
-  HIP_TRY_C(hipMemsetAsync(c->d_ticket, 0, 64, c->st));
+  HIP_TRY(M.alloc(&c->d_ticket, 16));
+  HIP_TRY(hipMemsetAsync(c->d_ticket, 0, 64, c->st));
   for (int s = 0; s < ns; ++s) {
     Species &S = c->sp[s];
-    S.nalloc = nalloc;
-    S.np = 0;
-    for (int b = 0; b < c->nblk; ++b) S.np += block_np(*in, s, c->blk0 + b, npe);
-    S.sc = make_species_const(SpeciesInput{in->iptcldist, in->species_charge[s], in->species_mass[s],
-                                           in->species_temperature[s], in->species_temperature2[s],
-                                           in->species_density[s], in->species_v0[s]}, s);
+    S.nalloc = P.nalloc;
+    S.np = P.np[s];
+    S.sc = make_species_const(SpeciesInput{in.iptcldist, in.species_charge[s], in.species_mass[s],
+                                           in.species_temperature[s], in.species_temperature2[s],
+                                           in.species_density[s], in.species_v0[s]}, s);
     S.rho = c->d_rho_sp + static_cast<size_t>(s) * nx;
     // x, v, w, p of a species interleaved in tiles in ONE slab (kernels.hpp: 32 B per
     // marker, 9e9 markers in 288 GB); the slab of the RK ping-pong set is allocated on
     // the first sub-step call that needs it (ensure_second_set) -- pic1dp_hip_step
     // never does
-    HIP_TRY_C(hipMalloc(&S.slab[0], sizeof(double) * static_cast<size_t>(slab_doubles(nalloc + 2))));
-    HIP_TRY_C(hipMalloc(&S.fxb, 4 * sizeof(double)));   // two bounds, a 64-bit count (kernel_stats 13), one word spare
-    HIP_TRY_C(hipMemsetAsync(S.fxb, 0, 4 * sizeof(double), c->st));
-    const int64_t as = slab_array_stride(nalloc + 2);
+    HIP_TRY(M.alloc(&S.slab[0], static_cast<size_t>(slab_doubles(P.nalloc + 2))));
+    HIP_TRY(M.alloc(&S.fxb, 4));   // two bounds, a 64-bit count (kernel_stats 13), one word spare
+    HIP_TRY(hipMemsetAsync(S.fxb, 0, 4 * sizeof(double), c->st));
+    const int64_t as = slab_array_stride(P.nalloc + 2);
     S.set[0].x = S.slab[0];
     S.set[0].v = S.slab[0] + as;
     S.set[0].w = S.slab[0] + 2 * as;
     S.p = S.slab[0] + 3 * as;
   }
-
-  // field storage and the operators of field_init (src/pic1dp_field.F90:158-210),
-  // evaluated on the host with libm like the reference, stored mode-major
-  HIP_TRY_C(hipMalloc(&c->d_charge, sizeof(double) * nx));
-  HIP_TRY_C(hipMalloc(&c->d_chargeden, sizeof(double) * nx));
-  HIP_TRY_C(hipMalloc(&c->d_E, sizeof(double) * nx));
-  HIP_TRY_C(hipMalloc(&c->d_Eh, sizeof(double) * nx));
-  HIP_TRY_C(hipMemsetAsync(c->d_Eh, 0, sizeof(double) * nx, c->st));
-  HIP_TRY_C(hipMalloc(&c->d_E0, sizeof(double) * nx));
-  HIP_TRY_C(hipMalloc(&c->d_rho_dummy, sizeof(double) * rho_doubles));
-  if (const char *e = std::getenv("PIC1DP_LAZY_CALLS")) c->lazy_calls = std::atoi(e) != 0;
-  if (const char *e = tuning_env("PIC1DP_CARRY")) c->carry = std::max(0, std::atoi(e));
-  if (const char *e = std::getenv("PIC1DP_PREDICT")) c->predict = std::atoi(e);
-  HIP_TRY_C(hipMalloc(&c->d_mode_re, sizeof(double) * nm));
-  HIP_TRY_C(hipMalloc(&c->d_mode_im, sizeof(double) * nm));
-  HIP_TRY_C(hipMalloc(&c->d_fre, sizeof(double) * nm * nx));
-  HIP_TRY_C(hipMalloc(&c->d_fim, sizeof(double) * nm * nx));
-  HIP_TRY_C(hipMalloc(&c->d_ginv, sizeof(double) * nm));
-  HIP_TRY_C(hipMalloc(&c->d_hist, sizeof(double) * kHistCap));
-  HIP_TRY_C(hipMalloc(&c->d_scratch, sizeof(double) * (kEnergyBlocks * 3 + 16)));
-  HIP_TRY_C(hipMemsetAsync(c->d_charge, 0, sizeof(double) * nx, c->st));
-  HIP_TRY_C(hipMemsetAsync(c->d_chargeden, 0, sizeof(double) * nx, c->st));
-  HIP_TRY_C(hipMemsetAsync(c->d_E, 0, sizeof(double) * nx, c->st));
-  HIP_TRY_C(hipMemsetAsync(c->d_mode_re, 0, sizeof(double) * nm, c->st));
-  HIP_TRY_C(hipMemsetAsync(c->d_mode_im, 0, sizeof(double) * nm, c->st));
-  {
-    std::vector<double> fre(static_cast<size_t>(nm) * nx), fim(static_cast<size_t>(nm) * nx), gi(nm);
-    for (int m = 0; m < nm; ++m) {
-      const double mode = static_cast<double>(in->modes[m]);
-      gi[m] = 1.0 / (2.0 * kPi / in->lx * mode);  // :166
-      // two loops, plain cos() and plain sin(), as the reference's two fills
-      // (:186-189, :194-197): a paired sincos can differ in the last bit
-      double (*volatile cos_fn)(double) = std::cos;
-      double (*volatile sin_fn)(double) = std::sin;
-      for (int ix = 0; ix < nx; ++ix) {
-        const double th = 2.0 * kPi / static_cast<double>(nx) * mode * static_cast<double>(ix);  // :188
-        fre[static_cast<size_t>(m) * nx + ix] = cos_fn(th);
-      }
-      for (int ix = 0; ix < nx; ++ix) {
-        const double th = 2.0 * kPi / static_cast<double>(nx) * mode * static_cast<double>(ix);  // :196
-        fim[static_cast<size_t>(m) * nx + ix] = -sin_fn(th);
-      }
-    }
-    // one pass per step: with prediction tiles where they fit the LDS (k_step_one), as six sums for larger
-    // grids with one kept mode (k_step_sums); PIC1DP_PRED_KIND=1|2|3 insists on tiles | sums | sums in registers (tests)
-    const bool private_fits = 2 * (step_one_private_lds_bytes(nx) + kStaticLds) <= kCuLds;
-    // The prediction tiles cost 2 + 4 nm LDS atomics at random cells per marker.  Measured against the two passes
-    // (profiles/r04/experiments/ab_kept_modes.log, 1e8 markers / nx 1024, ms per step): two kept modes 1.23 against 1.46,
-    // three 1.49 against 1.45, four 2.05 (nx 512) against 1.46.  With the tiles as fixed-point sums (round 6: kernels_step.hip
-    // FxTiles) two kept modes run 1.06 and three 1.17 ms against the two passes' 1.40 (profiles/r06/experiments/ab_fx_tiles.log,
-    // ab_nm3.log): the tiles serve up to three kept modes, four and more take the two passes.
-    if (nm <= PRED_MAX_MODES && step_one_lds_bytes(nx, nm) <= PARTICLE_LDS_CAP)
-      c->pred_kind = 1;
-    // (the six sums travel in the head of an nx-vector on the call-site path: nx >= 8)
-    else if (nm == 1 && nx >= 8 && step_sums_lds_bytes(nx) <= PARTICLE_LDS_CAP)
-      c->pred_kind = 2;
-    // One kept mode: the six sums in thread-private LDS slots (k_step_one<PRIV>) beat the tiles, whose six atomics per
-    // marker at random cells pay ~3x in bank conflicts: -2 % at 1e8 markers / nx 1024 (profiles/r03/experiments/
-    // ab_private_sums.log), and on the small grids too once the step is timed without per-kernel events in the stream:
-    // 6.4e6 / nx 192 83.8 -> 76.6 us per step, 1e7 / nx 256 123.7 -> 116.5 (profiles/r04/experiments/ab_fused_solve.log)
-    // -- wherever the slots of two workgroups fit (nx >= 8: the sums travel in the head of an nx-vector on the
-    // call-site path).
-    if (c->pred_kind == 1 && nm == 1 && nx >= 8 && private_fits) c->pred_kind = 2;
-    bool sums_in_registers = false;
-    if (const char *e = std::getenv("PIC1DP_PRED_KIND")) {
-      const int k = std::atoi(e);
-      if ((k == 2 || k == 3) && nm == 1 && nx >= 8 && step_sums_lds_bytes(nx) <= PARTICLE_LDS_CAP) c->pred_kind = 2;
-      if (k == 3) sums_in_registers = true;  // k_step_sums also where the private slots would fit (tests: the large-grid kernel at a small grid)
-      // 1: the tiles wherever they fit (else the choice above stands)
-      if (k == 1 && nm <= PRED_MAX_MODES && step_one_lds_bytes(nx, nm) <= PARTICLE_LDS_CAP) c->pred_kind = 1;
-    }
-    if (c->pred_kind == 2 && private_fits && !sums_in_registers) c->pred_private = 1;
-    if (c->pred_kind) {  // the tables: E = 2*(cos re + (-sin) im) (src/pic1dp_field.F90:251-257)
-      std::vector<double> ta(fre.size()), tb(fim.size());
-      for (size_t i = 0; i < fre.size(); ++i) ta[i] = 2.0 * fre[i], tb[i] = 2.0 * fim[i];
-      if (c->pred_kind == 2) {
-        PredTab &pt = c->pred_tab;
-        for (int ix = 0; ix < nx; ++ix) {
-          pt.sum_fre += fre[ix], pt.sum_fim += fim[ix];
-          pt.g11 += fre[ix] * fre[ix], pt.g22 += fim[ix] * fim[ix], pt.g12 += fre[ix] * fim[ix];
-        }
-      }
-      const size_t pred_doubles = c->pred_kind == 2 ? 8 * PRED_SUM_COPIES : static_cast<size_t>(ns) * (1 + 2 * nm) * nx;
-      HIP_TRY_C(hipMalloc(&c->d_tabA, sizeof(double) * nm * nx));
-      HIP_TRY_C(hipMalloc(&c->d_tabB, sizeof(double) * nm * nx));
-      c->pred_set_doubles = pred_doubles;
-      HIP_TRY_C(hipMalloc(&c->d_pred_all, sizeof(double) * 3 * pred_doubles));
-      c->d_pred = c->d_pred_all;
-      HIP_TRY_C(hipMalloc(&c->d_cd_h, sizeof(double) * nx));
-      HIP_TRY_C(hipMalloc(&c->d_Ehn, sizeof(double) * nx));
-      HIP_TRY_C(hipMalloc(&c->d_pack, sizeof(double) * pack_doubles(nx, nm, c->pred_kind)));
-      HIP_TRY_C(hipMalloc(&c->d_mode_h, sizeof(double) * 2 * nm));
-      HIP_TRY_C(hipMemcpy(c->d_tabA, ta.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
-      HIP_TRY_C(hipMemcpy(c->d_tabB, tb.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
-      HIP_TRY_C(hipMemset(c->d_pred_all, 0, sizeof(double) * 3 * pred_doubles));
-    }
-    HIP_TRY_C(hipMemcpy(c->d_fre, fre.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
-    HIP_TRY_C(hipMemcpy(c->d_fim, fim.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
-    HIP_TRY_C(hipMemcpy(c->d_ginv, gi.data(), sizeof(double) * nm, hipMemcpyHostToDevice));
+  HIP_TRY(M.alloc(&c->d_charge, nx));
+  HIP_TRY(M.alloc(&c->d_chargeden, nx));
+  HIP_TRY(M.alloc(&c->d_E, nx));
+  HIP_TRY(M.alloc(&c->d_Eh, nx));
+  HIP_TRY(hipMemsetAsync(c->d_Eh, 0, sizeof(double) * nx, c->st));
+  HIP_TRY(M.alloc(&c->d_E0, nx));
+  HIP_TRY(M.alloc(&c->d_rho_dummy, P.rho_set_doubles));
+  HIP_TRY(M.alloc(&c->d_mode_re, nm));
+  HIP_TRY(M.alloc(&c->d_mode_im, nm));
+  HIP_TRY(M.alloc(&c->d_fre, static_cast<size_t>(nm) * nx));
+  HIP_TRY(M.alloc(&c->d_fim, static_cast<size_t>(nm) * nx));
+  HIP_TRY(M.alloc(&c->d_ginv, nm));
+  HIP_TRY(M.alloc(&c->d_hist, kHistCap));
+  HIP_TRY(M.alloc(&c->d_scratch, kEnergyBlocks * 3 + 16));
+  HIP_TRY(hipMemsetAsync(c->d_charge, 0, sizeof(double) * nx, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_chargeden, 0, sizeof(double) * nx, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_E, 0, sizeof(double) * nx, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_mode_re, 0, sizeof(double) * nm, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_mode_im, 0, sizeof(double) * nm, c->st));
+  if (P.pred_kind) {
+    HIP_TRY(M.alloc(&c->d_tabA, static_cast<size_t>(nm) * nx));
+    HIP_TRY(M.alloc(&c->d_tabB, static_cast<size_t>(nm) * nx));
+    HIP_TRY(M.alloc(&c->d_pred_all, 3 * P.pred_set_doubles));
+    c->d_pred = c->d_pred_all;
+    HIP_TRY(M.alloc(&c->d_cd_h, nx));
+    HIP_TRY(M.alloc(&c->d_Ehn, nx));
+    HIP_TRY(M.alloc(&c->d_pack, P.pack_doubles));
+    HIP_TRY(M.alloc(&c->d_mode_h, 2 * static_cast<size_t>(nm)));
+    HIP_TRY(hipMemcpy(c->d_tabA, tab.tabA.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_tabB, tab.tabB.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->d_pred_all, 0, sizeof(double) * 3 * P.pred_set_doubles));
   }
+  HIP_TRY(hipMemcpy(c->d_fre, tab.fre.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_fim, tab.fim.data(), sizeof(double) * nm * nx, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_ginv, tab.ginv.data(), sizeof(double) * nm, hipMemcpyHostToDevice));
+
   FieldArgs &f = c->fa;
   f.rho_sp = c->d_rho_sp;
   f.rho_copies = c->grid.gcopies;
@@ -552,41 +432,55 @@ int pic1dp_hip_create(const pic1dp_input *in, const pic1dp_layout *layout, pic1d
   f.nx = nx;
   f.nmode = nm;
   f.nspecies = ns;
-  f.deltaf = in->deltaf;
-  f.npe = c->lay.npe;  // the summation order of the reference run being reproduced (PIC1DP_FIELD_ONE_RANK_ORDER=1: tests)
-  if (const char *e = tuning_env("PIC1DP_FIELD_ONE_RANK_ORDER"))
-    if (std::atoi(e) != 0) f.npe = 1;
-  f.tab_lds = (static_cast<size_t>(2) * nm * nx * sizeof(double) <= 96 * 1024) ? 1 : 0;
-  f.lx = in->lx;
+  f.deltaf = in.deltaf;
+  f.npe = P.field_npe;
+  f.tab_lds = P.tab_lds;
+  f.lx = in.lx;
   f.dnx = static_cast<double>(nx);
-  f.sc_re = 1.0 / static_cast<double>(nx);    // src/pic1dp_field.F90:239
-  f.sc_im = -1.0 / static_cast<double>(nx);   // :234
+  f.sc_re = P.sc_re;
+  f.sc_im = P.sc_im;
+  for (int s = 0; s < ns; ++s) {
+    f.Z[s] = in.species_charge[s];
+    f.n0[s] = in.species_density[s];
+  }
   // The serial forward sums through the FP64 matrix unit -- only if this device gives the sequential sums bit for bit
   // that way (device_field.hpp chain_rows_mfma): sixteen rows of 1031 values of mixed sign and magnitude against the
   // host's additions one after the other.  PIC1DP_CHAIN_MFMA=0 keeps the chain of additions in one lane.
   f.chain_mfma = 0;
-  {
-    const char *e = std::getenv("PIC1DP_CHAIN_MFMA");
-    if (!e || std::atoi(e) != 0) {
-      const int verdict = chain_selftest(c);
-      if (verdict == -2) {  // (the lane's own chain: the arithmetic every bit-identity claim of the solve rests on)
-        pic1dp_hip_destroy(c);
-        return fail(PIC1DP_ERR_HIP, "the device's serial sum differs from the host's sequential additions");
-      }
-      f.chain_mfma = verdict == 1 ? 1 : 0;  // -1 (the test itself could not run): the optimisation is simply off
-      c->chain_selftest = verdict;
-      if (e && std::atoi(e) > 0 && f.chain_mfma == 0) {
-        pic1dp_hip_destroy(c);
-        return fail(PIC1DP_ERR_HIP, "PIC1DP_CHAIN_MFMA asked for, but the matrix unit does not give the sequential sums on this device");
-      }
-    }
+  if (c->cfg.chain_mfma_req != 0) {
+    const int verdict = chain_selftest(c);
+    if (verdict == -2)  // (the lane's own chain: the arithmetic every bit-identity claim of the solve rests on)
+      return fail(PIC1DP_ERR_HIP, "the device's serial sum differs from the host's sequential additions");
+    f.chain_mfma = verdict == 1 ? 1 : 0;  // -1 (the test itself could not run): the optimisation is simply off
+    c->chain_selftest = verdict;
+    if (c->cfg.chain_mfma_req > 0 && f.chain_mfma == 0)
+      return fail(PIC1DP_ERR_HIP, "PIC1DP_CHAIN_MFMA asked for, but the matrix unit does not give the sequential sums on this device");
   }
-  for (int s = 0; s < ns; ++s) {
-    f.Z[s] = in->species_charge[s];
-    f.n0[s] = in->species_density[s];
+  HIP_TRY(hipStreamSynchronize(c->st));
+  return 0;
+}
+
+int pic1dp_hip_create(const pic1dp_input *in, const pic1dp_layout *layout, pic1dp_ctx **out) {
+  if (!in || !layout || !out) return fail(PIC1DP_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (int rc = validate(*in, *layout)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    return fail(PIC1DP_ERR_NODEVICE, "no HIP device visible: this engine has no CPU path");
   }
-  HIP_TRY_C(hipStreamSynchronize(c->st));
-#undef HIP_TRY_C
+  pic1dp_ctx *c = new pic1dp_ctx();
+  c->in = *in;
+  c->lay = *layout;
+  c->device = layout->device >= 0 ? layout->device : layout->rank % ndev;
+  if (c->device >= ndev) {
+    delete c;
+    return fail(PIC1DP_ERR_ARG, "device %d not present (%d visible)", layout->device, ndev);
+  }
+  if (int rc = create_filled(c)) {
+    pic1dp_hip_destroy(c);  // (releases what the context's owner has recorded so far)
+    return rc;
+  }
   *out = c;
   return 0;
 }
@@ -597,22 +491,7 @@ int pic1dp_hip_destroy(pic1dp_ctx *c) {
   if (c->st) (void)hipStreamSynchronize(c->st);
   comm_release(c);
   optimize_release(c);
-  fx_release(c);
-  dfx_release(c);
-  for (auto &S : c->sp) {
-    (void)hipFree(S.slab[0]);
-    (void)hipFree(S.slab[1]);
-    (void)hipFree(S.t2);
-    (void)hipFree(S.fxb);
-  }
-  double *bufs[] = {c->d_rho_all, c->d_charge, c->d_chargeden, c->d_E,   c->d_mode_re, c->d_mode_im,
-                    c->d_fre,    c->d_fim,    c->d_ginv,      c->d_hist, c->d_scratch, c->d_dist, c->d_Eh, c->d_diag_part, c->d_E0, c->d_rho_dummy, c->d_stage, c->d_tabA, c->d_tabB, c->d_pred_all, c->d_cd_h, c->d_mode_h, c->d_Ehn, c->d_pack};
-  for (double *b : bufs) (void)hipFree(b);
-  (void)hipFree(c->d_ticket);
-  (void)hipFree(c->d_fft_tw);
-  (void)hipFree(c->d_fft_idx);
-  (void)hipFree(c->d_rec);
-  (void)hipHostFree(c->h_pin);
+  c->mem.release_all();
   for (auto &e : c->evpool) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
@@ -627,7 +506,7 @@ int pic1dp_hip_destroy(pic1dp_ctx *c) {
 constexpr int64_t kStageDoubles = static_cast<int64_t>(8) << 20;  // 64 MiB
 
 static int ensure_stage(pic1dp_ctx *c) {
-  if (!c->d_stage) HIP_TRY(hipMalloc(&c->d_stage, sizeof(double) * kStageDoubles));
+  if (!c->d_stage) HIP_TRY(c->mem.alloc(&c->d_stage, kStageDoubles));
   return 0;
 }
 
@@ -695,6 +574,13 @@ static void fx_bounds_of(const pic1dp_input &in, int isp, const double *p, const
   if (std::isfinite(cb)) b[1] = std::max(b[1], cb);
 }
 
+// a species' bounds start over with new markers, and the count of terms past the bounds beside them
+static int seed_fx_bounds(Species &S, const double b[2]) {
+  HIP_TRY(hipMemcpy(S.fxb, b, 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(S.fxb + 2, 0, 2 * sizeof(double)));
+  return 0;
+}
+
 int pic1dp_hip_set_seed_offset(pic1dp_ctx *c, int32_t offset) {
   CHECK_CTX(c);
   if (offset < 0) return fail(PIC1DP_ERR_ARG, "seed offset < 0");
@@ -712,39 +598,31 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;  // a noted push of markers that are about to be replaced is void
   c->state_version++;
   const pic1dp_input &in = c->in;
-  const int npe = c->lay.npe, ns = in.nspecies;
+  const int ns = in.nspecies;
   const int nthreads = load_threads();
-  int64_t max_alloc = 0;
-  for (int b = 0; b < c->nblk; ++b)
-    max_alloc = std::max<int64_t>(max_alloc, block_alloc(in.nparticle_max, c->blk0 + b, npe));
+  const ContextPlan &P = c->plan;
+  const int64_t max_alloc = *std::max_element(P.blk_alloc.begin(), P.blk_alloc.end());
   double *stage = nullptr;
   HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&stage), sizeof(double) * 4 * static_cast<size_t>(max_alloc), 0));
   double *hx = stage, *hv = stage + max_alloc, *hp = stage + 2 * max_alloc, *hw = stage + 3 * max_alloc;
   // a (re)load restores the loader's marker counts and optimisation counters
-  for (int s = 0; s < ns; ++s) {
-    c->sp[s].np = 0;
-    for (int b = 0; b < c->nblk; ++b) {
-      c->blk_np[s][b] = block_np(in, s, c->blk0 + b, npe);
-      c->sp[s].np += c->blk_np[s][b];
-    }
-  }
-  c->imerge = in.nmerge > 0 ? 1 : 0;
-  c->iremove = in.nremove > 0 ? 1 : 0;
-  c->isplit = in.nsplit > 0 ? 1 : 0;
+  c->blk_np = P.blk_np;
+  for (int s = 0; s < ns; ++s) c->sp[s].np = P.np[s];
+  c->imerge = P.imerge, c->iremove = P.iremove, c->isplit = P.isplit;
   c->rng_ready = false;
   std::vector<int64_t> voff(ns, 0), toff(ns);
   for (int s = 0; s < ns; ++s) toff[s] = c->sp[s].np;
   std::vector<double> fxb(2 * static_cast<size_t>(ns), 0.0);
   int rc = 0;
-  for (int b = 0; b < c->nblk && !rc; ++b) {
-    const int mype = c->blk0 + b;
-    const int64_t n = block_alloc(in.nparticle_max, mype, npe);
+  for (int b = 0; b < c->plan.nblk && !rc; ++b) {
+    const int mype = c->plan.blk0 + b;
+    const int64_t n = P.blk_alloc[b];
     Multirand g;
     if ((rc = init_block_rng(in, mype + c->seed_offset, g)) != 0) break;
     for (int s = 0; s < ns && !rc; ++s) {
       Species &S = c->sp[s];
       load_block_species(in, s, g, n, hx, hv, hp, hw, nthreads);
-      const int64_t np = block_np(in, s, mype, npe), nt = n - np;
+      const int64_t np = P.blk_np[s][b], nt = n - np;
       fx_bounds_of(in, s, hp, hw, np, &fxb[2 * static_cast<size_t>(s)]);
       struct {
         double *d;
@@ -761,10 +639,8 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   }
   (void)hipHostFree(stage);
   if (rc) return rc;
-  for (int s = 0; s < ns; ++s) {
-    HIP_TRY(hipMemcpy(c->sp[s].fxb, &fxb[2 * static_cast<size_t>(s)], 2 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(c->sp[s].fxb + 2, 0, 2 * sizeof(double)));   // (the count of terms past the bounds starts over)
-  }
+  for (int s = 0; s < ns; ++s)
+    if ((rc = seed_fx_bounds(c->sp[s], &fxb[2 * static_cast<size_t>(s)])) != 0) return rc;
   c->rng_ready = true;
   diag_void_bounds(c);  // (new markers)
   c->cur = 0;
@@ -809,10 +685,9 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
   {  // (the prediction tiles' fixed-point bounds start over with these markers)
     double b[2] = {0.0, 0.0};
     fx_bounds_of(c->in, isp, p, w, np, b);
-    HIP_TRY(hipMemcpy(S.fxb, b, sizeof b, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(S.fxb + 2, 0, 2 * sizeof(double)));   // (the count of terms past the bounds starts over, as in particle_load)
+    if (int rc = seed_fx_bounds(S, b)) return rc;
   }
-  if (c->nblk == 1) c->blk_np[isp][0] = np;
+  if (c->plan.nblk == 1) c->blk_np[isp][0] = np;
   c->rng_ready = false;  // the host's loader owns the random stream now
   diag_void_bounds(c);
   c->loaded = true;

@@ -16,11 +16,9 @@ int diag_max_blocks(const pic1dp_ctx *c) { return 2 * c->num_cu; }
 int pinned(pic1dp_ctx *c, size_t ndoubles, double **out) {
   if (ndoubles > c->h_pin_doubles) {
     HIP_TRY(hipStreamSynchronize(c->st));  // (nothing in flight into the old buffer)
-    (void)hipHostFree(c->h_pin);
-    c->h_pin = nullptr;
     c->h_pin_doubles = 0;
     const size_t want = ndoubles + ndoubles / 4 + 64;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_pin), sizeof(double) * want, hipHostMallocDefault));
+    HIP_TRY(c->mem.regrow(&c->h_pin, want, true));
     c->h_pin_doubles = want;
   }
   *out = c->h_pin;
@@ -42,8 +40,8 @@ int diag_buffers(pic1dp_ctx *c) {
   const pic1dp_input &in = c->in;
   const int ns = in.nspecies;
   if (in.nx_opd < 1 || in.nv_opd < 2) return fail(PIC1DP_ERR_ARG, "nx_opd >= 1 and nv_opd >= 2 required");
-  if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, sizeof(double) * dist_len(in) * (ns + 1)));
-  if (!c->d_diag_part) HIP_TRY(hipMalloc(&c->d_diag_part, sizeof(double) * DIAG_PART * diag_max_blocks(c) * ns));
+  if (!c->d_dist) HIP_TRY(c->mem.alloc(&c->d_dist, dist_len(in) * (ns + 1)));
+  if (!c->d_diag_part) HIP_TRY(c->mem.alloc(&c->d_diag_part, static_cast<size_t>(DIAG_PART) * diag_max_blocks(c) * ns));
   return 0;
 }
 
@@ -57,9 +55,9 @@ void diag_void_bounds(pic1dp_ctx *c) {
 // max |p|, max |w| of the pass before with a margin (p changes with load / upload / events only, w by a few per cent a record)
 bool diag_fx_bounds(const pic1dp_ctx *c, int isp, double *bound_p, double *bound_w) {
   const DiagSpecies &D = c->diag[isp];
-  if (!(c->diag_fx && D.max_p > 0.0 && (c->in.deltaf != 1 || D.max_w > 0.0))) return false;
+  if (!(c->cfg.diag_fx && D.max_p > 0.0 && (c->in.deltaf != 1 || D.max_w > 0.0))) return false;
   *bound_p = 2.0 * D.max_p;
-  *bound_w = c->diag_fx_margin_w * D.max_w;
+  *bound_w = c->cfg.diag_fx_margin_w * D.max_w;
   return true;
 }
 
@@ -88,7 +86,7 @@ static int run_diag_pass(pic1dp_ctx *c, int isp, bool fixed) {
     if (fixed) (void)diag_fx_bounds(c, isp, &bp, &bw);
     const DiagLaunch dl = diag_launch(0, S.np, in.nx_opd, in.nv_opd, c->num_cu);
     blocks = dl.blocks;
-    HIP_TRY(launch_ptcldist(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, bp, bw, hist, diag_part_dev(c, isp), dl, c->dyn_tail,
+    HIP_TRY(launch_ptcldist(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, bp, bw, hist, diag_part_dev(c, isp), dl, c->cfg.dyn_tail,
                             c->st, &was_fixed));
   }
   diag_note_pass(c, isp, blocks, was_fixed, S.np > 0);
@@ -181,11 +179,6 @@ int ensure_diag(pic1dp_ctx *c, int isp) {
 // ---------------------------------------------------------------------------
 // kind 1 of the diagnostics sum (pic1dp_hip_set_diag_sum; kernels.hpp DiagFxArgs)
 // ---------------------------------------------------------------------------
-void dfx_release(pic1dp_ctx *c) {
-  (void)hipFree(c->d_dfx);
-  c->d_dfx = nullptr;
-}
-
 static const char *const kDfxNames[6] = {"markr", "total", "pertb", "sum v^2", "sum v^2 p", "sum v^2 w"};
 
 // the exact pass over species isp into its slot of d_dfx: the markers' histograms and kinetic terms, then the tail
@@ -201,7 +194,7 @@ static int run_diag_pass_exact(pic1dp_ctx *c, int isp) {
   HIP_TRY(hipMemsetAsync(a.acc, 0, sizeof(long long) * words, c->st));
   if (S.np > 0)
     HIP_TRY(launch_ptcldist_exact(A.x, A.v, S.p, A.w, S.np, dist_geom(c), in.deltaf == 1, a,
-                                  diag_launch(1, S.np, in.nx_opd, in.nv_opd, c->num_cu), c->dyn_tail, c->st));
+                                  diag_launch(1, S.np, in.nx_opd, in.nv_opd, c->num_cu), c->cfg.dyn_tail, c->st));
   HIP_TRY(launch_energy_sums_exact(S.set[0].v, S.p, in.deltaf ? S.set[0].w : nullptr, S.np, S.nalloc - S.np, a,
                                    in.nx_opd * in.nv_opd, c->st));
   diag_note_pass(c, isp, 0, false, true);
@@ -220,7 +213,7 @@ static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long
   const pic1dp_input &in = c->in;
   if (int rc = diag_buffers(c)) return rc;
   const size_t words = diag_fx_words(in.nx_opd, in.nv_opd), limbs = diag_fx_limbs(in.nx_opd, in.nv_opd);
-  if (!c->d_dfx) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_dfx), sizeof(long long) * words * (in.nspecies + 1)));
+  if (!c->d_dfx) HIP_TRY(c->mem.alloc(&c->d_dfx, words * (in.nspecies + 1)));
   if (int rc = dfx_refresh(c, isp)) return rc;
   const long long *src = c->d_dfx + words * isp;
   if (reduced && c->comm) {  // reduce a copy: the cached local limbs stay local
@@ -491,9 +484,8 @@ static int enqueue_record(pic1dp_ctx *c, const RecordLayout &L, double *h, bool 
   double *slot = c->d_scratch + kEnergyBlocks * 3;
   HIP_TRY(launch_field_energy(c->d_E, c->in.nx, c->in.lx, static_cast<double>(c->in.nx), slot, c->st));
   if (c->d_rec_doubles < L.total) {
-    if (c->d_rec) HIP_TRY(hipFree(c->d_rec));
-    c->d_rec = nullptr, c->d_rec_doubles = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_rec), sizeof(double) * L.total));
+    c->d_rec_doubles = 0;
+    HIP_TRY(c->mem.regrow(&c->d_rec, L.total));
     c->d_rec_doubles = L.total;
   }
   PackArgs pk{};

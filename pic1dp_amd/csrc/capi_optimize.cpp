@@ -112,7 +112,7 @@ void delete_opt_worker(void *w) { delete static_cast<OptWorker *>(w); }
 // share the block's random stream).  Same decisions, same bits, whatever the number of threads.
 int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
   const pic1dp_input &in = c->in;
-  const int ns = in.nspecies, nb = c->nblk, nv = in.nv;
+  const int ns = in.nspecies, nb = c->plan.nblk, nv = in.nv;
   if (int rc = ensure_second_set(c)) return rc;  // the re-packing target
   // PIC1DP_OPT_TIMING=1: wall clock of the event's phases to stderr (tools/opt_event_bench.py)
   const char *te = tuning_env("PIC1DP_OPT_TIMING");
@@ -128,7 +128,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
     Species &S = c->sp[s];
     int64_t voff = 0, toff = S.np;
     for (int b = 0; b < nb; ++b) {
-      const int64_t na = c->blk_alloc[b], np = c->blk_np[s][b];
+      const int64_t na = c->plan.blk_alloc[b], np = c->blk_np[s][b];
       ob[s][b] = OptBlock{S.set[0].x, S.set[0].v, S.p, S.set[0].w, voff, np, toff};
       voff += np;
       toff += na - np;
@@ -204,7 +204,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
         const double peak = *std::max_element(h, h + nv), limit = peak * th;
         int64_t &np = c->blk_np[s][b];
         if (np <= 0) continue;
-        if (c->blk_alloc[b] >= (static_cast<int64_t>(1) << 32)) return fail(PIC1DP_ERR_ARG, "a block of 2^32 slots or more");
+        if (c->plan.blk_alloc[b] >= (static_cast<int64_t>(1) << 32)) return fail(PIC1DP_ERR_ARG, "a block of 2^32 slots or more");
         // the moved markers' ids travel; the holes they move into are found on the device (opt_holes)
         auto upload_moves = [&](const OptMoves &m, uint32_t *&d_pos, uint32_t *&d_id, size_t extra, char *&d_extra) -> int {
           const size_t nm = m.id.size();
@@ -273,7 +273,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
           HIP_TRY(to_host(&flag, d_key.p, sizeof(uint8_t) * np));
           tph[0] += ms_since(t0), t0 = now();
           SplitPlan plan;
-          plan_split(in, static_cast<const uint8_t *>(flag), c->blk_rng[b], c->blk_alloc[b], np, plan);
+          plan_split(in, static_cast<const uint8_t *>(flag), c->blk_rng[b], c->plan.blk_alloc[b], np, plan);
           tph[1] += ms_since(t0), t0 = now();
           const size_t nsp = plan.ks.size();
           HIP_TRY(d_lists.alloc(sizeof(double) * plan.dv.size() + sizeof(uint32_t) * nsp + 64));
@@ -355,7 +355,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
     for (int b = 0; b < nb; ++b) S.np += c->blk_np[s][b];
     int64_t voff = 0, toff = S.np;
     for (int b = 0; b < nb; ++b) {
-      const int64_t na = c->blk_alloc[b], np = c->blk_np[s][b];
+      const int64_t na = c->plan.blk_alloc[b], np = c->blk_np[s][b];
       HIP_TRY(opt_copy_segment(ob[s][b], 0, np, nx_, nv_, np_, nw_, voff, c->st));
       HIP_TRY(opt_copy_segment(ob[s][b], np, na - np, nx_, nv_, np_, nw_, toff, c->st));
       voff += np;
@@ -384,7 +384,7 @@ extern "C" {
 // the event on host copies of the owned blocks (PIC1DP_OPT_HOST=1): every marker crosses PCIe twice, 64 B in all
 static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
   const pic1dp_input &in = c->in;
-  const int ns = in.nspecies, nb = c->nblk, nv = in.nv;
+  const int ns = in.nspecies, nb = c->plan.nblk, nv = in.nv;
   // host copy of every owned block, full allocation (valid markers + tail slots)
   struct Block {
     std::vector<double> a[4];  // x v p w
@@ -395,7 +395,7 @@ static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
     const double *dev[4] = {S.set[0].x, S.set[0].v, S.p, S.set[0].w};
     int64_t voff = 0, toff = S.np;
     for (int b = 0; b < nb; ++b) {
-      const int64_t na = c->blk_alloc[b], np = c->blk_np[s][b];
+      const int64_t na = c->plan.blk_alloc[b], np = c->blk_np[s][b];
       for (int k = 0; k < 4; ++k) {
         host[s][b].a[k].resize(static_cast<size_t>(na));
         if (int rc = get_range(c, dev[k], voff, host[s][b].a[k].data(), np)) return rc;
@@ -442,7 +442,7 @@ static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
         else if (kind == 1)
           opt_remove(in, th, h, c->blk_rng[b], np, B.a[0].data(), B.a[1].data(), B.a[2].data(), B.a[3].data());
         else
-          opt_split(in, th, h, c->blk_rng[b], c->blk_alloc[b], np, B.a[0].data(), B.a[1].data(), B.a[2].data(),
+          opt_split(in, th, h, c->blk_rng[b], c->plan.blk_alloc[b], np, B.a[0].data(), B.a[1].data(), B.a[2].data(),
                     B.a[3].data());
       }
     *counters[kind] += 1;
@@ -455,7 +455,7 @@ static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
     double *dev[4] = {S.set[0].x, S.set[0].v, S.p, S.set[0].w};
     int64_t voff = 0, toff = S.np;
     for (int b = 0; b < nb; ++b) {
-      const int64_t na = c->blk_alloc[b], np = c->blk_np[s][b];
+      const int64_t na = c->plan.blk_alloc[b], np = c->blk_np[s][b];
       for (int k = 0; k < 4; ++k) {
         if (int rc = put_range(c, dev[k], voff, host[s][b].a[k].data(), np)) return rc;
         if (int rc = put_range(c, dev[k], toff, host[s][b].a[k].data() + np, na - np)) return rc;
@@ -482,7 +482,7 @@ int pic1dp_hip_particle_optimize(pic1dp_ctx *c, int32_t irk, int32_t *flag_optim
                 "particle_remove / particle_split continue the loader's random stream: load the markers with "
                 "pic1dp_hip_particle_load");
   const pic1dp_input &in = c->in;
-  const int ns = in.nspecies, nb = c->nblk;
+  const int ns = in.nspecies, nb = c->plan.nblk;
   for (int s = 0; s < ns; ++s) {
     int64_t sum = 0;
     for (int b = 0; b < nb; ++b) sum += c->blk_np[s][b];
@@ -496,7 +496,7 @@ int pic1dp_hip_particle_optimize(pic1dp_ctx *c, int32_t irk, int32_t *flag_optim
   // the device path names positions inside a block with 32 bits (keys, move lists, bit masks): a block of 2^32 slots or
   // more -- 137 GB of markers in one reference block -- takes the host copies, which count in 64 bits
   for (int b = 0; b < nb; ++b)
-    if (c->blk_alloc[b] >= (int64_t{1} << 32) - 2) on_host = true;
+    if (c->plan.blk_alloc[b] >= (int64_t{1} << 32) - 2) on_host = true;
   if (int rc = on_host ? optimize_on_host(c, due) : optimize_on_device(c, due)) return rc;
   diag_void_bounds(c);  // (merged / rescaled / split weights)
   if (flag_optimized) *flag_optimized = 1;

@@ -17,14 +17,14 @@
 static bool dft_paths(const pic1dp_ctx *c) { return c->field_solver == 0 && c->field_transform == 0; }
 // the prediction is the six sums of ONE kept mode (k_step_sums, k_step_one<PRIV>): what the pair solve of the call sites,
 // the fused solve and the tail are written for
-static bool six_sums_one_mode(const pic1dp_ctx *c) { return c->pred_kind == 2 && c->in.nmode == 1; }
+static bool six_sums_one_mode(const pic1dp_ctx *c) { return c->plan.pred_kind == 2 && c->in.nmode == 1; }
 // the kept modes fit the one-workgroup field kernels (the wide kernels take more; no predicted or paired solve there)
 static bool modes_fit_field_kernel(const pic1dp_ctx *c) { return 2 * c->in.nmode <= FIELD_THREADS; }
 // -f0'/f0 of the distribution bears an exp (two-stream2, bump-on-tail)
 static bool exp_bearing(const pic1dp_ctx *c) { return c->in.deltaf && (c->in.iptcldist == 2 || c->in.iptcldist == 3); }
 
 // launch shapes (launch_policy.hpp) for this context
-static LaunchPolicy policy_of(const pic1dp_ctx *c) { return LaunchPolicy{c->num_cu, c->threads_req, c->bpc_req, c->osub_req}; }
+static LaunchPolicy policy_of(const pic1dp_ctx *c) { return LaunchPolicy{c->num_cu, c->threads_req, c->bpc_req, c->cfg.osub_req}; }
 static LaunchCfg particle_launch(const pic1dp_ctx *c, int64_t np, bool with_E, bool with_rho, bool exact = false) {
   return particle_launch(policy_of(c), c->in.nx, np, with_E, with_rho, exact);
 }
@@ -33,7 +33,7 @@ static LaunchCfg step_launch(const pic1dp_ctx *c, int64_t np, bool full) {
 }
 // the one-pass kernels (k_step_one, k_step_one<PRIV>, k_step_sums)
 static PredLaunch pred_launch(const pic1dp_ctx *c, int64_t np, bool priv) {
-  return pred_launch(policy_of(c), c->in.nx, c->in.nmode, np, priv, c->pred_kind, exp_bearing(c));
+  return pred_launch(policy_of(c), c->in.nx, c->in.nmode, np, priv, c->plan.pred_kind, exp_bearing(c));
 }
 
 // (kind 1 of the charge sum: its rho tile is twice as large -- up to nx 5080; beyond, the sub-step kernels)
@@ -55,10 +55,7 @@ static bool output_follows(const pic1dp_ctx *c) { return output_follows_at(c, c-
 // describe E), few kept modes, and LDS for E0, Eh, the mode tables and the four accumulators
 // (kind 1 of the charge sum: no prediction -- two passes per step)
 static bool predict_capable(const pic1dp_ctx *c) {
-  return c->charge_sum == 0 && c->predict && c->pred_kind != 0 && c->d_pred && dft_paths(c) && step_recompute_ok(c);
-}
-static size_t pred_doubles(const pic1dp_ctx *c) {
-  return c->pred_kind == 2 ? 8 * PRED_SUM_COPIES : static_cast<size_t>(c->in.nspecies) * (1 + 2 * c->in.nmode) * c->in.nx;
+  return c->charge_sum == 0 && c->cfg.predict && c->plan.pred_kind != 0 && c->d_pred && dft_paths(c) && step_recompute_ok(c);
 }
 
 // Does a step that output_all follows take the diagnostics inside its marker kernel (k_step_full<DIAG>)?
@@ -75,10 +72,10 @@ static bool diag_in_step(const pic1dp_ctx *c) {
 // the accumulator set the marker kernels deposit into from now on (d_rho_all / d_pred_all hold three)
 static void use_accumulators(pic1dp_ctx *c, int idx) {
   c->acc_idx = idx;
-  c->d_rho_sp = c->d_rho_all + static_cast<size_t>(idx) * c->rho_set_doubles;
+  c->d_rho_sp = c->d_rho_all + static_cast<size_t>(idx) * c->plan.rho_set_doubles;
   for (int s = 0; s < c->in.nspecies; ++s) c->sp[s].rho = c->d_rho_sp + static_cast<size_t>(s) * c->in.nx;
   c->fa.rho_sp = c->d_rho_sp;
-  if (c->d_pred_all) c->d_pred = c->d_pred_all + static_cast<size_t>(idx) * c->pred_set_doubles;
+  if (c->d_pred_all) c->d_pred = c->d_pred_all + static_cast<size_t>(idx) * c->plan.pred_set_doubles;
 }
 
 // the one-pass launch of the first species that has markers -- the one whose prologue would carry a fused solve -- can
@@ -101,7 +98,7 @@ static bool fused_solve_launch_fits(const pic1dp_ctx *c, bool priv, int *threads
 // per step, profiles/r04/experiments/ab_fused_solve.log).  What the fusion is worth where it applies: one dependency
 // gap and the field launch's start-up, 1-2 us of a step (the solve itself is a chain of dependent round trips either way).
 static bool fuse_capable(const pic1dp_ctx *c) {
-  if (!(c->fuse_solve && !several_ranks(c) && six_sums_one_mode(c) && dft_paths(c) && c->fa.npe <= 32 && predict_capable(c)))
+  if (!(c->cfg.fuse_solve && !several_ranks(c) && six_sums_one_mode(c) && dft_paths(c) && c->fa.npe <= 32 && predict_capable(c)))
     return false;
   // ... and serial forward sums that are short enough.  The solve costs inside a marker launch what it costs in its own: a
   // row of dependent round trips and the chain in the reference's order (12 cycles a term at the marker kernel's
@@ -113,8 +110,8 @@ static bool fuse_capable(const pic1dp_ctx *c) {
   // level to +0.3 % at nx 4096 (ab_fused_solve_mfma_chain.log; left unfused: its kernel stays the plain stream the profiles
   // price): the length that counts is the chain's cost in terms.
   const int chain_terms = (c->fa.npe == 1 && c->fa.chain_mfma) ? c->in.nx / 3 : c->in.nx / std::max(1, c->fa.npe);
-  if (c->fuse_solve != 2 && chain_terms > 1024) return false;
-  return fused_solve_launch_fits(c, c->pred_private && c->threads_req <= 0);  // (the first species launched carries the solve)
+  if (c->cfg.fuse_solve != 2 && chain_terms > 1024) return false;
+  return fused_solve_launch_fits(c, c->plan.pred_private && c->threads_req <= 0);  // (the first species launched carries the solve)
 }
 
 // the prediction in d_pred describes the next first sub-step of the markers as they are, and the kept
@@ -233,8 +230,8 @@ struct StepPlan {
 static StepPlan plan_step(const pic1dp_ctx *c, bool full, bool diag, bool pred, bool tail_ok) {
   StepPlan pl{};
   if (pred && (!full || diag || !predict_capable(c))) pred = false;
-  pl.priv = c->pred_kind == 2 && c->pred_private && c->threads_req <= 0;  // k_step_one<PRIV>: Eh from its tile
-  if (pred && c->pred_kind == 2 && !pl.priv && c->eh_modes == 0) pred = false;  // k_step_sums forms Eh from its kept mode
+  pl.priv = c->plan.pred_kind == 2 && c->plan.pred_private && c->threads_req <= 0;  // k_step_one<PRIV>: Eh from its tile
+  if (pred && c->plan.pred_kind == 2 && !pl.priv && c->eh_modes == 0) pred = false;  // k_step_sums forms Eh from its kept mode
   pl.pred = pred;
   // the diagnostics of output_all inside k_step_full: when asked for, the LDS holds them, and the
   // tuning build of the marker loop is the default one
@@ -247,7 +244,7 @@ static StepPlan plan_step(const pic1dp_ctx *c, bool full, bool diag, bool pred, 
   // several ranks, the six sums of one kept mode, the mode-filter solver: the packing of this rank's charge for the sum
   // over ranks rides in the tail of the last marker launch (RCCL: one all-reduce follows; exchange: posted at once)
   pl.tail_species = -1;
-  if (tail_ok && pred && c->tail_on && six_sums_one_mode(c) && dft_paths(c) && several_ranks(c)) {
+  if (tail_ok && pred && c->cfg.tail_on && six_sums_one_mode(c) && dft_paths(c) && several_ranks(c)) {
     pl.tail_mode = xchg_active(c) ? 2 : (c->comm != nullptr ? 1 : 0);
     for (int s = 0; s < c->in.nspecies; ++s)
       if (c->sp[s].np > 0) pl.tail_species = s;
@@ -256,7 +253,7 @@ static StepPlan plan_step(const pic1dp_ctx *c, bool full, bool diag, bool pred, 
   // x, v, w, p of all species against the 256 MiB Infinity Cache
   double state_bytes = 0.0;
   for (int s = 0; s < c->in.nspecies; ++s) state_bytes += 32.0 * static_cast<double>(c->sp[s].np);
-  pl.stream_nt = state_bytes > (full ? c->nt_threshold_full : c->nt_threshold_half) ? 1 : 0;
+  pl.stream_nt = state_bytes > (full ? c->cfg.nt_threshold_full : c->cfg.nt_threshold_half) ? 1 : 0;
   if (const char *e = tuning_env("PIC1DP_NT_FORCE")) {  // tuning build only, read per launch (tools/ab_nt.py)
     const int f = std::atoi(e);
     if (f == 0) pl.stream_nt = 0;
@@ -267,8 +264,8 @@ static StepPlan plan_step(const pic1dp_ctx *c, bool full, bool diag, bool pred, 
   return pl;
 }
 
-static int carry_buffer(Species &S) {
-  if (!S.t2) HIP_TRY(hipMalloc(&S.t2, sizeof(double) * static_cast<size_t>(S.nalloc + 2)));
+static int carry_buffer(pic1dp_ctx *c, Species &S) {
+  if (!S.t2) HIP_TRY(c->mem.alloc(&S.t2, static_cast<size_t>(S.nalloc + 2)));
   return 0;
 }
 
@@ -283,10 +280,10 @@ static int wire_carry(pic1dp_ctx *c, Species &S, StepArgsDev &a, bool full, bool
     // (tools/ab_pipe_carry.sh): bump-on-tail with T = 1.3, T2 = 0.7, m = 1.1 8.9e10 -> 9.85e10
     // updates/s; two-stream2 (one division fewer per exp pair) 1.05e11 either way, so only
     // bump-on-tail carries.  PIC1DP_CARRY=0 switches it off, 2 also carries for two-stream2.
-    const bool carry2 = c->carry != 0 && c->in.deltaf && !S.sc.pow2 && !S.sc.one_exp &&
-                        (c->in.iptcldist == 3 || (c->carry == 2 && c->in.iptcldist == 2));
+    const bool carry2 = c->cfg.carry != 0 && c->in.deltaf && !S.sc.pow2 && !S.sc.one_exp &&
+                        (c->in.iptcldist == 3 || (c->cfg.carry == 2 && c->in.iptcldist == 2));
     if (!carry2) return 0;
-    if (int rc = carry_buffer(S)) return rc;
+    if (int rc = carry_buffer(c, S)) return rc;
     // the second kernel may only load what the first one stored for these very markers
     if (!full || S.t2_version == read_version) a.t2 = S.t2;
     if (!full) S.t2_version = c->state_version;
@@ -299,9 +296,9 @@ static int wire_carry(pic1dp_ctx *c, Species &S, StepArgsDev &a, bool full, bool
   // Maxwellian and two-stream1 evaluate it in one or two operations.
   // With the one-exp form of -f0'/f0 (device_math.hpp) an evaluation costs about what its 16 B of carry
   // traffic cost: measured (profiles/r03/experiments/ab_one_exp.log), PIC1DP_CARRY=1 / 0 insists either way.
-  const bool carry_one = c->carry < 0 ? (S.sc.one_exp ? kCarryOneExpDefault : true) : c->carry > 0;
+  const bool carry_one = c->cfg.carry < 0 ? (S.sc.one_exp ? kCarryOneExpDefault : true) : c->cfg.carry > 0;
   if (!(exp_bearing(c) && carry_one)) return 0;
-  if (int rc = carry_buffer(S)) return rc;
+  if (int rc = carry_buffer(c, S)) return rc;
   a.t2 = S.t2;
   a.t2_mode = S.t2_version == read_version ? 2 : 1;
   S.t2_version = c->state_version;
@@ -369,7 +366,7 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
   a.nt = pl.stream_nt;
   // the drawn chunk tail of every whole-step kernel: half a workgroup's chunks, all of them for k_step_full (two passes
   // per step at 1e8 markers: 0.913 -> 0.898 ms with 16/16 against 8/16, profiles/r05/experiments/ab_dyn_tail_other.log)
-  a.dyn_tail = (full && !pred) ? c->dyn_tail_full : c->dyn_tail;
+  a.dyn_tail = (full && !pred) ? c->cfg.dyn_tail_full : c->cfg.dyn_tail;
   a.fx = fx_args(c, s);
   LaunchCfg lc = step_launch(c, S.np, full);
   if (pred && c->fuse_args.on) {  // this launch's prologue solves the previous step's field (first species launched)
@@ -384,12 +381,12 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
   if (pred) {  // k_step_one: the full step + the prediction of the next first sub-step's charge
     a.tabA = c->d_tabA;
     a.tabB = c->d_tabB;
-    a.pred = c->pred_kind == 2 ? c->d_pred  // six sums, all species together (Z folded in)
+    a.pred = c->plan.pred_kind == 2 ? c->d_pred  // six sums, all species together (Z folded in)
                                : c->d_pred + static_cast<size_t>(s) * (1 + 2 * c->in.nmode) * c->in.nx;
     a.pred_nm = c->in.nmode;
-    sa.family = c->pred_kind == 2 ? (pl.priv ? StepFamily::PrivateSums : StepFamily::Sums) : StepFamily::Tiles;
+    sa.family = c->plan.pred_kind == 2 ? (pl.priv ? StepFamily::PrivateSums : StepFamily::Sums) : StepFamily::Tiles;
     a.fxb = S.fxb;
-    if (c->pred_kind == 2) {
+    if (c->plan.pred_kind == 2) {
       a.eh_re = c->eh_modes == 2 ? c->d_mode_h : c->fa.mode_re;
       a.eh_im = c->eh_modes == 2 ? c->d_mode_h + 1 : c->fa.mode_im;
     }
@@ -405,7 +402,7 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
     kb.wr = full ? 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0)) : 0.0;
     kb.carry = 0.0;
     if (a.t2) kb.carry = pred ? (a.t2_mode == 2 ? 16.0 : 8.0) : 8.0;  // k_step_one: 8 read (mode 2) + 8 written
-    std::snprintf(kb.name, sizeof kb.name, "%s%s%s", pred ? (c->pred_kind == 2 ? (pl.priv ? "k_step_one<sums>" : "k_step_sums") : "k_step_one")
+    std::snprintf(kb.name, sizeof kb.name, "%s%s%s", pred ? (c->plan.pred_kind == 2 ? (pl.priv ? "k_step_one<sums>" : "k_step_sums") : "k_step_one")
                                                           : (full ? (pl.diag ? "k_step_full<DIAG>" : "k_step_full") : "k_step_half"),
                   a.fx.acc ? "<EXACT>" : "", S.sc.one_exp && c->in.deltaf ? " (one-exp -f0'/f0)" : "");
     if (a.fused.on) std::strncat(kb.name, " + field solve", sizeof kb.name - std::strlen(kb.name) - 1);
@@ -427,7 +424,7 @@ static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const doub
   c->tail_done = 0;
   const StepPlan pl = plan_step(c, full, diag, pred, tail_ok);
   if (pl.pred && c->pred_version != 0)  // a prediction nobody used: the accumulators start from zero
-    HIP_TRY(hipMemsetAsync(c->d_pred, 0, sizeof(double) * pred_doubles(c), c->st));
+    HIP_TRY(hipMemsetAsync(c->d_pred, 0, sizeof(double) * c->plan.pred_set_doubles, c->st));
   if (pl.diag)
     if (int rc = diag_buffers(c)) return rc;
   for (int s = 0; s < c->in.nspecies; ++s)
@@ -481,7 +478,7 @@ static int pred_reduce(pic1dp_ctx *c) {
 static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = false) {
   c->pred_version = 0;  // consumed: the accumulators are zero again afterwards
   const bool multi = several_ranks(c);
-  if (c->pred_kind == 2) {
+  if (c->plan.pred_kind == 2) {
     if (f.chargeden == c->d_chargeden) c->cd_kept_mode_only = true;
     if (defer && !multi && dft_paths(c) && f.tab_lds)  // the sums' combination, chargeden and the solve in the
       return set_owed(c, Owed::PredSums);               // launch of the solve_field that follows
@@ -537,12 +534,11 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
   if (will_pack) {
     if (tail_done != 1) {  // the species sum and the packing are collect_charge's share of the step (src/pic1dp_interaction.F90:126-127)
       Span pk(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
-      HIP_TRY(launch_charge_pack(c->fa, c->d_pred, c->in.nmode, c->pred_kind, c->d_pack, c->st));
+      HIP_TRY(launch_charge_pack(c->fa, c->d_pred, c->in.nmode, c->plan.pred_kind, c->d_pack, c->st));
       if (int rc = pk.end()) return rc;
     }
     Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
-    ncclResult_t r = rccl().AllReduce(c->d_pack, c->d_pack, pack_doubles(c->in.nx, c->in.nmode, c->pred_kind), ncclDouble,
-                                      ncclSum, c->comm, c->st);
+    ncclResult_t r = rccl().AllReduce(c->d_pack, c->d_pack, c->plan.pack_doubles, ncclDouble, ncclSum, c->comm, c->st);
     if (r != ncclSuccess) return fail(PIC1DP_ERR_COMM, "ncclAllReduce: %s", rccl().GetErrorString(r));
     if (int rc = sp.end()) return rc;
   } else if (multi && !fused_xchg) {
@@ -555,10 +551,10 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
   // one-pass step on one rank or with the exchange: both fields (the new state's, and the next step's
   // half-step field from the prediction) in ONE launch
   if (c->fused_dirty >= 0) {  // the set the last fused launch read: no launch follows that would zero it
-    HIP_TRY(hipMemsetAsync(c->d_rho_all + static_cast<size_t>(c->fused_dirty) * c->rho_set_doubles, 0,
-                           sizeof(double) * c->rho_set_doubles, c->st));
-    HIP_TRY(hipMemsetAsync(c->d_pred_all + static_cast<size_t>(c->fused_dirty) * c->pred_set_doubles, 0,
-                           sizeof(double) * c->pred_set_doubles, c->st));
+    HIP_TRY(hipMemsetAsync(c->d_rho_all + static_cast<size_t>(c->fused_dirty) * c->plan.rho_set_doubles, 0,
+                           sizeof(double) * c->plan.rho_set_doubles, c->st));
+    HIP_TRY(hipMemsetAsync(c->d_pred_all + static_cast<size_t>(c->fused_dirty) * c->plan.pred_set_doubles, 0,
+                           sizeof(double) * c->plan.pred_set_doubles, c->st));
     c->fused_dirty = -1;
   }
   const bool pair = pred && c->pred_version == c->state_version && (!multi || fused_xchg || will_pack) &&
@@ -567,7 +563,7 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
     // (cd_h: the tiles' scratch; with the six sums the kept mode's content of the half-step charge density -- what the call
     // sites adopt into field_chargeden when the host's next push(1), collect_charge, solve_field are served from this solve,
     // which they are after a step() as after the call sites' own pair: round 6's fuzz campaign found the stale copy)
-    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->pred_kind, c->pred_tab, 0};
+    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->plan.pred_kind, c->pred_tab, 0};
     XchgArgs x1;
     const XchgArgs *xchg = nullptr;
     if (will_pack) {  // both charge sums of the step came in ONE all-reduce (pack_doubles)
@@ -618,10 +614,10 @@ static int step_phase(pic1dp_ctx *c, bool full, double *Eout, bool record, bool 
     fs.E_h = c->d_Eh;
     fs.mode_h = c->d_mode_h;
     const int read = c->acc_idx, dirty = c->fused_dirty;
-    fs.zero_rho = c->d_rho_all + static_cast<size_t>(dirty >= 0 ? dirty : read) * c->rho_set_doubles;
-    fs.zero_rho_n = dirty >= 0 ? static_cast<int64_t>(c->rho_set_doubles) : 0;
-    fs.zero_pred = dirty >= 0 ? c->d_pred_all + static_cast<size_t>(dirty) * c->pred_set_doubles
-                              : c->d_pred_all + static_cast<size_t>((read + 2) % 3) * c->pred_set_doubles;  // (zero already)
+    fs.zero_rho = c->d_rho_all + static_cast<size_t>(dirty >= 0 ? dirty : read) * c->plan.rho_set_doubles;
+    fs.zero_rho_n = dirty >= 0 ? static_cast<int64_t>(c->plan.rho_set_doubles) : 0;
+    fs.zero_pred = dirty >= 0 ? c->d_pred_all + static_cast<size_t>(dirty) * c->plan.pred_set_doubles
+                              : c->d_pred_all + static_cast<size_t>((read + 2) % 3) * c->plan.pred_set_doubles;  // (zero already)
     use_accumulators(c, (read + 1) % 3);  // zero: nobody has deposited into it since it was last zeroed
     c->fused_dirty = read;
     c->fused_pending = false;
@@ -756,7 +752,7 @@ int pic1dp_host::set_call_state(pic1dp_ctx *c, Seq seq, Owed owed) {
   if (seq >= Seq::N || owed >= Owed::N || !kCallStateLegal[static_cast<int>(seq)][static_cast<int>(owed)])
     return fail(PIC1DP_ERR_STATE, "internal: call-site state (%d, %d) cannot occur (from (%d, %d))", static_cast<int>(seq),
                 static_cast<int>(owed), static_cast<int>(c->seq), static_cast<int>(c->owed));
-  if (seq != Seq::Clean && !c->lazy_calls) return fail(PIC1DP_ERR_STATE, "internal: a push noted by eager call sites");
+  if (seq != Seq::Clean && !c->cfg.lazy_calls) return fail(PIC1DP_ERR_STATE, "internal: a push noted by eager call sites");
   c->seq = seq;
   c->owed = owed;
   return 0;
@@ -797,7 +793,7 @@ int pic1dp_host::require_loaded(pic1dp_ctx *c) {
 // path itself are the whole-step path's (tests: test_lazy_call_sites_*).
 // ---------------------------------------------------------------------------
 static bool lazy_ok(const pic1dp_ctx *c) {
-  return c->lazy_calls && step_recompute_ok(c) && !optimize_due_any(c);
+  return c->cfg.lazy_calls && step_recompute_ok(c) && !optimize_due_any(c);
 }
 
 // wrap of x stored back, as the deposit of collect_charge does, charge discarded
@@ -910,7 +906,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   // after a noted push(1) whose half-step FIELD the previous solve_field has already solved (the pair, below): nothing
   // to launch at all
   // (the six sums of one kept mode: with the tiles collect_charge owes the host the whole half-step charge density)
-  if (c->seq == Seq::Push1 && c->call_pair && c->lazy_calls && !several_ranks(c) && predict_capable(c) &&
+  if (c->seq == Seq::Push1 && c->cfg.call_pair && c->cfg.lazy_calls && !several_ranks(c) && predict_capable(c) &&
       six_sums_one_mode(c) && c->eh_version == c->state_version && c->eh_field_version == c->field_version) {
     c->cd_kept_mode_only = true;  // (field_chargeden is not the half step's: asking for it rebuilds, get_field)
     c->adopt_cd_version = c->cd_version;
@@ -920,7 +916,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
     if (int rc = save_step_start_field(c)) return rc;
     if (int rc = set_call_state(c, Seq::Half, Owed::Nothing)) return rc;   // (a stale AdoptHalfField ends here)
     Span tm(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
-    if (int rc = pred_to_chargeden(c, c->fa, c->lazy_calls != 0)) return rc;
+    if (int rc = pred_to_chargeden(c, c->fa, c->cfg.lazy_calls != 0)) return rc;
     return tm.end();
   }
   c->cd_kept_mode_only = false;  // a deposit follows: the whole vector again
@@ -937,7 +933,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   const bool multi = fp64_rank_sum(c);
   if (multi)
     if (int rc = reduce_charge(c)) return rc;
-  if (c->lazy_calls) {  // the species sum (one rank) and the scaling: in the launch of the solve_field that follows
+  if (c->cfg.lazy_calls) {  // the species sum (one rank) and the scaling: in the launch of the solve_field that follows
     if (int rc = set_owed(c, multi ? Owed::Scale : Owed::SumScale)) return rc;
   } else {
     HIP_TRY(launch_chargeden(c->fa, !multi, c->st));
@@ -973,8 +969,13 @@ int pic1dp_hip_set_field_transform(pic1dp_ctx *c, int32_t transform) {
     return fail(PIC1DP_ERR_ARG, "the FFT field transform needs nx = 2^a 3^b 5^c, even up to %d or odd up to %d (nx = %d)", FFT_MAX_NX,
                 FFT_MAX_ODD_NX, c->in.nx);
   HIP_TRY(hipSetDevice(c->device));
-  if (transform == 1 && !c->fft.tw)
-    HIP_TRY(fft_plan_upload(c->in.nx, c->in.modes, c->in.nmode, c->fft, &c->d_fft_tw, &c->d_fft_idx));
+  if (transform == 1 && !c->fft.tw) {
+    const bool had_tw = c->d_fft_tw != nullptr, had_idx = c->d_fft_idx != nullptr;
+    const hipError_t e = fft_plan_upload(c->in.nx, c->in.modes, c->in.nmode, c->fft, &c->d_fft_tw, &c->d_fft_idx);
+    if (!had_tw) c->mem.adopt(c->d_fft_tw);  // (the plan builder allocates what is missing: the context owns it from here)
+    if (!had_idx) c->mem.adopt(c->d_fft_idx);
+    HIP_TRY(e);
+  }
   if (c->owed == Owed::AdoptHalfField && transform != c->field_transform) {  // a half-step field of the OTHER transform waits
     if (int rc = rebuild_half_step_chargeden(c)) return rc;                // to be adopted: the half-step charge is deposited
     if (int rc = set_owed(c, Owed::Nothing)) return rc;                    // for real instead
@@ -1005,9 +1006,9 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   // One rank, behind the collect_charge of push(2) whose kernel has predicted the next half-step charge: BOTH fields in
   // one launch, as pic1dp_hip_step solves them -- the next step's push(1), collect_charge, solve_field then launch nothing
   // and a time step through the three call sites is two launches (round 5; three and a copy before)
-  if (pending == Owed::SumScale && c->call_pair && c->lazy_calls && dft_paths(c) && c->seq == Seq::Clean && pred_usable(c) &&
+  if (pending == Owed::SumScale && c->cfg.call_pair && c->cfg.lazy_calls && dft_paths(c) && c->seq == Seq::Clean && pred_usable(c) &&
       six_sums_one_mode(c)) {
-    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->pred_kind, c->pred_tab, 0};
+    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->plan.pred_kind, c->pred_tab, 0};
     HIP_TRY(launch_field_solve_pair(f, pa, nullptr, c->st));
     pair_solved(c);
     return tm.end();
@@ -1054,7 +1055,7 @@ int pic1dp_hip_set_step_mode(pic1dp_ctx *c, int32_t mode) {
 int pic1dp_hip_predict_kind(pic1dp_ctx *c, int32_t *kind) {
   CHECK_CTX(c);
   if (!kind) return fail(PIC1DP_ERR_ARG, "null argument");
-  *kind = predict_capable(c) ? c->pred_kind : 0;
+  *kind = predict_capable(c) ? c->plan.pred_kind : 0;
   return 0;
 }
 
@@ -1112,7 +1113,7 @@ int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
   if (c->seq == Seq::Push1 && pred_usable(c)) {  // predicted by the previous step's kernel: no marker pass
     if (int rc = save_step_start_field(c)) return rc;
     if (int rc = set_seq(c, Seq::Half)) return rc;
-    if (c->pred_kind == 2) {  // the six sums in charge2[0..5], zeros behind: the host's sum over ranks sums them
+    if (c->plan.pred_kind == 2) {  // the six sums in charge2[0..5], zeros behind: the host's sum over ranks sums them
       HIP_TRY(launch_pred_to_charge(c->fa, c->d_pred, c->st));
       c->charge_pending_pred = true;
     } else {
@@ -1145,7 +1146,7 @@ int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
     HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, nullptr, c->d_charge, c->st));
     return 0;
   }
-  if (c->lazy_calls) return set_owed(c, Owed::Scale);
+  if (c->cfg.lazy_calls) return set_owed(c, Owed::Scale);
   HIP_TRY(launch_chargeden(c->fa, false, c->st));
   return 0;
 }
@@ -1179,7 +1180,7 @@ int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *c, const int64_t *limbs) {
   c->charge_pending = false;
   c->cd_version++;
   HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st));
-  if (c->lazy_calls) return set_owed(c, Owed::SumScale);
+  if (c->cfg.lazy_calls) return set_owed(c, Owed::SumScale);
   HIP_TRY(launch_chargeden(c->fa, true, c->st));
   return 0;
 }
@@ -1204,18 +1205,18 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   // checked here cannot be violated any more.  What is left relates the state to the CONTEXT it is held in:
   const bool one_rank = !several_ranks(c);
   INVARIANT(kCallStateLegal[static_cast<int>(c->seq)][static_cast<int>(c->owed)]);
-  INVARIANT(c->seq == Seq::Clean || (c->lazy_calls && c->loaded));    // a push is only noted by the lazy call sites
-  INVARIANT(c->owed == Owed::Nothing || c->lazy_calls);
+  INVARIANT(c->seq == Seq::Clean || (c->cfg.lazy_calls && c->loaded));    // a push is only noted by the lazy call sites
+  INVARIANT(c->owed == Owed::Nothing || c->cfg.lazy_calls);
   INVARIANT(c->owed < Owed::SumScale || one_rank || c->charge_sum == 1);  // species sum / prediction left to solve_field: one rank
                                                                       // (or exact sums, already summed over ranks)
   // kind 1 of the charge sum: no prediction pending, no tiles, sums or half-step field owed
   INVARIANT(c->charge_sum == 0 || c->pred_version == 0);
   INVARIANT(c->charge_sum == 0 || (c->owed != Owed::PredTiles && c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField &&
                                    !pair_of(c->seq)));
-  INVARIANT(c->owed != Owed::PredTiles || c->pred_kind == 1);
+  INVARIANT(c->owed != Owed::PredTiles || c->plan.pred_kind == 1);
   INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || six_sums_one_mode(c));
-  INVARIANT(!pair_of(c->seq) || (c->call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
-  INVARIANT(!c->cd_kept_mode_only || c->pred_kind == 2);
+  INVARIANT(!pair_of(c->seq) || (c->cfg.call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
+  INVARIANT(!c->cd_kept_mode_only || c->plan.pred_kind == 2);
   // an owed adoption is current: made for the field_chargeden the eager calls hold now (and, by kCallStateLegal, while the
   // markers still stand at the half step)
   INVARIANT(c->owed != Owed::AdoptHalfField || c->adopt_cd_version == c->cd_version);
@@ -1255,18 +1256,18 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
       if (v[off + i] != 0.0) return true;  // (NaN != 0: a poisoned accumulator counts)
     return false;
   };
-  std::vector<double> h(3 * c->rho_set_doubles);
+  std::vector<double> h(3 * c->plan.rho_set_doubles);
   HIP_TRY(hipMemcpy(h.data(), c->d_rho_all, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
   for (int k = 0; k < 3; ++k) {
-    const bool nz = nonzero(h, k * c->rho_set_doubles, c->rho_set_doubles);
+    const bool nz = nonzero(h, k * c->plan.rho_set_doubles, c->plan.rho_set_doubles);
     if (k != c->acc_idx) INVARIANT(!nz && "a species accumulator set that is not the current one holds deposits");
     else if (c->owed != Owed::SumScale && c->owed != Owed::PredTiles && !c->charge_pending) INVARIANT(!nz && "deposits nobody is going to sum");
   }
-  if (c->d_pred_all && c->pred_set_doubles) {
-    h.assign(3 * c->pred_set_doubles, 0.0);
+  if (c->d_pred_all && c->plan.pred_set_doubles) {
+    h.assign(3 * c->plan.pred_set_doubles, 0.0);
     HIP_TRY(hipMemcpy(h.data(), c->d_pred_all, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; ++k) {
-      const bool nz = nonzero(h, k * c->pred_set_doubles, c->pred_set_doubles);
+      const bool nz = nonzero(h, k * c->plan.pred_set_doubles, c->plan.pred_set_doubles);
       if (k != c->acc_idx) INVARIANT(!nz && "a prediction accumulator set that is not the current one holds sums");
       else if (c->pred_version == 0 && c->owed != Owed::PredTiles && c->owed != Owed::PredSums && !c->charge_pending)
         INVARIANT(!nz && "prediction sums that belong to no state");

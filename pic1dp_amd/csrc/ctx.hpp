@@ -1,6 +1,9 @@
 // ctx.hpp -- what the translation units behind the C ABI share: the context (one process = one GPU = one HIP stream),
 // the error convention, the event spans, and the internal entry points one unit offers the others.
-//   capi.cpp           context, input, transfers, field access, timers and knobs
+//   capi.cpp           context (create: settings -> plan -> tables -> allocate -> self-test), input, transfers, field access, timers and knobs
+//   settings.cpp       what a context takes from the environment, read once (settings.hpp: pic1dp_ctx::cfg; no HIP call)
+//   context_plan.cpp   create()'s decisions as a pure function, and the mode tables (context_plan.hpp: pic1dp_ctx::plan; no HIP call)
+//   device_mem.hpp     the one owner of a context's device and pinned memory (pic1dp_ctx::mem)
 //   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
@@ -20,12 +23,15 @@
 #include <vector>
 
 #include "../../include/pic1dp_hip.h"
+#include "context_plan.hpp"
+#include "device_mem.hpp"
 #include "kernels.hpp"
 #include "launch_policy.hpp"
 #include "loader.hpp"
 #include "multirand.hpp"
 #include "optimize.hpp"
 #include "rccl_dyn.hpp"
+#include "settings.hpp"
 
 using namespace pic1dp;
 
@@ -150,13 +156,14 @@ using namespace pic1dp_host;
 struct pic1dp_ctx {
   pic1dp_input in{};
   pic1dp_layout lay{};
+  Settings cfg{};      // the environment as create() found it: constants of the context
+  ContextPlan plan{};  // what create() derived from input, layout and settings: constants too (blocks, one-pass kind, sizes)
+  DeviceMem mem;       // owns every device and pinned buffer below (allocated at create() or lazily; released by destroy())
   int device = 0, num_cu = 256;
   hipStream_t st = nullptr;
   int cur = 0;  // which particle set is particle_x/v/w right now
   std::vector<Species> sp;
-  int blk0 = 0, nblk = 1;  // owned reference blocks [blk0, blk0+nblk)
-  std::vector<int64_t> blk_alloc;                 // [nblk] allocated slots of each owned block
-  std::vector<std::vector<int64_t>> blk_np;       // [nspecies][nblk] valid markers
+  std::vector<std::vector<int64_t>> blk_np;       // [nspecies][nblk] valid markers of the owned blocks now (plan.blk_np: as loaded)
   std::vector<Multirand> blk_rng;                 // [nblk] generators as particle_load left them
   bool rng_ready = false;
   int imerge = 0, iremove = 0, isplit = 0;        // particle_imerge / _iremove / _isplit
@@ -168,9 +175,7 @@ struct pic1dp_ctx {
   // Species::rho / fa.rho_sp / d_pred always name the set the marker kernels deposit into NOW (acc_idx); all sets are
   // zero whenever no fused launch sequence is under way
   double *d_rho_all = nullptr, *d_pred_all = nullptr;
-  size_t rho_set_doubles = 0, pred_set_doubles = 0;
   int acc_idx = 0;
-  int fuse_solve = 1;           // PIC1DP_FUSE_SOLVE=0: the field solve always in a launch of its own; 2: fused whatever the grid
   bool fused_pending = false;   // step(): the last marker launch left the solve of its step to the next launch's prologue
   int fused_dirty = -1;         // accumulator set the last fused launch read (still holding that step's deposits), or -1
   FusedSolve fuse_args{};       // what the next marker launch's prologue has to solve (on = 1), consumed by step_particles
@@ -179,25 +184,17 @@ struct pic1dp_ctx {
   // one pass per step (kernels_step.hip k_step_one): mode tables with E = sum re_m A_m + im_m B_m, the
   // prediction accumulators [nspecies][1 + 2 nm][nx], the combined half-step charge density
   double *d_tabA = nullptr, *d_tabB = nullptr, *d_pred = nullptr, *d_cd_h = nullptr, *d_mode_h = nullptr;
-  int osub_req = 0;                // PIC1DP_OSUB: grid size of the marker kernels in units of the resident one (0: auto)
-  int dyn_tail_full = 16;          // ... of k_step_full (PIC1DP_DYN_TAIL sets both, PIC1DP_DYN_TAIL_FULL this one)
-  int dyn_tail = 8;                // PIC1DP_DYN_TAIL: sixteenths of a workgroup's 64-pair chunks its waves DRAW from an LDS counter (every whole-step kernel)
-  int pred_kind = 0;               // 0 no one-pass step here, 1 prediction tiles (k_step_one), 2 six sums (k_step_sums)
-  int pred_private = 0;            // pred_kind 2 and E0, Eh, the table tiles and the private sums of two workgroups fit a
-                                   // CU's LDS: the sums are taken by k_step_one<PRIV> (thread-private LDS slots)
   PredTab pred_tab{};              // kind 2: sums / Gram matrix of the kept mode's tables (host, libm)
   int eh_modes = 0;                // kind 2: where the kept mode of the Eh about to be used lies: 0 nowhere, 1 fa.mode_*, 2 d_mode_h
   bool charge_pending_pred = false;  // kind 2: charge_local handed out the six sums, not a charge vector
   double *d_Ehn = nullptr;         // half-step field predicted for the NEXT step (d_Eh stays the last step's)
   double *d_pack = nullptr;        // [2 + 2 nmode][nx] one all-reduce per one-pass step (RCCL path)
   // several ranks, six-sum prediction: the marker launch's last workgroup packs / posts this rank's charge (kernels.hpp
-  // StepTail) instead of a launch of its own in front of the sum over ranks.  PIC1DP_TAIL=0: the separate launch
+  // StepTail) instead of a launch of its own in front of the sum over ranks.  cfg.tail_on 0: the separate launch
   unsigned int *d_ticket = nullptr;  // the tail's arrival counter (zero between launches)
-  int tail_on = 1;
   int tail_done = 0;                 // what the last marker launch's tail did: 0 nothing, 1 packed into d_pack, 2 posted (tail_x)
   XchgArgs tail_x{};                 // tail_done == 2: the exchange the field launch has to finish
   int64_t tail_launches = 0;         // marker launches that carried a tail so far (kernel_stats 10)
-  int predict = 1;                 // PIC1DP_PREDICT=0: always two passes per step
   uint64_t pred_version = 0;       // state_version the accumulators in d_pred belong to (0: none)
   uint64_t eh_version = 0;         // state_version d_Eh has been predicted for (step() path)
   uint64_t field_version = 1, eh_field_version = 0, modes_field_version = 0;  // who wrote d_E last
@@ -205,16 +202,14 @@ struct pic1dp_ctx {
   double *d_Eh = nullptr;  // field after the first sub-step of the last whole-step call
   // The reference's three call sites at whole-step cost (see "lazy call sites"
   // below): a push is only noted; the collect_charge that follows runs the
-  // whole-step kernel instead of push + deposit.
-  int lazy_calls = 1;            // PIC1DP_LAZY_CALLS=0: every call launches its own kernel at once
+  // whole-step kernel instead of push + deposit (cfg.lazy_calls).
   // Call sites, one rank: the solve_field that follows the collect_charge of push(2) solves BOTH fields in one launch
   // (the pair kernels of pic1dp_hip_step) -- the new state's into field_electric, the next step's half-step field from the
   // prediction into d_Ehn / d_mode_h.  The next push(1) / collect_charge / solve_field then launch nothing: the
   // "Pair" states of Seq say that the half-step field lies in d_Ehn (field_electric still holds the step-start field, d_E0 is
   // not filled), the "Solved" ones that the host has called solve_field for it -- what it may look at from then on is the
   // half-step field, so every inspection first settles (capi_step.cpp settle_half_pair: copies, memory as eager calls leave it).
-  // PIC1DP_CALL_PAIR=0: the three launches per step of rounds 2-4.
-  int call_pair = 1;
+  // cfg.call_pair 0: the three launches per step of rounds 2-4.
   int64_t call_pair_skips = 0;   // solve_field calls of a half step served without a launch (kernel_stats 11)
   // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step): materialize_cd()
   // before anything else looks at charge, chargeden or the accumulators.
@@ -236,8 +231,6 @@ struct pic1dp_ctx {
   bool e_step_start = false;
   double *d_E0 = nullptr;        // field the noted push(1) saw
   double *d_rho_dummy = nullptr; // accumulator of a wrap-only deposit
-  int carry = -1;          // whole-step kernels carry -f0'/f0 between them: -1 where measured to pay, 0 never
-                           // (PIC1DP_CARRY=0), 1 wherever -f0'/f0 bears an exp, 2 also two-stream2 between k_step_half / _full
   int step_mode = 0;       // 0 auto (recompute path when the LDS allows), 1 two fused sub-steps
   int field_solver = 0;    // 0 the reference's mode-filter DFT solve, 1 finite-difference tridiagonal (opt-in)
   // how the mode-filter solve computes its DFT (pic1dp_hip_set_field_transform; kernels_fft.hip): 0 the dense tables, the
@@ -247,28 +240,12 @@ struct pic1dp_ctx {
   FftArgs fft{};
   double *d_fft_tw = nullptr;
   int *d_fft_idx = nullptr;
-  // marker state (bytes) above which k_step_half / k_step_full stream non-temporally
-  // The two kernels leave the caches to each other, so the pairs were compared inside
-  // one process on the same arrays (tools/ab_nt.py, nx = 1024, half + full in ms):
-  //   markers   plain/plain   nt/nt    half nt, full plain   half plain, full nt
-  //   6.4e6       0.102*      0.114         0.105                 0.106
-  //   1e7         0.159       0.169         0.158*                0.158*
-  //   2e7         0.372       0.332         0.326                 0.319*
-  //   3e7         0.539       0.497         0.492                 0.483*
-  //   5e7         0.886       0.829*        0.835                 0.828*
-  //   1e8         1.745       1.657*        1.676                 1.678
-  // => both plain below 288 MiB of marker state, the full kernel non-temporal above
-  //    it, the half kernel only above 2 GiB
-  double nt_threshold_half = 2048.0 * 1048576.0, nt_threshold_full = 288.0 * 1048576.0;
   int64_t hist_count = 0;
   // marker diagnostics of output_all: one fused pass per species (histograms +
   // kinetic sums), kept until the markers change
   uint64_t state_version = 1;              // bumped by everything that writes marker arrays
   std::vector<DiagSpecies> diag;           // [nspecies]
   double *d_diag_part = nullptr;           // [nspecies][diag_max_blocks][DIAG_PART] per-workgroup partial sums of the pass
-  // (PIC1DP_DIAG_FX=0: the histograms always as double sums)
-  int diag_fx = 1;
-  double diag_fx_margin_w = 16.0;   // bound on |w| = this x the last pass's max |w| (PIC1DP_DIAG_FX_MARGIN: tests)
   int64_t diag_fx_passes = 0, diag_fx_repeats = 0;   // fixed-point passes so far; passes repeated in doubles after an overflow
   int fuse_output = 0;                     // take the diagnostics inside k_step_full on steps output_all follows
   double *d_rec = nullptr;                 // output_all's record gathered on the device (kernels.hpp PackArgs), grow-only
@@ -452,7 +429,6 @@ void optimize_release(pic1dp_ctx *c);     // the optimisation events' workers (s
 FxArgs fx_args(const pic1dp_ctx *c, int isp);   // the marker kernels' exact accumulators of species isp (acc null in kind 0)
 int fx_settle(pic1dp_ctx *c);             // deposits -> summed over ranks -> the species accumulators (copy 0)
 int fx_check(pic1dp_ctx *c);              // PIC1DP_ERR_ARG once per batch of contributions beyond 2^62 quanta
-void fx_release(pic1dp_ctx *c);
 // ---- capi_diag.cpp ----
 int diag_buffers(pic1dp_ctx *c);
 int diag_max_blocks(const pic1dp_ctx *c);
@@ -463,6 +439,5 @@ void diag_note_pass(pic1dp_ctx *c, int isp, int blocks, bool fixed, bool launche
 const DistGeom &dist_geom(pic1dp_ctx *c);
 int pinned(pic1dp_ctx *c, size_t ndoubles, double **out);   // the context's pinned staging with room for ndoubles
 size_t dist_len(const pic1dp_input &in);
-void dfx_release(pic1dp_ctx *c);
 
 }  // namespace pic1dp_host

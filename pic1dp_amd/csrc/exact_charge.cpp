@@ -87,13 +87,6 @@ int fx_check(pic1dp_ctx *c) {
   return 0;
 }
 
-void fx_release(pic1dp_ctx *c) {
-  (void)hipFree(c->d_fx);
-  c->d_fx = nullptr;
-  if (c->h_fx_ovf) (void)hipHostFree(c->h_fx_ovf);
-  c->h_fx_ovf = nullptr;
-}
-
 }  // namespace pic1dp_host
 
 extern "C" {
@@ -131,18 +124,18 @@ int pic1dp_hip_set_charge_sum(pic1dp_ctx *c, int32_t kind) {
       c->fx_inv_q[s] = std::ldexp(1.0, -e);
     }
     if (!c->d_fx) {
-      const size_t bytes = sizeof(long long) * 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
-      HIP_TRY(hipMalloc(&c->d_fx, bytes));
-      HIP_TRY(hipMemsetAsync(c->d_fx, 0, bytes, c->st));
+      const size_t words = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
+      HIP_TRY(c->mem.alloc(&c->d_fx, words));
+      HIP_TRY(hipMemsetAsync(c->d_fx, 0, sizeof(long long) * words, c->st));
     }
     if (!c->h_fx_ovf) {
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_fx_ovf), 8 * sizeof(unsigned long long), hipHostMallocDefault));
+      HIP_TRY(c->mem.alloc_pinned(&c->h_fx_ovf, 8));
       std::memset(c->h_fx_ovf, 0, 8 * sizeof(unsigned long long));
       std::memset(c->fx_ovf_seen, 0, sizeof c->fx_ovf_seen);
     }
     // a prediction the last one-pass step left: kind 1 does not use it (two passes per step), its sums go
     if (c->pred_version != 0 && c->d_pred_all)
-      HIP_TRY(hipMemsetAsync(c->d_pred_all, 0, sizeof(double) * 3 * c->pred_set_doubles, c->st));
+      HIP_TRY(hipMemsetAsync(c->d_pred_all, 0, sizeof(double) * 3 * c->plan.pred_set_doubles, c->st));
     c->pred_version = 0;
   }
   c->charge_sum = kind;

@@ -1,9 +1,11 @@
-// policy_probe.cpp -- the launch policy (launch_policy.hpp) and the LDS layouts of the field kernels (field_lds.hpp) behind
-// the C ABI of the probe library, for the host tests that pin every shape (tests/test_launch_policy_host.py,
-// tests/test_field_lds_host.py, tests/test_diag_launch_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
+// decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
+// them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
+// tests/test_context_plan_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 
 #include "../../include/pic1dp_probe.h"
+#include "context_plan.hpp"
 #include "field_lds.hpp"
 #include "launch_policy.hpp"
 
@@ -61,5 +63,40 @@ extern "C" int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t 
   DistScale fx{};
   out[0] = make_dist_scale(np, blocks, deltaf != 0, bound_p, bound_w, &fx, threads);
   for (int k = 0; k < 3; ++k) out[1 + k] = fx.sc[k] > 0.0 ? std::ilogb(fx.sc[k]) : 0;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_context_plan(const pic1dp_input *in, const pic1dp_layout *lay, int32_t pred_kind_req,
+                                              int32_t gcopies_req, int32_t one_rank_order, int64_t *out, int64_t cap,
+                                              double sc[2]) {
+  if (!in || !lay || !out || !sc || in->nspecies < 1 || in->nspecies > PIC1DP_MAX_SPECIES || lay->nranks < 1) return 1;
+  Settings cfg;
+  cfg.pred_kind_req = pred_kind_req;
+  cfg.gcopies_req = accepted_gcopies(gcopies_req);  // (as settings_from_env takes it)
+  cfg.field_one_rank_order = one_rank_order;
+  const ContextPlan p = plan_context(*in, *lay, cfg);
+  const int ns = in->nspecies;
+  if (cap < 16 + ns + static_cast<int64_t>(p.nblk) * (1 + ns)) return 1;
+  const int64_t head[16] = {p.npe, p.nblk, p.blk0, p.nalloc, p.imerge, p.iremove, p.isplit, p.gcopies, p.gstride,
+                            static_cast<int64_t>(p.rho_set_doubles), p.pred_kind, p.pred_private,
+                            static_cast<int64_t>(p.pred_set_doubles), static_cast<int64_t>(p.pack_doubles), p.tab_lds, p.field_npe};
+  int64_t *o = out;
+  for (int64_t v : head) *o++ = v;
+  for (int s = 0; s < ns; ++s) *o++ = p.np[s];
+  for (int b = 0; b < p.nblk; ++b) *o++ = p.blk_alloc[b];
+  for (int s = 0; s < ns; ++s)
+    for (int b = 0; b < p.nblk; ++b) *o++ = p.blk_np[s][b];
+  sc[0] = p.sc_re, sc[1] = p.sc_im;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]) {
+  if (!iv || !dv) return 1;
+  const Settings s = settings_from_env();
+  const int32_t v[15] = {s.fuse_solve, s.tail_on, s.call_pair, s.lazy_calls, s.predict, s.carry, s.osub_req, s.dyn_tail,
+                         s.dyn_tail_full, s.diag_fx, s.pred_kind_req, s.chain_mfma_req, s.gcopies_req, s.field_one_rank_order,
+                         s.chain_selftest_verbose};
+  for (int i = 0; i < 15; ++i) iv[i] = v[i];
+  dv[0] = s.nt_threshold_half, dv[1] = s.nt_threshold_full, dv[2] = s.diag_fx_margin_w;
   return 0;
 }

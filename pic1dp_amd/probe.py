@@ -52,7 +52,14 @@ SIGNATURES = {
     "pic1dp_probe_host_field_lds": [C.c_int32] * 7 + [_I64],
     "pic1dp_probe_host_diag_launch": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
+    "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
+    "pic1dp_probe_host_settings": [_I32, _D],
 }
+PLAN_FIELDS = ("npe", "nblk", "blk0", "nalloc", "imerge", "iremove", "isplit", "gcopies", "gstride", "rho_set_doubles", "pred_kind",
+               "pred_private", "pred_set_doubles", "pack_doubles", "tab_lds", "field_npe")
+SETTINGS_INTS = ("fuse_solve", "tail_on", "call_pair", "lazy_calls", "predict", "carry", "osub_req", "dyn_tail", "dyn_tail_full",
+                 "diag_fx", "pred_kind_req", "chain_mfma_req", "gcopies_req", "field_one_rank_order", "chain_selftest_verbose")
+SETTINGS_DOUBLES = ("nt_threshold_half", "nt_threshold_full", "diag_fx_margin_w")
 
 _lib = None
 
@@ -219,3 +226,32 @@ def host_dist_scale(np_, blocks, deltaf, bound_p, bound_w, threads=1024):
     if load().pic1dp_probe_host_dist_scale(int(np_), blocks, deltaf, bound_p, bound_w, threads, out) != 0:
         raise ValueError("pic1dp_probe_host_dist_scale")
     return tuple(out)
+
+
+def host_context_plan(inp, nranks=1, npe=0, rank=0, pred_kind_req=0, gcopies_req=0, one_rank_order=0):
+    """what pic1dp_hip_create would decide before its first allocation (csrc/context_plan.hpp plan_context), on the host, as
+    a dict: PLAN_FIELDS, np [nspecies], blk_alloc [nblk], blk_np [nspecies][nblk], sc_re, sc_im; inp: a pic1dp_amd Input"""
+    from ._lib import Layout
+    lay = Layout(rank, nranks, npe, -1)
+    ns, nblk = inp.nspecies, (npe if npe > 0 else nranks) // nranks
+    cap = len(PLAN_FIELDS) + ns + nblk * (1 + ns)
+    out, sc = (C.c_int64 * cap)(), (C.c_double * 2)()
+    if load().pic1dp_probe_host_context_plan(C.addressof(inp), C.addressof(lay), pred_kind_req, gcopies_req, one_rank_order,
+                                             out, cap, sc) != 0:
+        raise ValueError("pic1dp_probe_host_context_plan: bad argument")
+    v = list(out)
+    plan = dict(zip(PLAN_FIELDS, v))
+    k = len(PLAN_FIELDS)
+    plan["np"] = v[k:k + ns]
+    plan["blk_alloc"] = v[k + ns:k + ns + nblk]
+    plan["blk_np"] = [v[k + ns + nblk * (1 + s):k + ns + nblk * (2 + s)] for s in range(ns)]
+    plan["sc_re"], plan["sc_im"] = sc[0], sc[1]
+    return plan
+
+
+def host_settings():
+    """the settings a context created now would take from the environment (csrc/settings.hpp), as a dict"""
+    iv, dv = (C.c_int32 * len(SETTINGS_INTS))(), (C.c_double * len(SETTINGS_DOUBLES))()
+    if load().pic1dp_probe_host_settings(iv, dv) != 0:
+        raise ValueError("pic1dp_probe_host_settings")
+    return dict(list(zip(SETTINGS_INTS, iv)) + list(zip(SETTINGS_DOUBLES, dv)))
