@@ -525,6 +525,68 @@ int pic1dp_hip_diag_local_exact(pic1dp_ctx *ctx, int32_t ispecies, int64_t *limb
 int pic1dp_hip_diag_convert_exact(pic1dp_ctx *ctx, int32_t ispecies, const int64_t *limbs, double sums[3], double *dist);
 int pic1dp_hip_diag_convert(const pic1dp_input *in, int32_t ispecies, const int64_t *limbs, double sums[3], double *dist);
 
+/* ---- state digest, checkpoint and restart (the file format: INTEGRATION.md 7) -----------------
+ * THE DIGEST.  For species s and array k (0 x, 1 v, 2 w, 3 p of the current particle set) take every slot i in
+ * [0, nalloc_s) -- the tail slots beyond np included; i is the logical index, as particles_download orders the
+ * slots, not the offset in the tiled storage -- and let u be the 64 bits of the double:
+ *     z = u + (i + 1) * 0x9E3779B97F4A7C15         (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31)
+ *     D[s][k] = sum over i of z                    (mod 2^64)
+ * An integer sum: its order does not matter.  It depends on position (swapping two different markers changes it)
+ * and on every bit (+0 and -0 differ, and so do NaN payloads).
+ * state_digest: out[nspecies][4] = D of the markers on the device, in one streaming pass per species (32 B read
+ *   per slot).  A noted push is put into memory first, exactly as pic1dp_hip_particles_download does; between time
+ *   steps it launches the digest kernel only, waits, and changes nothing: the one-pass prediction and the cached
+ *   diagnostics survive.
+ * host_digest: the same sum over a host array of n doubles, *out = D (no device, no context). */
+int pic1dp_hip_state_digest(pic1dp_ctx *ctx, uint64_t *out);
+int pic1dp_hip_host_digest(const double *a, int64_t n, uint64_t *out);
+
+/* what pic1dp_hip_checkpoint_info reports of a file besides the input */
+typedef struct pic1dp_checkpoint_info {
+  int32_t format_version;
+  int32_t nspecies;
+  int64_t file_bytes;
+  int64_t input_size;          /* sizeof(pic1dp_input) of the writer */
+  pic1dp_layout layout;        /* rank, nranks, npe of the writing context; device = -1 */
+  int32_t settings[8];         /* charge_sum, diag_sum, field_transform, field_solver, step_mode, output fusion,
+                                  seed_offset; one spare */
+  int32_t itime, nblk;         /* global_itime; reference blocks the writer owned */
+  double time;
+  int32_t imerge, iremove, isplit, rng_ready;  /* the events' counters; 1: the file carries the blocks' generators */
+  int64_t hist_count;          /* entries of the energy history */
+  int64_t nalloc[PIC1DP_MAX_SPECIES], np[PIC1DP_MAX_SPECIES];
+  uint64_t digest[PIC1DP_MAX_SPECIES][4];      /* D[s][k] of the marker sections */
+  uint64_t checksum;           /* of everything else */
+} pic1dp_checkpoint_info;
+
+/* checkpoint_write: everything that decides later bits into ONE file per context (per rank; no collective call):
+ *   input, layout and the seven settings above; itime and time; per species nalloc, np, the per-block counts and
+ *   x, v, w, p in logical order (untiled); field_electric, field_chargeden, the kept modes; the energy history; the
+ *   events' counters and every owned block's generator; the prediction tiles' fixed-point bounds; the diagnostics
+ *   pass's scales; the digests of the marker sections and one checksum over the rest.
+ *   Only between time steps: with a push noted or a charge_local pending it returns PIC1DP_ERR_STATE and creates no
+ *   file.  What collect_charge left to the next solve_field is settled first.  The markers cross in chunks through
+ *   the context's pinned staging; the file appears under its name only when it is complete.
+ *   Afterwards everything the file does NOT carry -- the one-pass prediction, the predicted half-step field, cached
+ *   diagnostics, the accumulator sets, the call sites' state -- is put into the one defined state that
+ *   checkpoint_read produces too: THE WRITING CONTEXT AND A CONTEXT RESTORED FROM THE FILE CONTINUE BIT FOR BIT
+ *   ALIKE.  The price: the step after a checkpoint takes two passes over the markers.
+ * checkpoint_read: into a context created with the same input and layout and set to the same seven settings --
+ *   otherwise PIC1DP_ERR_ARG naming the first field that differs, the context untouched.  Lengths and checksum are
+ *   verified before the device is touched; then the markers are uploaded, the digest kernel runs and its words are
+ *   compared with the file's: a mismatch returns PIC1DP_ERR_ARG naming species and array and leaves the context
+ *   without markers (the next step reports "no particles").  Touches neither communicator nor exchange.
+ * checkpoint_info: input (may be NULL) and the description above, from a file whose lengths and checksum hold.
+ * checkpoint_verify: info's checks and every marker section against its digest (pic1dp_hip_host_digest), naming
+ *   what fails.  Both host only: no device, no context. */
+int pic1dp_hip_checkpoint_write(pic1dp_ctx *ctx, const char *path);
+int pic1dp_hip_checkpoint_read(pic1dp_ctx *ctx, const char *path);
+int pic1dp_hip_checkpoint_info(const char *path, pic1dp_input *in, pic1dp_checkpoint_info *info);
+int pic1dp_hip_checkpoint_verify(const char *path);
+
 /* ---- multi-GPU: RCCL communicator (replaces MPI_Allreduce at
  * src/pic1dp_interaction.F90:132) ------------------------------------------
  * rank 0 obtains an id, the host distributes the 128 bytes to every rank

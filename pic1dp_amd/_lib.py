@@ -66,6 +66,16 @@ class Layout(C.Structure):
                 ("device", C.c_int32)]
 
 
+class CheckpointInfo(C.Structure):
+    """struct pic1dp_checkpoint_info"""
+    _fields_ = [("format_version", C.c_int32), ("nspecies", C.c_int32), ("file_bytes", C.c_int64),
+                ("input_size", C.c_int64), ("layout", Layout), ("settings", C.c_int32 * 8),
+                ("itime", C.c_int32), ("nblk", C.c_int32), ("time", C.c_double),
+                ("imerge", C.c_int32), ("iremove", C.c_int32), ("isplit", C.c_int32), ("rng_ready", C.c_int32),
+                ("hist_count", C.c_int64), ("nalloc", C.c_int64 * MAX_SPECIES), ("np", C.c_int64 * MAX_SPECIES),
+                ("digest", (C.c_uint64 * 4) * MAX_SPECIES), ("checksum", C.c_uint64)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _INP = C.POINTER(Input)
@@ -154,6 +164,12 @@ SIGNATURES = {
     "pic1dp_hip_output_scalars_from": [_P, _P, _P, C.c_int32],
     "pic1dp_hip_ptcldist_finish": [_P, C.c_int32, _P, _P, _P, _P, _P, _P],
     "pic1dp_hip_kernel_bytes": [_P, C.c_int32, _D, _D, _D, C.c_char_p, C.c_int32],
+    "pic1dp_hip_state_digest": [_P, _P],
+    "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
+    "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],
+    "pic1dp_hip_checkpoint_read": [_P, C.c_char_p],
+    "pic1dp_hip_checkpoint_info": [C.c_char_p, _INP, C.POINTER(CheckpointInfo)],
+    "pic1dp_hip_checkpoint_verify": [C.c_char_p],
 }
 
 _lib = None

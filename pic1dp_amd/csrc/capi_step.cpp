@@ -760,6 +760,46 @@ int pic1dp_host::set_call_state(pic1dp_ctx *c, Seq seq, Owed owed) {
 int pic1dp_host::set_seq(pic1dp_ctx *c, Seq seq) { return set_call_state(c, seq, c->owed); }
 int pic1dp_host::set_owed(pic1dp_ctx *c, Owed owed) { return set_call_state(c, c->seq, owed); }
 
+// What a checkpoint does not carry, in a defined state: call sites Clean with nothing owed; the markers count as changed
+// (state_version), so no prediction, no predicted half-step field, no carried -f0'/f0 and no cached diagnostics belong to
+// them; the field counts as written by something else than a solve (its kept modes are data, not a description the
+// one-pass kernels may build Eh from); every accumulator set and the exact accumulators zero, set 0 the current one;
+// nothing of a fused solve or a tail left over.  The step after it takes two passes.
+int pic1dp_host::reset_derived_state(pic1dp_ctx *c) {
+  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;
+  c->state_version++;
+  c->pred_version = c->eh_version = 0;
+  c->eh_field_version = 0;
+  c->field_version++;
+  c->modes_field_version = 0;
+  c->eh_modes = 0;
+  c->e_step_start = false;
+  c->cd_kept_mode_only = false;
+  c->cd_version++;
+  c->adopt_cd_version = 0;
+  c->charge_pending = c->charge_pending_pred = false;
+  for (Species &S : c->sp) S.t2_version = 0;
+  for (DiagSpecies &D : c->diag) {
+    D.version = 0;
+    D.pending = false;
+    D.blocks = 0;
+    D.sums[0] = D.sums[1] = D.sums[2] = 0.0;
+  }
+  c->fused_pending = false;
+  c->fused_dirty = -1;
+  c->fuse_args = FusedSolve{};
+  c->tail_done = 0;
+  c->tail_x = XchgArgs{};
+  use_accumulators(c, 0);
+  HIP_TRY(hipMemsetAsync(c->d_rho_all, 0, sizeof(double) * 3 * c->plan.rho_set_doubles, c->st));
+  if (c->d_pred_all) HIP_TRY(hipMemsetAsync(c->d_pred_all, 0, sizeof(double) * 3 * c->plan.pred_set_doubles, c->st));
+  if (c->d_fx) HIP_TRY(hipMemsetAsync(c->d_fx, 0, sizeof(long long) * 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_ticket, 0, 64, c->st));
+  HIP_TRY(hipMemsetAsync(c->d_Eh, 0, sizeof(double) * c->in.nx, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  return 0;
+}
+
 // checks only: for the call sites that take part in the lazy scheme themselves
 static int require_loaded_keep_lazy(pic1dp_ctx *c) {
   if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");

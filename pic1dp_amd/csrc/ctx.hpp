@@ -9,6 +9,7 @@
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
 //   capi_diag.cpp      diagnostics of output_all
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
+//   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -199,6 +200,7 @@ struct pic1dp_ctx {
   uint64_t eh_version = 0;         // state_version d_Eh has been predicted for (step() path)
   uint64_t field_version = 1, eh_field_version = 0, modes_field_version = 0;  // who wrote d_E last
   double *d_stage = nullptr;  // contiguous staging buffer between host arrays and the tiled marker arrays
+  unsigned long long *d_digest = nullptr;  // [nspecies][4] the state digest's words (capi_checkpoint.cpp; allocated at the first digest)
   double *d_Eh = nullptr;  // field after the first sub-step of the last whole-step call
   // The reference's three call sites at whole-step cost (see "lazy call sites"
   // below): a push is only noted; the collect_charge that follows runs the
@@ -411,6 +413,9 @@ int settle_half_pair(pic1dp_ctx *c);      // call sites: the half-step field the
 int settle_field_view(pic1dp_ctx *c);     // ... for readers of the field only
 int settle_step_start_field(pic1dp_ctx *c);  // field_electric <- the half-step field the second collect_charge left aside (e_step_start)
 int adopt_half_field(pic1dp_ctx *c);
+// Everything a checkpoint file does not carry put into ONE defined state: checkpoint_write and
+// checkpoint_read both end here, so the writing context and one restored from its file continue identically
+int reset_derived_state(pic1dp_ctx *c);
 // ---- capi_comm.cpp ----
 int allreduce_charge(pic1dp_ctx *c);
 int allreduce_doubles(pic1dp_ctx *c, double *d, size_t n);

@@ -202,6 +202,12 @@ struct DiagLaunch {
   bool nt;        // non-temporal marker loads
 };
 
+// launch shape of the state digest's pass (launch_policy.hpp digest_launch)
+struct DigestLaunch {
+  int blocks, threads;
+  bool nt;        // non-temporal marker loads
+};
+
 // dynamic LDS any kernel may ask for: 160 KiB per CU minus 1 KiB, the most static LDS a kernel that asks for more than
 // 64 KiB holds (the particle kernels' exp table; k_field_fd: 144 B)
 constexpr size_t PARTICLE_LDS_CAP = 159 * 1024;
@@ -558,6 +564,15 @@ hipError_t launch_ptcldist_exact(const double *x, const double *v, const double 
 // ... and the kinetic sums of the tail slots [i0, i0 + n) into the same accumulators
 hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
                                     const DiagFxArgs &a, int nxv, hipStream_t st);
+// The state digest of one species (kernels_digest.hip; the definition: include/pic1dp_hip.h pic1dp_hip_state_digest).
+// Array k (0 x, 1 v, 2 w, 3 p): slot i < np is read from cur[k] (the current particle set), slot i >= np from first[k]
+// (set 0, where the tail slots live); out[k] += sum of the mixed words of slots [0, nalloc) (64-bit integer atomics).
+struct DigestArgs {
+  const double *cur[4], *first[4];
+  int64_t np, nalloc;
+  unsigned long long *out;   // [4] device words
+};
+hipError_t launch_state_digest(const DigestArgs &a, const DigestLaunch &dl, hipStream_t st);
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

@@ -147,6 +147,15 @@ DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu) {
   return d;
 }
 
+DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
+  DigestLaunch d{};
+  d.threads = 256;
+  d.nt = 32.0 * static_cast<double>(nalloc) > 288.0 * 1048576.0;
+  const int64_t npair = (nalloc + 1) >> 1;
+  d.blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(static_cast<int64_t>(num_cu) * 8, (npair + d.threads - 1) / d.threads)));
+  return d;
+}
+
 int tail_sum_blocks(int64_t ntail) {
   return ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
 }

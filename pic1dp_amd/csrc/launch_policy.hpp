@@ -50,4 +50,10 @@ DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu);
 // workgroups of 256 threads for the kinetic sums of ntail tail slots (0: none)
 int tail_sum_blocks(int64_t ntail);
 
+// ---- the state digest (kernels_digest.hip) ----
+// one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
+// (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs
+// ask for; non-temporal loads above the threshold of diag_launch
+DigestLaunch digest_launch(int64_t nalloc, int num_cu);
+
 }  // namespace pic1dp

@@ -28,6 +28,18 @@ class Multirand {
   void fill_real(double *a, int64_t n);    // multirand_real_array64
   void fill_gaussian(double *a, int64_t n);  // multirand_gaussian_array64
 
+  // the whole state, for a checkpoint: engine, state words, position, the spare Gaussian of the polar method
+  static constexpr int state_words() { return kStateWords; }
+  void export_state(int32_t *engine, int32_t *pos, int32_t *held, double *val, std::vector<uint64_t> *q) const {
+    *engine = engine_, *pos = pos_, *held = gauss_held_ ? 1 : 0, *val = gauss_val_, *q = q_;
+  }
+  // false: not a state of this generator (nothing is changed)
+  bool import_state(int32_t engine, int32_t pos, int32_t held, double val, const std::vector<uint64_t> &q) {
+    if (engine < KISS64 || engine > SUPERKISS64 || pos < 0 || pos > kStateWords || q.size() != static_cast<size_t>(kStateWords)) return false;
+    engine_ = engine, pos_ = pos, gauss_held_ = held != 0, gauss_val_ = val, q_ = q;
+    return true;
+  }
+
   static double to_real(uint64_t bits) {
     // INT2REAL64: signed value / (2**64-1 rounded to double) + 0.5
     return static_cast<double>(static_cast<int64_t>(bits)) / 18446744073709551615.0 + 0.5;

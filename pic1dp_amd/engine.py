@@ -15,6 +15,7 @@ All compute runs in hand-written HIP kernels on one MI355X; nothing here
 computes, and there is no CPU fallback.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -129,6 +130,48 @@ class Pic1dp:
         out = [np.zeros(n) for _ in range(3)]
         check(self.L.pic1dp_hip_particles_download_bak(self._ctx, ispecies, *[_ptr(a) for a in out], n))
         return dict(zip(("xb", "vb", "wb"), [a[:npv] for a in out]))
+
+    # -- state digest, checkpoint and restart -----------------
+    def state_digest(self):
+        """D[s][k] of the markers on the device (include/pic1dp_hip.h): uint64 [nspecies][4], k = 0 x, 1 v, 2 w, 3 p;
+        equals host_digest() of what particles_download() returns, array by array"""
+        out = np.zeros((self.inp.nspecies, 4), dtype=np.uint64)
+        check(self.L.pic1dp_hip_state_digest(self._ctx, _ptr(out)))
+        return out
+
+    def checkpoint_write(self, path):
+        """everything that decides later bits into one file (only between time steps); afterwards this context and one
+        restored from the file continue bit for bit alike -- the next step takes two passes"""
+        check(self.L.pic1dp_hip_checkpoint_write(self._ctx, os.fsencode(path)))
+
+    def checkpoint_read(self, path):
+        """restore from a file written by a context of the same input, layout and settings"""
+        check(self.L.pic1dp_hip_checkpoint_read(self._ctx, os.fsencode(path)))
+
+    SETTING_NAMES = ("charge_sum", "diag_sum", "field_transform", "field_solver", "step_mode", "fuse_output", "seed_offset")
+
+    def apply_settings(self, settings):
+        """the seven settings a checkpoint carries (checkpoint_info()["settings"]), through their own calls"""
+        self.set_seed_offset(settings["seed_offset"])
+        self.set_step_mode(settings["step_mode"])
+        check(self.L.pic1dp_hip_set_output_fusion(self._ctx, int(settings["fuse_output"])))
+        self.set_field_solver(settings["field_solver"])
+        self.set_field_transform(settings["field_transform"])
+        self.set_charge_sum(settings["charge_sum"])
+        self.set_diag_sum(settings["diag_sum"])
+
+    @classmethod
+    def from_checkpoint(cls, path, device=-1):
+        """a fresh context from the file's input and layout, with its seven settings, holding its state"""
+        info = checkpoint_info(path)
+        sim = cls(info["input"], rank=info["rank"], nranks=info["nranks"], npe=info["npe"], device=device)
+        try:
+            sim.apply_settings(info["settings"])
+            sim.checkpoint_read(path)
+        except Exception:
+            sim.close()
+            raise
+        return sim
 
     # -- the hot path, under the reference's names -----------------------------
     def interaction_collect_charge(self):
@@ -566,6 +609,34 @@ def diag_convert(inp, limbs, ispecies=0):
     sums, dist = np.empty(3), np.empty(3 * nxv + 3 * nvo)
     check(_lib.load().pic1dp_hip_diag_convert(C.byref(inp), int(ispecies), _ptr(a), _ptr(sums), _ptr(dist)))
     return sums, _split_dist(dist, nxv, nvo)
+
+
+def host_digest(a):
+    """the state digest's sum over a host array of doubles (include/pic1dp_hip.h), as a Python int; no device"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out = C.c_uint64()
+    check(_lib.load().pic1dp_hip_host_digest(_ptr(a), a.size, C.byref(out)))
+    return int(out.value)
+
+
+def checkpoint_info(path):
+    """what a checkpoint file says about itself (lengths and checksum verified; host only): the input, the layout, the
+    seven settings by name, itime, time, counters, sizes and the marker sections' digests"""
+    inp, info = Input(), _lib.CheckpointInfo()
+    check(_lib.load().pic1dp_hip_checkpoint_info(os.fsencode(path), C.byref(inp), C.byref(info)))
+    ns = info.nspecies
+    return {"input": inp, "format_version": info.format_version, "file_bytes": info.file_bytes, "input_size": info.input_size,
+            "rank": info.layout.rank, "nranks": info.layout.nranks, "npe": info.layout.npe, "nblk": info.nblk,
+            "settings": {n: int(info.settings[i]) for i, n in enumerate(Pic1dp.SETTING_NAMES)},
+            "itime": info.itime, "time": info.time, "imerge": info.imerge, "iremove": info.iremove, "isplit": info.isplit,
+            "rng_ready": bool(info.rng_ready), "hist_count": info.hist_count,
+            "nalloc": [int(info.nalloc[s]) for s in range(ns)], "np": [int(info.np[s]) for s in range(ns)],
+            "digest": [[int(info.digest[s][k]) for k in range(4)] for s in range(ns)], "checksum": int(info.checksum)}
+
+
+def checkpoint_verify(path):
+    """every checksum and digest of a checkpoint file recomputed on the host; raises Pic1dpError naming what fails"""
+    check(_lib.load().pic1dp_hip_checkpoint_verify(os.fsencode(path)))
 
 
 def field_transform_supported(nx, transform=1):

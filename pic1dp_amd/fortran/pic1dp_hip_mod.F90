@@ -49,7 +49,60 @@ type, bind(C) :: pic1dp_layout_t
   integer(c_int32_t) :: rank, nranks, npe, device
 end type pic1dp_layout_t
 
+! struct pic1dp_checkpoint_info: what pic1dp_hip_checkpoint_info reports of a file besides the input
+type, bind(C) :: pic1dp_checkpoint_info_t
+  integer(c_int32_t) :: format_version, nspecies
+  integer(c_int64_t) :: file_bytes, input_size
+  type(pic1dp_layout_t) :: layout
+  integer(c_int32_t) :: settings(8)
+  integer(c_int32_t) :: itime, nblk
+  real(c_double) :: time
+  integer(c_int32_t) :: imerge, iremove, isplit, rng_ready
+  integer(c_int64_t) :: hist_count
+  integer(c_int64_t) :: nalloc(PIC1DP_MAX_SPECIES), np(PIC1DP_MAX_SPECIES)
+  integer(c_int64_t) :: digest(4, PIC1DP_MAX_SPECIES)   ! D[s][k] as digest(k + 1, s + 1), the 64 bits of an unsigned word
+  integer(c_int64_t) :: checksum
+end type pic1dp_checkpoint_info_t
+
 interface
+  ! state digest, checkpoint and restart (include/pic1dp_hip.h; file names are C strings: trim(name) // c_null_char)
+  function pic1dp_hip_state_digest(ctx, out) bind(C, name="pic1dp_hip_state_digest") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int64_t), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_state_digest
+  function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
+    import
+    real(c_double), intent(in) :: a(*)
+    integer(c_int64_t), value :: n
+    integer(c_int64_t), intent(out) :: out
+    integer(c_int) :: ierr
+  end function pic1dp_hip_host_digest
+  function pic1dp_hip_checkpoint_write(ctx, path) bind(C, name="pic1dp_hip_checkpoint_write") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    character(kind=c_char), intent(in) :: path(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_checkpoint_write
+  function pic1dp_hip_checkpoint_read(ctx, path) bind(C, name="pic1dp_hip_checkpoint_read") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    character(kind=c_char), intent(in) :: path(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_checkpoint_read
+  function pic1dp_hip_checkpoint_info(path, inp, info) bind(C, name="pic1dp_hip_checkpoint_info") result(ierr)
+    import
+    character(kind=c_char), intent(in) :: path(*)
+    type(pic1dp_input_t), intent(out) :: inp
+    type(pic1dp_checkpoint_info_t), intent(out) :: info
+    integer(c_int) :: ierr
+  end function pic1dp_hip_checkpoint_info
+  function pic1dp_hip_checkpoint_verify(path) bind(C, name="pic1dp_hip_checkpoint_verify") result(ierr)
+    import
+    character(kind=c_char), intent(in) :: path(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_checkpoint_verify
   function pic1dp_hip_last_error_c() bind(C, name="pic1dp_hip_last_error") result(msg)
     import
     type(c_ptr) :: msg

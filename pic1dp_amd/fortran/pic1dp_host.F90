@@ -27,6 +27,13 @@
 ! global_itime / global_time itself, exactly as src/pic1dp.F90:92-93); with
 ! PIC1DP_FUSED=3 all the steps up to the next output_all are ONE call,
 ! pic1dp_hip_step(ctx, pic1dp_hip_steps_to_output): one launch per time step.
+! Checkpoint and restart (options of this host program; the file: INTEGRATION.md section 7):
+!   PIC1DP_CHECKPOINT_AT=<n> with PIC1DP_CHECKPOINT=<file>: after time step n every rank r writes <file>.r<r>
+!                         (pic1dp_hip_checkpoint_write) and the run goes on;
+!   PIC1DP_RESTART=<file> every rank r reads <file>.r<r> into its freshly created context instead of loading markers
+!                         (pic1dp_hip_checkpoint_read) and enters the time loop at the file's itime and time, without the
+!                         initial deposit, solve and record: with the exact sums (PIC1DP_CHARGE_SUM=exact,
+!                         PIC1DP_DIAG_SUM=exact) its records are byte for byte those the writing run wrote after step n.
 ! PIC1DP_HOST_PROFILE=1 prints the wall clock of the run split into the time loop's steps, output_all's
 ! diagnostics and the writes of pic1dp.out (the steps are then waited for, pic1dp_hip_sync, before the clock is read).
 program pic1dp_host
@@ -44,8 +51,9 @@ integer(c_int32_t) :: global_irk, global_itime, itermination, due, flag_optimize
 real(c_double) :: global_time, ms_push, ms_charge, ms_field
 real(c_double) :: t_run0, t_loop0, t_a, steps_s, load_s
 character(len=8) :: buf
-character(len=512) :: dump_path
-integer :: stat, verbosity, fail_at
+character(len=512) :: dump_path, ckpt_path, restart_path
+integer :: stat, verbosity, fail_at, ckpt_at
+logical :: restart
 integer(c_int32_t) :: timer_mode
 logical :: fused, whole_step, batched, use_rccl, loop_profile
 integer(c_signed_char) :: handle(PIC1DP_XCHG_HANDLE_BYTES), comm_id(PIC1DP_COMM_ID_BYTES)
@@ -109,23 +117,38 @@ fail_at = -1
 call get_environment_variable('PIC1DP_HOST_FAIL_AT', buf, status=stat)
 if (stat == 0) read (buf, *, iostat=stat) fail_at
 
+ckpt_at = -1
+call get_environment_variable('PIC1DP_CHECKPOINT_AT', buf, status=stat)
+if (stat == 0) read (buf, *, iostat=stat) ckpt_at
+call get_environment_variable('PIC1DP_CHECKPOINT', ckpt_path, status=stat)
+if (stat /= 0) ckpt_at = -1
+call get_environment_variable('PIC1DP_RESTART', restart_path, status=stat)
+restart = (stat == 0)
+
 t_run0 = output_wall()
-call pic1dp_hip_check(pic1dp_hip_particle_load(ctx), 'particle_load')
+if (.not. restart) call pic1dp_hip_check(pic1dp_hip_particle_load(ctx), 'particle_load')
 if (output_profile) call pic1dp_hip_check(pic1dp_hip_sync(ctx), 'sync')
 load_s = output_wall() - t_run0
 call pic1dp_hip_check(pic1dp_hip_timers_enable(ctx, timer_mode), 'timers_enable')
 ! output_all is called at the reference's cadence below: steps it follows take its diagnostics along
 call pic1dp_hip_check(pic1dp_hip_set_output_fusion(ctx, 1), 'set_output_fusion')
 
-global_itime = 0
-global_time = 0.0_c_double
-call pic1dp_hip_check(pic1dp_hip_set_time(ctx, global_itime, global_time), 'set_time')
+if (restart) then
+  ! the file's state, counters included (the settings above are the ones it was written under, or the read says which is not)
+  call pic1dp_hip_check(pic1dp_hip_checkpoint_read(ctx, rank_file(restart_path)), 'checkpoint_read')
+  call pic1dp_hip_check(pic1dp_hip_get_time(ctx, global_itime, global_time), 'get_time')
+  if (verbosity == 1) write (*, '(a/a)') 'Info: progress:', 'progrss  itime     time  int E^2 dx'
+else
+  global_itime = 0
+  global_time = 0.0_c_double
+  call pic1dp_hip_check(pic1dp_hip_set_time(ctx, global_itime, global_time), 'set_time')
 
-! solve initial field
-call pic1dp_hip_check(pic1dp_hip_collect_charge(ctx), 'collect_charge')
-call pic1dp_hip_check(pic1dp_hip_solve_field(ctx), 'solve_field')
-if (verbosity == 1) write (*, '(a/a)') 'Info: progress:', 'progrss  itime     time  int E^2 dx'
-call output_all(ctx, inp, verbosity)
+  ! solve initial field
+  call pic1dp_hip_check(pic1dp_hip_collect_charge(ctx), 'collect_charge')
+  call pic1dp_hip_check(pic1dp_hip_solve_field(ctx), 'solve_field')
+  if (verbosity == 1) write (*, '(a/a)') 'Info: progress:', 'progrss  itime     time  int E^2 dx'
+  call output_all(ctx, inp, verbosity)
+end if
 
 call pic1dp_hip_check(pic1dp_hip_check_termination(ctx, itermination), 'check_termination')
 t_loop0 = output_wall()
@@ -161,6 +184,8 @@ do while (itermination == 0)                 ! main time evolution loop
   call pic1dp_hip_check(pic1dp_hip_check_termination(ctx, itermination), 'check_termination')
   call pic1dp_hip_check(pic1dp_hip_output_due(ctx, itermination, due), 'output_due')
   if (due == 1) call output_all(ctx, inp, verbosity)
+  ! (after the record of step n, if it has one: the file holds what every later record is made from)
+  if (global_itime == ckpt_at) call pic1dp_hip_check(pic1dp_hip_checkpoint_write(ctx, rank_file(ckpt_path)), 'checkpoint_write')
 end do
 
 if (ranks_rank == 0) call output_final
@@ -195,6 +220,15 @@ call pic1dp_hip_check(pic1dp_hip_destroy(ctx), 'destroy')   ! particle_final + f
 call ranks_finalize()
 
 contains
+
+! <name>.r<rank> as a C string
+function rank_file(name) result(path)
+  character(len=*), intent(in) :: name
+  character(len=:), allocatable :: path
+  character(len=16) :: r
+  write (r, '(i0)') ranks_rank
+  path = trim(name) // '.r' // trim(r) // c_null_char
+end function rank_file
 
 ! PIC1DP_DUMP_MARKERS=<file>: this rank's markers of species 0 at the end of the run, raw native doubles
 ! [np as one double | x | v | p | w] -- for tests that compare two runs of the host bit for bit
