@@ -544,6 +544,40 @@ int pic1dp_hip_diag_convert(const pic1dp_input *in, int32_t ispecies, const int6
 int pic1dp_hip_state_digest(pic1dp_ctx *ctx, uint64_t *out);
 int pic1dp_hip_host_digest(const double *a, int64_t n, uint64_t *out);
 
+/* ---- velocity moments of the markers on the field grid ------------------------
+ * pic1dp_hip_moments(ctx, ispecies, which, out): the moments sum q v^k, k = 0 ... 3, of one species' markers, deposited
+ * on the nx cells of the field grid with the deposit's own linear weights, computed on the device in streaming passes.
+ *   - which is 1 (weights p: total f), 2 (weights w: delta f) or 3 (both, p first).
+ *   - out[(j * 4 + k) * nx + ix], where j counts the selected weight sets in that order and k = 0 ... 3 is the power of v:
+ *     4 nx doubles for which = 1 or 2, 8 nx for which = 3.
+ *   - The sums are raw: no nx / lx, no Z, no background.
+ * For every valid marker i < np of the species, on the state a pic1dp_hip_particles_download at that moment would return:
+ *     px = wrap(x)                  the deposit's wrap (src/pic1dp_interaction.F90:102-104), NOT stored back
+ *     (ix, wl) = locate(px)         the deposit's cell and left weight; ix == nx folds to 0; ir = (ix + 1 == nx) ? 0 : ix + 1
+ *     a0 = wl * q                   q = p or w: the very products of the deposit
+ *     b0 = (1.0 - wl) * q
+ *     a1 = a0 * v    a2 = a1 * v    a3 = a2 * v        likewise b1 ... b3: every product rounded separately
+ *     M[q][k][ix] += a_k            M[q][k][ir] += b_k
+ *   - Tail slots (i >= np) do not count.
+ *   - Markers with |v| >= v_max do count; this is not the rule of output_ptcldist's histograms.
+ *   - The arithmetic is plain IEEE.  A non-finite term makes its bin non-finite; there is no counter and no trap.
+ *   - The sums are FP64 and their order is free: the result is defined up to that order.  With n_b terms in a bin and B
+ *     workgroups, |result - exact sum| <= (n_b + B) 2^-53 sum |terms| to first order.
+ *   - Plane (w, 0) is the charge of the species before  * Z * nx / lx.  Normalisations, with f = total (p) or delta f (w):
+ *     density n = M0 nx / lx, current J = Z M1 nx / lx, second moment (pressure + flow) P = m M2 nx / lx, third moment
+ *     (heat flux + convected terms) Q = m M3 nx / lx; a full-f run (deltaf = 0) subtracts its background n0 itself.
+ *   - which & 2 on a full-f context (deltaf = 0, no w) is PIC1DP_ERR_ARG; so are an unknown `which` and an unknown species.
+ *   - The result is LOCAL to the context: the sum over ranks is an element-wise addition by the host, as with
+ *     pic1dp_hip_charge_local.  No communicator is used.
+ *   - There is no exact (fixed-quanta) kind: pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect the call.
+ * When the call may come.  Between time steps it launches its own passes and nothing else and changes nothing: markers,
+ * fields, the one-pass prediction, a pending fused solve and cached diagnostics survive (the rule of
+ * pic1dp_hip_state_digest).  Inside a time step (a push noted) it first puts the noted push into memory, as every entry point
+ * outside the sequence does; the moments are those of the memory eager calls would hold.
+ * Cost: one pass over x, v and p and / or w (24 or 32 B per marker) while the selected planes fit a workgroup's LDS (all
+ * eight up to nx 2400); four planes per pass up to nx 4800 (which = 3: two passes), two per pass beyond (four, or two). */
+int pic1dp_hip_moments(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
+
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
   int32_t format_version;
@@ -690,7 +724,9 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 14: *launches = contributions of the exact charge sum (set_charge_sum(1)) beyond 2^62 quanta so far, which
  * were not summed (each batch is reported once as PIC1DP_ERR_ARG), *ms = 0 (waits for the stream)
  * which = 15: *launches = terms the passes of the exact diagnostics sum (set_diag_sum(1)) did not sum so far (counted
- * when a pass's results are first handed out), *ms = 0 */
+ * when a pass's results are first handed out), *ms = 0;
+ * which = 16: *launches = passes of pic1dp_hip_moments (k_moments) launched so far, *ms = their accumulated device
+ * milliseconds while kernel stats were enabled */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

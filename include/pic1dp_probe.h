@@ -109,6 +109,13 @@ int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t nx_opd, int3
 int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w, int32_t threads,
                                  int32_t out[4]);
 
+/* The passes of one pic1dp_hip_moments call (launch_policy.hpp moments_plan), on the HOST: out[0] = passes (0: an unknown
+ * `which`, w asked of a full-f run, nx out of range), out[1] = planes selected (4 or 8), out[2] = planes per pass (8, 4, 2),
+ * then per pass i eight words at out[3 + 8 i]: {blocks, threads, non-temporal loads, dynamic LDS bytes, weight sets (bit 0
+ * p, bit 1 w), powers of v (bit k: v^k), first plane in the output, planes}.  out holds 3 + 8 * 4 words.  Nonzero: null
+ * argument. */
+int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]);
+
 /* What pic1dp_hip_create decides before its first allocation (pic1dp_amd/csrc/context_plan.hpp plan_context), on the HOST,
  * for an input, a layout and the three requests of the settings that bear on it (0: none): PIC1DP_PRED_KIND,
  * PIC1DP_RHO_GLOBAL_COPIES as given (refused like settings_from_env refuses it), PIC1DP_FIELD_ONE_RANK_ORDER.  The input is taken as it is (not validated).

@@ -164,6 +164,7 @@ SIGNATURES = {
     "pic1dp_hip_output_scalars_from": [_P, _P, _P, C.c_int32],
     "pic1dp_hip_ptcldist_finish": [_P, C.c_int32, _P, _P, _P, _P, _P, _P],
     "pic1dp_hip_kernel_bytes": [_P, C.c_int32, _D, _D, _D, C.c_char_p, C.c_int32],
+    "pic1dp_hip_moments": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

@@ -993,7 +993,13 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 15) return fail(PIC1DP_ERR_ARG, "which must be 0..15");
+  if (which < 0 || which > 16) return fail(PIC1DP_ERR_ARG, "which must be 0..16");
+  if (which == 16) {  // passes of pic1dp_hip_moments (k_moments) launched so far; *ms: their device time while kernel stats were enabled
+    if (int rc = ev_resolve(c)) return rc;
+    if (ms) *ms = c->acc_ms[kTagMoments];
+    if (launches) *launches = c->moments_passes;
+    return PIC1DP_OK;
+  }
   if (which == 15) {  // kind 1 of the diagnostics sum: terms its passes did not sum so far (reported as PIC1DP_ERR_ARG)
     if (launches) *launches = c->dfx_rejected;
     if (ms) *ms = 0.0;

@@ -1,5 +1,6 @@
 // capi_diag.cpp -- diagnostics of output_all (src/pic1dp_output.F90:100-189, 196-477): the kinetic sums and the
-// (x, v) / v histograms, one fused pass per species, cached against state_version.
+// (x, v) / v histograms, one fused pass per species, cached against state_version; and the velocity moments on the field
+// grid (pic1dp_hip_moments), passes of their own that cache nothing and change nothing.
 #include "ctx.hpp"
 
 namespace pic1dp_host {
@@ -570,6 +571,40 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
   HIP_TRY(hipStreamSynchronize(c->st));
   if (int rc = xchg_check(c)) return rc;
   return settle_record(c, L, h, scalars, E, cd, re, im, dist);
+}
+
+// ---------------------------------------------------------------------------
+// velocity moments of the markers on the field grid (include/pic1dp_hip.h pic1dp_hip_moments)
+// ---------------------------------------------------------------------------
+int pic1dp_hip_moments(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
+  CHECK_CTX(c);
+  if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "moments: bad species index %d", isp);
+  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "moments: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", which);
+  if ((which & 2) && !c->in.deltaf)
+    return fail(PIC1DP_ERR_ARG, "moments: which = %d asks for the planes of w (which & 2), but a full-f context (deltaf = 0) has no w", which);
+  if (!out) return fail(PIC1DP_ERR_ARG, "moments: null output");
+  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = materialize(c)) return rc;   // (as state_digest: a noted push becomes memory; clean: nothing is launched)
+  const int nx = c->in.nx;
+  const Species &S = c->sp[isp];
+  const MomentsPlan plan = moments_plan(nx, which, c->in.deltaf, S.np, c->num_cu);
+  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: moments_plan has no pass for nx %d, which %d", nx, which);
+  if (!c->d_mom) HIP_TRY(c->mem.alloc(&c->d_mom, static_cast<size_t>(8) * nx));
+  if (!c->h_mom) HIP_TRY(c->mem.alloc_pinned(&c->h_mom, static_cast<size_t>(8) * nx));
+  const size_t n = static_cast<size_t>(plan.selected) * nx;
+  HIP_TRY(hipMemsetAsync(c->d_mom, 0, sizeof(double) * n, c->st));
+  const PSet &A = S.set[c->cur];
+  for (int i = 0; i < plan.npass && S.np > 0; ++i) {
+    Span ks(c, kTagMoments, c->stats_on);
+    HIP_TRY(launch_moments(A.x, A.v, S.p, A.w, S.np, c->grid, c->d_mom, plan.pass[i], c->cfg.dyn_tail, c->st));
+    if (int rc = ks.end()) return rc;
+    c->moments_passes++;
+  }
+  HIP_TRY(hipMemcpyAsync(c->h_mom, c->d_mom, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  std::memcpy(out, c->h_mom, sizeof(double) * n);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// kernels.hpp -- launch interface of the gfx950 kernels (kernels_step.hip, kernels_push.hip, kernels_field.hip, kernels_diag.hip).
+// kernels.hpp -- launch interface of the gfx950 kernels (kernels_step.hip, kernels_push.hip, kernels_field.hip, kernels_diag.hip,
+// kernels_moments.hip, ...).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,6 +201,25 @@ struct DiagLaunch {
   bool lds;       // the histograms as a copy per workgroup in its LDS; false: straight into memory
   size_t bytes;   // dynamic LDS
   bool nt;        // non-temporal marker loads
+};
+
+// One pass of pic1dp_hip_moments over a species' markers (launch_policy.hpp moments_plan; kernels_moments.hip k_moments): the
+// planes it holds in the workgroup's LDS are powers `kmask` (bit k: v^k) of the weight sets p and / or w, in output order
+struct MomentsPass {
+  int blocks, threads;
+  bool nt;          // non-temporal marker loads
+  size_t bytes;     // dynamic LDS: the planes, [plane][cell] doubles, and nothing else
+  bool p, w;        // the weight sets of this pass (both: p's planes first)
+  int kmask;        // 0xF, 0x3 or 0xC
+  int first_plane;  // where the pass's first plane lies in the output [sets selected][4][nx], in planes
+  int planes;       // planes of the pass
+};
+constexpr int MOMENTS_MAX_PASSES = 4;
+struct MomentsPlan {
+  int selected;     // planes asked for: 4 or 8
+  int group;        // planes a pass holds: 8, 4 or 2
+  int npass;
+  MomentsPass pass[MOMENTS_MAX_PASSES];
 };
 
 // launch shape of the state digest's pass (launch_policy.hpp digest_launch)
@@ -564,6 +584,11 @@ hipError_t launch_ptcldist_exact(const double *x, const double *v, const double 
 // ... and the kinetic sums of the tail slots [i0, i0 + n) into the same accumulators
 hipError_t launch_energy_sums_exact(const double *v, const double *p, const double *w, int64_t i0, int64_t n,
                                     const DiagFxArgs &a, int nxv, hipStream_t st);
+// One pass of the velocity moments on the field grid (kernels_moments.hip; the definition: include/pic1dp_hip.h
+// pic1dp_hip_moments) over markers [0, np): out = the species' planes [sets selected][4][nx], zeroed by the caller before a
+// call's passes; the pass adds its planes (ps.first_plane ...) with one global atomic per non-zero LDS word and workgroup
+hipError_t launch_moments(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
+                          double *out, const MomentsPass &ps, int dyn_tail, hipStream_t st);
 // The state digest of one species (kernels_digest.hip; the definition: include/pic1dp_hip.h pic1dp_hip_state_digest).
 // Array k (0 x, 1 v, 2 w, 3 p): slot i < np is read from cur[k] (the current particle set), slot i >= np from first[k]
 // (set 0, where the tail slots live); out[k] += sum of the mixed words of slots [0, nalloc) (64-bit integer atomics).

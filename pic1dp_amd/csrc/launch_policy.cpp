@@ -147,6 +147,31 @@ DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu) {
   return d;
 }
 
+MomentsPlan moments_plan(int nx, int which, int deltaf, int64_t np, int num_cu) {
+  MomentsPlan m{};
+  if (which < 1 || which > 3 || ((which & 2) && !deltaf) || nx < 1) return m;
+  m.selected = which == 3 ? 8 : 4;
+  const size_t fit = kDiagLdsCap / (sizeof(double) * static_cast<size_t>(nx));
+  m.group = fit >= 8 && m.selected == 8 ? 8 : (fit >= 4 ? 4 : (fit >= 2 ? 2 : 0));
+  if (m.group == 0) return m;   // (nx > 9600: no context has such a grid)
+  m.npass = m.selected / m.group;
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(num_cu, ((np >> 1) + 1023) / 1024));
+  for (int i = 0; i < m.npass; ++i) {
+    MomentsPass &ps = m.pass[i];
+    ps.first_plane = i * m.group;
+    ps.planes = m.group;
+    const int set = ps.first_plane / 4;          // of the sets selected, in output order
+    ps.p = m.group == 8 || (which != 2 && set == 0);
+    ps.w = m.group == 8 || which == 2 || set == 1;
+    ps.kmask = m.group >= 4 ? 0xF : (ps.first_plane % 4 == 0 ? 0x3 : 0xC);
+    ps.threads = 1024;
+    ps.blocks = static_cast<int>(blocks);
+    ps.bytes = sizeof(double) * static_cast<size_t>(m.group) * static_cast<size_t>(nx);
+    ps.nt = 8.0 * (2 + (ps.p ? 1 : 0) + (ps.w ? 1 : 0)) * static_cast<double>(np) > 288.0 * 1048576.0;
+  }
+  return m;
+}
+
 DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
   DigestLaunch d{};
   d.threads = 256;

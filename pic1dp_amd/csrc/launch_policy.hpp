@@ -50,6 +50,16 @@ DiagLaunch diag_launch(int kind, int64_t np, int nxo, int nvo, int num_cu);
 // workgroups of 256 threads for the kinetic sums of ntail tail slots (0: none)
 int tail_sum_blocks(int64_t ntail);
 
+// ---- the velocity moments on the field grid (kernels_moments.hip; include/pic1dp_hip.h pic1dp_hip_moments) ----
+// The passes of one call: which = 1 (p), 2 (w), 3 (both, p first) selects 4 or 8 planes in output order (weight set, then
+// power of v).  A pass holds at most kDiagLdsCap / (8 nx) of them in its workgroup's LDS, as doubles [plane][cell]; groups
+// are cut in output order, never across two weight sets unless all eight fit, and only as the kernel is instantiated:
+// eight planes (nx <= 2400), four (nx <= 4800: one pass per weight set) or two (powers {0, 1}, then {2, 3}).  Every nx a
+// context accepts (<= 8192) is served from LDS.  One workgroup of 1024 threads per CU, never more than the marker pairs ask
+// for; non-temporal loads once the arrays the pass reads (x, v and p and / or w: 24 or 32 B per marker) exceed the
+// threshold of diag_launch.  npass = 0: an unknown `which`, w asked of a full-f run (deltaf = 0), or nx out of range.
+MomentsPlan moments_plan(int nx, int which, int deltaf, int64_t np, int num_cu);
+
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
 // (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs

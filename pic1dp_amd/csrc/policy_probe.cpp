@@ -1,7 +1,7 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_moments_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 
 #include "../../include/pic1dp_probe.h"
@@ -54,6 +54,20 @@ extern "C" int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t n
   out[3] = static_cast<int64_t>(d.bytes);
   out[4] = d.nt;
   out[5] = tail_sum_blocks(ntail);
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]) {
+  if (!out) return 1;
+  const MomentsPlan m = moments_plan(nx, which, deltaf, np, num_cu);
+  for (int i = 0; i < 35; ++i) out[i] = 0;
+  out[0] = m.npass, out[1] = m.selected, out[2] = m.group;
+  for (int i = 0; i < m.npass; ++i) {
+    const MomentsPass &ps = m.pass[i];
+    const int64_t v[8] = {ps.blocks, ps.threads, ps.nt, static_cast<int64_t>(ps.bytes), (ps.p ? 1 : 0) | (ps.w ? 2 : 0), ps.kmask,
+                          ps.first_plane, ps.planes};
+    for (int k = 0; k < 8; ++k) out[3 + 8 * i + k] = v[k];
+  }
   return 0;
 }
 

@@ -131,6 +131,22 @@ class Pic1dp:
         check(self.L.pic1dp_hip_particles_download_bak(self._ctx, ispecies, *[_ptr(a) for a in out], n))
         return dict(zip(("xb", "vb", "wb"), [a[:npv] for a in out]))
 
+    # -- velocity moments on the field grid ---------------------
+    def moments(self, ispecies=0, which=3):
+        """sum q v^k, k = 0 ... 3, of a species' markers on the nx cells of the field grid, with the deposit's linear
+        weights, computed on the GPU (include/pic1dp_hip.h pic1dp_hip_moments).  which: 1 the weights p (total f), 2 the
+        weights w (delta f), 3 both.  Returns {"total": (4, nx), "pertb": (4, nx)} with only the sets asked for; row k is
+        the power of v.  The sums are raw and local to this context (ranks: add element by element): density
+        n = M[0] nx / lx, current J = Z M[1] nx / lx, second moment m M[2] nx / lx, third moment m M[3] nx / lx; "pertb"[0]
+        is the species' deposited charge before Z nx / lx.  Markers beyond v_max count; tail slots do not.  Between time
+        steps the call changes nothing; inside one it first puts a noted push into memory."""
+        nx = self.inp.nx
+        nsets = 2 if which == 3 else 1
+        out = np.empty((nsets, 4, nx))
+        check(self.L.pic1dp_hip_moments(self._ctx, int(ispecies), int(which), _ptr(out)))
+        names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
+        return {n: out[j] for j, n in enumerate(names)}
+
     # -- state digest, checkpoint and restart (DESIGN.md 2.13) -----------------
     def state_digest(self):
         """D[s][k] of the markers on the device (include/pic1dp_hip.h): uint64 [nspecies][4], k = 0 x, 1 v, 2 w, 3 p;

@@ -72,6 +72,15 @@ interface
     integer(c_int64_t), intent(inout) :: out(*)
     integer(c_int) :: ierr
   end function pic1dp_hip_state_digest
+  ! velocity moments on the field grid: out(nx, 4, sets selected), which = 1 (p), 2 (w), 3 (both, p first); raw local sums
+  function pic1dp_hip_moments(ctx, ispecies, which, out) bind(C, name="pic1dp_hip_moments") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

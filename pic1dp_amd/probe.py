@@ -51,6 +51,7 @@ SIGNATURES = {
     "pic1dp_probe_host_launch_shape": [C.POINTER(LaunchQuery), _I64],
     "pic1dp_probe_host_field_lds": [C.c_int32] * 7 + [_I64],
     "pic1dp_probe_host_diag_launch": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _I64],
+    "pic1dp_probe_host_moments_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
@@ -217,6 +218,20 @@ def host_diag_launch(kind, np_, nx_opd, nv_opd, num_cu, ntail=0):
     if load().pic1dp_probe_host_diag_launch(kind, int(np_), nx_opd, nv_opd, num_cu, int(ntail), out) != 0:
         raise ValueError("pic1dp_probe_host_diag_launch: unknown kind %r" % (kind,))
     return tuple(out)
+
+
+MOMENTS_PASS_FIELDS = ("blocks", "threads", "nt", "bytes", "sets", "kmask", "first_plane", "planes")
+
+
+def host_moments_plan(nx, which, deltaf, np_, num_cu):
+    """the passes of one moments call (csrc/launch_policy.hpp moments_plan), on the host: dict(selected, group, passes) with
+    one dict of MOMENTS_PASS_FIELDS per pass (sets: bit 0 p, bit 1 w; kmask: bit k = v^k); no pass: an unknown `which`, w
+    asked of a full-f run, nx out of range"""
+    out = (C.c_int64 * 35)()
+    if load().pic1dp_probe_host_moments_plan(int(nx), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_moments_plan")
+    return dict(selected=out[1], group=out[2],
+                passes=[dict(zip(MOMENTS_PASS_FIELDS, out[3 + 8 * i:11 + 8 * i])) for i in range(out[0])])
 
 
 def host_dist_scale(np_, blocks, deltaf, bound_p, bound_w, threads=1024):
