@@ -569,7 +569,8 @@ int pic1dp_hip_host_digest(const double *a, int64_t n, uint64_t *out);
  *   - which & 2 on a full-f context (deltaf = 0, no w) is PIC1DP_ERR_ARG; so are an unknown `which` and an unknown species.
  *   - The result is LOCAL to the context: the sum over ranks is an element-wise addition by the host, as with
  *     pic1dp_hip_charge_local.  No communicator is used.
- *   - There is no exact (fixed-quanta) kind: pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect the call.
+ *   - pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect the call.  The exact (fixed-quanta) kind is an
+ *     entry point of its own: pic1dp_hip_moments_exact below.
  * When the call may come.  Between time steps it launches its own passes and nothing else and changes nothing: markers,
  * fields, the one-pass prediction, a pending fused solve and cached diagnostics survive (the rule of
  * pic1dp_hip_state_digest).  Inside a time step (a push noted) it first puts the noted push into memory, as every entry point
@@ -577,6 +578,42 @@ int pic1dp_hip_host_digest(const double *a, int64_t n, uint64_t *out);
  * Cost: one pass over x, v and p and / or w (24 or 32 B per marker) while the selected planes fit a workgroup's LDS (all
  * eight up to nx 2400); four planes per pass up to nx 4800 (which = 3: two passes), two per pass beyond (four, or two). */
 int pic1dp_hip_moments(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
+
+/* ---- exact, order-independent velocity moments ------------------------------------
+ * The moments above with integer sums: fixed by the input and the markers alone, independent of launch shape, storage order
+ * of the markers and split over ranks.  The exactness is in the entry point, not in a mode: set_diag_sum and set_charge_sum
+ * do not affect these calls, and the checkpoint carries nothing of them.
+ *   Terms.  The very terms of pic1dp_hip_moments: for every valid marker i < np the deposit's wrap and locate,
+ *     a0 = wl * q, b0 = (1.0 - wl) * q, a_k = a_(k-1) * v, b_k alike, every product rounded on its own; a_k goes to cell ix,
+ *     b_k to cell ir.  The chain runs through powers a pass does not hold, so a term has the same bits whichever pass adds
+ *     it.  Tail slots do not count.
+ *   Quanta.  Term t of plane (q, k) becomes n = rint(t 2^-e[k]), one rounding to nearest even, with
+ *         e[k] = kb + k * kvm - 40          the same for q = p and q = w,
+ *     kb = ceil(log2 B_s), B_s the bound of pic1dp_hip_charge_quantum (kb = charge_quantum + 52), kvm = ceil(log2 v_max).
+ *     A term of 2^44 quanta or more, or a NaN, is not summed: it is counted per plane instead.  At the bounds |q| <= B_s
+ *     and |v| <= v_max a term is at most 2^40 quanta, so the loader's markers are always in range, with a factor 16 of
+ *     headroom for |q| |v|^k.
+ *   Sums.  The integers are summed exactly -- in the LDS, across workgroups, across passes, and across ranks by the host.
+ *     A bin's total is converted to double once (round to nearest even) and multiplied by 2^e[k].
+ *   Limbs.  limbs[((j * 4 + k) * 2 + h) * nx + ix] as int64: j counts the selected weight sets in output order (p first),
+ *     k is the power of v, h = 0 the hi limb, h = 1 the lo limb; a bin's total is hi 2^32 + lo quanta.  What
+ *     moments_local_exact hands out is NORMALISED, 0 <= lo < 2^32: the limbs themselves are fixed by the markers.  What
+ *     moments_convert accepts need not be: element-wise sums over ranks (MPI_Allreduce of MPI_INT64_T) are accepted.
+ * moments_quanta: e[4] of a species from the input alone.  Host only.
+ * moments_limbs_len: *n = 8 nx per selected weight set (which = 1, 2: 8 nx; 3: 16 nx).  Host only.
+ * moments_local_exact: this context's exact sums as limbs.  Validation, the rule for a noted push and "between time steps
+ *   nothing changes" are those of pic1dp_hip_moments.  No communicator is used.
+ * moments_convert: limbs -> out, laid out as pic1dp_hip_moments lays it out.  Host only.
+ * moments_exact: moments_local_exact followed by moments_convert, for one rank.
+ *   - Terms that were not summed: the call returns PIC1DP_ERR_ARG naming the species, the weight set, the power and the
+ *     count, and writes nothing to the caller's buffer.  The next call starts from zero counters: a counted error path, no
+ *     trap.  Markers the call cannot sum are the caller's to fix; pic1dp_hip_moments is unaffected.
+ *   - which & 2 on a full-f context or input, an unknown `which`, an unknown species and a null pointer are PIC1DP_ERR_ARG. */
+int pic1dp_hip_moments_quanta(const pic1dp_input *in, int32_t ispecies, int32_t log2_quantum[4]);
+int pic1dp_hip_moments_limbs_len(int32_t which, int32_t nx, int64_t *n);
+int pic1dp_hip_moments_local_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, int64_t *limbs);
+int pic1dp_hip_moments_convert(const pic1dp_input *in, int32_t ispecies, int32_t which, const int64_t *limbs, double *out);
+int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
 
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
@@ -726,7 +763,11 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 15: *launches = terms the passes of the exact diagnostics sum (set_diag_sum(1)) did not sum so far (counted
  * when a pass's results are first handed out), *ms = 0;
  * which = 16: *launches = passes of pic1dp_hip_moments (k_moments) launched so far, *ms = their accumulated device
- * milliseconds while kernel stats were enabled */
+ * milliseconds while kernel stats were enabled;
+ * which = 17: *launches = passes of pic1dp_hip_moments_exact / _moments_local_exact (k_moments_exact) launched so far,
+ * *ms = their accumulated device milliseconds while kernel stats were enabled;
+ * which = 18: *launches = terms those passes did not sum so far (2^44 quanta or more, or NaN; each call that met some
+ * returned PIC1DP_ERR_ARG), *ms = 0 */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

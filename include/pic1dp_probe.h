@@ -115,6 +115,9 @@ int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, dou
  * p, bit 1 w), powers of v (bit k: v^k), first plane in the output, planes}.  out holds 3 + 8 * 4 words.  Nonzero: null
  * argument. */
 int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]);
+/* ... and of one pic1dp_hip_moments_exact call (launch_policy.hpp moments_plan_exact): the same words; only `blocks`
+ * differs, max(1, min(num_cu, ceil(np / 2^17))). */
+int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]);
 
 /* What pic1dp_hip_create decides before its first allocation (pic1dp_amd/csrc/context_plan.hpp plan_context), on the HOST,
  * for an input, a layout and the three requests of the settings that bear on it (0: none): PIC1DP_PRED_KIND,

@@ -165,6 +165,11 @@ SIGNATURES = {
     "pic1dp_hip_ptcldist_finish": [_P, C.c_int32, _P, _P, _P, _P, _P, _P],
     "pic1dp_hip_kernel_bytes": [_P, C.c_int32, _D, _D, _D, C.c_char_p, C.c_int32],
     "pic1dp_hip_moments": [_P, C.c_int32, C.c_int32, _P],
+    "pic1dp_hip_moments_quanta": [_INP, C.c_int32, C.POINTER(C.c_int32)],
+    "pic1dp_hip_moments_limbs_len": [C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_moments_local_exact": [_P, C.c_int32, C.c_int32, _P],
+    "pic1dp_hip_moments_convert": [_INP, C.c_int32, C.c_int32, _P, _P],
+    "pic1dp_hip_moments_exact": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

@@ -993,7 +993,18 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 16) return fail(PIC1DP_ERR_ARG, "which must be 0..16");
+  if (which < 0 || which > 18) return fail(PIC1DP_ERR_ARG, "which must be 0..18");
+  if (which == 18) {  // the exact moments: terms their passes did not sum so far (each call that met some returned PIC1DP_ERR_ARG)
+    if (launches) *launches = c->moments_exact_rejected;
+    if (ms) *ms = 0.0;
+    return PIC1DP_OK;
+  }
+  if (which == 17) {  // passes of pic1dp_hip_moments_exact / _local_exact (k_moments_exact) so far; *ms: their device time while kernel stats were enabled
+    if (int rc = ev_resolve(c)) return rc;
+    if (ms) *ms = c->acc_ms[kTagMomentsExact];
+    if (launches) *launches = c->moments_exact_passes;
+    return PIC1DP_OK;
+  }
   if (which == 16) {  // passes of pic1dp_hip_moments (k_moments) launched so far; *ms: their device time while kernel stats were enabled
     if (int rc = ev_resolve(c)) return rc;
     if (ms) *ms = c->acc_ms[kTagMoments];

@@ -7,7 +7,7 @@
 //   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
-//   capi_diag.cpp      diagnostics of output_all; the velocity moments on the field grid (pic1dp_hip_moments)
+//   capi_diag.cpp      diagnostics of output_all; the velocity moments on the field grid (pic1dp_hip_moments, _moments_exact)
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
 //   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
@@ -56,7 +56,7 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kNumTags = 128;
+              kTagMoments = 107, kTagMomentsExact = 108, kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
@@ -262,6 +262,11 @@ struct pic1dp_ctx {
   // pic1dp_hip_moments (capi_diag.cpp): the planes [8][nx] on the device and their pinned copy, allocated at the first call
   double *d_mom = nullptr, *h_mom = nullptr;
   int64_t moments_passes = 0;              // k_moments passes launched so far (kernel_stats 16)
+  // pic1dp_hip_moments_exact / _local_exact (capi_diag.cpp): the limbs [8][2][nx] and the 8 counters of terms not summed
+  // on the device, and their pinned copy, allocated at the first call
+  long long *d_momfx = nullptr, *h_momfx = nullptr;
+  int64_t moments_exact_passes = 0;        // k_moments_exact passes launched so far (kernel_stats 17)
+  int64_t moments_exact_rejected = 0;      // terms they did not sum so far (kernel_stats 18)
   int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field
   int chain_selftest = 0;                  // create()'s verdict on the serial sums through the matrix unit: 1 identical, 0 differs, -1 could not run
   int32_t itime = 0;

@@ -589,6 +589,17 @@ hipError_t launch_energy_sums_exact(const double *v, const double *p, const doub
 // call's passes; the pass adds its planes (ps.first_plane ...) with one global atomic per non-zero LDS word and workgroup
 hipError_t launch_moments(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
                           double *out, const MomentsPass &ps, int dyn_tail, hipStream_t st);
+// The exact kind of the moments (kernels_moments.hip k_moments_exact; the definition: include/pic1dp_hip.h
+// pic1dp_hip_moments_exact): a pass adds whole quanta into acc = the call's limbs [sets selected][4][2][nx] (hi row, lo row,
+// as FxArgs) and counts the terms it does not sum (DIAG_FX_LIMIT quanta or more, NaN) in rej = [sets selected][4].  Both are
+// zeroed by the caller before a call's passes; launch_moments_exact moves them to the pass's first weight set.
+struct MomentsFxArgs {
+  long long *acc, *rej;
+  double inv_q[4];   // 2^-e[k], by power of v
+};
+// ps: a pass of moments_plan_exact (its bytes are the planes as 64-bit words)
+hipError_t launch_moments_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
+                                const MomentsFxArgs &a, const MomentsPass &ps, int dyn_tail, hipStream_t st);
 // The state digest of one species (kernels_digest.hip; the definition: include/pic1dp_hip.h pic1dp_hip_state_digest).
 // Array k (0 x, 1 v, 2 w, 3 p): slot i < np is read from cur[k] (the current particle set), slot i >= np from first[k]
 // (set 0, where the tail slots live); out[k] += sum of the mixed words of slots [0, nalloc) (64-bit integer atomics).

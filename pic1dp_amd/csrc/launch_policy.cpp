@@ -172,6 +172,14 @@ MomentsPlan moments_plan(int nx, int which, int deltaf, int64_t np, int num_cu) 
   return m;
 }
 
+MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int num_cu) {
+  MomentsPlan m = moments_plan(nx, which, deltaf, np, num_cu);   // (a 64-bit word per (plane, cell): the bytes are the doubles')
+  // the exact diagnostics' rule (diag_launch, kind 1): a workgroup's final flush costs what a few trips cost
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(num_cu, (np + (int64_t{1} << 17) - 1) >> 17));
+  for (int i = 0; i < m.npass; ++i) m.pass[i].blocks = static_cast<int>(blocks);
+  return m;
+}
+
 DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
   DigestLaunch d{};
   d.threads = 256;

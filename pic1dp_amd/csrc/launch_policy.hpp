@@ -59,6 +59,10 @@ int tail_sum_blocks(int64_t ntail);
 // for; non-temporal loads once the arrays the pass reads (x, v and p and / or w: 24 or 32 B per marker) exceed the
 // threshold of diag_launch.  npass = 0: an unknown `which`, w asked of a full-f run (deltaf = 0), or nx out of range.
 MomentsPlan moments_plan(int nx, int which, int deltaf, int64_t np, int num_cu);
+// The passes of pic1dp_hip_moments_exact (k_moments_exact): groups, bytes (one 64-bit word per plane and cell), NT, weight
+// sets, powers and first planes are moments_plan's; the grid is max(1, min(num_cu, ceil(np / 2^17))) workgroups, the exact
+// diagnostics' rule: every workgroup flushes two global atomics per non-zero word at its end, which costs what a few trips cost.
+MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int num_cu);
 
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU

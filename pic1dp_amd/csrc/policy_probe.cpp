@@ -1,7 +1,7 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py, tests/test_moments_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 
 #include "../../include/pic1dp_probe.h"
@@ -57,9 +57,8 @@ extern "C" int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t n
   return 0;
 }
 
-extern "C" int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]) {
+static int moments_plan_words(const MomentsPlan &m, int64_t out[35]) {
   if (!out) return 1;
-  const MomentsPlan m = moments_plan(nx, which, deltaf, np, num_cu);
   for (int i = 0; i < 35; ++i) out[i] = 0;
   out[0] = m.npass, out[1] = m.selected, out[2] = m.group;
   for (int i = 0; i < m.npass; ++i) {
@@ -69,6 +68,15 @@ extern "C" int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t
     for (int k = 0; k < 8; ++k) out[3 + 8 * i + k] = v[k];
   }
   return 0;
+}
+
+extern "C" int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]) {
+  return moments_plan_words(moments_plan(nx, which, deltaf, np, num_cu), out);
+}
+
+extern "C" int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
+                                                    int64_t out[35]) {
+  return moments_plan_words(moments_plan_exact(nx, which, deltaf, np, num_cu), out);
 }
 
 extern "C" int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w,

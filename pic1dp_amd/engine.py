@@ -147,6 +147,27 @@ class Pic1dp:
         names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
         return {n: out[j] for j, n in enumerate(names)}
 
+    # -- exact, order-independent velocity moments ---------------
+    def moments_exact(self, ispecies=0, which=3):
+        """moments() with integer sums (include/pic1dp_hip.h pic1dp_hip_moments_exact): every term rounded once to whole
+        quanta 2^e[k] (moments_quanta), the integers summed exactly, every bin converted once.  The same dict as moments();
+        fixed by the input and the markers alone.  Pic1dpError naming species, weight set and power if a term lay at or
+        beyond 2^44 quanta (kernel_stats(18) counts them)."""
+        nsets = 2 if which == 3 else 1
+        out = np.empty((nsets, 4, self.inp.nx))
+        check(self.L.pic1dp_hip_moments_exact(self._ctx, int(ispecies), int(which), _ptr(out)))
+        names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
+        return {n: out[j] for j, n in enumerate(names)}
+
+    def moments_local_exact(self, ispecies=0, which=3):
+        """this context's exact sums as int64 limbs of shape (nsets, 4, 2, nx): [j, k, 0] the hi limb, [j, k, 1] the lo limb,
+        normalised (0 <= lo < 2^32); a bin's total is hi 2^32 + lo quanta.  Ranks: add element by element, then
+        moments_convert"""
+        nsets = 2 if which == 3 else 1
+        out = np.zeros((nsets, 4, 2, self.inp.nx), dtype=np.int64)
+        check(self.L.pic1dp_hip_moments_local_exact(self._ctx, int(ispecies), int(which), _ptr(out)))
+        return out
+
     # -- state digest, checkpoint and restart (DESIGN.md 2.13) -----------------
     def state_digest(self):
         """D[s][k] of the markers on the device (include/pic1dp_hip.h): uint64 [nspecies][4], k = 0 x, 1 v, 2 w, 3 p;
@@ -625,6 +646,34 @@ def diag_convert(inp, limbs, ispecies=0):
     sums, dist = np.empty(3), np.empty(3 * nxv + 3 * nvo)
     check(_lib.load().pic1dp_hip_diag_convert(C.byref(inp), int(ispecies), _ptr(a), _ptr(sums), _ptr(dist)))
     return sums, _split_dist(dist, nxv, nvo)
+
+
+def moments_quanta(inp, ispecies=0):
+    """e[k] = kb + k ceil(log2 v_max) - 40, k = 0 ... 3, the log2 quanta of the exact moments of a species, from the input
+    alone (no device); kb = charge_quantum + 52"""
+    e = (C.c_int32 * 4)()
+    check(_lib.load().pic1dp_hip_moments_quanta(C.byref(inp), int(ispecies), e))
+    return list(e)
+
+
+def moments_limbs_len(which, nx):
+    """int64 words of the limbs of the exact moments: 8 nx per selected weight set"""
+    n = C.c_int64()
+    check(_lib.load().pic1dp_hip_moments_limbs_len(int(which), int(nx), C.byref(n)))
+    return n.value
+
+
+def moments_convert(inp, limbs, which=3, ispecies=0):
+    """the dict of Pic1dp.moments() from limbs (nsets, 4, 2, nx) as moments_local_exact returns them, or their element-wise
+    sum over ranks (lo need not be normalised), from the input alone (no context, no device)"""
+    a = np.ascontiguousarray(limbs, dtype=np.int64)
+    nsets = 2 if which == 3 else 1
+    if a.size != nsets * 8 * inp.nx:
+        raise ValueError("limbs must have 8 * nx entries per selected weight set")
+    out = np.empty((nsets, 4, inp.nx))
+    check(_lib.load().pic1dp_hip_moments_convert(C.byref(inp), int(ispecies), int(which), _ptr(a), _ptr(out)))
+    names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
+    return {n: out[j] for j, n in enumerate(names)}
 
 
 def host_digest(a):

@@ -81,6 +81,46 @@ interface
     real(c_double), intent(inout) :: out(*)
     integer(c_int) :: ierr
   end function pic1dp_hip_moments
+  ! the exact kind: limbs(nx, 2, 4, sets selected) int64 (hi, lo), summed over ranks by the host (MPI_INT64_T), then converted
+  function pic1dp_hip_moments_quanta(inp, ispecies, log2_quantum) bind(C, name="pic1dp_hip_moments_quanta") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), intent(out) :: log2_quantum(4)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments_quanta
+  function pic1dp_hip_moments_limbs_len(which, nx, n) bind(C, name="pic1dp_hip_moments_limbs_len") result(ierr)
+    import
+    integer(c_int32_t), value :: which, nx
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments_limbs_len
+  function pic1dp_hip_moments_local_exact(ctx, ispecies, which, limbs) bind(C, name="pic1dp_hip_moments_local_exact") &
+      result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(inout) :: limbs(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments_local_exact
+  function pic1dp_hip_moments_convert(inp, ispecies, which, limbs, out) bind(C, name="pic1dp_hip_moments_convert") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(in) :: limbs(*)
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments_convert
+  function pic1dp_hip_moments_exact(ctx, ispecies, which, out) bind(C, name="pic1dp_hip_moments_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_moments_exact
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

@@ -52,6 +52,7 @@ SIGNATURES = {
     "pic1dp_probe_host_field_lds": [C.c_int32] * 7 + [_I64],
     "pic1dp_probe_host_diag_launch": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _I64],
     "pic1dp_probe_host_moments_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_moments_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
@@ -230,6 +231,16 @@ def host_moments_plan(nx, which, deltaf, np_, num_cu):
     out = (C.c_int64 * 35)()
     if load().pic1dp_probe_host_moments_plan(int(nx), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
         raise ValueError("pic1dp_probe_host_moments_plan")
+    return dict(selected=out[1], group=out[2],
+                passes=[dict(zip(MOMENTS_PASS_FIELDS, out[3 + 8 * i:11 + 8 * i])) for i in range(out[0])])
+
+
+def host_moments_plan_exact(nx, which, deltaf, np_, num_cu):
+    """the passes of one moments_exact call (csrc/launch_policy.hpp moments_plan_exact), as host_moments_plan returns them:
+    the same groups, bytes, NT, sets and powers; blocks = max(1, min(num_cu, ceil(np / 2^17)))"""
+    out = (C.c_int64 * 35)()
+    if load().pic1dp_probe_host_moments_plan_exact(int(nx), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_moments_plan_exact")
     return dict(selected=out[1], group=out[2],
                 passes=[dict(zip(MOMENTS_PASS_FIELDS, out[3 + 8 * i:11 + 8 * i])) for i in range(out[0])])
 
