@@ -210,6 +210,31 @@ int pic1dp_hip_particle_load(pic1dp_ctx *ctx);
  * 94-122,136-231) -- this is the reproducible form of that.  Block sizes, weights
  * and everything else are those of the npe-rank load. */
 int pic1dp_hip_set_seed_offset(pic1dp_ctx *ctx, int32_t offset);
+/* The initial condition made ON THE DEVICE: one streaming kernel pass per species writes x, v, p, w of
+ * every slot, nothing crosses PCIe and no sequential stream is drawn.  A marker is a function of its GLOBAL index alone:
+ * valid slot i of species s is global marker g = G0_s + i, G0_s = the valid markers of the reference blocks before the
+ * first one this process owns (pic1dp_hip_load_origin), so a run has the same markers whatever npe and nranks are.
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64)
+ *   kind 1, counter-based random: key = mix64(0x7069633164704C44 + 256 seed_offset + s), r(c) = mix64(key + (c + 1)
+ *     0x9E3779B97F4A7C15), u_v = (r(2g) >> 11) 2^-53, u_x = (r(2g + 1) >> 11) 2^-53   (seed_offset: set_seed_offset);
+ *   kind 2, quiet start: u_v = (bitrev64(g) >> 11) 2^-53, the base-2 radical inverse; u_x = R3(g) / 3^21, R3 the
+ *     reversal of the 21 base-3 digits of g, one IEEE division.  The same sequence for every species.  It needs
+ *     species_nparticle_init <= 3^21 = 10 460 353 203 and seed offset 0.
+ * Marker values: the imarker = 2 branch of particle_load in its operation order -- v = (u_v - 0.5) 2 v_max, p from the
+ * iptcldist formula (exp: the kernels' table-driven exp, within 1 ulp of libm), x = u_x lx, w = amp p with amp the sum
+ * over init_mode of cos, sin (the device's sincos), p += w in a nonlinear run.  Tail slots [np, nalloc) hold +0.0.
+ * The context is left as pic1dp_hip_particle_load leaves it (counts, optimisation counters, every owned block's
+ * generator initialised with no draw consumed, time 0, empty energy history).
+ * PIC1DP_ERR_ARG, with the context untouched: kind not 1 or 2; imarker = 1; kind 2 with a seed offset or with more than
+ * 3^21 markers of a species. */
+int pic1dp_hip_particle_load_device(pic1dp_ctx *ctx, int32_t kind);
+/* host only: G0 of species `ispecies` for the process `layout` describes (rank, nranks, npe; null: one rank, one block) */
+int pic1dp_hip_load_origin(const pic1dp_input *in, const pic1dp_layout *layout, int32_t ispecies, int64_t *g0);
+/* host only: u_v and u_x of the global markers g0 ... g0 + n - 1 of a species, as defined above (uv, ux: n doubles each).
+ * PIC1DP_ERR_ARG: kind not 1 or 2, ispecies outside [0, PIC1DP_MAX_SPECIES), seed_offset < 0 (as set_seed_offset), g0 < 0,
+ * kind 2 with seed_offset != 0 or g0 + n > 3^21 */
+int pic1dp_hip_host_load_uniforms(int32_t kind, int32_t seed_offset, int32_t ispecies, int64_t g0, int64_t n, double *uv,
+                                  double *ux);
 /* alternative for a host that ran the reference's own particle_load:
  * hand over HOST arrays of one species (n = allocated slots, np = valid) --
  * the VecGetArrayF90 view of particle_x/v/p/w (src/pic1dp_particle.F90:34-36) */
@@ -767,7 +792,9 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 17: *launches = passes of pic1dp_hip_moments_exact / _moments_local_exact (k_moments_exact) launched so far,
  * *ms = their accumulated device milliseconds while kernel stats were enabled;
  * which = 18: *launches = terms those passes did not sum so far (2^44 quanta or more, or NaN; each call that met some
- * returned PIC1DP_ERR_ARG), *ms = 0 */
+ * returned PIC1DP_ERR_ARG), *ms = 0;
+ * which = 19: *launches = passes of pic1dp_hip_particle_load_device (k_load, one per species and call) launched so far,
+ * *ms = their accumulated device milliseconds while kernel stats were enabled */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

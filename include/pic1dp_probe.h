@@ -134,6 +134,21 @@ int pic1dp_probe_host_context_plan(const pic1dp_input *in, const pic1dp_layout *
  * nt_threshold_full, diag_fx_margin_w}. */
 int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]);
 
+
+/* The launch shape of the on-device particle load's pass over nalloc slots (launch_policy.hpp load_launch), on the HOST:
+ * out = {workgroups, threads, non-temporal stores, markers a workgroup takes at a time}.  Workgroup b takes the chunks b,
+ * b + workgroups, ... of [0, nalloc).  Nonzero: null argument, nalloc < 0 or num_cu < 1. */
+int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int64_t out[4]);
+/* GB/s of the load kernel's stores WITHOUT its arithmetic: slots [0, n) of the four arrays of a tiled slab written as the
+ * kernel writes them (launch_policy.hpp load_launch: chunks of one tile group per workgroup, non-temporal above the
+ * threshold), reps launches between two events after one warm-up -- the stream k_load is measured against. */
+int pic1dp_probe_write_stream(int32_t device, int64_t n, int32_t reps, double *gbytes_per_s);
+/* The load kernel's index function (pic1dp_amd/csrc/device_load.hpp load_uniforms_dev) on the DEVICE over a list of n global
+ * marker indices g (kind 2: below 3^21): uv[i], ux[i] as k_load forms them for marker g[i] of species ispecies -- to be held
+ * against pic1dp_hip_host_load_uniforms bit for bit, beyond 2^32 too, without allocating that many markers. */
+int pic1dp_probe_load_uniforms(int32_t device, int32_t kind, int32_t seed_offset, int32_t ispecies, const int64_t *g, int64_t n,
+                               double *uv, double *ux);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,9 @@ SIGNATURES = {
     "pic1dp_hip_set_step_mode": [_P, C.c_int32],
     "pic1dp_hip_set_output_fusion": [_P, C.c_int32],
     "pic1dp_hip_set_seed_offset": [_P, C.c_int32],
+    "pic1dp_hip_particle_load_device": [_P, C.c_int32],
+    "pic1dp_hip_load_origin": [_INP, C.POINTER(Layout), C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_host_load_uniforms": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P],
     "pic1dp_hip_predict_kind": [_P, C.POINTER(C.c_int32)],
     "pic1dp_hip_get_field_half": [_P, _P],
     "pic1dp_hip_set_field_solver": [_P, C.c_int32],

@@ -550,18 +550,12 @@ int pic1dp_hip_local_sizes(pic1dp_ctx *c, int32_t isp, int64_t *nalloc, int64_t 
 }
 
 
-// Bounds for the prediction tiles' fixed-point sums (kernels_step.hip FxTiles) from markers the host holds: b[0] >= |q|
+// Bounds for the prediction tiles' fixed-point sums (kernels_step.hip FxTiles) from max |p|, max |w| of the markers: b[0] >= |q|
 // (w, or p in a full-f run), b[1] >= |c| = dt/2 |p - w| |f0'/f0|(v) |Z/m| -- the latter from max |p| + max |w| and a bound on
 // |f0'/f0| over the velocities markers can reach (src/pic1dp_interaction.F90:274-326: a blend of v / (T/m) and
 // (v - v0) / (T2/m); two-stream1's v - 2/v only away from v = 0).  They need not be tight, nor even hold: a term beyond
 // 16x its bound takes the kernel's double path, and the kernels raise the bounds to what they meet.
-static void fx_bounds_of(const pic1dp_input &in, int isp, const double *p, const double *w, int64_t n, double b[2]) {
-  double maxp = 0.0, maxw = 0.0;
-  for (int64_t i = 0; i < n; ++i) {
-    const double ap = std::fabs(p[i]), aw = std::fabs(w[i]);
-    if (ap > maxp) maxp = ap;   // (NaN compares false)
-    if (aw > maxw) maxw = aw;
-  }
+static void fx_bounds_from_maxima(const pic1dp_input &in, int isp, double maxp, double maxw, double b[2]) {
   const double m = std::fabs(in.species_mass[isp]), tm = std::fabs(in.species_temperature[isp]) / m,
                tm2 = std::fabs(in.species_temperature2[isp]) / m, v0 = std::fabs(in.species_v0[isp]);
   const double vm = 1.5 * in.v_max + v0;
@@ -572,6 +566,16 @@ static void fx_bounds_of(const pic1dp_input &in, int isp, const double *p, const
   const double cb = 0.5 * in.dt * (maxp + maxw) * d * std::fabs(in.species_charge[isp]) / m;
   b[0] = std::max(b[0], in.deltaf ? maxw : maxp);
   if (std::isfinite(cb)) b[1] = std::max(b[1], cb);
+}
+// ... from markers the host holds
+static void fx_bounds_of(const pic1dp_input &in, int isp, const double *p, const double *w, int64_t n, double b[2]) {
+  double maxp = 0.0, maxw = 0.0;
+  for (int64_t i = 0; i < n; ++i) {
+    const double ap = std::fabs(p[i]), aw = std::fabs(w[i]);
+    if (ap > maxp) maxp = ap;   // (NaN compares false)
+    if (aw > maxw) maxw = aw;
+  }
+  fx_bounds_from_maxima(in, isp, maxp, maxw, b);
 }
 
 // a species' bounds start over with new markers, and the count of terms past the bounds beside them
@@ -648,6 +652,89 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   c->itime = 0;
   c->time = 0.0;
   c->hist_count = 0;
+  return 0;
+}
+
+// The initial condition made on the device (load_seq.hpp; kernels_load.hip): particle_load's prologue and epilogue around
+// one k_load pass per species instead of the host loop.  Everything that can refuse the call comes first.
+int pic1dp_hip_particle_load_device(pic1dp_ctx *c, int32_t kind) {
+  CHECK_CTX(c);
+  const pic1dp_input &in = c->in;
+  if (const char *why = load_refusal(in, kind, c->seed_offset)) return fail(PIC1DP_ERR_ARG, "%s", why);
+  const ContextPlan &P = c->plan;
+  std::vector<Multirand> rng(static_cast<size_t>(P.nblk));  // remove / split draw from the blocks' streams, as after particle_load
+  for (int b = 0; b < P.nblk; ++b)
+    if (int rc = init_block_rng(in, P.blk0 + b + c->seed_offset, rng[b])) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->d_loadmax) HIP_TRY(c->mem.alloc(&c->d_loadmax, 2 * static_cast<size_t>(PIC1DP_MAX_SPECIES)));  // (the last thing that can refuse)
+  if (int rc = materialize_cd(c)) return rc;  // deposits of the old markers are consumed, not mixed with the new ones
+  if (c->owed == Owed::AdoptHalfField)
+    if (int rc = rebuild_half_step_chargeden(c)) return rc;
+  HIP_TRY(hipStreamSynchronize(c->st));  // kernels of an earlier run may still be writing the arrays
+  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;
+  c->state_version++;
+  const int ns = in.nspecies;
+  HIP_TRY(hipMemsetAsync(c->d_loadmax, 0, sizeof(unsigned long long) * 2 * PIC1DP_MAX_SPECIES, c->st));
+  c->blk_np = P.blk_np;
+  for (int s = 0; s < ns; ++s) c->sp[s].np = P.np[s];
+  c->imerge = P.imerge, c->iremove = P.iremove, c->isplit = P.isplit;
+  c->rng_ready = false;
+  for (int s = 0; s < ns; ++s) {
+    Species &S = c->sp[s];
+    LoadArgs a{};
+    a.x = S.set[0].x, a.v = S.set[0].v, a.w = S.set[0].w, a.p = S.p;
+    a.np = S.np, a.nalloc = S.nalloc;
+    a.g0 = static_cast<unsigned long long>(load_origin(in, s, P.blk0, P.npe));
+    a.key = load_key(c->seed_offset, s);
+    a.maxpw = c->d_loadmax + 2 * s;
+    a.k = make_load_const(in, s);
+    Span sp(c, kTagLoad, c->stats_on);
+    if (sp.rc) return sp.rc;
+    HIP_TRY(launch_load(a, kind, in.iptcldist, in.linear == 0, load_launch(S.nalloc, c->num_cu), c->st));
+    if (int rc = sp.end()) return rc;
+    c->load_passes++;
+  }
+  unsigned long long hmax[2 * PIC1DP_MAX_SPECIES];
+  HIP_TRY(hipMemcpyAsync(hmax, c->d_loadmax, sizeof hmax, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  for (int s = 0; s < ns; ++s) {
+    double mx[2], b[2] = {0.0, 0.0};
+    std::memcpy(mx, &hmax[2 * s], sizeof mx);
+    fx_bounds_from_maxima(in, s, mx[0], mx[1], b);
+    if (int rc = seed_fx_bounds(c->sp[s], b)) return rc;
+  }
+  for (int b = 0; b < P.nblk; ++b) c->blk_rng[b] = rng[b];
+  c->rng_ready = true;
+  diag_void_bounds(c);  // (new markers)
+  c->cur = 0;
+  c->loaded = true;
+  c->itime = 0;
+  c->time = 0.0;
+  c->hist_count = 0;
+  return 0;
+}
+
+int pic1dp_hip_load_origin(const pic1dp_input *in, const pic1dp_layout *layout, int32_t isp, int64_t *g0) {
+  if (!in || !g0) return fail(PIC1DP_ERR_ARG, "null argument");
+  pic1dp_layout one{0, 1, 1, -1};
+  const pic1dp_layout &lay = layout ? *layout : one;
+  if (int rc = validate(*in, lay)) return rc;
+  if (isp < 0 || isp >= in->nspecies) return fail(PIC1DP_ERR_ARG, "bad species index");
+  const int npe = lay.npe > 0 ? lay.npe : lay.nranks;
+  *g0 = load_origin(*in, isp, lay.rank * (npe / lay.nranks), npe);
+  return 0;
+}
+
+int pic1dp_hip_host_load_uniforms(int32_t kind, int32_t seed_offset, int32_t isp, int64_t g0, int64_t n, double *uv, double *ux) {
+  if (kind != LOAD_RANDOM && kind != LOAD_QUIET) return fail(PIC1DP_ERR_ARG, "load kind must be 1 (counter-based random) or 2 (quiet start)");
+  if (isp < 0 || isp >= PIC1DP_MAX_SPECIES) return fail(PIC1DP_ERR_ARG, "bad species index");
+  if (seed_offset < 0) return fail(PIC1DP_ERR_ARG, "seed offset < 0");
+  if (!uv || !ux || n < 0 || g0 < 0 || g0 > INT64_MAX - n) return fail(PIC1DP_ERR_ARG, "bad range or null array");
+  if (kind == LOAD_QUIET && seed_offset != 0) return fail(PIC1DP_ERR_ARG, "a quiet start (kind 2) is one sequence: it takes no seed offset");
+  if (kind == LOAD_QUIET && static_cast<uint64_t>(g0 + n) > LOAD_R3_SPAN)
+    return fail(PIC1DP_ERR_ARG, "a quiet start (kind 2) serves at most 3^21 markers per species");
+  const uint64_t key = load_key(seed_offset, isp);
+  for (int64_t i = 0; i < n; ++i) load_uniforms(kind, key, static_cast<uint64_t>(g0 + i), &uv[i], &ux[i]);
   return 0;
 }
 
@@ -993,7 +1080,13 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 18) return fail(PIC1DP_ERR_ARG, "which must be 0..18");
+  if (which < 0 || which > 19) return fail(PIC1DP_ERR_ARG, "which must be 0..19");
+  if (which == 19) {  // passes of pic1dp_hip_particle_load_device (k_load) so far; *ms: their device time while kernel stats were enabled
+    if (int rc = ev_resolve(c)) return rc;
+    if (ms) *ms = c->acc_ms[kTagLoad];
+    if (launches) *launches = c->load_passes;
+    return PIC1DP_OK;
+  }
   if (which == 18) {  // the exact moments: terms their passes did not sum so far (each call that met some returned PIC1DP_ERR_ARG)
     if (launches) *launches = c->moments_exact_rejected;
     if (ms) *ms = 0.0;

@@ -56,7 +56,7 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kTagMomentsExact = 108, kNumTags = 128;
+              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
@@ -200,6 +200,8 @@ struct pic1dp_ctx {
   uint64_t eh_version = 0;         // state_version d_Eh has been predicted for (step() path)
   uint64_t field_version = 1, eh_field_version = 0, modes_field_version = 0;  // who wrote d_E last
   double *d_stage = nullptr;  // contiguous staging buffer between host arrays and the tiled marker arrays
+  unsigned long long *d_loadmax = nullptr;  // [nspecies][2] bit patterns of max |p|, max |w| of a device load (capi.cpp; allocated at the first one)
+  int64_t load_passes = 0;                 // k_load passes launched so far (kernel_stats 19)
   unsigned long long *d_digest = nullptr;  // [nspecies][4] the state digest's words (capi_checkpoint.cpp; allocated at the first digest)
   double *d_Eh = nullptr;  // field after the first sub-step of the last whole-step call
   // The reference's three call sites at whole-step cost (see "lazy call sites"

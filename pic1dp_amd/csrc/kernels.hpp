@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pic1dp_hip.h"
+#include "load_seq.hpp"
 
 #include <cstdint>
 #include <cstdlib>
@@ -609,6 +610,26 @@ struct DigestArgs {
   unsigned long long *out;   // [4] device words
 };
 hipError_t launch_state_digest(const DigestArgs &a, const DigestLaunch &dl, hipStream_t st);
+// The on-device particle load of one species (kernels_load.hip k_load; the definition: load_seq.hpp): one
+// streaming pass over slots [0, nalloc) of set 0's arrays.  Slot i < np is global marker g0 + i; slots beyond hold +0.0.
+// maxpw[0], maxpw[1] <- max with the bit patterns of max |p|, max |w| over the valid markers (non-negative doubles order as
+// unsigned integers); zeroed by the caller.
+struct LoadArgs {
+  double *x, *v, *w, *p;
+  int64_t np, nalloc;
+  unsigned long long g0, key;   // key: load_key(seed offset, species) (kind 1)
+  unsigned long long *maxpw;    // [2] device words
+  LoadConst k;
+};
+// launch shape of the load's pass (launch_policy.hpp load_launch)
+struct LoadLaunch {
+  int blocks, threads;
+  bool nt;        // non-temporal stores
+};
+// markers a workgroup of k_load takes at a time: one tile group, so that the four arrays' tiles are written together
+constexpr int64_t LOAD_CHUNK = TILE_LOG2 ? TILE : 4096;
+hipError_t launch_load(const LoadArgs &a, int kind, int iptcldist, bool nonlinear, const LoadLaunch &ll, hipStream_t st);
+
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

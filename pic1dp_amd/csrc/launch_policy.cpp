@@ -189,6 +189,15 @@ DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
   return d;
 }
 
+LoadLaunch load_launch(int64_t nalloc, int num_cu) {
+  LoadLaunch l{};
+  l.threads = 256;
+  l.nt = 32.0 * static_cast<double>(nalloc) > 288.0 * 1048576.0;
+  const int64_t nchunk = (nalloc + LOAD_CHUNK - 1) / LOAD_CHUNK;
+  l.blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(static_cast<int64_t>(num_cu) * 8, nchunk)));
+  return l;
+}
+
 int tail_sum_blocks(int64_t ntail) {
   return ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
 }

@@ -70,4 +70,10 @@ MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int nu
 // ask for; non-temporal loads above the threshold of diag_launch
 DigestLaunch digest_launch(int64_t nalloc, int num_cu);
 
+// ---- the on-device particle load (kernels_load.hip) ----
+// one streaming pass that writes the nalloc slots of a species: workgroups of 256 threads that take whole chunks of
+// LOAD_CHUNK markers (a tile group: 128 KiB of the slab in one piece), eight per CU, never more than there are chunks, at
+// least one; non-temporal stores once the bytes written exceed the threshold of diag_launch
+LoadLaunch load_launch(int64_t nalloc, int num_cu);
+
 }  // namespace pic1dp

@@ -1,7 +1,7 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 
 #include "../../include/pic1dp_probe.h"
@@ -54,6 +54,16 @@ extern "C" int pic1dp_probe_host_diag_launch(int32_t kind, int64_t np, int32_t n
   out[3] = static_cast<int64_t>(d.bytes);
   out[4] = d.nt;
   out[5] = tail_sum_blocks(ntail);
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int64_t out[4]) {
+  if (!out || nalloc < 0 || num_cu < 1) return 1;
+  const LoadLaunch l = load_launch(nalloc, num_cu);
+  out[0] = l.blocks;
+  out[1] = l.threads;
+  out[2] = l.nt;
+  out[3] = LOAD_CHUNK;
   return 0;
 }
 

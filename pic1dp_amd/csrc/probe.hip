@@ -14,7 +14,9 @@
 #include "check_values.hpp"
 #include "device_diag.hpp"
 #include "device_fx.hpp"
+#include "device_load.hpp"
 #include "device_math.hpp"
+#include "launch_policy.hpp"
 
 namespace pic1dp {
 
@@ -252,6 +254,56 @@ hipError_t launch_dlnf0_array(const SpeciesConst &c, const double *v, double *y,
 }
 
 }  // namespace
+
+namespace {
+// the load kernel's index function (device_load.hpp load_uniforms_dev) over a list of global marker indices
+template <int KIND>
+__global__ void k_load_uniforms(unsigned long long key, const unsigned long long *g, int64_t n, double *uv, double *ux) {
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+    load_uniforms_dev<KIND>(key, g[i], uv[i], ux[i]);
+}
+}  // namespace
+
+hipError_t launch_load_uniforms(int kind, unsigned long long key, const unsigned long long *g, int64_t n, double *uv, double *ux,
+                                hipStream_t st) {
+  const int blocks = static_cast<int>(n < 256 * 1024 ? (n + 255) / 256 : 1024);
+  if (kind == LOAD_RANDOM)
+    hipLaunchKernelGGL(k_load_uniforms<LOAD_RANDOM>, dim3(blocks), dim3(256), 0, st, key, g, n, uv, ux);
+  else
+    hipLaunchKernelGGL(k_load_uniforms<LOAD_QUIET>, dim3(blocks), dim3(256), 0, st, key, g, n, uv, ux);
+  return hipGetLastError();
+}
+
+namespace {
+// the load kernel's stores without its arithmetic: slots [0, n) of the four arrays of a tiled slab, a chunk of LOAD_CHUNK
+// markers (one tile group) per workgroup at a time, pairs as double2 -- the write stream k_load is measured against
+template <bool NT>
+__global__ void __launch_bounds__(256) k_write_stream(double *slab, int64_t as, int64_t n) {   // as: slab_array_stride
+  double2 *x = reinterpret_cast<double2 *>(slab), *v = reinterpret_cast<double2 *>(slab + as),
+          *w = reinterpret_cast<double2 *>(slab + 2 * as), *p = reinterpret_cast<double2 *>(slab + 3 * as);
+  const int64_t nchunk = (n + LOAD_CHUNK - 1) / LOAD_CHUNK, npair = n >> 1;
+  for (int64_t t = blockIdx.x; t < nchunk; t += gridDim.x)
+    for (int jj = threadIdx.x; jj < static_cast<int>(LOAD_CHUNK / 2); jj += blockDim.x) {
+      const int64_t j = t * (LOAD_CHUNK / 2) + jj;
+      if (j >= npair) break;
+      const int64_t o = tidx2(j);
+      const double a = static_cast<double>(j);
+      st2t<NT>(x + o, a, a);
+      st2t<NT>(v + o, a, a);
+      st2t<NT>(w + o, a, a);
+      st2t<NT>(p + o, a, a);
+    }
+}
+}  // namespace
+
+hipError_t launch_write_stream(double *slab, int64_t n, int blocks, bool nt, hipStream_t st) {
+  const int64_t as = slab_array_stride(n + 2);
+  if (nt)
+    hipLaunchKernelGGL(k_write_stream<true>, dim3(blocks), dim3(256), 0, st, slab, as, n);
+  else
+    hipLaunchKernelGGL(k_write_stream<false>, dim3(blocks), dim3(256), 0, st, slab, as, n);
+  return hipGetLastError();
+}
 
 hipError_t launch_exp_array(const double *x, double *y, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_exp_array, dim3(1024), dim3(256), 0, st, x, y, n);
@@ -491,6 +543,47 @@ int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n) {
   PROBE_TRY(launch_exp_array(dx, dx + n, n, nullptr));
   PROBE_TRY(hipDeviceSynchronize());
   PROBE_TRY(hipMemcpy(y, dx + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pic1dp_probe_write_stream(int32_t device, int64_t n, int32_t reps, double *gbytes_per_s) {
+  if (!gbytes_per_s || n < 2 || reps < 1) return pfail("bad argument");
+  PROBE_TRY(hipSetDevice(device));
+  const LoadLaunch ll = load_launch(n, num_cu(device));
+  DevBuf d;
+  PROBE_TRY(hipMalloc(&d.p, sizeof(double) * static_cast<size_t>(slab_doubles(n + 2))));
+  double *slab = static_cast<double *>(d.p);
+  Events ev;
+  PROBE_TRY(hipEventCreate(&ev.a));
+  PROBE_TRY(hipEventCreate(&ev.b));
+  PROBE_TRY(launch_write_stream(slab, n, ll.blocks, ll.nt, nullptr));  // warm-up
+  PROBE_TRY(hipEventRecord(ev.a, nullptr));
+  for (int r = 0; r < reps; ++r) PROBE_TRY(launch_write_stream(slab, n, ll.blocks, ll.nt, nullptr));
+  PROBE_TRY(hipEventRecord(ev.b, nullptr));
+  PROBE_TRY(hipEventSynchronize(ev.b));
+  float ms = 0.f;
+  PROBE_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+  *gbytes_per_s = 32.0 * static_cast<double>(n & ~int64_t{1}) * reps / (ms * 1e-3) / 1e9;
+  return 0;
+}
+
+int pic1dp_probe_load_uniforms(int32_t device, int32_t kind, int32_t seed_offset, int32_t ispecies, const int64_t *g, int64_t n,
+                               double *uv, double *ux) {
+  if (!g || !uv || !ux || n < 0 || (kind != LOAD_RANDOM && kind != LOAD_QUIET) || ispecies < 0 || ispecies >= PIC1DP_MAX_SPECIES || seed_offset < 0)
+    return pfail("bad argument");
+  for (int64_t i = 0; i < n; ++i)
+    if (g[i] < 0 || (kind == LOAD_QUIET && static_cast<uint64_t>(g[i]) >= LOAD_R3_SPAN)) return pfail("marker index out of range");
+  if (n == 0) return 0;
+  PROBE_TRY(hipSetDevice(device));
+  DevBuf d;
+  PROBE_TRY(hipMalloc(&d.p, sizeof(double) * 3 * static_cast<size_t>(n)));
+  double *duv = static_cast<double *>(d.p), *dux = duv + n;
+  unsigned long long *dg = reinterpret_cast<unsigned long long *>(dux + n);
+  PROBE_TRY(hipMemcpy(dg, g, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+  PROBE_TRY(launch_load_uniforms(kind, load_key(seed_offset, ispecies), dg, n, duv, dux, nullptr));
+  PROBE_TRY(hipDeviceSynchronize());
+  PROBE_TRY(hipMemcpy(uv, duv, sizeof(double) * n, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(ux, dux, sizeof(double) * n, hipMemcpyDeviceToHost));
   return 0;
 }
 

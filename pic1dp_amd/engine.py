@@ -106,6 +106,11 @@ class Pic1dp:
     def particle_load(self):
         check(self.L.pic1dp_hip_particle_load(self._ctx))
 
+    def particle_load_device(self, kind=2):
+        """the initial condition made on the GPU, every marker a function of its global index (so the same markers whatever
+        npe and nranks): kind 1 counter-based random, 2 quiet start (bit-reversed v, base-3 reversed x)"""
+        check(self.L.pic1dp_hip_particle_load_device(self._ctx, int(kind)))
+
     def set_seed_offset(self, offset):
         """ensemble member: reference block b of the next particle_load draws from RNG stream mype = b + offset
         (0: the reference's constant-seed run)"""
@@ -682,6 +687,21 @@ def host_digest(a):
     out = C.c_uint64()
     check(_lib.load().pic1dp_hip_host_digest(_ptr(a), a.size, C.byref(out)))
     return int(out.value)
+
+
+def load_origin(inp, ispecies=0, rank=0, nranks=1, npe=0):
+    """global index of the first valid marker of species `ispecies` that the process (rank, nranks, npe) owns under
+    particle_load_device: the valid markers of the reference blocks before its first one (host only, no device)"""
+    lay, g0 = Layout(rank, nranks, npe, -1), C.c_int64()
+    check(_lib.load().pic1dp_hip_load_origin(C.byref(inp), C.byref(lay), int(ispecies), C.byref(g0)))
+    return g0.value
+
+
+def load_uniforms(kind, g0, n, seed_offset=0, ispecies=0):
+    """(u_v, u_x) of the global markers g0 ... g0 + n - 1 under particle_load_device(kind), computed on the host"""
+    uv, ux = np.empty(int(n)), np.empty(int(n))
+    check(_lib.load().pic1dp_hip_host_load_uniforms(int(kind), int(seed_offset), int(ispecies), int(g0), int(n), _ptr(uv), _ptr(ux)))
+    return uv, ux
 
 
 def checkpoint_info(path):

@@ -241,6 +241,31 @@ interface
     type(c_ptr), value :: ctx
     integer(c_int) :: ierr
   end function pic1dp_hip_particle_load
+  function pic1dp_hip_particle_load_device(ctx, kind) bind(C, name="pic1dp_hip_particle_load_device") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: kind
+    integer(c_int) :: ierr
+  end function pic1dp_hip_particle_load_device
+  function pic1dp_hip_load_origin(inp, layout, ispecies, g0) bind(C, name="pic1dp_hip_load_origin") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    type(pic1dp_layout_t), intent(in) :: layout
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), intent(out) :: g0
+    integer(c_int) :: ierr
+  end function pic1dp_hip_load_origin
+  function pic1dp_hip_host_load_uniforms(kind, seed_offset, ispecies, g0, n, uv, ux) bind(C, name="pic1dp_hip_host_load_uniforms") result(ierr)
+    import
+    integer(c_int32_t), value :: kind
+    integer(c_int32_t), value :: seed_offset
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), value :: g0
+    integer(c_int64_t), value :: n
+    real(c_double), intent(inout) :: uv(*)
+    real(c_double), intent(inout) :: ux(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_host_load_uniforms
   function pic1dp_hip_particles_upload(ctx, ispecies, x, v, p, w, n, np) bind(C, name="pic1dp_hip_particles_upload") result(ierr)
     import
     type(c_ptr), value :: ctx

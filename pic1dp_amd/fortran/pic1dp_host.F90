@@ -34,6 +34,9 @@
 !                         (pic1dp_hip_checkpoint_read) and enters the time loop at the file's itime and time, without the
 !                         initial deposit, solve and record: with the exact sums (PIC1DP_CHARGE_SUM=exact,
 !                         PIC1DP_DIAG_SUM=exact) its records are byte for byte those the writing run wrote after step n.
+! PIC1DP_LOAD=host|random|quiet (an option of this host program; default host): the initial condition from the reference's
+! generator on the host (pic1dp_hip_particle_load), or made on the GPU from the markers' global indices
+! (pic1dp_hip_particle_load_device: kind 1 counter-based random, kind 2 quiet start) -- the same markers on any number of ranks.
 ! PIC1DP_HOST_PROFILE=1 prints the wall clock of the run split into the time loop's steps, output_all's
 ! diagnostics and the writes of pic1dp.out (the steps are then waited for, pic1dp_hip_sync, before the clock is read).
 program pic1dp_host
@@ -53,12 +56,27 @@ real(c_double) :: t_run0, t_loop0, t_a, steps_s, load_s
 character(len=8) :: buf
 character(len=512) :: dump_path, ckpt_path, restart_path
 integer :: stat, verbosity, fail_at, ckpt_at
+integer(c_int32_t) :: load_kind
+character(len=16) :: load_opt
 logical :: restart
 integer(c_int32_t) :: timer_mode
 logical :: fused, whole_step, batched, use_rccl, loop_profile
 integer(c_signed_char) :: handle(PIC1DP_XCHG_HANDLE_BYTES), comm_id(PIC1DP_COMM_ID_BYTES)
 integer(c_signed_char), allocatable :: handles(:)
 
+! PIC1DP_LOAD (an option of this host program): which load makes the markers; a word that is none of the three stops the run here
+load_kind = 0
+call get_environment_variable('PIC1DP_LOAD', load_opt, status=stat)   ! (status -1: longer than any of the three words)
+if (stat == 0 .or. stat == -1) then
+  if (stat == 0 .and. load_opt == 'random') then
+    load_kind = 1
+  else if (stat == 0 .and. load_opt == 'quiet') then
+    load_kind = 2
+  else if (stat /= 0 .or. load_opt /= 'host') then
+    write (*, '(a)') 'Error: PIC1DP_LOAD must be host, random or quiet'
+    stop 1
+  end if
+end if
 call input_fill(inp)
 call ranks_init()                           ! MPI_Comm_rank / MPI_Comm_size, src/pic1dp.F90:50-52
 lay = pic1dp_layout_t(ranks_rank, ranks_size, 0, -1)   ! one process per GPU (device = rank mod visible GPUs)
@@ -126,7 +144,8 @@ call get_environment_variable('PIC1DP_RESTART', restart_path, status=stat)
 restart = (stat == 0)
 
 t_run0 = output_wall()
-if (.not. restart) call pic1dp_hip_check(pic1dp_hip_particle_load(ctx), 'particle_load')
+if (.not. restart .and. load_kind == 0) call pic1dp_hip_check(pic1dp_hip_particle_load(ctx), 'particle_load')
+if (.not. restart .and. load_kind /= 0) call pic1dp_hip_check(pic1dp_hip_particle_load_device(ctx, load_kind), 'particle_load_device')
 if (output_profile) call pic1dp_hip_check(pic1dp_hip_sync(ctx), 'sync')
 load_s = output_wall() - t_run0
 call pic1dp_hip_check(pic1dp_hip_timers_enable(ctx, timer_mode), 'timers_enable')

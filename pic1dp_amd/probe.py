@@ -56,6 +56,9 @@ SIGNATURES = {
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
+    "pic1dp_probe_host_load_launch": [C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_write_stream": [C.c_int32, C.c_int64, C.c_int32, _D],
+    "pic1dp_probe_load_uniforms": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
 }
 PLAN_FIELDS = ("npe", "nblk", "blk0", "nalloc", "imerge", "iremove", "isplit", "gcopies", "gstride", "rho_set_doubles", "pred_kind",
                "pred_private", "pred_set_doubles", "pack_doubles", "tab_lds", "field_npe")
@@ -281,3 +284,27 @@ def host_settings():
     if load().pic1dp_probe_host_settings(iv, dv) != 0:
         raise ValueError("pic1dp_probe_host_settings")
     return dict(list(zip(SETTINGS_INTS, iv)) + list(zip(SETTINGS_DOUBLES, dv)))
+
+
+def host_load_launch(nalloc, num_cu=256):
+    """launch shape of the on-device particle load's pass: {blocks, threads, nt, chunk} (host arithmetic, no GPU)"""
+    out = (C.c_int64 * 4)()
+    if load().pic1dp_probe_host_load_launch(int(nalloc), num_cu, out) != 0:
+        raise RuntimeError("pic1dp_probe_host_load_launch: bad argument")
+    return dict(blocks=out[0], threads=out[1], nt=bool(out[2]), chunk=out[3])
+
+
+def load_uniforms(kind, g, seed_offset=0, ispecies=0, device=0):
+    """(u_v, u_x) of the global marker indices g as the load KERNEL's index function forms them (on the GPU)"""
+    g = np.ascontiguousarray(g, dtype=np.int64)
+    uv, ux = np.empty(g.size), np.empty(g.size)
+    _check(load().pic1dp_probe_load_uniforms(device, kind, seed_offset, ispecies, g.ctypes.data, g.size, uv.ctypes.data,
+                                             ux.ctypes.data))
+    return uv, ux
+
+
+def write_stream(n, reps=10, device=0):
+    """GB/s of the load kernel's stores without its arithmetic: the four arrays of a tiled slab of n slots written"""
+    g = C.c_double()
+    _check(load().pic1dp_probe_write_stream(device, int(n), reps, C.byref(g)))
+    return g.value
