@@ -34,7 +34,7 @@ PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_st
     ("exact_charge.cpp", [], "exact_charge"), ("capi_checkpoint.cpp", [], "capi_checkpoint"), ("checkpoint.cpp", [], "checkpoint")]
 PROBE_UNITS = [("probe.hip", [], "probe"), ("optcheck.cpp", [], "optcheck"), ("policy_probe.cpp", [], "policy_probe")]
 PROBE_SHARED = ["species", "hostcheck", "optimize", "multirand", "launch_policy", "settings", "context_plan", "loader", "load_seq"]      # objects of the product the probe library links as well
-HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_moments.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "loader.hpp",
+HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_moments.hpp", "device_sweep.hpp", "device_fxsum.hpp", "fx_limbs.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "loader.hpp",
            "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "launch_policy.hpp", "field_lds.hpp", "settings.hpp", "context_plan.hpp", "device_mem.hpp", "digest.hpp", "checkpoint.hpp", "moments_fx.hpp", "load_seq.hpp", "device_load.hpp",
            os.path.join("..", "..", "include", "pic1dp_hip.h"), os.path.join("..", "..", "include", "pic1dp_probe.h")]
 

@@ -3,6 +3,7 @@
 // grid (pic1dp_hip_moments; the exact kind: pic1dp_hip_moments_exact and its split phase), passes of their own that cache
 // nothing and change nothing.
 #include "ctx.hpp"
+#include "fx_limbs.hpp"
 #include "moments_fx.hpp"
 
 namespace pic1dp_host {
@@ -245,36 +246,31 @@ static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long
   return 0;
 }
 
-// limbs -> the raw sums of the pass: every bin's total converted once (fx_limbs_to_double) and times 2^e; the v
-// histograms are the integer row sums over ix of the planes.  dist: [3 nxv + 3 nv_opd] as ptcldist(finish = 0), or null
-static void dfx_convert(const pic1dp_input &in, const int32_t e[6], const long long *limbs, double *sums, double *dist) {
+// limbs -> the raw sums of the pass: every bin's total converted once (fx_limbs.hpp) and times 2^e; the v histograms are
+// the integer row sums over ix of the planes.  dist: [3 nxv + 3 nv_opd] as ptcldist(finish = 0), or null
+static void dfx_convert(const pic1dp_input &in, const int32_t e[6], const int64_t *limbs, double *sums, double *dist) {
   const int nxo = in.nx_opd, nvo = in.nv_opd;
   const size_t nxv = static_cast<size_t>(nxo) * nvo;
   for (int k = 0; k < 3 && dist; ++k) {
-    const long long *hi = limbs + 2 * k * nxv, *lo = hi + nxv;
+    const int64_t *hi = limbs + 2 * k * nxv, *lo = hi + nxv;
     const double q = std::ldexp(1.0, e[k]);
-    for (size_t i = 0; i < nxv; ++i) dist[k * nxv + i] = fx_limbs_to_double(hi[i], static_cast<unsigned long long>(lo[i])) * q;
+    fx_row_to_double(hi, lo, nxv, q, dist + k * nxv);
     for (int iv = 0; iv < nvo; ++iv) {
-      long long H = 0;
-      unsigned long long L = 0;   // (each bin normalised first: the row's lo sum stays below nx_opd 2^32)
-      for (int ix = 0; ix < nxo; ++ix) {
-        const unsigned long long l = static_cast<unsigned long long>(lo[static_cast<size_t>(iv) * nxo + ix]);
-        H += hi[static_cast<size_t>(iv) * nxo + ix] + static_cast<long long>(l >> 32);
-        L += l & 0xffffffffull;
-      }
-      dist[3 * nxv + static_cast<size_t>(k) * nvo + iv] = fx_limbs_to_double(H, L) * q;
+      int64_t H, L;
+      fx_row_sum(hi + static_cast<size_t>(iv) * nxo, lo + static_cast<size_t>(iv) * nxo, nxo, &H, &L);
+      fx_row_to_double(&H, &L, 1, q, dist + 3 * nxv + static_cast<size_t>(k) * nvo + iv);
     }
   }
   for (int k = 0; k < 3 && sums; ++k)
-    sums[k] = fx_limbs_to_double(limbs[6 * nxv + 2 * k], static_cast<unsigned long long>(limbs[6 * nxv + 2 * k + 1])) *
-              std::ldexp(1.0, e[3 + k]);
+    fx_row_to_double(limbs + 6 * nxv + 2 * k, limbs + 6 * nxv + 2 * k + 1, 1, std::ldexp(1.0, e[3 + k]), sums + k);
 }
 
 // what the calls of kind 1 serve from: the raw kinetic sums and / or histograms of species isp
 static int dfx_serve(pic1dp_ctx *c, int isp, bool reduced, double *sums, double *dist) {
   std::vector<long long> limbs;
   if (int rc = dfx_limbs_host(c, isp, reduced, limbs)) return rc;
-  dfx_convert(c->in, c->dfx_e[isp], limbs.data(), sums, dist);
+  static_assert(sizeof(long long) == sizeof(int64_t), "limbs are 64-bit");
+  dfx_convert(c->in, c->dfx_e[isp], reinterpret_cast<const int64_t *>(limbs.data()), sums, dist);
   return 0;
 }
 
@@ -728,9 +724,7 @@ int pic1dp_hip_diag_quanta(const pic1dp_input *in, int32_t ispecies, int32_t log
   const int kb = e + 52;  // |p|, |w| <= 2^kb
   const double v2 = in->v_max * in->v_max;
   if (!(v2 > 0.0) || !std::isfinite(v2)) return fail(PIC1DP_ERR_ARG, "v_max must be positive and finite");
-  int kv = 0;
-  const double f = std::frexp(v2, &kv);  // ceil(log2 v_max^2) = kv, or kv - 1 for a power of two
-  if (f == 0.5) kv -= 1;
+  const int kv = ceil_log2(v2);
   log2_quantum[0] = -40;
   log2_quantum[1] = log2_quantum[2] = kb - 40;
   log2_quantum[3] = kv - 52;
@@ -784,8 +778,7 @@ int pic1dp_hip_diag_convert(const pic1dp_input *in, int32_t isp, const int64_t *
   int32_t e[6];
   if (int rc = pic1dp_hip_diag_quanta(in, isp, e)) return rc;
   if (in->nx_opd < 1 || in->nv_opd < 2) return fail(PIC1DP_ERR_ARG, "nx_opd >= 1 and nv_opd >= 2 required");
-  static_assert(sizeof(long long) == sizeof(int64_t), "limbs are 64-bit");
-  dfx_convert(*in, e, reinterpret_cast<const long long *>(limbs), sums, dist);
+  dfx_convert(*in, e, limbs, sums, dist);
   if (sums && !in->deltaf) sums[2] = sums[1];
   return 0;
 }

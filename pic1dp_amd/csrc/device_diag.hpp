@@ -2,6 +2,7 @@
 // (ptcldist_one, with the cell stencil in its own text; ptcldist_one_exact on dist_stencil) and their finishes.  Shared by
 // k_ptcldist, k_ptcldist_exact (kernels_diag.hip) and the DIAG variant of k_step_full (kernels_step.hip)
 #pragma once
+#include "device_fxsum.hpp"
 #include "device_math.hpp"
 
 namespace pic1dp {
@@ -263,10 +264,10 @@ __device__ __forceinline__ void ptcldist_finish(const DistGeom &dg, const DistBi
 
 // ---------------------------------------------------------------------------
 // Kind 1 of the diagnostics sum (kernels.hpp DiagFxArgs): the same terms, each rounded once to whole
-// quanta, summed as integers.  A workgroup's LDS copy (LDS = true) holds ONE signed 64-bit word per bin, the three
-// planes interleaved as above; terms stay below 2^44 quanta and a bin receives at most 4 * 2^17 of them between two
-// flushes, so the word stays below 2^63.  The flush splits every word into (hi, lo 32 bits) and adds the two into
-// the global rows with non-returning integer atomics.  LDS = false adds a term's limbs straight into the global rows.
+// quanta, summed as integers (device_fxsum.hpp).  A workgroup's LDS copy (LDS = true) holds ONE signed 64-bit word per
+// bin, the three planes interleaved as above; that the word cannot overflow between two flushes is the window rule of
+// device_sweep.hpp.  The flush adds every word's limbs into the global (hi, lo) rows; LDS = false adds a term's limbs
+// straight into them.
 // The v histograms are not accumulated at all: they are the integer row sums of the planes, formed by the host.
 // ---------------------------------------------------------------------------
 struct DistBinsFx {
@@ -277,42 +278,38 @@ struct DistBinsFx {
 struct KinFx {
   unsigned long long lo[3] = {0ull, 0ull, 0ull}, hi[3] = {0ull, 0ull, 0ull};   // two-limb sums of this thread
 };
-__device__ __forceinline__ void glb_add_u64(unsigned long long *p, unsigned long long v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ unsigned long long *dfx_rejected(const DistBinsFx &b, int k) {
   return b.acc + 6 * static_cast<size_t>(b.nxv) + 6 + k;
 }
-// a 64-bit word of plane k, cell into the global (hi, lo 32 bits) rows
+// a 64-bit word of plane k, cell into the global (hi, lo 32 bits) rows.  Not fx_add_limbs: with LDS = false this runs twelve
+// times per marker, and a row's address formed before its limb is tested costs k_ptcldist_exact<false, ...> two VGPRs
 __device__ __forceinline__ void dfx_limbs_add(const DistBinsFx &b, int k, int cell, unsigned long long w) {
-  const unsigned long long lo = w & 0xffffffffull;
-  const unsigned long long hi = static_cast<unsigned long long>(static_cast<long long>(w) >> 32);
-  if (lo) glb_add_u64(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
-  if (hi) glb_add_u64(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
+  const unsigned long long lo = fx_lo(w), hi = fx_hi(w);
+  if (lo) fx_glb_add(b.acc + (2 * k + 1) * static_cast<size_t>(b.nxv) + cell, lo);
+  if (hi) fx_glb_add(b.acc + (2 * k) * static_cast<size_t>(b.nxv) + cell, hi);
 }
 template <bool LDS>
 __device__ __forceinline__ void dfx_bin_add(const DistBinsFx &b, int k, int cell, double term, double inv_q) {
-  const double t = __builtin_rint(term * inv_q);   // term 2^-e is exact: ONE rounding, to nearest even
-  if (!(fabs(t) < DIAG_FX_LIMIT)) {                // (NaN too) not summed: counted, reported by the host
-    glb_add_u64(dfx_rejected(b, k), 1ull);
+  unsigned long long n;
+  if (!fx_word44(term, inv_q, &n)) {   // not summed: counted, reported by the host
+    fx_glb_add(dfx_rejected(b, k), 1ull);
     return;
   }
-  // the integer t as two's complement (|t| < 2^44: the sum with 1.5 * 2^52 is exact, its low bits are t)
-  const unsigned long long n = static_cast<unsigned long long>(__double_as_longlong(t + 6755399441055744.0)) - 0x4338000000000000ull;
   if constexpr (LDS) {
     __hip_atomic_fetch_add(&b.s[3 * cell + k], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   } else {
     dfx_limbs_add(b, k, cell, n);
   }
 }
+// the kinetic sums take terms up to FX_LIMIT = 2^62 quanta: two limbs per thread, no LDS word
 __device__ __forceinline__ void dfx_kin_add(KinFx &s, const DistBinsFx &b, int k, double term, double inv_q) {
   long long n;
   if (!diag_fx_quantise(term, inv_q, FX_LIMIT, &n)) {
-    glb_add_u64(dfx_rejected(b, 3 + k), 1ull);
+    fx_glb_add(dfx_rejected(b, 3 + k), 1ull);
     return;
   }
-  s.lo[k] += static_cast<unsigned long long>(n) & 0xffffffffull;
-  s.hi[k] += static_cast<unsigned long long>(n >> 32);
+  s.lo[k] += fx_lo(static_cast<unsigned long long>(n));
+  s.hi[k] += fx_hi(static_cast<unsigned long long>(n));
 }
 // the kinetic terms of one marker slot (src/pic1dp_output.F90:126-151)
 template <bool DELTAF>
@@ -341,17 +338,13 @@ __device__ __forceinline__ void ptcldist_one_exact(double px, double pv, double 
 }
 // the workgroup's LDS copy into the global rows, zeroed on the way; the caller puts barriers around it
 __device__ __forceinline__ void dfx_flush(const DistBinsFx &b) {
-  const int n = 3 * b.nxv;
-  const int rot = static_cast<int>((static_cast<long long>(blockIdx.x) * n) / gridDim.x);
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    int j = i + rot;                                    // j: plane k, cell -- the order of the global rows
-    if (j >= n) j -= n;
+  rotated_words(3 * b.nxv, [&](int j) {                 // j: plane k, cell -- the order of the global rows
     const int k = j / b.nxv, cell = j - k * b.nxv;
     const unsigned long long w = b.s[3 * cell + k];
-    if (w == 0ull) continue;
+    if (w == 0ull) return;
     b.s[3 * cell + k] = 0ull;
     dfx_limbs_add(b, k, cell, w);
-  }
+  });
 }
 // the threads' two-limb kinetic sums over the workgroup (integers: any order), then one pair of global atomics per sum;
 // sK: six zeroed LDS words
@@ -376,7 +369,7 @@ __device__ __forceinline__ void dfx_kin_finish(const KinFx &sm, const DistBinsFx
     } else {
       w += sK[threadIdx.x + 1] >> 32;
     }
-    if (w) glb_add_u64(b.acc + 6 * static_cast<size_t>(b.nxv) + threadIdx.x, w);
+    if (w) fx_glb_add(b.acc + 6 * static_cast<size_t>(b.nxv) + threadIdx.x, w);
   }
 }
 

@@ -3,6 +3,7 @@
 // step that turns the integer accumulators into the species accumulators, and the overflow report.  The kernels:
 // device_math.hpp RhoFx (deposit, flush), kernels_field.hip k_fx_* (normalise, exchange, conversion).
 #include "ctx.hpp"
+#include "fx_limbs.hpp"
 
 namespace pic1dp_host {
 
@@ -103,9 +104,7 @@ int pic1dp_hip_charge_quantum(const pic1dp_input *in, int32_t ispecies, int32_t 
     *log2_quantum = -52;
     return 0;
   }
-  int k = 0;
-  const double f = std::frexp(b, &k);  // b = f 2^k, f in [0.5, 1): ceil(log2 b) = k, or k - 1 for a power of two
-  *log2_quantum = (f == 0.5 ? k - 1 : k) - 52;
+  *log2_quantum = ceil_log2(b) - 52;
   return 0;
 }
 

@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 // Environment variables.  The product library reads the fifteen of INTEGRATION.md section 6 with std::getenv: switches
 // between paths that exist for a functional reason (eager / lazy call sites, two passes / one, tiles / sums, the solve in a
@@ -251,6 +252,17 @@ hipError_t launch_kernel(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t 
   }
   hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
   return hipGetLastError();
+}
+
+// run-time bools as compile-time arguments: f(std::bool_constant...), one per bool
+template <class F>
+hipError_t with_bools(F &&f) {
+  return f();
+}
+template <class F, class... Bools>
+hipError_t with_bools(F &&f, bool first, Bools... rest) {
+  auto next = [&](auto B) { return with_bools([&](auto... r) { return f(B, r...); }, rest...); };
+  return first ? next(std::true_type{}) : next(std::false_type{});
 }
 
 struct FieldArgs {

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <type_traits>
 #include "device_math.hpp"
+#include "device_sweep.hpp"
 #include "launch_policy.hpp"
 
 namespace pic1dp {
@@ -57,45 +58,6 @@ k_cell_indices(const double *x, int64_t np, const GridConst g, int32_t *ixo,
 
 namespace {
 
-// A workgroup's rows of marker pairs (device_math.hpp pair_rows), the last dyn_tail / 16 of them drawn chunk by chunk by
-// its waves: with one workgroup of sixteen waves per CU, the waves that are done would idle a quarter of the CU each.
-// Pairs as double2 (the marker kernels' access shape), the NEXT trip's loads issued before this trip's work, non-temporal
-// loads where NT says so (round 5, below).  one(x, v, p, w) per marker; after_trip(k) once per trip, k the trips done.
-template <bool DELTAF, bool NT, class One, class After>
-__device__ __forceinline__ void pair_sweep(const double *x, const double *v, const double *p, const double *w, int64_t npair,
-                                           const PairRows &rows, unsigned *sDraw, One &&one, After &&after_trip) {
-  const double2 *x2 = reinterpret_cast<const double2 *>(x), *v2 = reinterpret_cast<const double2 *>(v);
-  const double2 *p2 = reinterpret_cast<const double2 *>(p), *w2 = reinterpret_cast<const double2 *>(w);
-  int k = 0;
-  int64_t j = rows.first + threadIdx.x;
-  bool have = rows.dealt > 0 || draw_chunk(rows, sDraw, j);
-  double2 X = make_double2(0.0, 0.0), V = X, P = X, W = X;
-  if (have && j < npair) {
-    const int64_t o = tidx2(j);
-    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
-    if constexpr (DELTAF) W = ld2t<NT>(w2 + o);
-  }
-  while (have) {
-    int64_t jn = j + rows.stride;
-    bool have_n = true;
-    if (++k >= rows.dealt) have_n = draw_chunk(rows, sDraw, jn);
-    double2 Xn = make_double2(0.0, 0.0), Vn = Xn, Pn = Xn, Wn = Xn;
-    if (have_n && jn < npair) {  // the next trip's loads are under way while this trip's atomics run
-      const int64_t o = tidx2(jn);
-      Xn = ld2t<NT>(x2 + o), Vn = ld2t<NT>(v2 + o), Pn = ld2t<NT>(p2 + o);
-      if constexpr (DELTAF) Wn = ld2t<NT>(w2 + o);
-    }
-    if (j < npair) {
-      one(X.x, V.x, P.x, W.x);
-      one(X.y, V.y, P.y, W.y);
-    }
-    after_trip(k);
-    X = Xn, V = Vn, P = Pn, W = Wn;
-    j = jn;
-    have = have_n;
-  }
-}
-
 // One pass over a species for everything output_all needs from the markers:
 // * the (x,v) and v histograms of output_ptcldist, src/pic1dp_output.F90:239-315:
 //   4-point bilinear weights on an nx_opd x nv_opd grid, markers with
@@ -135,23 +97,12 @@ k_ptcldist(const double *x, const double *v, const double *p, const double *w, i
   __syncthreads();
   DistSums sm;
   auto one = [&](double px, double pv, double pp, double pw) { ptcldist_one<LDS, DELTAF, FX>(px, pv, pp, pw, dg, b, sm, &fx); };
-  pair_sweep<DELTAF, NT>(x, v, p, w, np >> 1, pair_rows(np >> 1, dyn_tail), sDraw, one, [](int) {});
+  pair_sweep<true, DELTAF, NT>(x, v, p, w, np >> 1, pair_rows(np >> 1, dyn_tail), sDraw, one, [](int) {});
   if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // (after the pairs: the FP64 kinetic sums depend on the order)
     const int64_t i = tidx(np - 1);
     one(x[i], v[i], p[i], DELTAF ? w[i] : 0.0);
   }
   ptcldist_finish<LDS, DELTAF, FX>(dg, b, sm, scr, out, partial, &fx);
-}
-
-// run-time bools as compile-time arguments: f(std::bool_constant...), one per bool
-template <class F>
-hipError_t with_bools(F &&f) {
-  return f();
-}
-template <class F, class... Bools>
-hipError_t with_bools(F &&f, bool first, Bools... rest) {
-  auto next = [&](auto B) { return with_bools([&](auto... r) { return f(B, r...); }, rest...); };
-  return first ? next(std::true_type{}) : next(std::false_type{});
 }
 
 }  // namespace
@@ -180,11 +131,8 @@ hipError_t launch_ptcldist(const double *x, const double *v, const double *p, co
 namespace {
 
 // The sweep of k_ptcldist with integer sums: no max |p|, max |w| or overflow bookkeeping and no repeat pass (the quanta
-// come from the input), the kinetic sums reduced over the workgroup as integers.  LDS: the workgroup's copy is flushed
-// every DIAG_FX_WINDOW_TRIPS dealt trips and once at the end; the drawn rows are capped one below that, and the odd marker
-// falls into the first window, so a word sees fewer than 2^17 markers = 2^19 terms of less than 2^44 quanta between two
-// flushes.  The dealt trips are the same number for every thread of the workgroup, so the barriers around a flush inside
-// the sweep are met by all.
+// come from the input), the kinetic sums reduced over the workgroup as integers.  LDS: the workgroup's copy is flushed by the
+// window rule of device_sweep.hpp, with the odd last marker before the sweep.
 template <bool LDS, bool DELTAF, bool NT>
 __global__ void __launch_bounds__(1024)
 k_ptcldist_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const DistGeom dg,
@@ -205,18 +153,10 @@ k_ptcldist_exact(const double *x, const double *v, const double *p, const double
     const int64_t i = tidx(np - 1);
     one(x[i], v[i], p[i], DELTAF ? w[i] : 0.0);
   }
-  PairRows rows = pair_rows(np >> 1, dyn_tail);
-  {
-    const int waves = static_cast<int>(blockDim.x >> 6);
-    const int extra = rows.drawn_total / waves - (DIAG_FX_WINDOW_TRIPS - 1);
-    if (extra > 0) {
-      rows.dealt += extra;
-      rows.drawn_total -= extra * waves;
-    }
-  }
-  pair_sweep<DELTAF, NT>(x, v, p, w, np >> 1, rows, sDraw, one, [&](int k) {
+  const PairRows rows = window_rows(pair_rows(np >> 1, dyn_tail));
+  pair_sweep<true, DELTAF, NT>(x, v, p, w, np >> 1, rows, sDraw, one, [&](int k) {
     if constexpr (LDS) {
-      if (k <= rows.dealt && (k & (DIAG_FX_WINDOW_TRIPS - 1)) == 0) {   // (k: dealt trips done -- uniform over the workgroup)
+      if (window_due(k, rows)) {
         __syncthreads();
         dfx_flush(b);
         __syncthreads();

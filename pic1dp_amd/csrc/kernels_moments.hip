@@ -5,6 +5,8 @@
 // in 64-bit integer words of the same size.  gfx950, wave64.
 #include "device_moments.hpp"
 
+#include <type_traits>
+#include "device_sweep.hpp"
 #include "launch_policy.hpp"
 
 namespace pic1dp {
@@ -27,12 +29,11 @@ k_moments(const double *x, const double *v, const double *p, const double *w, in
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ unsigned sDraw;   // the drawn chunks' counter
   double *sM = reinterpret_cast<double *>(smem);
-  constexpr int NPL = ((P ? 1 : 0) + (W ? 1 : 0)) * moments_nk<KMASK>();
-  for (int i = threadIdx.x; i < NPL * g.nx; i += blockDim.x) sM[i] = 0.0;
+  for (int i = threadIdx.x; i < moments_npl<P, W, KMASK>() * g.nx; i += blockDim.x) sM[i] = 0.0;
   if (threadIdx.x == 0) sDraw = 0u;
   __syncthreads();
   auto one = [&](double px, double pv, double pp, double pw) { moments_one<P, W, KMASK>(px, pv, pp, pw, g, sM); };
-  moments_sweep<P, W, NT>(x, v, p, w, np >> 1, pair_rows(np >> 1, dyn_tail), &sDraw, one, [](int) {});
+  pair_sweep<P, W, NT>(x, v, p, w, np >> 1, pair_rows(np >> 1, dyn_tail), &sDraw, one, [](int) {});
   if ((np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // the odd last marker
     const int64_t i = tidx(np - 1);
     one(x[i], v[i], P ? p[i] : 0.0, W ? w[i] : 0.0);
@@ -41,22 +42,8 @@ k_moments(const double *x, const double *v, const double *p, const double *w, in
   moments_flush<P, W, KMASK>(sM, out, g.nx);
 }
 
-template <bool P, bool W, int KMASK>
-hipError_t launch_one(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
-                      double *out, const MomentsPass &ps, int dyn_tail, hipStream_t st) {
-  const dim3 grid(static_cast<unsigned>(ps.blocks)), block(static_cast<unsigned>(ps.threads));
-  if (ps.nt) return launch_kernel(k_moments<P, W, KMASK, true>, grid, block, ps.bytes, st, x, v, p, w, np, g, out, dyn_tail);
-  return launch_kernel(k_moments<P, W, KMASK, false>, grid, block, ps.bytes, st, x, v, p, w, np, g, out, dyn_tail);
-}
-
 // The exact kind: k_moments' sweep over integer planes (device_moments.hpp mfx_*).  The LDS holds one signed 64-bit word per
-// (plane, cell) and nothing else.  The window: a workgroup flushes its words into the global (hi, lo) rows every
-// DIAG_FX_WINDOW_TRIPS dealt trips and once at the end; the drawn rows are capped one below that, and the odd last marker is
-// taken BEFORE the sweep, so it falls into the first window.  Between two flushes a word therefore sees at most
-// DIAG_FX_WINDOW_TRIPS trips of 2 x 1024 markers and that marker, or DIAG_FX_WINDOW_TRIPS - 1 dealt and as many drawn
-// trips: fewer than 2^17 markers.  A marker adds one term to a word (nx >= 2), or two (nx = 1: ix == ir), each below 2^44
-// quanta: fewer than 2^18 terms, the word stays below 2^62 in magnitude.  The dealt trips are the same number for every thread
-// of the workgroup, so the barriers around a flush inside the sweep are met by all.
+// (plane, cell) and nothing else; it is flushed by the window rule of device_sweep.hpp, with the odd last marker before the sweep.
 template <bool P, bool W, int KMASK, bool NT>
 __global__ void __launch_bounds__(1024)
 k_moments_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst g,
@@ -64,8 +51,7 @@ k_moments_exact(const double *x, const double *v, const double *p, const double 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ unsigned sDraw;   // the drawn chunks' counter
   unsigned long long *sM = reinterpret_cast<unsigned long long *>(smem);
-  constexpr int NPL = ((P ? 1 : 0) + (W ? 1 : 0)) * moments_nk<KMASK>();
-  for (int i = threadIdx.x; i < NPL * g.nx; i += blockDim.x) sM[i] = 0ull;
+  for (int i = threadIdx.x; i < moments_npl<P, W, KMASK>() * g.nx; i += blockDim.x) sM[i] = 0ull;
   if (threadIdx.x == 0) sDraw = 0u;
   __syncthreads();
   auto one = [&](double px, double pv, double pp, double pw) { mfx_one<P, W, KMASK>(px, pv, pp, pw, g, sM, a); };
@@ -73,17 +59,9 @@ k_moments_exact(const double *x, const double *v, const double *p, const double 
     const int64_t i = tidx(np - 1);
     one(x[i], v[i], P ? p[i] : 0.0, W ? w[i] : 0.0);
   }
-  PairRows rows = pair_rows(np >> 1, dyn_tail);
-  {
-    const int waves = static_cast<int>(blockDim.x >> 6);
-    const int extra = rows.drawn_total / waves - (DIAG_FX_WINDOW_TRIPS - 1);
-    if (extra > 0) {
-      rows.dealt += extra;
-      rows.drawn_total -= extra * waves;
-    }
-  }
-  moments_sweep<P, W, NT>(x, v, p, w, np >> 1, rows, &sDraw, one, [&](int k) {
-    if (k <= rows.dealt && (k & (DIAG_FX_WINDOW_TRIPS - 1)) == 0) {   // (k: dealt trips done -- uniform over the workgroup)
+  const PairRows rows = window_rows(pair_rows(np >> 1, dyn_tail));
+  pair_sweep<P, W, NT>(x, v, p, w, np >> 1, rows, &sDraw, one, [&](int k) {
+    if (window_due(k, rows)) {
       __syncthreads();
       mfx_flush<P, W, KMASK>(sM, a, g.nx);
       __syncthreads();
@@ -93,64 +71,58 @@ k_moments_exact(const double *x, const double *v, const double *p, const double 
   mfx_flush<P, W, KMASK>(sM, a, g.nx);
 }
 
-template <bool P, bool W, int KMASK>
-hipError_t launch_one_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
-                            const MomentsFxArgs &a, const MomentsPass &ps, int dyn_tail, hipStream_t st) {
-  const dim3 grid(static_cast<unsigned>(ps.blocks)), block(static_cast<unsigned>(ps.threads));
-  if (ps.nt) return launch_kernel(k_moments_exact<P, W, KMASK, true>, grid, block, ps.bytes, st, x, v, p, w, np, g, a, dyn_tail);
-  return launch_kernel(k_moments_exact<P, W, KMASK, false>, grid, block, ps.bytes, st, x, v, p, w, np, g, a, dyn_tail);
+// what the kernel indexes must be what the plan sized: the LDS holds exactly the pass's planes, in words of word_bytes
+bool check_pass(const MomentsPass &ps, const GridConst &g, size_t word_bytes) {
+  const int sets = (ps.p ? 1 : 0) + (ps.w ? 1 : 0);
+  const int nk = ps.kmask == 0xF ? 4 : 2;
+  return sets != 0 && ps.planes == sets * nk && ps.bytes == word_bytes * static_cast<size_t>(ps.planes) * g.nx && ps.threads == 1024 &&
+         ps.blocks >= 1 && (sets == 1 || ps.kmask == 0xF);
+}
+
+// f(P, W, KMASK, NT) with a pass's weight sets, powers and loads as compile-time constants: the seven (P, W, KMASK)
+// combinations moments_plan hands out -- both sets with all four powers, one set with 0xF, 0x3 or 0xC --, each with and
+// without non-temporal loads, and no others
+template <class F>
+hipError_t with_pass(const MomentsPass &ps, F &&f) {
+  return with_bools(
+      [&](auto P, auto W, auto NT) {
+        if constexpr (P || W) {
+          if (ps.kmask == 0xF) return f(P, W, std::integral_constant<int, 0xF>{}, NT);
+          if constexpr (!(P && W)) {
+            if (ps.kmask == 0x3) return f(P, W, std::integral_constant<int, 0x3>{}, NT);
+            if (ps.kmask == 0xC) return f(P, W, std::integral_constant<int, 0xC>{}, NT);
+          }
+        }
+        return hipErrorInvalidValue;
+      },
+      ps.p, ps.w, ps.nt);
 }
 
 }  // namespace
 
-// the seven (P, W, KMASK) combinations moments_plan hands out, each with and without non-temporal loads
 hipError_t launch_moments(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
                           double *out, const MomentsPass &ps, int dyn_tail, hipStream_t st) {
   if (np <= 0) return hipSuccess;
-  const int sets = (ps.p ? 1 : 0) + (ps.w ? 1 : 0);
-  const int nk = ps.kmask == 0xF ? 4 : 2;
-  // what the kernel indexes must be what the plan sized: the LDS holds exactly the pass's planes
-  if (sets == 0 || ps.planes != sets * nk || ps.bytes != sizeof(double) * static_cast<size_t>(ps.planes) * g.nx || ps.threads != 1024 ||
-      ps.blocks < 1 || (sets == 2 && ps.kmask != 0xF))
-    return hipErrorInvalidValue;
+  if (!check_pass(ps, g, sizeof(double))) return hipErrorInvalidValue;
   double *dst = out + static_cast<size_t>(ps.first_plane / 4) * 4 * g.nx;   // the first plane of the pass's (first) weight set
-  if (ps.p && ps.w) return launch_one<true, true, 0xF>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-  if (ps.p) {
-    if (ps.kmask == 0xF) return launch_one<true, false, 0xF>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-    if (ps.kmask == 0x3) return launch_one<true, false, 0x3>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-    if (ps.kmask == 0xC) return launch_one<true, false, 0xC>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-  } else {
-    if (ps.kmask == 0xF) return launch_one<false, true, 0xF>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-    if (ps.kmask == 0x3) return launch_one<false, true, 0x3>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-    if (ps.kmask == 0xC) return launch_one<false, true, 0xC>(x, v, p, w, np, g, dst, ps, dyn_tail, st);
-  }
-  return hipErrorInvalidValue;
+  return with_pass(ps, [&](auto P, auto W, auto KMASK, auto NT) {
+    return launch_kernel(k_moments<P, W, KMASK, NT>, dim3(static_cast<unsigned>(ps.blocks)), dim3(static_cast<unsigned>(ps.threads)),
+                         ps.bytes, st, x, v, p, w, np, g, dst, dyn_tail);
+  });
 }
 
-// the same seven combinations for the passes of moments_plan_exact
+// ps: a pass of moments_plan_exact
 hipError_t launch_moments_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
                                 const MomentsFxArgs &a, const MomentsPass &ps, int dyn_tail, hipStream_t st) {
   if (np <= 0) return hipSuccess;
-  const int sets = (ps.p ? 1 : 0) + (ps.w ? 1 : 0);
-  const int nk = ps.kmask == 0xF ? 4 : 2;
-  // what the kernel indexes must be what the plan sized: the LDS holds exactly the pass's planes, as 64-bit words
-  if (sets == 0 || ps.planes != sets * nk || ps.bytes != sizeof(long long) * static_cast<size_t>(ps.planes) * g.nx || ps.threads != 1024 ||
-      ps.blocks < 1 || (sets == 2 && ps.kmask != 0xF) || !a.acc || !a.rej)
-    return hipErrorInvalidValue;
+  if (!check_pass(ps, g, sizeof(long long)) || !a.acc || !a.rej) return hipErrorInvalidValue;
   MomentsFxArgs b = a;   // the first plane and the counters of the pass's (first) weight set
   b.acc = a.acc + static_cast<size_t>(ps.first_plane / 4) * 4 * 2 * g.nx;
   b.rej = a.rej + (ps.first_plane / 4) * 4;
-  if (ps.p && ps.w) return launch_one_exact<true, true, 0xF>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-  if (ps.p) {
-    if (ps.kmask == 0xF) return launch_one_exact<true, false, 0xF>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-    if (ps.kmask == 0x3) return launch_one_exact<true, false, 0x3>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-    if (ps.kmask == 0xC) return launch_one_exact<true, false, 0xC>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-  } else {
-    if (ps.kmask == 0xF) return launch_one_exact<false, true, 0xF>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-    if (ps.kmask == 0x3) return launch_one_exact<false, true, 0x3>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-    if (ps.kmask == 0xC) return launch_one_exact<false, true, 0xC>(x, v, p, w, np, g, b, ps, dyn_tail, st);
-  }
-  return hipErrorInvalidValue;
+  return with_pass(ps, [&](auto P, auto W, auto KMASK, auto NT) {
+    return launch_kernel(k_moments_exact<P, W, KMASK, NT>, dim3(static_cast<unsigned>(ps.blocks)),
+                         dim3(static_cast<unsigned>(ps.threads)), ps.bytes, st, x, v, p, w, np, g, b, dyn_tail);
+  });
 }
 
 }  // namespace pic1dp

@@ -137,6 +137,55 @@ def test_order_of_the_markers_does_not_matter(amd, n):
     assert np.count_nonzero(runs[0]["raw"][0]["pertb_xv"]) > 100 and eng.kernel_stats(15)[1] == 0
 
 
+N_WINDOW = (1 << 18) + 3
+
+
+def normalised(limbs, nxv):
+    """a context's limbs as the host normalises them: hi += lo >> 32, lo &= 2^32 - 1.  (What a context hands out is the sum
+    of its workgroups' flushes, limb by limb: how a total splits into hi and lo depends on where the windows fall)"""
+    out = np.array(limbs, dtype=np.int64)
+    for pairs in (out[:6 * nxv].reshape(3, 2, nxv), out[6 * nxv:6 * nxv + 6].reshape(3, 2, 1)):
+        pairs[:, 0] += pairs[:, 1] >> 32
+        pairs[:, 1] &= 0xffffffff
+    return out
+
+
+@pytest.fixture(scope="module")
+def window_cases(amd):
+    """N_WINDOW crafted markers on the 64 x 64 grid, delta f and full f: the markers, the definition's limbs and the limbs
+    of a context at the default setting, once"""
+    out = {}
+    for case in ("deltaf", "fullf"):
+        inp, eng = make(amd, n=N_WINDOW, **CASES[case])
+        eng.particle_load()
+        marks = crafted(amd, inp, eng, 0)
+        eng.particles_upload(*marks[:4], np_valid=marks[4])
+        eng.set_diag_sum(1)
+        want = dx.limbs_of(restatement(amd, inp, 0, marks)["ints"], 64 * 64)
+        assert np.array_equal(normalised(want, 64 * 64), want)
+        out[case] = (marks, want, normalised(eng.diag_local_exact(0), 64 * 64))
+        eng.close()
+    return out
+
+
+@pytest.mark.parametrize("case", ["deltaf", "fullf"])
+@pytest.mark.parametrize("drawn", ["0", "16"])
+def test_rows_all_dealt_and_all_drawn_then_capped(amd, monkeypatch, tuning, window_cases, drawn, case):
+    """tuning knob PIC1DP_DYN_TAIL at its two ends, the branches the shared sweep and window_rows (device_sweep.hpp) own: every
+    row of a workgroup dealt, and every row drawn, of which the cap deals all but 31 again.  The normalised limbs are those
+    of the default setting and of the definition, bit for bit"""
+    marks, want, base = window_cases[case]
+    monkeypatch.setenv("PIC1DP_DYN_TAIL", drawn)
+    inp, eng = make(amd, n=N_WINDOW, **CASES[case])
+    eng.particle_load()
+    eng.particles_upload(*marks[:4], np_valid=marks[4])
+    eng.set_diag_sum(1)
+    got = normalised(eng.diag_local_exact(0), 64 * 64)
+    assert np.array_equal(got, base), np.flatnonzero(got != base)[:5]
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:5]
+    assert np.any(got[:6 * 64 * 64:7]) and eng.kernel_stats(15)[1] == 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 RANK_KW = dict(nparticle_max=40_001, nx=64)
 

@@ -240,6 +240,33 @@ def uploaded(amd, sc):
     return eng
 
 
+N_ROWS = (1 << 18) + 3
+
+
+@pytest.fixture(scope="module")
+def rows_case(amd):
+    """N_ROWS loaded markers of the default case and their reference, once"""
+    inp = amd.make_input(nparticle_max=N_ROWS, nx=64)
+    with amd.Pic1dp(inp) as eng:
+        eng.particle_load()
+        na, npv = eng.local_sizes(0)
+        g = eng.particles_download(0)
+    return inp, g, npv, species_reference(g, na, npv, inp), one_marker(g, inp, npv - 1)
+
+
+@pytest.mark.parametrize("drawn", ["0", "16"])
+def test_rows_all_dealt_and_all_drawn(amd, monkeypatch, tuning, rows_case, drawn):
+    """tuning knob PIC1DP_DYN_TAIL at its two ends -- every row of a workgroup dealt, every row drawn by its waves: the
+    histograms of the double pass and the kinetic sums within the bounds of the default setting"""
+    inp, g, npv, ref, one = rows_case
+    monkeypatch.setenv("PIC1DP_DYN_TAIL", drawn)
+    with amd.Pic1dp(inp) as eng:
+        eng.particles_upload(g["x"], g["v"], g["p"], g["w"], np_valid=npv)
+        compare(eng.ptcldist(0, finish=False), ref, inp, None, "PIC1DP_DYN_TAIL=%s (double)" % drawn, one)
+        assert eng.kernel_stats(12)[1] == 0
+        check_sums(eng, [ref], "PIC1DP_DYN_TAIL=%s" % drawn)
+
+
 @pytest.mark.parametrize("scale", ["bump"], indirect=True)
 def test_scale_deltaf_bump_on_tail(amd, scale, monkeypatch):
     """(a) delta f bump-on-tail, default geometry: the double pass, the fixed-point pass, output_all -- on the engine

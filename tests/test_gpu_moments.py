@@ -133,6 +133,20 @@ def test_shapes_of_the_sweep(amd, loader_markers, n):
         assert not np.any(got["total"]) and not np.any(got["pertb"])
 
 
+@pytest.mark.parametrize("drawn", ["0", "16"])
+def test_rows_all_dealt_and_all_drawn(amd, monkeypatch, tuning, loader_markers, drawn):
+    """tuning knob PIC1DP_DYN_TAIL at its two ends -- every row of a workgroup dealt, every row drawn by its waves: every pair
+    exactly once whoever takes it, each weight set alone and both, within the bound of the default setting"""
+    g = loader_markers
+    monkeypatch.setenv("PIC1DP_DYN_TAIL", drawn)
+    e = uploaded(amd, g["x"], g["v"], g["p"], g["w"], nx=192)
+    _, ref = check_against_markers(e, 3, what="PIC1DP_DYN_TAIL=%s" % drawn)
+    for which, name in ((1, "total"), (2, "pertb")):
+        got = e.moments(0, which)
+        assert list(got) == [name]
+        within(got[name], ref[name], MR.workgroups(g["x"].size), 1.0, "PIC1DP_DYN_TAIL=%s which %d" % (drawn, which))
+
+
 def test_tail_slots_do_not_count(amd, loader_markers):
     n = 2049
     g = {k: a[:n] for k, a in loader_markers.items()}

@@ -162,6 +162,40 @@ def test_shapes_of_the_sweep(amd, probe, loader_markers, n):
         assert e.kernel_stats(17)[0] > 0.0
 
 
+N_WINDOW = 2**17 + 2**12 + 3     # two workgroups of 34 and 33 rows
+
+
+@pytest.fixture(scope="module")
+def window_case(amd, loader_markers):
+    """N_WINDOW markers, their definition and the limbs of a context at the default setting, once"""
+    g = {k: a[:N_WINDOW] for k, a in loader_markers.items()}
+    e = context(amd, N_WINDOW, g["x"], g["v"], g["p"], g["w"], nx=192)
+    ref = MX.reference(g["x"], g["v"], g["p"], g["w"], e.inp, which=3)
+    assert MX.in_range(ref)
+    base = e.moments_local_exact(0, 3)
+    e.close()
+    return g, ref, base
+
+
+@pytest.mark.parametrize("which", [1, 2, 3])
+@pytest.mark.parametrize("drawn", ["0", "16"])
+def test_rows_all_dealt_and_all_drawn_then_capped(amd, probe, monkeypatch, tuning, window_case, drawn, which):
+    """tuning knob PIC1DP_DYN_TAIL at its two ends, the branches the shared sweep and window_rows (device_sweep.hpp) own: every
+    row dealt -- the flush inside the sweep runs after trip 32 --, and every row drawn, of which the cap deals all but 31
+    again.  The limbs are those of the default setting and of the definition, bit for bit"""
+    g, ref, base = window_case
+    blocks = probe.host_moments_plan_exact(192, which, 1, N_WINDOW, 256)["passes"][0]["blocks"]
+    trips = [dealt_trips(N_WINDOW, blocks, int(drawn), b) for b in range(blocks)]
+    assert blocks == 2 and trips == ([34, 33] if drawn == "0" else [3, 2])
+    monkeypatch.setenv("PIC1DP_DYN_TAIL", drawn)
+    e = context(amd, N_WINDOW, g["x"], g["v"], g["p"], g["w"], nx=192)
+    limbs = e.moments_local_exact(0, which)
+    sets = {1: slice(0, 1), 2: slice(1, 2), 3: slice(0, 2)}[which]
+    assert np.array_equal(limbs, base[sets]), np.argwhere(limbs != base[sets])[:5]
+    assert np.array_equal(limbs, ref["limbs"][sets]), np.argwhere(limbs != ref["limbs"][sets])[:5]
+    assert e.kernel_stats(18)[1] == 0
+
+
 # ---------------------------------------------------------------------------
 # 3. one cell, one sign
 # ---------------------------------------------------------------------------

@@ -4,6 +4,7 @@ tests/moments_exact.py's numpy evaluation against its own plain-Python one."""
 import ctypes as C
 import math
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -96,6 +97,22 @@ def test_convert_against_python_integers(amd):
         one = amd.moments_convert(inp, limbs[j:j + 1], which)
         assert list(one) == [name] and one[name].tobytes() == want[j].tobytes()
     assert not np.any(amd.moments_convert(inp, np.zeros((2, 4, 2, nx), dtype=np.int64), 3)["total"])
+
+
+def test_limb_arithmetic_under_the_host_sanitizers(tmp_path):
+    """tests/fx_limbs_check.cpp, a program of its own, built with AddressSanitizer and UndefinedBehaviorSanitizer (host code
+    only; nothing of it touches a GPU): csrc/fx_limbs.hpp against __int128 arithmetic"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("pic1dp_amd_build", os.path.join(ROOT, "pic1dp_amd", "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    exe = str(tmp_path / "fx_limbs_check")
+    subprocess.check_call([build.hipcc(), "--offload-arch=gfx950", "-x", "hip", "--offload-host-only", "-O1", "-g", "-std=c++17",
+                           "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "fx_limbs_check.cpp"), "-o", exe, "-lpthread"])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().endswith("0 failed"), r.stdout
 
 
 # ---------------------------------------------------------------------------
