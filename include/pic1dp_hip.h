@@ -640,6 +640,51 @@ int pic1dp_hip_moments_local_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t wh
 int pic1dp_hip_moments_convert(const pic1dp_input *in, int32_t ispecies, int32_t which, const int64_t *limbs, double *out);
 int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
 
+/* ---- velocity-resolved wave-particle power on the output grid ---------------------
+ * pic1dp_hip_power(ctx, ispecies, which, out): the power the field does on the markers, q v E(x) per marker, of one species,
+ * resolved on the nx_opd x nv_opd output grid of output_ptcldist (the field-particle correlation), computed on the device in
+ * streaming passes over the markers with the field in the workgroups' LDS.
+ *   - which is 1 (weights p: total f), 2 (weights w: delta f) or 3 (both, p first).
+ *   - out, per selected weight set in that order: [nv_opd * nx_opd plane | nv_opd v-profile | rest], that is
+ *     nx_opd * nv_opd + nv_opd + 1 doubles per set; the plane's index is iv * nx_opd + ix.
+ *   - pic1dp_hip_power_len(in, which, &n): n = nsets * (nx_opd * nv_opd + nv_opd + 1).  Host only.
+ * For every valid marker i < np of the species, on the state a pic1dp_hip_particles_download at that moment would return,
+ * with E = field_electric as pic1dp_hip_get_field would return it at that moment:
+ *     px = wrap(x)                                  the deposit's wrap (src/pic1dp_interaction.F90:102-104), NOT stored back
+ *     (ix, wl) = locate(px)                         ix == nx folds to 0; ir = (ix + 1 == nx) ? 0 : ix + 1
+ *     e = E[ix] * wl;  e = e + E[ir] * (1.0 - wl)   the push's gather, in the push's order (src/pic1dp_interaction.F90:254-257)
+ *     c = v * e
+ *     t_q = c * q                                   q = p and / or w
+ *   - Bins.  The four cells and bilinear weights of output_ptcldist's histograms (src/pic1dp_output.F90:239-315) for
+ *     (px, v), edge rules included: the x cell nx_opd folds to 0, the right-hand neighbour of the last x cell is cell 0, the
+ *     top v row keeps a marker whose upper row would carry weight 0, and |v| >= v_max gives no bins.
+ *         P[q][c00] += w00 * t_q    P[q][c01] += w01 * t_q    P[q][c10] += w10 * t_q    P[q][c11] += w11 * t_q
+ *     with w00 = sx * sv, w01 = sx * svu, w10 = sxr * sv, w11 = sxr * svu as the histograms form them.
+ *   - A marker without bins adds t_q to one scalar per set: rest[q] += t_q.  Bins plus rest account for every marker.
+ *   - The v-profile is the plane summed over ix ascending, in doubles, on the host after the transfer.
+ *   - Tail slots (i >= np) do not count.
+ *   - The arithmetic is plain IEEE, every product and sum rounded on its own.  A non-finite term makes its bin non-finite;
+ *     there is no counter and no trap.
+ *   - The sums are FP64 and their order is free: the result is defined up to that order.  With n_b terms in a bin (or in
+ *     rest) and B workgroups, |result - exact sum| <= (n_b + B) 2^-53 sum |terms| to first order.  There is no exact
+ *     (integer) kind of these planes.
+ *   - Normalisation.  The sums are raw and LOCAL to the context: the sum over ranks is an element-wise addition by the
+ *     host; no communicator is used.  Z_s * t is the rate at which the field does work on that marker's share of f (q = p)
+ *     or delta f (q = w); 2 (Z / m) sum t_w is the part of d/dt sum v^2 w that comes from the acceleration at fixed weights.
+ *     No nx / lx, no bin widths: divide by (lx / nx_opd) (2 v_max / (nv_opd - 1)) for a density in (x, v).
+ *   - which & 2 on a full-f context (deltaf = 0, no w) is PIC1DP_ERR_ARG; so are an unknown `which`, an unknown species, a
+ *     null pointer, and nx_opd < 1 or nv_opd < 2.
+ *   - pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect the call, and the checkpoint carries nothing of it.
+ * When the call may come.  The rule of pic1dp_hip_moments, and pic1dp_hip_get_field's for the field.  Between time steps it
+ * launches its own passes and nothing else and changes nothing: markers, fields, the one-pass prediction, the fused solve
+ * and cached diagnostics survive.  Inside a time step (a push noted) the noted push becomes memory first; markers and field
+ * are then those eager call sites would hold.
+ * Cost: one pass over x, v and p and / or w (24 or 32 B per marker) while the E tile (8 (nx + 1) B) and the selected planes
+ * fit a workgroup's LDS (150 KiB); one pass per set where only one plane fits; planes that do not fit at all are summed
+ * straight in memory. */
+int pic1dp_hip_power(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
+int pic1dp_hip_power_len(const pic1dp_input *in, int32_t which, int64_t *n);   /* host only */
+
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
   int32_t format_version;
@@ -794,7 +839,9 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 18: *launches = terms those passes did not sum so far (2^44 quanta or more, or NaN; each call that met some
  * returned PIC1DP_ERR_ARG), *ms = 0;
  * which = 19: *launches = passes of pic1dp_hip_particle_load_device (k_load, one per species and call) launched so far,
- * *ms = their accumulated device milliseconds while kernel stats were enabled */
+ * *ms = their accumulated device milliseconds while kernel stats were enabled;
+ * which = 20: *launches = passes of pic1dp_hip_power (k_power) launched so far, *ms = their accumulated device
+ * milliseconds while kernel stats were enabled */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

@@ -119,6 +119,14 @@ int pic1dp_probe_host_moments_plan(int32_t nx, int32_t which, int32_t deltaf, in
  * differs, max(1, min(num_cu, ceil(np / 2^17))). */
 int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu, int64_t out[35]);
 
+/* The passes of one pic1dp_hip_power call (launch_policy.hpp power_plan), on the HOST: out[0] = passes (0: an unknown `which`,
+ * w asked of a full-f run, a grid out of range), out[1] = weight sets selected (1 or 2), out[2] = bytes of the E tile,
+ * out[3] = bytes of one plane, then per pass i eight words at out[4 + 8 i]: {blocks, threads, non-temporal loads, dynamic
+ * LDS bytes, weight sets (bit 0 p, bit 1 w), planes in LDS (1) or straight in memory (0), first set in the output, sets}.
+ * out holds 4 + 8 * 2 words.  Nonzero: null argument. */
+int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
+                                 int32_t num_cu, int64_t out[20]);
+
 /* What pic1dp_hip_create decides before its first allocation (pic1dp_amd/csrc/context_plan.hpp plan_context), on the HOST,
  * for an input, a layout and the three requests of the settings that bear on it (0: none): PIC1DP_PRED_KIND,
  * PIC1DP_RHO_GLOBAL_COPIES as given (refused like settings_from_env refuses it), PIC1DP_FIELD_ONE_RANK_ORDER.  The input is taken as it is (not validated).

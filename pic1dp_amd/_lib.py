@@ -173,6 +173,8 @@ SIGNATURES = {
     "pic1dp_hip_moments_local_exact": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_moments_convert": [_INP, C.c_int32, C.c_int32, _P, _P],
     "pic1dp_hip_moments_exact": [_P, C.c_int32, C.c_int32, _P],
+    "pic1dp_hip_power": [_P, C.c_int32, C.c_int32, _P],
+    "pic1dp_hip_power_len": [_INP, C.c_int32, C.POINTER(C.c_int64)],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

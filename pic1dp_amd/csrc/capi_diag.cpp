@@ -606,6 +606,70 @@ int pic1dp_hip_moments(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
 }
 
 // ---------------------------------------------------------------------------
+// velocity-resolved wave-particle power on the output grid (include/pic1dp_hip.h pic1dp_hip_power)
+// ---------------------------------------------------------------------------
+// the refusals that need no context: which, w of a full-f run, the output grid
+static int power_args(const char *who, int deltaf, int nx_opd, int nv_opd, int32_t which) {
+  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "%s: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", who, which);
+  if ((which & 2) && !deltaf)
+    return fail(PIC1DP_ERR_ARG, "%s: which = %d asks for the plane of w (which & 2), but a full-f context (deltaf = 0) has no w", who, which);
+  if (nx_opd < 1 || nv_opd < 2) return fail(PIC1DP_ERR_ARG, "%s: nx_opd = %d, nv_opd = %d: nx_opd >= 1 and nv_opd >= 2 required", who, nx_opd, nv_opd);
+  return 0;
+}
+
+int pic1dp_hip_power_len(const pic1dp_input *in, int32_t which, int64_t *n) {
+  if (!in || !n) return fail(PIC1DP_ERR_ARG, "power_len: null argument");
+  if (int rc = power_args("power_len", in->deltaf, in->nx_opd, in->nv_opd, which)) return rc;
+  const int64_t nxv = static_cast<int64_t>(in->nx_opd) * in->nv_opd;
+  *n = (which == 3 ? 2 : 1) * (nxv + in->nv_opd + 1);
+  return 0;
+}
+
+int pic1dp_hip_power(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
+  CHECK_CTX(c);
+  const pic1dp_input &in = c->in;
+  if (isp < 0 || isp >= in.nspecies) return fail(PIC1DP_ERR_ARG, "power: bad species index %d", isp);
+  if (int rc = power_args("power", in.deltaf, in.nx_opd, in.nv_opd, which)) return rc;
+  if (!out) return fail(PIC1DP_ERR_ARG, "power: null output");
+  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = materialize(c)) return rc;          // (as pic1dp_hip_moments: a noted push becomes memory; clean: nothing is launched)
+  if (int rc = settle_field_view(c)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
+  const Species &S = c->sp[isp];
+  const PowerPlan plan = power_plan(in.nx, in.nx_opd, in.nv_opd, which, in.deltaf, S.np, c->num_cu);
+  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: power_plan has no pass for nx %d, %d x %d, which %d", in.nx, in.nx_opd, in.nv_opd, which);
+  const size_t nxv = static_cast<size_t>(in.nx_opd) * in.nv_opd, nvo = static_cast<size_t>(in.nv_opd);
+  if (!c->d_pow) HIP_TRY(c->mem.alloc(&c->d_pow, 2 * nxv + 2));
+  if (!c->h_pow) HIP_TRY(c->mem.alloc_pinned(&c->h_pow, 2 * nxv + 2));
+  const size_t nsets = static_cast<size_t>(plan.selected), n = nsets * nxv + nsets;   // the planes, then a rest word per set
+  double *d_rest = c->d_pow + nsets * nxv;
+  HIP_TRY(hipMemsetAsync(c->d_pow, 0, sizeof(double) * n, c->st));
+  const PSet &A = S.set[c->cur];
+  for (int i = 0; i < plan.npass && S.np > 0; ++i) {
+    Span ks(c, kTagPower, c->stats_on);
+    HIP_TRY(launch_power(A.x, A.v, S.p, A.w, S.np, c->grid, dist_geom(c), c->d_E, c->d_pow, d_rest, plan.pass[i], c->cfg.dyn_tail, c->st));
+    if (int rc = ks.end()) return rc;
+    c->power_passes++;
+  }
+  HIP_TRY(hipMemcpyAsync(c->h_pow, c->d_pow, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  if (int rc = xchg_check(c)) return rc;
+  // per set: [plane | v-profile = the plane summed over ix ascending | rest]
+  for (size_t j = 0; j < nsets; ++j) {
+    const double *plane = c->h_pow + j * nxv;
+    double *o = out + j * (nxv + nvo + 1);
+    std::memcpy(o, plane, sizeof(double) * nxv);
+    for (size_t iv = 0; iv < nvo; ++iv) {
+      double acc = 0.0;
+      for (int ix = 0; ix < in.nx_opd; ++ix) acc += plane[iv * in.nx_opd + ix];
+      o[nxv + iv] = acc;
+    }
+    o[nxv + nvo] = c->h_pow[nsets * nxv + j];
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // the exact kind of the moments (include/pic1dp_hip.h pic1dp_hip_moments_exact): the same terms in whole
 // quanta, integer sums.  The arithmetic on the host is moments_fx.cpp's.
 // ---------------------------------------------------------------------------

@@ -56,7 +56,7 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kNumTags = 128;
+              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
@@ -269,6 +269,10 @@ struct pic1dp_ctx {
   long long *d_momfx = nullptr, *h_momfx = nullptr;
   int64_t moments_exact_passes = 0;        // k_moments_exact passes launched so far (kernel_stats 17)
   int64_t moments_exact_rejected = 0;      // terms they did not sum so far (kernel_stats 18)
+  // pic1dp_hip_power (capi_diag.cpp): the planes [2][nx_opd nv_opd] and the two rest words on the device and their pinned
+  // copy, allocated at the first call
+  double *d_pow = nullptr, *h_pow = nullptr;
+  int64_t power_passes = 0;                // k_power passes launched so far (kernel_stats 20)
   int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field
   int chain_selftest = 0;                  // create()'s verdict on the serial sums through the matrix unit: 1 identical, 0 differs, -1 could not run
   int32_t itime = 0;

@@ -224,6 +224,27 @@ struct MomentsPlan {
   MomentsPass pass[MOMENTS_MAX_PASSES];
 };
 
+// One pass of pic1dp_hip_power over a species' markers (launch_policy.hpp power_plan; kernels_power.hip k_power): the planes
+// of `sets` weight sets from `first_set` on (of the sets selected, in output order), in the workgroup's LDS behind the E
+// tile (lds) or straight in memory
+struct PowerPass {
+  int blocks, threads;
+  bool nt;          // non-temporal marker loads
+  size_t bytes;     // dynamic LDS: the E tile, and behind it the pass's planes where lds
+  bool p, w;        // the weight sets of this pass (both: p's plane first)
+  bool lds;         // the planes as a copy per workgroup in its LDS; false: straight into memory
+  int first_set;    // where the pass's first plane lies in the output, in weight sets
+  int sets;         // weight sets of the pass
+};
+constexpr int POWER_MAX_PASSES = 2;
+struct PowerPlan {
+  int selected;     // weight sets asked for: 1 or 2
+  int npass;
+  size_t tile;      // bytes of the E tile: nx + 1 doubles, rounded up to 16
+  size_t plane;     // bytes of one plane: nx_opd * nv_opd doubles
+  PowerPass pass[POWER_MAX_PASSES];
+};
+
 // launch shape of the state digest's pass (launch_policy.hpp digest_launch)
 struct DigestLaunch {
   int blocks, threads;
@@ -613,6 +634,12 @@ struct MomentsFxArgs {
 // ps: a pass of moments_plan_exact (its bytes are the planes as 64-bit words)
 hipError_t launch_moments_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
                                 const MomentsFxArgs &a, const MomentsPass &ps, int dyn_tail, hipStream_t st);
+// One pass of the wave-particle power on the output grid (kernels_power.hip k_power; the definition: include/pic1dp_hip.h
+// pic1dp_hip_power) over markers [0, np): E = field_electric [nx]; planes = [sets selected][nx_opd nv_opd] and rest = [sets
+// selected], both zeroed by the caller before a call's passes; the pass adds into those of its weight sets (ps.first_set ...)
+hipError_t launch_power(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
+                        const DistGeom &dg, const double *E, double *planes, double *rest, const PowerPass &ps, int dyn_tail,
+                        hipStream_t st);
 // The state digest of one species (kernels_digest.hip; the definition: include/pic1dp_hip.h pic1dp_hip_state_digest).
 // Array k (0 x, 1 v, 2 w, 3 p): slot i < np is read from cur[k] (the current particle set), slot i >= np from first[k]
 // (set 0, where the tail slots live); out[k] += sum of the mixed words of slots [0, nalloc) (64-bit integer atomics).

@@ -180,6 +180,33 @@ MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int nu
   return m;
 }
 
+PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu) {
+  PowerPlan m{};
+  if (which < 1 || which > 3 || ((which & 2) && !deltaf) || nx < 1 || nx_opd < 1 || nv_opd < 2) return m;
+  m.tile = power_tile_bytes(nx);
+  m.plane = sizeof(double) * static_cast<size_t>(nx_opd) * static_cast<size_t>(nv_opd);
+  if (m.tile > kDiagLdsCap) return m;
+  m.selected = which == 3 ? 2 : 1;
+  const bool all_fit = m.tile + m.selected * m.plane <= kDiagLdsCap;
+  const bool one_fits = m.tile + m.plane <= kDiagLdsCap;
+  m.npass = all_fit || !one_fits ? 1 : m.selected;
+  const int per_pass = m.selected / m.npass;
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(num_cu, ((np >> 1) + 1023) / 1024));
+  for (int i = 0; i < m.npass; ++i) {
+    PowerPass &ps = m.pass[i];
+    ps.first_set = i * per_pass;
+    ps.sets = per_pass;
+    ps.p = per_pass == 2 || (which != 2 && i == 0);
+    ps.w = per_pass == 2 || which == 2 || i == 1;
+    ps.lds = one_fits;
+    ps.threads = 1024;
+    ps.blocks = static_cast<int>(blocks);
+    ps.bytes = m.tile + (ps.lds ? per_pass * m.plane : 0);
+    ps.nt = 8.0 * (2 + per_pass) * static_cast<double>(np) > 288.0 * 1048576.0;
+  }
+  return m;
+}
+
 DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
   DigestLaunch d{};
   d.threads = 256;

@@ -64,6 +64,19 @@ MomentsPlan moments_plan(int nx, int which, int deltaf, int64_t np, int num_cu);
 // diagnostics' rule: every workgroup flushes two global atomics per non-zero word at its end, which costs what a few trips cost.
 MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int num_cu);
 
+// ---- the wave-particle power on the output grid (kernels_power.hip; include/pic1dp_hip.h pic1dp_hip_power) ----
+// The passes of one call: which = 1 (p), 2 (w), 3 (both, p first) selects one or two planes of nx_opd x nv_opd doubles.  A
+// workgroup's dynamic LDS begins with the E tile, tile = round16(8 (nx + 1)) bytes (cell nx: the push's guard), the planes
+// follow it; with plane = 8 nx_opd nv_opd and cap = kDiagLdsCap:
+//   tile + nsets plane <= cap : one pass, all sets, planes in LDS
+//   tile + plane <= cap       : one pass per set, in output order, planes in LDS
+//   else                      : one pass, all sets, planes straight in memory (dynamic LDS: the tile alone)
+// One workgroup of 1024 threads per CU, never more than the marker pairs fill; non-temporal loads once the arrays a pass
+// reads (x, v and p and / or w: 24 or 32 B per marker) exceed the threshold of diag_launch.  npass = 0: an unknown `which`,
+// w asked of a full-f run (deltaf = 0), nx < 1, nx_opd < 1, nv_opd < 2, or a tile beyond the cap (no context has such a grid).
+constexpr size_t power_tile_bytes(int nx) { return (sizeof(double) * (static_cast<size_t>(nx) + 1) + 15) & ~static_cast<size_t>(15); }
+PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu);
+
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
 // (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs

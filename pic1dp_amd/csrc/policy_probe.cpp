@@ -89,6 +89,21 @@ extern "C" int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, i
   return moments_plan_words(moments_plan_exact(nx, which, deltaf, np, num_cu), out);
 }
 
+extern "C" int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
+                                            int32_t num_cu, int64_t out[20]) {
+  if (!out) return 1;
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  const PowerPlan m = power_plan(nx, nx_opd, nv_opd, which, deltaf, np, num_cu);
+  out[0] = m.npass, out[1] = m.selected, out[2] = static_cast<int64_t>(m.tile), out[3] = static_cast<int64_t>(m.plane);
+  for (int i = 0; i < m.npass; ++i) {
+    const PowerPass &ps = m.pass[i];
+    const int64_t v[8] = {ps.blocks, ps.threads, ps.nt, static_cast<int64_t>(ps.bytes), (ps.p ? 1 : 0) | (ps.w ? 2 : 0), ps.lds,
+                          ps.first_set, ps.sets};
+    for (int k = 0; k < 8; ++k) out[4 + 8 * i + k] = v[k];
+  }
+  return 0;
+}
+
 extern "C" int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w,
                                             int32_t threads, int32_t out[4]) {
   if (!out) return 1;

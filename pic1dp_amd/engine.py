@@ -173,6 +173,27 @@ class Pic1dp:
         check(self.L.pic1dp_hip_moments_local_exact(self._ctx, int(ispecies), int(which), _ptr(out)))
         return out
 
+    # -- velocity-resolved wave-particle power on the output grid --
+    def power(self, ispecies=0, which=3):
+        """the power the field does on a species' markers, q v E(x) per marker, on the nx_opd x nv_opd output grid, computed
+        on the GPU (include/pic1dp_hip.h pic1dp_hip_power).  which: 1 the weights p (total f), 2 the weights w (delta f),
+        3 both.  Returns {"total": {"xv": (nv_opd, nx_opd), "v": (nv_opd,), "rest": float}, "pertb": {...}} with only the
+        sets asked for: "xv" the plane, "v" its sum over x, "rest" the sum over the markers with |v| >= v_max, which have no
+        bins.  The sums are raw and local to this context (ranks: add element by element); species_charge * t is the rate
+        of work on the marker's share of f or delta f."""
+        n = C.c_int64()
+        check(self.L.pic1dp_hip_power_len(C.byref(self.inp), int(which), C.byref(n)))
+        nxo, nvo = self.inp.nx_opd, self.inp.nv_opd
+        per = nxo * nvo + nvo + 1
+        out = np.zeros(n.value)
+        check(self.L.pic1dp_hip_power(self._ctx, int(ispecies), int(which), _ptr(out)))
+        names = [name for bit, name in ((1, "total"), (2, "pertb")) if which & bit]
+        res = {}
+        for j, name in enumerate(names):
+            o = out[j * per:(j + 1) * per]
+            res[name] = {"xv": o[:nxo * nvo].reshape(nvo, nxo).copy(), "v": o[nxo * nvo:nxo * nvo + nvo].copy(), "rest": float(o[-1])}
+        return res
+
     # -- state digest, checkpoint and restart (DESIGN.md 2.13) -----------------
     def state_digest(self):
         """D[s][k] of the markers on the device (include/pic1dp_hip.h): uint64 [nspecies][4], k = 0 x, 1 v, 2 w, 3 p;

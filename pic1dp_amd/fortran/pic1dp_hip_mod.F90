@@ -121,6 +121,23 @@ interface
     real(c_double), intent(inout) :: out(*)
     integer(c_int) :: ierr
   end function pic1dp_hip_moments_exact
+  ! wave-particle power on the output grid: per selected set out = [plane(nx_opd, nv_opd) | v-profile(nv_opd) | rest], which = 1
+  ! (p), 2 (w), 3 (both, p first); raw local sums.  power_len: the doubles of out, from the input alone
+  function pic1dp_hip_power(ctx, ispecies, which, out) bind(C, name="pic1dp_hip_power") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power
+  function pic1dp_hip_power_len(inp, which, n) bind(C, name="pic1dp_hip_power_len") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_len
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

@@ -53,6 +53,7 @@ SIGNATURES = {
     "pic1dp_probe_host_diag_launch": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _I64],
     "pic1dp_probe_host_moments_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_moments_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_power_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
@@ -225,6 +226,18 @@ def host_diag_launch(kind, np_, nx_opd, nv_opd, num_cu, ntail=0):
 
 
 MOMENTS_PASS_FIELDS = ("blocks", "threads", "nt", "bytes", "sets", "kmask", "first_plane", "planes")
+POWER_PASS_FIELDS = ("blocks", "threads", "nt", "bytes", "sets", "lds", "first_set", "nsets")
+
+
+def host_power_plan(nx, nx_opd, nv_opd, which, deltaf, np_, num_cu):
+    """the passes of one power call (csrc/launch_policy.hpp power_plan), on the host: dict(selected, tile, plane, passes) with
+    one dict of POWER_PASS_FIELDS per pass (sets: bit 0 p, bit 1 w; lds: the planes in the workgroup's LDS, 0: straight in
+    memory); no pass: an unknown `which`, w asked of a full-f run, a grid out of range"""
+    out = (C.c_int64 * 20)()
+    if load().pic1dp_probe_host_power_plan(int(nx), int(nx_opd), int(nv_opd), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_power_plan")
+    return dict(selected=out[1], tile=out[2], plane=out[3],
+                passes=[dict(zip(POWER_PASS_FIELDS, out[4 + 8 * i:12 + 8 * i])) for i in range(out[0])])
 
 
 def host_moments_plan(nx, which, deltaf, np_, num_cu):
