@@ -31,6 +31,16 @@ int pic1dp_probe_layout(int32_t device, int64_t n, int32_t log2_tile, int64_t st
                         int32_t blocks, int32_t threads, double ms[6]);
 int pic1dp_probe_release(void);
 
+/* launch pairs of the tiled read/write traffic above, back to back over ONE slab of n markers, in 64-pair chunks:
+ * alternate 0 every launch forward, 1 forward and backward (mirrored chunk addresses) in turn, so that a launch starts
+ * on the pairs the one before it ended on.  plain_bytes: the marker state (32 B per marker) at either slab end that
+ * is accessed with plain loads and stores (head_only != 0: at the slab's head alone), the rest non-temporal; 0 non-temporal
+ * everywhere, < 0 plain everywhere.
+ * Two pairs of warm-up, then ms[t], t < trials: ms per LAUNCH over `pairs` pairs.  blocks / threads 0: two workgroups
+ * of 768 per CU. */
+int pic1dp_probe_sweep(int32_t device, int64_t n, int32_t log2_tile, int32_t alternate, int64_t plain_bytes, int32_t head_only,
+                       int32_t pairs, int32_t trials, int32_t blocks, int32_t threads, double *ms);
+
 /* x / lx by reciprocal + two FMA corrections (div_lx) against the IEEE division on n generated positions (cell
  * boundaries +- a few ulp, wide exponent range): *mismatches counts results that differ in any bit.  On the device,
  * and the same algorithm with the host's fma. */
@@ -147,6 +157,10 @@ int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]);
  * out = {workgroups, threads, non-temporal stores, markers a workgroup takes at a time}.  Workgroup b takes the chunks b,
  * b + workgroups, ... of [0, nalloc).  Nonzero: null argument, nalloc < 0 or num_cu < 1. */
 int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int64_t out[4]);
+/* The 64-pair chunks at the head of a species' slab that a one-pass launch accesses with plain loads and stores while the
+ * rest streams non-temporally (launch_policy.hpp stream_plain_chunks), on the HOST; nt: the launch is a non-temporal one.
+ * Nonzero: null argument or a negative count. */
+int pic1dp_probe_host_plain_chunks(int64_t np_all_species, int64_t np_species, int32_t nt, int64_t *chunks);
 /* GB/s of the load kernel's stores WITHOUT its arithmetic: slots [0, n) of the four arrays of a tiled slab written as the
  * kernel writes them (launch_policy.hpp load_launch: chunks of one tile group per workgroup, non-temporal above the
  * threshold), reps launches between two events after one warm-up -- the stream k_load is measured against. */

@@ -391,6 +391,11 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
       a.eh_im = c->eh_modes == 2 ? c->d_mode_h + 1 : c->fa.mode_im;
     }
     lc = pred_launch(c, S.np, pl.priv).lc;
+    {  // a non-temporal launch keeps the head of the slab in the Infinity Cache (launch_policy.hpp)
+      int64_t np_all = 0;
+      for (int k = 0; k < c->in.nspecies; ++k) np_all += c->sp[k].np;
+      a.plain_chunks = static_cast<int>(stream_plain_chunks(np_all, S.np, pl.stream_nt != 0));
+    }
     if (pl.tail_mode != 0 && s == pl.tail_species && !a.fused.on) wire_tail(c, a.tail, pl.tail_mode);
   }
   if (pl.diag)

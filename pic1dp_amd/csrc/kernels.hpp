@@ -376,6 +376,8 @@ struct StepArgsDev {
   GridConst g;
   SpeciesConst s;
   int nt;              // 1: non-temporal loads/stores (state larger than the Infinity Cache)
+  int plain_chunks;    // one-pass kernels, nt = 1: the first plain_chunks 64-pair chunks of the slab use plain accesses all
+                       // the same -- the share of the state kept in the cache (launch_policy.hpp stream_plain_chunks)
   double *t2;          // [np + 2] -f0'/f0 at the step-start velocity, carried from k_step_half to k_step_full (or null)
   // full kernel only: the diagnostics of output_all taken on the new state in the same pass (kernels_step.hip DIAG)
   DistGeom dg;

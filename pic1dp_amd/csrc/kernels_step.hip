@@ -650,6 +650,42 @@ __device__ __forceinline__ double priv_sums(const One &n, double p, int ix, doub
   return pred_one_private<DIST, MODE, POW2>(n, p, ix, wl, sAB, sS, a);
 }
 
+// The marker rows of a pair in the one-pass kernels.  A non-temporal launch (the state outgrows the 256 MiB Infinity
+// Cache) keeps the HEAD of the slab in that cache: its first StepArgsDev::plain_chunks 64-pair chunks are loaded and stored
+// with PLAIN accesses, the others non-temporally.  Non-temporal accesses pass the cache by and evict nothing from it, so
+// what the plain chunks bring in is still there when the next step comes round (tools/sweep_direction_probe.py,
+// profiles/r23/sweep_probe.log; launch_policy.hpp stream_plain_chunks sizes the share).  The choice is per chunk, hence
+// wave-uniform: a scalar branch around the loads and around the stores, the same arithmetic between them.  A plain
+// launch (NT = false) compiles to what it was.
+template <bool NT>
+__device__ __forceinline__ bool chunk_plain(int64_t j, const StepArgsDev &a) {
+  if constexpr (!NT) return false;
+  return __builtin_amdgcn_readfirstlane(static_cast<int>(j >> 6)) < a.plain_chunks;
+}
+template <bool NT, bool HAS_W>
+__device__ __forceinline__ void ld_marker_rows(bool plain, const double2 *x2, const double2 *v2, const double2 *w2, const double2 *p2,
+                                               int64_t o, double2 &X, double2 &V, double2 &W, double2 &P) {
+  if (NT && plain) {
+    X = ld2t<false>(x2 + o), V = ld2t<false>(v2 + o), P = ld2t<false>(p2 + o);
+    if constexpr (HAS_W) W = ld2t<false>(w2 + o);
+  } else {
+    X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
+    if constexpr (HAS_W) W = ld2t<NT>(w2 + o);
+  }
+}
+template <bool NT, bool PUSH_V, bool HAS_W>
+__device__ __forceinline__ void st_marker_rows(bool plain, double2 *x2, double2 *v2, double2 *w2, int64_t o, const One &n0, const One &n1) {
+  if (NT && plain) {
+    st2t<false>(x2 + o, n0.x, n1.x);
+    if constexpr (PUSH_V) st2t<false>(v2 + o, n0.v, n1.v);
+    if constexpr (HAS_W) st2t<false>(w2 + o, n0.w, n1.w);
+  } else {
+    st2t<NT>(x2 + o, n0.x, n1.x);
+    if constexpr (PUSH_V) st2t<NT>(v2 + o, n0.v, n1.v);
+    if constexpr (HAS_W) st2t<NT>(w2 + o, n0.w, n1.w);
+  }
+}
+
 // T2: 0 no carry of -f0'/f0; 1 this step evaluates it, the next step's value is stored; 2 this
 // step's value is loaded (stored by the previous k_step_one), the next step's stored
 // NM: kept modes of the prediction tiles (1 .. PRED_MAX_MODES); PRIV (NM = 1): six sums in thread-private slots instead
@@ -761,9 +797,9 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
     }
     if (j >= npair) continue;
     const int64_t o = tidx2(j);
-    const double2 X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
-    double2 W = make_double2(0.0, 0.0), T = make_double2(0.0, 0.0);
-    if constexpr (HAS_W) W = ld2t<NT>(w2 + o);
+    const bool plain = chunk_plain<NT>(j, a);
+    double2 X, V, P, W = make_double2(0.0, 0.0), T = make_double2(0.0, 0.0);
+    ld_marker_rows<NT, HAS_W>(plain, x2, v2, w2, p2, o, X, V, W, P);
     if constexpr (CARRY_IN) T = ld2t<NT>(t2 + j);
     int i0, i1;
     double l0, l1;
@@ -781,9 +817,7 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
       u1 = priv_sums<DIST, MODE, POW2, NM>(n1, P.y, i1, l1, sAB, sP + threadIdx.x, a);
     else
       u1 = pred_one<DIST, MODE, POW2, NM>(n1, P.y, i1, l1, sAB, sP, a, fx);
-    st2t<NT>(x2 + o, n0.x, n1.x);
-    if constexpr (PUSH_V) st2t<NT>(v2 + o, n0.v, n1.v);
-    if constexpr (HAS_W) st2t<NT>(w2 + o, n0.w, n1.w);
+    st_marker_rows<NT, PUSH_V, HAS_W>(plain, x2, v2, w2, o, n0, n1);
     if constexpr (CARRY_OUT) st2t<NT>(t2 + j, u0, u1);
   }
   if ((a.np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1000,9 +1034,9 @@ __global__ void __launch_bounds__(1024) PIC1DP_SUMS_ATTR k_step_sums(const StepA
     }
     if (j >= npair) continue;
     const int64_t o = tidx2(j);
-    const double2 X = ld2t<NT>(x2 + o), V = ld2t<NT>(v2 + o), P = ld2t<NT>(p2 + o);
-    double2 W = make_double2(0.0, 0.0), T = make_double2(0.0, 0.0);
-    if constexpr (HAS_W) W = ld2t<NT>(w2 + o);
+    const bool plain = chunk_plain<NT>(j, a);
+    double2 X, V, P, W = make_double2(0.0, 0.0), T = make_double2(0.0, 0.0);
+    ld_marker_rows<NT, HAS_W>(plain, x2, v2, w2, p2, o, X, V, W, P);
     if constexpr (CARRY_IN) T = ld2t<NT>(t2 + j);
     int i0, i1;
     double l0, l1;
@@ -1013,9 +1047,7 @@ __global__ void __launch_bounds__(1024) PIC1DP_SUMS_ATTR k_step_sums(const StepA
     const One n1 = step_full_one<DIST, MODE, POW2, CARRY_IN>(X.y, V.y, W.y, P.y, sE0, sEh, sR, a, T.y, &i1, &l1);
     PAIR_FENCE();
     const double u1 = pred_one_sums<DIST, MODE, POW2>(n1, P.y, i1, l1, sA, sB, ks, a);
-    st2t<NT>(x2 + o, n0.x, n1.x);
-    if constexpr (PUSH_V) st2t<NT>(v2 + o, n0.v, n1.v);
-    if constexpr (HAS_W) st2t<NT>(w2 + o, n0.w, n1.w);
+    st_marker_rows<NT, PUSH_V, HAS_W>(plain, x2, v2, w2, o, n0, n1);
     if constexpr (CARRY_OUT) st2t<NT>(t2 + j, u0, u1);
   }
   if ((a.np & 1) && blockIdx.x == 0 && threadIdx.x == 0) {

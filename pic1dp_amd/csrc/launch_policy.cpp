@@ -225,6 +225,14 @@ LoadLaunch load_launch(int64_t nalloc, int num_cu) {
   return l;
 }
 
+int64_t stream_plain_chunks(int64_t np_all_species, int64_t np_species, bool nt) {
+  if (!nt || np_species <= 0 || np_all_species < np_species) return 0;
+  // this species' share of the budget, in whole chunks of 64 pairs (4096 B of state)
+  const double share = static_cast<double>(np_species) / static_cast<double>(np_all_species);
+  const int64_t chunks = static_cast<int64_t>(share * static_cast<double>(kPlainStateBytes)) / 4096;
+  return std::min(chunks, ((np_species >> 1) + 63) >> 6);  // (a slab within the budget: every chunk)
+}
+
 int tail_sum_blocks(int64_t ntail) {
   return ntail > 0 ? static_cast<int>(std::min<int64_t>(kEnergyBlocks, (ntail + 255) / 256)) : 0;
 }

@@ -41,6 +41,17 @@ inline bool fits_fused_solve(const PredLaunch &pl) {
   return pl.lc.blocks <= pl.resident && pl.lc.threads >= 128 && pl.lc.threads % 64 == 0;
 }
 
+// ---- the share of the marker state a non-temporal one-pass launch keeps in the Infinity Cache ----
+// The 64-pair chunks at the HEAD of this species' slab that k_step_one / k_step_sums access with plain loads and stores
+// (StepArgsDev::plain_chunks) while the rest streams non-temporally: non-temporal accesses pass the cache by, so the plain
+// share stays resident from step to step.  All species together get kPlainStateBytes of state (x, v, w, p: 32 B a marker,
+// 4096 B a chunk), each species its share by marker count.  Measured on the pure 4-read / 3-write stream
+// (tools/sweep_direction_probe.py, profiles/r23/sweep_probe.log) at 1e7, 1.25e7 and 1e8 markers: 224 ... 272 MiB at the
+// head do alike (as 2 x 112 ... 2 x 128 MiB at the two ends do), less keeps less, more begins to thrash.
+// 0: a plain launch (the state fits the cache as it is), no markers.
+constexpr int64_t kPlainStateBytes = static_cast<int64_t>(256) << 20;
+int64_t stream_plain_chunks(int64_t np_all_species, int64_t np_species, bool nt);
+
 // ---- the diagnostics passes of output_all (kernels_diag.hip) ----
 constexpr size_t kDiagLdsCap = 150 * 1024;  // a workgroup's LDS copy of the histograms: one workgroup of 1024 threads per CU
 constexpr int kEnergyBlocks = 1024;         // most workgroups a pass over tail slots gets

@@ -67,6 +67,12 @@ extern "C" int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int
   return 0;
 }
 
+extern "C" int pic1dp_probe_host_plain_chunks(int64_t np_all_species, int64_t np_species, int32_t nt, int64_t *chunks) {
+  if (!chunks || np_all_species < 0 || np_species < 0) return 1;
+  *chunks = stream_plain_chunks(np_all_species, np_species, nt != 0);
+  return 0;
+}
+
 static int moments_plan_words(const MomentsPlan &m, int64_t out[35]) {
   if (!out) return 1;
   for (int i = 0; i < 35; ++i) out[i] = 0;

@@ -157,7 +157,48 @@ __global__ void __launch_bounds__(1024) k_layout_probe(double2 *base, int64_t st
   }
 }
 
+// Sweep probe (tuning only): the tiled read/write traffic of k_layout_probe, grid-stride, in 64-pair chunks, with the
+// chunk ADDRESSES either as they stand (dir 0) or mirrored (dir 1: chunk c of the launch's time order lies at
+// nchunk - 1 - c; lanes stay ascending within a chunk).  Launched forward and backward in turn over one slab, the
+// pairs a launch ends on are the ones the next launch starts on: their reuse distance is twice their distance from
+// the turning end, not the slab.  The first plain_head and the last plain_tail chunks use plain loads and stores, the
+// others non-temporal ones (a wave-uniform choice): 0, 0 is non-temporal everywhere, >= nchunk plain everywhere.
+template <bool NT>
+__device__ __forceinline__ void sweep_probe_pair(double2 *base, int64_t o, int64_t d) {
+  const double2 a = ld2t<NT>(base + o), b = ld2t<NT>(base + o + d), c = ld2t<NT>(base + o + 2 * d), e = ld2t<NT>(base + o + 3 * d);
+  const double sx = a.x + b.x + c.x + e.x, sy = a.y + b.y + c.y + e.y;
+  st2t<NT>(base + o, sx * 0.25, sy * 0.25);
+  st2t<NT>(base + o + d, sx * 0.125, sy * 0.125);
+  st2t<NT>(base + o + 2 * d, sx * 0.0625, sy * 0.0625);
+}
+__global__ void __launch_bounds__(1024) k_sweep_probe(double2 *base, int lt2, int64_t npair, int dir, int64_t plain_head,
+                                                      int64_t plain_tail) {
+  const int64_t mask = (static_cast<int64_t>(1) << lt2) - 1, d = static_cast<int64_t>(1) << lt2;
+  const int64_t nchunk = (npair + 63) >> 6;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t j0 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j0 < (nchunk << 6); j0 += stride) {
+    const int64_t c = j0 >> 6, cm = dir ? nchunk - 1 - c : c;
+    const int64_t j = (cm << 6) + (threadIdx.x & 63);
+    if (j >= npair) continue;
+    const int64_t o = ((j >> lt2) << (lt2 + 2)) + (j & mask);
+    const int plain = __builtin_amdgcn_readfirstlane(static_cast<int>(cm < plain_head || cm >= nchunk - plain_tail));
+    if (plain)
+      sweep_probe_pair<false>(base, o, d);
+    else
+      sweep_probe_pair<true>(base, o, d);
+  }
+}
+
 }  // namespace
+
+// one launch of the sweep probe over a tiled slab of n markers (n a multiple of the tile, threads a multiple of 64)
+hipError_t launch_sweep_probe(double *base, int log2_tile, int64_t n, int dir, int64_t plain_head, int64_t plain_tail, int blocks,
+                              int threads, hipStream_t st) {
+  if (threads <= 0 || (threads & 63) || log2_tile < 7 || (n & ((static_cast<int64_t>(1) << log2_tile) - 1))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sweep_probe, dim3(blocks), dim3(threads), 0, st, reinterpret_cast<double2 *>(base), log2_tile - 1, n >> 1,
+                     dir, plain_head, plain_tail);
+  return hipGetLastError();
+}
 
 // variant: bit 0 tiled, bit 1 read-only (k_step_half's shape), bit 2 one workgroup per tile
 hipError_t launch_layout_probe(double *base, int64_t step_doubles, int log2_tile, int64_t n, int variant, int blocks,
@@ -442,6 +483,41 @@ int pic1dp_probe_layout(int32_t device, int64_t n, int32_t log2_tile, int64_t st
   if (keep) {
     g_keep.push_back(base.p);
     base.p = nullptr;
+  }
+  return 0;
+}
+
+int pic1dp_probe_sweep(int32_t device, int64_t n, int32_t log2_tile, int32_t alternate, int64_t plain_bytes, int32_t head_only,
+                       int32_t pairs, int32_t trials, int32_t blocks, int32_t threads, double *ms) {
+  if (!ms || n < 2 || pairs < 1 || trials < 1 || log2_tile < 7 || log2_tile > 24) return pfail("bad argument");
+  PROBE_TRY(hipSetDevice(device));
+  if (threads <= 0) threads = 768;  // the whole-step kernels' shape: two workgroups of 768 per CU
+  if (blocks <= 0) blocks = num_cu(device) * 2;
+  if (threads & 63) return pfail("threads must be a multiple of 64");
+  const int64_t tile = static_cast<int64_t>(1) << log2_tile;
+  n = n / tile * tile;
+  if (n < tile) return pfail("n below one tile");
+  const int64_t nchunk = ((n >> 1) + 63) >> 6;
+  // plain_bytes of marker state (32 B per marker, 64 pairs per chunk) at either end, or at the head alone; < 0: plain everywhere
+  const int64_t plain_head = plain_bytes < 0 ? nchunk : plain_bytes / (32 * 128), plain_tail = head_only ? 0 : plain_head;
+  DevBuf base;
+  PROBE_TRY(hipMalloc(&base.p, sizeof(double) * 4 * static_cast<size_t>(n)));
+  PROBE_TRY(hipMemset(base.p, 0, sizeof(double) * 4 * static_cast<size_t>(n)));
+  Events ev;
+  PROBE_TRY(hipEventCreate(&ev.a));
+  PROBE_TRY(hipEventCreate(&ev.b));
+  double *b = static_cast<double *>(base.p);
+  // every pair is (forward, forward) or (forward, backward); the direction keeps alternating across the trials
+  for (int t = -1; t < trials; ++t) {  // t = -1: two pairs of warm-up
+    if (t >= 0) PROBE_TRY(hipEventRecord(ev.a, nullptr));
+    for (int r = 0; r < 2 * (t < 0 ? 2 : pairs); ++r)
+      PROBE_TRY(launch_sweep_probe(b, log2_tile, n, alternate ? (r & 1) : 0, plain_head, plain_tail, blocks, threads, nullptr));
+    if (t < 0) continue;
+    PROBE_TRY(hipEventRecord(ev.b, nullptr));
+    PROBE_TRY(hipEventSynchronize(ev.b));
+    float e = 0.f;
+    PROBE_TRY(hipEventElapsedTime(&e, ev.a, ev.b));
+    ms[t] = e / (2 * pairs);
   }
   return 0;
 }

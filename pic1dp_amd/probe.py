@@ -35,6 +35,7 @@ SIGNATURES = {
     "pic1dp_probe_last_error": [],
     "pic1dp_probe_stream": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D],
     "pic1dp_probe_layout": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D],
+    "pic1dp_probe_sweep": [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D],
     "pic1dp_probe_release": [],
     "pic1dp_probe_div_lx": [C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
     "pic1dp_probe_host_div_lx": [C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
@@ -58,6 +59,7 @@ SIGNATURES = {
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
     "pic1dp_probe_host_load_launch": [C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_plain_chunks": [C.c_int64, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_write_stream": [C.c_int32, C.c_int64, C.c_int32, _D],
     "pic1dp_probe_load_uniforms": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
 }
@@ -112,6 +114,17 @@ def layout(n, log2_tile=12, reps=10, device=0, stagger_bytes=0, keep=0, blocks=0
     the same read-only]"""
     ms = (C.c_double * 6)()
     _check(load().pic1dp_probe_layout(device, int(n), log2_tile, int(stagger_bytes), reps, keep, blocks, threads, ms))
+    return list(ms)
+
+
+def sweep(n, alternate, plain_bytes=0, pairs=10, trials=5, head_only=False, log2_tile=12, device=0, blocks=0, threads=0):
+    """ms per launch, one figure per trial, of launch pairs of the tiled 4-read / 3-write traffic back to back over one
+    slab of n markers: alternate 0 forward -> forward, 1 forward -> backward (mirrored 64-pair chunks).  plain_bytes of
+    marker state at either slab end (head_only: at the head alone) use plain accesses, the rest non-temporal ones (0: none,
+    < 0: all plain)"""
+    ms = (C.c_double * trials)()
+    _check(load().pic1dp_probe_sweep(device, int(n), log2_tile, int(alternate), int(plain_bytes), int(bool(head_only)), pairs, trials, blocks,
+                                     threads, ms))
     return list(ms)
 
 
@@ -305,6 +318,15 @@ def host_load_launch(nalloc, num_cu=256):
     if load().pic1dp_probe_host_load_launch(int(nalloc), num_cu, out) != 0:
         raise RuntimeError("pic1dp_probe_host_load_launch: bad argument")
     return dict(blocks=out[0], threads=out[1], nt=bool(out[2]), chunk=out[3])
+
+
+def host_plain_chunks(np_all_species, np_species, nt=True):
+    """the 64-pair chunks at the head of a species' slab that a non-temporal one-pass launch keeps in the Infinity Cache
+    with plain accesses (csrc/launch_policy.hpp stream_plain_chunks), on the host"""
+    out = C.c_int64(-1)
+    if load().pic1dp_probe_host_plain_chunks(int(np_all_species), int(np_species), int(bool(nt)), C.byref(out)) != 0:
+        raise ValueError("pic1dp_probe_host_plain_chunks: bad argument")
+    return out.value
 
 
 def load_uniforms(kind, g, seed_offset=0, ispecies=0, device=0):
