@@ -685,6 +685,75 @@ int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, d
 int pic1dp_hip_power(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
 int pic1dp_hip_power_len(const pic1dp_input *in, int32_t which, int64_t *n);   /* host only */
 
+/* ---- select and gather markers on the device: phase-space samples and tracers ----------
+ * pic1dp_hip_select hands out the markers of one species that lie in a window of (x, v), thinned by a hash of their global
+ * index, in ascending logical index; pic1dp_hip_gather hands out the markers at given logical indices.  Neither moves the
+ * species over PCIe: what crosses is 40 B (select) or 32 B (gather) per marker handed out. */
+typedef struct pic1dp_select {
+  double x_lo, x_hi;   /* window in the WRAPPED position px */
+  double v_lo, v_hi;   /* window in v */
+  uint64_t thin;       /* 0: keep every marker of the window; else keep iff h(g) < thin */
+  uint64_t key;        /* of the thinning hash */
+  int64_t origin;      /* g = origin + i: pass pic1dp_hip_load_origin's G0 and a sample no longer depends on the split over ranks */
+} pic1dp_select;
+/* The rule.  It applies to every valid marker i < np of the species, in the logical order of pic1dp_hip_particles_download,
+ * on the state a pic1dp_hip_particles_download at that moment would return:
+ *     px = wrap(x)                                  the deposit's wrap (src/pic1dp_interaction.F90:102-104: fmod, then + lx
+ *                                                   where negative), NOT stored back; px == lx, the known rounding case of
+ *                                                   a tiny negative x, is used as it is
+ *     in_x = x_lo <= px && px < x_hi                when x_lo <= x_hi
+ *     in_x = px >= x_lo || px < x_hi                when x_lo > x_hi: the window straddles the periodic boundary
+ *     in_v = v_lo <= v && v < v_hi
+ *     h(g) = mix64(key + (g + 1) * 0x9E3779B97F4A7C15) mod 2^64,  g = origin + i      (mix64: particle_load_device above)
+ *     selected = in_x && in_v && (thin == 0 || h(g) < thin)
+ *   - Bounds.  +-inf bounds are allowed: that is how a caller says "all".  x_lo == x_hi is the empty window.
+ *     A NaN bound is PIC1DP_ERR_ARG.  A NaN px or v is never selected: every comparison with it is false.  The upper
+ *     bounds are strict, so neither is v = +inf (an infinite x wraps to NaN).
+ *   - Thinning.  The hash depends on the marker's index alone, not on its values: the same markers are kept at every
+ *     time, which makes a thinned selection a tracer set.  It is a hash and not a stride: global marker g of a quiet
+ *     start has u_v = bitrev64(g) 2^-64, so "every 2^k-th marker" is one band of velocities.
+ *     pic1dp_hip_select_thin(fraction, &thin): fraction >= 1 gives 0 (keep all), fraction <= 0 or NaN is PIC1DP_ERR_ARG,
+ *     otherwise thin = max(1, floor(fraction 2^64)).  Host only.
+ *   - Tail slots (i >= np) are never selected, whatever they hold.
+ *   - Output.  The selected markers in ascending i: the stored bits of x (unwrapped, as download gives it), v, p and w,
+ *     and i itself.  On a full-f context (deltaf = 0) w is whatever pic1dp_hip_particles_download gives there.  The
+ *     result equals a boolean mask on the downloaded arrays bit for bit, whatever the launch shape.
+ * pic1dp_hip_select_count: *count = the number of markers selected.
+ * pic1dp_hip_select: *count = the number selected (the total, whatever max is); the first min(count, max) of them are
+ *   written to index, x, v, p, w (max elements each), so truncation shows as count > max.  Any output pointer may be NULL
+ *   (that array is not handed out).  max = 0 is legal and equals select_count.  max < 0, a null sel or count, a NaN bound
+ *   or an unknown species is PIC1DP_ERR_ARG with nothing written.
+ * pic1dp_hip_gather: x[k], v[k], p[k], w[k] (any may be NULL) = the values of the marker at logical index index[k],
+ *   k < n.  Indices in any order, duplicates allowed, 0 <= index < nalloc: tail slots included, as download returns
+ *   them.  The indices are checked on the host before anything is launched; one outside the range is PIC1DP_ERR_ARG
+ *   naming the first offender.  n = 0 is a no-op that returns 0; n < 0 or a null index is PIC1DP_ERR_ARG.
+ * pic1dp_hip_host_select: the rule on HOST arrays x, v of np markers (lx from the input): *count and the first
+ *   min(count, max) logical indices (index may be NULL).  Host only, no device, no context.
+ * When the calls may come.  The rule of pic1dp_hip_moments.  Between time steps they launch their own passes and nothing
+ * else and change nothing: markers, fields, the one-pass prediction, a pending fused solve, cached diagnostics and the
+ * state digest survive.  Inside a time step (a push noted) the noted push becomes memory first.  No communicator is used;
+ * the results are LOCAL to the context.  pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect them, and
+ * the checkpoint carries nothing of them.
+ * Memory.  The chunk counts (8 B per 16384 markers), the device buffer of the result (min(count, max) x 40 B) and a
+ * gather's index and result buffers (n x 40 B) live for the call only: the context's standing allocation does not grow.
+ * An allocation that fails is PIC1DP_ERR_NOMEM.  The transfer to the host goes through the context's pinned staging in
+ * slices of at most 32 MiB, as the checkpoint's does.
+ * Cost: pic1dp_hip_select_count is one pass over x and v (16 B per marker) and a one-workgroup prefix sum of the chunk
+ * counts; pic1dp_hip_select adds a second pass over x and v of the chunks that hold a selected marker of rank < max
+ * (chunks without one are skipped), 16 B read of p and w and 40 B written per marker handed out.  No per-marker bitmap
+ * is kept between the passes.  pic1dp_hip_gather is four 8-byte reads at random places and four stores per entry.
+ * Measured at 1e8 markers on one MI355X, device time: select_count 0.26 ms (0.97 of a pure read stream
+ * of x and v), a select of 2^20 markers 0.67 ms, a gather of 2^20 random indices 0.11 ms; 7 ms of wall clock per select
+ * call with its transfer, against 600 ms for pic1dp_hip_particles_download and a mask on the host. */
+int pic1dp_hip_select_count(pic1dp_ctx *ctx, int32_t ispecies, const pic1dp_select *sel, int64_t *count);
+int pic1dp_hip_select(pic1dp_ctx *ctx, int32_t ispecies, const pic1dp_select *sel, int64_t max, int64_t *count,
+                      int64_t *index, double *x, double *v, double *p, double *w);
+int pic1dp_hip_gather(pic1dp_ctx *ctx, int32_t ispecies, const int64_t *index, int64_t n,
+                      double *x, double *v, double *p, double *w);
+int pic1dp_hip_host_select(const pic1dp_input *in, const pic1dp_select *sel, const double *x, const double *v, int64_t np,
+                           int64_t max, int64_t *count, int64_t *index);          /* host only, no device */
+int pic1dp_hip_select_thin(double fraction, uint64_t *thin);                      /* host only */
+
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
   int32_t format_version;
@@ -841,7 +910,14 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * which = 19: *launches = passes of pic1dp_hip_particle_load_device (k_load, one per species and call) launched so far,
  * *ms = their accumulated device milliseconds while kernel stats were enabled;
  * which = 20: *launches = passes of pic1dp_hip_power (k_power) launched so far, *ms = their accumulated device
- * milliseconds while kernel stats were enabled */
+ * milliseconds while kernel stats were enabled;
+ * which = 21: *launches = passes over the markers of pic1dp_hip_select_count and pic1dp_hip_select launched so far -- the
+ * count pass (k_select_count, with the prefix sum of the chunk counts behind it) and the write pass (k_select_write) count
+ * one each: 1 per select_count, 2 per select that hands markers out, 1 per select with nothing to write (max = 0, no
+ * marker selected, or every output pointer NULL), 0 for a species without valid markers -- *ms = their accumulated device
+ * milliseconds while kernel stats were enabled;
+ * which = 22: *launches = launches of pic1dp_hip_gather (k_gather, one per call with n > 0) so far, *ms = their accumulated
+ * device milliseconds while kernel stats were enabled */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);

@@ -16,7 +16,7 @@ extern "C" {
 
 const char *pic1dp_probe_last_error(void);
 
-/* nread (1, 4, 7) arrays of n doubles read and nwrite (0, 1, 3) written, 16 B per lane, grid-stride, reps launches
+/* nread (1, 2, 4, 7) arrays of n doubles read and nwrite (0, 1, 3) written, 16 B per lane, grid-stride, reps launches
  * after one warm-up; variant 0 plain, 1 non-temporal (the marker kernels' accesses), 2 plain with two pairs per
  * lane.  blocks / threads 0: the sub-step kernels' launch shape (four workgroups of 512 per CU). */
 int pic1dp_probe_stream(int32_t device, int32_t nread, int32_t nwrite, int64_t n, int32_t reps, int32_t blocks,
@@ -136,6 +136,13 @@ int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, int32_t delt
  * out holds 4 + 8 * 2 words.  Nonzero: null argument. */
 int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
                                  int32_t num_cu, int64_t out[20]);
+
+/* The count and write passes of a selection over np valid markers (launch_policy.hpp select_plan), on the HOST: out = {pairs
+ * of a chunk, chunks, workgroups, threads, non-temporal loads, threads of the prefix sum's one workgroup}.  Chunk c holds the
+ * logical pairs [c * pairs, min((c + 1) * pairs, np / 2)), and the odd last marker (np odd) belongs to the last chunk; np = 0:
+ * no chunk, nothing is launched (the grid is still reported as 1).  threads_req / bpc_req: pic1dp_hip_set_launch's (0: the
+ * library's choice).  Nonzero: null argument. */
+int pic1dp_probe_host_select_plan(int64_t np, int32_t num_cu, int32_t threads_req, int32_t bpc_req, int64_t out[6]);
 
 /* What pic1dp_hip_create decides before its first allocation (pic1dp_amd/csrc/context_plan.hpp plan_context), on the HOST,
  * for an input, a layout and the three requests of the settings that bear on it (0: none): PIC1DP_PRED_KIND,

@@ -76,6 +76,12 @@ class CheckpointInfo(C.Structure):
                 ("digest", (C.c_uint64 * 4) * MAX_SPECIES), ("checksum", C.c_uint64)]
 
 
+class Select(C.Structure):
+    """struct pic1dp_select: a window of (wrapped x, v) and the thinning hash's threshold, key and index origin"""
+    _fields_ = [("x_lo", C.c_double), ("x_hi", C.c_double), ("v_lo", C.c_double), ("v_hi", C.c_double),
+                ("thin", C.c_uint64), ("key", C.c_uint64), ("origin", C.c_int64)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _INP = C.POINTER(Input)
@@ -175,6 +181,11 @@ SIGNATURES = {
     "pic1dp_hip_moments_exact": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_power": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_power_len": [_INP, C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_select_count": [_P, C.c_int32, C.POINTER(Select), C.POINTER(C.c_int64)],
+    "pic1dp_hip_select": [_P, C.c_int32, C.POINTER(Select), C.c_int64, C.POINTER(C.c_int64), _P, _P, _P, _P, _P],
+    "pic1dp_hip_gather": [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P],
+    "pic1dp_hip_host_select": [_INP, C.POINTER(Select), _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _P],
+    "pic1dp_hip_select_thin": [C.c_double, C.POINTER(C.c_uint64)],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

@@ -1080,7 +1080,13 @@ int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
 
 int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
   CHECK_CTX(c);
-  if (which < 0 || which > 20) return fail(PIC1DP_ERR_ARG, "which must be 0..20");
+  if (which < 0 || which > 22) return fail(PIC1DP_ERR_ARG, "which must be 0..22");
+  if (which == 21 || which == 22) {  // passes of pic1dp_hip_select_count / _select (21), launches of pic1dp_hip_gather (22); *ms: their device time while kernel stats were enabled
+    if (int rc = ev_resolve(c)) return rc;
+    if (ms) *ms = c->acc_ms[which == 21 ? kTagSelect : kTagGather];
+    if (launches) *launches = which == 21 ? c->select_passes : c->gather_launches;
+    return PIC1DP_OK;
+  }
   if (which == 20) {  // passes of pic1dp_hip_power (k_power) launched so far; *ms: their device time while kernel stats were enabled
     if (int rc = ev_resolve(c)) return rc;
     if (ms) *ms = c->acc_ms[kTagPower];

@@ -8,6 +8,8 @@
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
 //   capi_diag.cpp      diagnostics of output_all; the velocity moments on the field grid (pic1dp_hip_moments, _moments_exact)
+//   capi_select.cpp    select and gather markers on the device (pic1dp_hip_select_count, _select, _gather); the rule on the
+//                      host and the thinning threshold: select_host.cpp (select_rule.hpp; no HIP call)
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
 //   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
@@ -56,7 +58,7 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kNumTags = 128;
+              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kTagSelect = 111, kTagGather = 112, kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
@@ -273,6 +275,9 @@ struct pic1dp_ctx {
   // copy, allocated at the first call
   double *d_pow = nullptr, *h_pow = nullptr;
   int64_t power_passes = 0;                // k_power passes launched so far (kernel_stats 20)
+  // pic1dp_hip_select_count / _select / _gather (capi_select.cpp): every buffer of theirs lives for the call only
+  int64_t select_passes = 0;               // k_select_count and k_select_write passes launched so far (kernel_stats 21)
+  int64_t gather_launches = 0;             // k_gather launches so far (kernel_stats 22)
   int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field
   int chain_selftest = 0;                  // create()'s verdict on the serial sums through the matrix unit: 1 identical, 0 differs, -1 could not run
   int32_t itime = 0;

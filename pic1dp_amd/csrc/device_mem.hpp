@@ -33,6 +33,18 @@ class DeviceMem {
     *slot = nullptr;
     return take(reinterpret_cast<void **>(slot), sizeof(T) * n, pinned);
   }
+  // a buffer that lives for one call (capi_select.cpp: a selection's result, a gather's indices) goes back before the call
+  // returns: freed, forgotten, *slot null.  The standing allocation of the context is what it was before the call.
+  template <class T>
+  void release(T **slot) {
+    for (size_t i = 0; i < held.size(); ++i)
+      if (held[i].p == static_cast<void *>(*slot)) {
+        free_one(held[i]);
+        held.erase(held.begin() + static_cast<long>(i));
+        break;
+      }
+    *slot = nullptr;
+  }
   // device memory allocated elsewhere (hipMalloc) becomes this owner's
   void adopt(void *p) {
     if (p) held.push_back(Held{p, false});

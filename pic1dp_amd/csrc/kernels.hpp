@@ -671,6 +671,48 @@ struct LoadLaunch {
 constexpr int64_t LOAD_CHUNK = TILE_LOG2 ? TILE : 4096;
 hipError_t launch_load(const LoadArgs &a, int kind, int iptcldist, bool nonlinear, const LoadLaunch &ll, hipStream_t st);
 
+// ---- select and gather markers (kernels_select.hip; the definition: include/pic1dp_hip.h pic1dp_hip_select) ----
+// The valid markers are cut into fixed contiguous chunks of SELECT_CHUNK_PAIRS logical pairs (2 j, 2 j + 1): chunk c holds
+// pairs [c CP, min((c + 1) CP, np / 2)), and the odd last marker (np odd) belongs to the last chunk.  The cut depends on np
+// alone, never on the launch shape: that, and ranks inside a chunk from ballots in lane order, fix the output order.
+// 8192 pairs = 128 trips of a one-wave workgroup (eight of 1024 threads) = 256 KiB of x and v: 6104 chunks at 1e8 markers, a
+// prefix sum one workgroup does in six rounds, about a chunk per workgroup of the default grid.
+constexpr int64_t SELECT_CHUNK_PAIRS = 8192;
+// the rule as the kernels take it (pic1dp_select and lx; straddle: x_lo > x_hi)
+struct SelectRule {
+  double lx, x_lo, x_hi, v_lo, v_hi;
+  unsigned long long thin, key, origin;
+  int straddle;
+};
+// launch shape of the count and write passes (launch_policy.hpp select_plan)
+struct SelectPlan {
+  int64_t chunk_pairs, nchunk;   // nchunk = 0: no valid marker, nothing is launched
+  int blocks, threads;           // workgroups take chunks grid-stride; threads a multiple of 64, <= 1024
+  bool nt;                       // non-temporal loads of x and v
+  int scan_threads;              // the prefix sum's one workgroup
+};
+// where a species' markers live: x, v, p, w of slots below np (the current set; p has one copy) and of the tail slots (set 0)
+struct SelectArrays {
+  const double *x, *v, *p, *w;
+};
+// what a selection hands out, device arrays of `cap` elements each, any of them null
+struct SelectOut {
+  long long *index;
+  double *x, *v, *p, *w;
+};
+// counts[c] <- markers of chunk c the rule selects, c < nchunk (counts: nchunk + 1 words)
+hipError_t launch_select_count(const SelectArrays &a, int64_t np, const SelectRule &r, unsigned long long *counts,
+                               const SelectPlan &pl, hipStream_t st);
+// counts[c] <- sum of counts[0 .. c - 1] in place, counts[nchunk] <- the total; one workgroup
+hipError_t launch_select_scan(unsigned long long *counts, const SelectPlan &pl, hipStream_t st);
+// the selected markers of global rank r < cap to out[r], in ascending logical index; prefix: what launch_select_scan left
+hipError_t launch_select_write(const SelectArrays &a, int64_t np, const SelectRule &r, const unsigned long long *prefix,
+                               int64_t cap, const SelectOut &out, const SelectPlan &pl, hipStream_t st);
+// out.x/v/p/w[k] <- the marker at logical index index[k], k < n: from cur while index[k] < np, from tail beyond; the caller
+// has checked 0 <= index[k] < nalloc
+hipError_t launch_gather(const SelectArrays &cur, const SelectArrays &tail, int64_t np, const long long *index, int64_t n,
+                         const SelectOut &out, hipStream_t st);
+
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

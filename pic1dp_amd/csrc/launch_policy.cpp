@@ -207,6 +207,19 @@ PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int6
   return m;
 }
 
+SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req) {
+  SelectPlan s{};
+  s.chunk_pairs = SELECT_CHUNK_PAIRS;
+  const int64_t npair = np > 0 ? np >> 1 : 0;
+  s.nchunk = np > 0 ? std::max<int64_t>(1, (npair + s.chunk_pairs - 1) / s.chunk_pairs) : 0;
+  s.threads = threads_req > 0 && threads_req <= 1024 && threads_req % 64 == 0 ? threads_req : 64;
+  const int bpc = bpc_req > 0 ? bpc_req : 24;
+  s.blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(static_cast<int64_t>(num_cu) * bpc, s.nchunk)));
+  s.nt = 16.0 * static_cast<double>(np) > 288.0 * 1048576.0;
+  s.scan_threads = 1024;
+  return s;
+}
+
 DigestLaunch digest_launch(int64_t nalloc, int num_cu) {
   DigestLaunch d{};
   d.threads = 256;

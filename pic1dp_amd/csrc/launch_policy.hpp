@@ -88,6 +88,18 @@ MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int nu
 constexpr size_t power_tile_bytes(int nx) { return (sizeof(double) * (static_cast<size_t>(nx) + 1) + 15) & ~static_cast<size_t>(15); }
 PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu);
 
+// ---- select and gather markers (kernels_select.hip; include/pic1dp_hip.h pic1dp_hip_select) ----
+// The count pass and the write pass of a selection over np valid markers, one shape for both: chunks of SELECT_CHUNK_PAIRS
+// pairs (kernels.hpp), nchunk = max(1, ceil((np / 2) / chunk pairs)) for np > 0 (one marker alone is the odd last marker of
+// chunk 0) and 0 for np = 0; workgroups of ONE wave (64 threads), 24 per CU = six waves per SIMD, what 79 registers and 106
+// scalar ones admit, never more than there are chunks,
+// at least one.  A wave of its own needs nobody's totals: the write pass's barrier per trip is free, where at 512 threads x 3
+// it costs a fifth of the selection (measured at 1e8 markers, DESIGN.md 2.18: 0.674 against 0.803 ms; 1024 x 2: 1.07 ms).
+// pic1dp_hip_set_launch's threads and workgroups per CU are taken literally when given
+// (threads_req a multiple of 64, <= 1024; 0: the choice above): the result does not depend on them.  Non-temporal loads
+// once x and v (16 B per marker) exceed the threshold of diag_launch.  The prefix sum runs in one workgroup of 1024.
+SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req);
+
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
 // (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs

@@ -110,6 +110,14 @@ extern "C" int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t 
   return 0;
 }
 
+extern "C" int pic1dp_probe_host_select_plan(int64_t np, int32_t num_cu, int32_t threads_req, int32_t bpc_req, int64_t out[6]) {
+  if (!out) return 1;
+  const SelectPlan s = select_plan(np, num_cu, threads_req, bpc_req);
+  const int64_t v[6] = {s.chunk_pairs, s.nchunk, s.blocks, s.threads, s.nt, s.scan_threads};
+  for (int k = 0; k < 6; ++k) out[k] = v[k];
+  return 0;
+}
+
 extern "C" int pic1dp_probe_host_dist_scale(int64_t np, int32_t blocks, int32_t deltaf, double bound_p, double bound_w,
                                             int32_t threads, int32_t out[4]) {
   if (!out) return 1;

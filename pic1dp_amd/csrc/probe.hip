@@ -228,6 +228,7 @@ hipError_t launch_stream_probe(double *const *in, int nr, double *const *out, in
   a.npair = n >> 1;
   switch (nr) {
     case 1: return launch_probe_nr<1>(a, nw, variant, blocks, threads, st);
+    case 2: return launch_probe_nr<2>(a, nw, variant, blocks, threads, st);   // x and v alone: the selection's passes
     case 4: return launch_probe_nr<4>(a, nw, variant, blocks, threads, st);
     case 7: return launch_probe_nr<7>(a, nw, variant, blocks, threads, st);
     default: return hipErrorInvalidValue;
@@ -421,8 +422,8 @@ const char *pic1dp_probe_last_error(void) { return g_perr.c_str(); }
 int pic1dp_probe_stream(int32_t device, int32_t nread, int32_t nwrite, int64_t n, int32_t reps, int32_t blocks,
                         int32_t threads, int32_t variant, double *gbytes_per_s) {
   if (!gbytes_per_s || n < 2 || reps < 1) return pfail("bad argument");
-  if ((nread != 1 && nread != 4 && nread != 7) || (nwrite != 0 && nwrite != 1 && nwrite != 3))
-    return pfail("nread must be 1, 4 or 7 and nwrite 0, 1 or 3");
+  if ((nread != 1 && nread != 2 && nread != 4 && nread != 7) || (nwrite != 0 && nwrite != 1 && nwrite != 3))
+    return pfail("nread must be 1, 2, 4 or 7 and nwrite 0, 1 or 3");
   PROBE_TRY(hipSetDevice(device));
   if (threads <= 0) threads = 512;  // the sub-step kernels' shape: four workgroups of 512 per CU
   if (blocks <= 0) blocks = num_cu(device) * (2048 / threads);

@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Input, Layout, Pic1dpError, check  # noqa: F401
+from ._lib import Input, Layout, Pic1dpError, Select, check  # noqa: F401
 
 
 def make_input(**kw):
@@ -193,6 +193,48 @@ class Pic1dp:
             o = out[j * per:(j + 1) * per]
             res[name] = {"xv": o[:nxo * nvo].reshape(nvo, nxo).copy(), "v": o[nxo * nvo:nxo * nvo + nvo].copy(), "rest": float(o[-1])}
         return res
+
+    # -- select and gather markers on the GPU --------------------
+    def _selection(self, ispecies, x, v, fraction, key, origin):
+        if origin is None:
+            origin = load_origin(self.inp, ispecies, self.rank, self.nranks, self.npe)
+        return make_select(x, v, fraction, key, origin)
+
+    def select_count(self, ispecies=0, x=(-np.inf, np.inf), v=(-np.inf, np.inf), fraction=1.0, key=0, origin=None):
+        """how many valid markers of a species select() would hand out (include/pic1dp_hip.h pic1dp_hip_select_count): one
+        pass over x and v on the GPU, nothing but the count crosses to the host"""
+        sel, n = self._selection(int(ispecies), x, v, fraction, key, origin), C.c_int64()
+        check(self.L.pic1dp_hip_select_count(self._ctx, int(ispecies), C.byref(sel), C.byref(n)))
+        return n.value
+
+    def select(self, ispecies=0, x=(-np.inf, np.inf), v=(-np.inf, np.inf), fraction=1.0, key=0, origin=None, max=None):
+        """the valid markers of a species inside a window, thinned by a hash of their global index, selected and compacted
+        on the GPU (include/pic1dp_hip.h pic1dp_hip_select).  x = (lo, hi): lo <= wrap(x) < hi, or the window across the
+        periodic boundary when lo > hi; v = (lo, hi): lo <= v < hi; +-inf says "all".  fraction: the share of the
+        window's markers to keep, the same markers at every time (a tracer set) and, with origin = this context's
+        load_origin (the default, None), the same markers however the run is split over ranks.  Returns dict(count, index,
+        x, v, p, w) in ascending logical index: `count` is the number selected, the arrays hold the first min(count, max)
+        of them (max=None: all -- it counts first and sizes the arrays from the count); x is as stored, not wrapped."""
+        isp = int(ispecies)
+        sel, n = self._selection(isp, x, v, fraction, key, origin), C.c_int64()
+        if max is None:
+            check(self.L.pic1dp_hip_select_count(self._ctx, isp, C.byref(sel), C.byref(n)))
+            max = n.value
+        index = np.empty(int(max), dtype=np.int64)
+        out = [np.empty(int(max)) for _ in range(4)]
+        check(self.L.pic1dp_hip_select(self._ctx, isp, C.byref(sel), int(max), C.byref(n), _ptr(index), *[_ptr(a) for a in out]))
+        m = min(n.value, int(max))
+        res = {"count": n.value, "index": index[:m]}
+        res.update({k: a[:m] for k, a in zip("xvpw", out)})
+        return res
+
+    def gather(self, ispecies, index):
+        """x, v, p, w of the markers at the given logical indices (any order, duplicates allowed, tail slots included), read
+        on the GPU (include/pic1dp_hip.h pic1dp_hip_gather): dict(x, v, p, w), equal to particles_download()[..][index]"""
+        idx = np.ascontiguousarray(index, dtype=np.int64).ravel()
+        out = [np.empty(idx.size) for _ in range(4)]
+        check(self.L.pic1dp_hip_gather(self._ctx, int(ispecies), _ptr(idx), idx.size, *[_ptr(a) for a in out]))
+        return dict(zip("xvpw", out))
 
     # -- state digest, checkpoint and restart (DESIGN.md 2.13) -----------------
     def state_digest(self):
@@ -708,6 +750,39 @@ def host_digest(a):
     out = C.c_uint64()
     check(_lib.load().pic1dp_hip_host_digest(_ptr(a), a.size, C.byref(out)))
     return int(out.value)
+
+
+def select_thin(fraction):
+    """the threshold `thin` of a kept fraction (include/pic1dp_hip.h pic1dp_hip_select_thin): 0 (keep all) for fraction >= 1,
+    else max(1, floor(fraction 2^64)); host only"""
+    t = C.c_uint64()
+    check(_lib.load().pic1dp_hip_select_thin(float(fraction), C.byref(t)))
+    return int(t.value)
+
+
+def make_select(x=(-np.inf, np.inf), v=(-np.inf, np.inf), fraction=1.0, key=0, origin=0, thin=None):
+    """struct pic1dp_select from windows (lo, hi), a kept fraction (or the threshold itself: thin), the hash's key and the
+    global index of logical marker 0"""
+    return Select(float(x[0]), float(x[1]), float(v[0]), float(v[1]), select_thin(fraction) if thin is None else int(thin),
+                  int(key) & (2**64 - 1), int(origin))
+
+
+def host_select(inp, x, v, x_window=(-np.inf, np.inf), v_window=(-np.inf, np.inf), fraction=1.0, key=0, origin=0, max=None,
+                thin=None):
+    """the selection rule on host arrays x, v of valid markers (include/pic1dp_hip.h pic1dp_hip_host_select; lx from the
+    input; no device): (count, the first min(count, max) logical indices); max=None: all of them"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if x.size != v.size:
+        raise ValueError("x and v must have one length")
+    sel, n = make_select(x_window, v_window, fraction, key, origin, thin), C.c_int64()
+    L = _lib.load()
+    if max is None:
+        check(L.pic1dp_hip_host_select(C.byref(inp), C.byref(sel), _ptr(x), _ptr(v), x.size, 0, C.byref(n), None))
+        max = n.value
+    index = np.empty(int(max), dtype=np.int64)
+    check(L.pic1dp_hip_host_select(C.byref(inp), C.byref(sel), _ptr(x), _ptr(v), x.size, int(max), C.byref(n), _ptr(index)))
+    return n.value, index[:min(n.value, int(max))]
 
 
 def load_origin(inp, ispecies=0, rank=0, nranks=1, npe=0):

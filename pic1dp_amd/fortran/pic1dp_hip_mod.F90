@@ -64,6 +64,13 @@ type, bind(C) :: pic1dp_checkpoint_info_t
   integer(c_int64_t) :: checksum
 end type pic1dp_checkpoint_info_t
 
+! struct pic1dp_select: a window of (wrapped x, v) and the thinning hash's threshold, key and index origin.  thin and key are
+! uint64_t in C: the same 64 bits (a threshold of 2^63 or more is a negative number here; pic1dp_hip_select_thin fills it in)
+type, bind(C) :: pic1dp_select_t
+  real(c_double) :: x_lo, x_hi, v_lo, v_hi
+  integer(c_int64_t) :: thin, key, origin
+end type pic1dp_select_t
+
 interface
   ! state digest, checkpoint and restart (include/pic1dp_hip.h; file names are C strings: trim(name) // c_null_char)
   function pic1dp_hip_state_digest(ctx, out) bind(C, name="pic1dp_hip_state_digest") result(ierr)
@@ -138,6 +145,52 @@ interface
     integer(c_int64_t), intent(out) :: n
     integer(c_int) :: ierr
   end function pic1dp_hip_power_len
+  ! select and gather markers on the device: the valid markers inside the window, thinned by a hash of their global index, in
+  ! ascending logical index (0-based, as the C side counts); count = the number selected, the first min(count, nmax) are
+  ! written.  Arrays not wanted: pass c_null_ptr through the type(c_ptr) arguments
+  function pic1dp_hip_select_count(ctx, ispecies, sel, count) bind(C, name="pic1dp_hip_select_count") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    type(pic1dp_select_t), intent(in) :: sel
+    integer(c_int64_t), intent(out) :: count
+    integer(c_int) :: ierr
+  end function pic1dp_hip_select_count
+  function pic1dp_hip_select(ctx, ispecies, sel, nmax, count, index, x, v, p, w) bind(C, name="pic1dp_hip_select") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    type(pic1dp_select_t), intent(in) :: sel
+    integer(c_int64_t), value :: nmax
+    integer(c_int64_t), intent(out) :: count
+    type(c_ptr), value :: index, x, v, p, w
+    integer(c_int) :: ierr
+  end function pic1dp_hip_select
+  function pic1dp_hip_gather(ctx, ispecies, index, n, x, v, p, w) bind(C, name="pic1dp_hip_gather") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int64_t), intent(in) :: index(*)
+    integer(c_int64_t), value :: n
+    type(c_ptr), value :: x, v, p, w
+    integer(c_int) :: ierr
+  end function pic1dp_hip_gather
+  function pic1dp_hip_host_select(inp, sel, x, v, np, nmax, count, index) bind(C, name="pic1dp_hip_host_select") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    type(pic1dp_select_t), intent(in) :: sel
+    real(c_double), intent(in) :: x(*), v(*)
+    integer(c_int64_t), value :: np, nmax
+    integer(c_int64_t), intent(out) :: count
+    type(c_ptr), value :: index
+    integer(c_int) :: ierr
+  end function pic1dp_hip_host_select
+  function pic1dp_hip_select_thin(fraction, thin) bind(C, name="pic1dp_hip_select_thin") result(ierr)
+    import
+    real(c_double), value :: fraction
+    integer(c_int64_t), intent(out) :: thin
+    integer(c_int) :: ierr
+  end function pic1dp_hip_select_thin
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

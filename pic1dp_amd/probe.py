@@ -55,6 +55,7 @@ SIGNATURES = {
     "pic1dp_probe_host_moments_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_moments_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_power_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_select_plan": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
@@ -251,6 +252,19 @@ def host_power_plan(nx, nx_opd, nv_opd, which, deltaf, np_, num_cu):
         raise ValueError("pic1dp_probe_host_power_plan")
     return dict(selected=out[1], tile=out[2], plane=out[3],
                 passes=[dict(zip(POWER_PASS_FIELDS, out[4 + 8 * i:12 + 8 * i])) for i in range(out[0])])
+
+
+SELECT_PLAN_FIELDS = ("chunk_pairs", "nchunk", "blocks", "threads", "nt", "scan_threads")
+
+
+def host_select_plan(np_, num_cu, threads=0, blocks_per_cu=0):
+    """the count and write passes of a selection over np_ valid markers (csrc/launch_policy.hpp select_plan), on the host: a
+    dict of SELECT_PLAN_FIELDS.  Chunk c holds the logical pairs [c chunk_pairs, min((c + 1) chunk_pairs, np_ // 2)), the
+    odd last marker belongs to the last chunk"""
+    out = (C.c_int64 * 6)()
+    if load().pic1dp_probe_host_select_plan(int(np_), int(num_cu), int(threads), int(blocks_per_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_select_plan")
+    return dict(zip(SELECT_PLAN_FIELDS, out[:]))
 
 
 def host_moments_plan(nx, which, deltaf, np_, num_cu):
