@@ -1,5 +1,6 @@
-// capi.cpp -- context, input, transfers, field access, timers and knobs behind the C ABI of include/pic1dp_hip.h (the hot
-// path and the state machine of the lazy call sites: capi_step.cpp; the other units: ctx.hpp).
+// capi.cpp -- context, input, transfers, field access and knobs behind the C ABI of include/pic1dp_hip.h (the hot
+// path and the state machine of the lazy call sites: capi_step.cpp; timers and kernel statistics: capi_timing.cpp; the
+// other units: ctx.hpp).
 //
 // One context = one process = one GPU = one HIP stream.  Every compute entry
 // point only enqueues kernels (and at most one RCCL all-reduce) on that stream;
@@ -332,6 +333,7 @@ static int create_filled(pic1dp_ctx *c) {
     return fail(PIC1DP_ERR_NODEVICE, "device arch %s: the kernels are built for gfx950 only", prop.gcnArchName);
   c->num_cu = prop.multiProcessorCount;
   HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  c->tm.st = c->st;
 
   const int nx = in.nx, nm = in.nmode, ns = in.nspecies;
   c->blk_np = P.blk_np;
@@ -492,7 +494,7 @@ int pic1dp_hip_destroy(pic1dp_ctx *c) {
   comm_release(c);
   optimize_release(c);
   c->mem.release_all();
-  for (auto &e : c->evpool) {
+  for (auto &e : c->tm.evpool) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
   }
@@ -688,11 +690,8 @@ int pic1dp_hip_particle_load_device(pic1dp_ctx *c, int32_t kind) {
     a.key = load_key(c->seed_offset, s);
     a.maxpw = c->d_loadmax + 2 * s;
     a.k = make_load_const(in, s);
-    Span sp(c, kTagLoad, c->stats_on);
-    if (sp.rc) return sp.rc;
-    HIP_TRY(launch_load(a, kind, in.iptcldist, in.linear == 0, load_launch(S.nalloc, c->num_cu), c->st));
-    if (int rc = sp.end()) return rc;
-    c->load_passes++;
+    auto pass = [&](int) { return launch_load(a, kind, in.iptcldist, in.linear == 0, load_launch(S.nalloc, c->num_cu), c->st); };
+    if (int rc = run_passes(c, kTagLoad, c->cnt.load_passes, 1, 1, pass)) return rc;
   }
   unsigned long long hmax[2 * PIC1DP_MAX_SPECIES];
   HIP_TRY(hipMemcpyAsync(hmax, c->d_loadmax, sizeof hmax, hipMemcpyDeviceToHost, c->st));
@@ -1015,47 +1014,7 @@ int pic1dp_hip_cell_indices(pic1dp_ctx *c, int32_t isp, int32_t *ix, int64_t *co
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// timers and knobs
-// ---------------------------------------------------------------------------
-int pic1dp_hip_timers_enable(pic1dp_ctx *c, int32_t on) {
-  CHECK_CTX(c);
-  if (on < 0) return fail(PIC1DP_ERR_ARG, "timers_enable: 0 off, 1 every launch, n >= 2 every n-th launch of a timer");
-  if (int rc = ev_resolve(c)) return rc;
-  c->timers_on = on != 0;
-  c->timer_every = on > 1 ? on : 1;
-  return 0;
-}
-
-int pic1dp_hip_timer_ms(pic1dp_ctx *c, int32_t iwt, double *ms) {
-  CHECK_CTX(c);
-  if (iwt < 0 || iwt >= 100 || !ms) return fail(PIC1DP_ERR_ARG, "bad timer id");
-  if (int rc = ev_resolve(c)) return rc;
-  *ms = c->acc_ms[iwt];
-  // sampled timers: the spans that were timed stand for the ones that were only counted -- apart from the first block of
-  // the timer id (first launches, the run's first step), which is always timed and enters as it is
-  const int64_t later = c->span_seen[iwt] - c->head_n[iwt];
-  if (c->acc_n[iwt] > 0 && later > c->acc_n[iwt]) *ms *= static_cast<double>(later) / static_cast<double>(c->acc_n[iwt]);
-  *ms += c->head_ms[iwt];
-  // (no later block timed yet -- a short run, or a timer id with few launches: the first block's mean stands for them)
-  if (c->acc_n[iwt] == 0 && c->head_n[iwt] > 0 && later > 0)
-    *ms += c->head_ms[iwt] * static_cast<double>(later) / static_cast<double>(c->head_n[iwt]);
-  return 0;
-}
-
-int pic1dp_hip_timers_reset(pic1dp_ctx *c) {
-  CHECK_CTX(c);
-  if (int rc = ev_resolve(c)) return rc;
-  for (int i = 0; i < kNumTags; ++i) {
-    c->acc_ms[i] = 0.0;
-    c->acc_n[i] = 0;
-    c->span_seen[i] = 0;
-    c->head_ms[i] = 0.0;
-    c->head_n[i] = 0;
-  }
-  return 0;
-}
-
+// ---- knobs (timers and kernel statistics: capi_timing.cpp) ----
 int pic1dp_hip_set_launch(pic1dp_ctx *c, int32_t threads, int32_t bpc) {
   CHECK_CTX(c);
   if (threads < 0 || threads > 1024 || (threads % 64)) return fail(PIC1DP_ERR_ARG, "threads must be a multiple of 64, <= 1024");
@@ -1069,126 +1028,6 @@ int pic1dp_hip_get_stream(pic1dp_ctx *c, void **stream) {
   CHECK_CTX(c);
   if (!stream) return fail(PIC1DP_ERR_ARG, "null output");
   *stream = reinterpret_cast<void *>(c->st);
-  return 0;
-}
-
-int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *c, int32_t on) {
-  CHECK_CTX(c);
-  c->stats_on = on != 0;
-  return 0;
-}
-
-int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *launches) {
-  CHECK_CTX(c);
-  if (which < 0 || which > 22) return fail(PIC1DP_ERR_ARG, "which must be 0..22");
-  if (which == 21 || which == 22) {  // passes of pic1dp_hip_select_count / _select (21), launches of pic1dp_hip_gather (22); *ms: their device time while kernel stats were enabled
-    if (int rc = ev_resolve(c)) return rc;
-    if (ms) *ms = c->acc_ms[which == 21 ? kTagSelect : kTagGather];
-    if (launches) *launches = which == 21 ? c->select_passes : c->gather_launches;
-    return PIC1DP_OK;
-  }
-  if (which == 20) {  // passes of pic1dp_hip_power (k_power) launched so far; *ms: their device time while kernel stats were enabled
-    if (int rc = ev_resolve(c)) return rc;
-    if (ms) *ms = c->acc_ms[kTagPower];
-    if (launches) *launches = c->power_passes;
-    return PIC1DP_OK;
-  }
-  if (which == 19) {  // passes of pic1dp_hip_particle_load_device (k_load) so far; *ms: their device time while kernel stats were enabled
-    if (int rc = ev_resolve(c)) return rc;
-    if (ms) *ms = c->acc_ms[kTagLoad];
-    if (launches) *launches = c->load_passes;
-    return PIC1DP_OK;
-  }
-  if (which == 18) {  // the exact moments: terms their passes did not sum so far (each call that met some returned PIC1DP_ERR_ARG)
-    if (launches) *launches = c->moments_exact_rejected;
-    if (ms) *ms = 0.0;
-    return PIC1DP_OK;
-  }
-  if (which == 17) {  // passes of pic1dp_hip_moments_exact / _local_exact (k_moments_exact) so far; *ms: their device time while kernel stats were enabled
-    if (int rc = ev_resolve(c)) return rc;
-    if (ms) *ms = c->acc_ms[kTagMomentsExact];
-    if (launches) *launches = c->moments_exact_passes;
-    return PIC1DP_OK;
-  }
-  if (which == 16) {  // passes of pic1dp_hip_moments (k_moments) launched so far; *ms: their device time while kernel stats were enabled
-    if (int rc = ev_resolve(c)) return rc;
-    if (ms) *ms = c->acc_ms[kTagMoments];
-    if (launches) *launches = c->moments_passes;
-    return PIC1DP_OK;
-  }
-  if (which == 15) {  // kind 1 of the diagnostics sum: terms its passes did not sum so far (reported as PIC1DP_ERR_ARG)
-    if (launches) *launches = c->dfx_rejected;
-    if (ms) *ms = 0.0;
-    return PIC1DP_OK;
-  }
-  if (which == 14) {  // kind 1 of the charge sum: contributions beyond 2^62 quanta so far (not summed; reported as PIC1DP_ERR_ARG)
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    int64_t n = 0;
-    if (c->h_fx_ovf)
-      for (int s = 0; s < c->in.nspecies; ++s) n += static_cast<int64_t>(reinterpret_cast<volatile unsigned long long *>(c->h_fx_ovf)[s]);
-    if (launches) *launches = n;
-    if (ms) *ms = 0.0;
-    return PIC1DP_OK;
-  }
-  if (which == 13) {  // prediction tiles: terms that went past the fixed-point sums (beyond 16x the bound); *ms: the first species' bound on |q|
-    HIP_TRY(hipStreamSynchronize(c->st));
-    int64_t n = 0;
-    double b0 = 0.0;
-    for (size_t s = 0; s < c->sp.size(); ++s) {
-      double h[3] = {0.0, 0.0, 0.0};
-      HIP_TRY(hipMemcpy(h, c->sp[s].fxb, sizeof h, hipMemcpyDeviceToHost));
-      int64_t k;
-      std::memcpy(&k, &h[2], sizeof k);
-      n += k;
-      if (s == 0) b0 = h[0];
-    }
-    if (launches) *launches = n;
-    if (ms) *ms = b0;
-    return PIC1DP_OK;
-  }
-  if (which == 12) {  // diagnostics passes with 64-bit fixed-point histogram sums; *ms: of them, repeated in doubles (overflow)
-    if (ms) *ms = static_cast<double>(c->diag_fx_repeats);
-    if (launches) *launches = c->diag_fx_passes;
-    return 0;
-  }
-  if (which == 11) {  // call sites: solve_field calls of a half step that launched nothing (the pair solve before them had it)
-    if (ms) *ms = 0.0;
-    if (launches) *launches = c->call_pair_skips;
-    return 0;
-  }
-  if (which == 10) {  // marker launches whose last workgroup packed / posted this rank's charge (kernels.hpp StepTail)
-    if (ms) *ms = 0.0;
-    if (launches) *launches = c->tail_launches;
-    return 0;
-  }
-  if (which == 9) {  // how the serial forward sums of the one-rank order run: 0 chains of additions, 1 the matrix unit
-    if (ms) *ms = static_cast<double>(c->chain_selftest);  // create()'s self-test: 1 identical, 0 differs, -1 could not run
-    if (launches) *launches = c->fa.chain_mfma;
-    return 0;
-  }
-  if (which == 5 || which == 7 || which == 8) {  // counts: separate diagnostics passes (k_ptcldist), field solves inside
-                                                 // marker launches, bytes marker optimisation events moved over PCIe
-    if (ms) *ms = 0.0;
-    if (launches) *launches = which == 5 ? c->diag_passes : (which == 7 ? c->fused_solves : c->opt_pcie_bytes);
-    return 0;
-  }
-  if (int rc = ev_resolve(c)) return rc;
-  const int tag = which == 6 ? kTagStepOne : kTagFused + which;
-  if (ms) *ms = c->acc_ms[tag];
-  if (launches) *launches = c->acc_n[tag];
-  return 0;
-}
-
-int pic1dp_hip_kernel_bytes(pic1dp_ctx *c, int32_t which, double *read_bytes, double *written_bytes, double *carry_bytes,
-                            char *name, int32_t name_len) {
-  CHECK_CTX(c);
-  if (which < 0 || which > 6 || which == 5) return fail(PIC1DP_ERR_ARG, "which must be 0..4 or 6");
-  const pic1dp_ctx::KernelBytes &kb = c->kbytes[which == 6 ? kTagStepOne : kTagFused + which];
-  if (read_bytes) *read_bytes = kb.rd;
-  if (written_bytes) *written_bytes = kb.wr;
-  if (carry_bytes) *carry_bytes = kb.carry;
-  if (name && name_len > 0) std::snprintf(name, static_cast<size_t>(name_len), "%s", kb.name);
   return 0;
 }
 

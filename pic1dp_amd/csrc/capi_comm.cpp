@@ -12,7 +12,7 @@ int allreduce_charge(pic1dp_ctx *c) {
   if (c->lay.nranks == 1 && !c->comm) return 0;
   if (!c->comm)
     return fail(PIC1DP_ERR_STATE, "nranks > 1 but no communicator: call pic1dp_hip_comm_init, connect the one-hop exchange (xchg_create / xchg_connect / set_allreduce), or use charge_local/charge_reduced");
-  Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
+  Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
   ncclResult_t r = rccl().AllReduce(c->d_charge, c->d_charge, static_cast<size_t>(c->in.nx), ncclDouble,
                                     ncclSum, c->comm, c->st);
   if (r != ncclSuccess) return fail(PIC1DP_ERR_COMM, "ncclAllReduce: %s", rccl().GetErrorString(r));
@@ -78,7 +78,7 @@ XchgArgs next_xchg_args(pic1dp_ctx *c) {
   x.rank = c->lay.rank;
   x.nranks = c->lay.nranks;
   x.vstride = xchg_vec(c) * c->in.nx;
-  x.ticks = c->timers_on ? c->xc.ticks : nullptr;
+  x.ticks = c->tm.timers_on ? c->xc.ticks : nullptr;
   return x;
 }
 
@@ -96,7 +96,7 @@ int xchg_check(pic1dp_ctx *c) {
 // k_charge_local + RCCL all-reduce (src/pic1dp_interaction.F90:126-135)
 int reduce_charge(pic1dp_ctx *c) {
   if (xchg_active(c)) {
-    Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
+    Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
     HIP_TRY(launch_charge_exchange(c->fa, next_xchg_args(c), c->st));
     return sp.end();
   }

@@ -1,10 +1,8 @@
 // capi_diag.cpp -- diagnostics of output_all (src/pic1dp_output.F90:100-189, 196-477): the kinetic sums and the
-// (x, v) / v histograms, one fused pass per species, cached against state_version; and the velocity moments on the field
-// grid (pic1dp_hip_moments; the exact kind: pic1dp_hip_moments_exact and its split phase), passes of their own that cache
-// nothing and change nothing.
+// (x, v) / v histograms, one fused pass per species, cached against state_version; the FP64 kind and the exact kind
+// (pic1dp_hip_set_diag_sum).  The products computed on demand, which cache nothing: capi_products.cpp.
 #include "ctx.hpp"
 #include "fx_limbs.hpp"
-#include "moments_fx.hpp"
 
 namespace pic1dp_host {
 
@@ -70,8 +68,8 @@ bool diag_fx_bounds(const pic1dp_ctx *c, int isp, double *bound_p, double *bound
 void diag_note_pass(pic1dp_ctx *c, int isp, int blocks, bool fixed, bool launched) {
   DiagSpecies &D = c->diag[isp];
   D.blocks = blocks, D.fixed = fixed, D.pending = true, D.version = c->state_version;
-  if (launched) c->diag_passes++;
-  if (fixed) c->diag_fx_passes++;
+  if (launched) c->cnt.diag_passes++;
+  if (fixed) c->cnt.diag_fx_passes++;
 }
 
 // the diagnostics' own pass over species isp (k_ptcldist) into its cached histograms; fixed: 64-bit fixed-point sums where
@@ -150,7 +148,7 @@ static int diag_collect(pic1dp_ctx *c, int isp, const DiagSlots &at, bool with_h
       for (int k = 0; k < 3; ++k) D.sums[k] += at.tail[b * 3 + k];
     if (D.blocks > 0) D.max_p = maxp, D.max_w = maxw;
     if (!(D.fixed && over > 0.0)) break;
-    c->diag_fx_repeats++;   // (the repeat is no fixed-point pass: the next round ends the loop)
+    c->cnt.diag_fx_repeats++;   // (the repeat is no fixed-point pass: the next round ends the loop)
     if (int rc = run_diag_pass(c, isp, false)) return rc;
     if (D.blocks > diag_max_blocks(c)) return fail(PIC1DP_ERR_STATE, "diagnostics: more partial sums than their slot holds");
     if (D.blocks > 0)
@@ -234,7 +232,7 @@ static int dfx_limbs_host(pic1dp_ctx *c, int isp, bool reduced, std::vector<long
   HIP_TRY(hipStreamSynchronize(c->st));
   const long long *rej = out.data() + limbs;
   if (c->diag[isp].pending) {
-    for (int k = 0; k < 6; ++k) c->dfx_rejected += rej[k];
+    for (int k = 0; k < 6; ++k) c->cnt.dfx_rejected += rej[k];
     c->diag[isp].pending = false;
   }
   for (int k = 0; k < 6; ++k)
@@ -569,213 +567,6 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
   HIP_TRY(hipStreamSynchronize(c->st));
   if (int rc = xchg_check(c)) return rc;
   return settle_record(c, L, h, scalars, E, cd, re, im, dist);
-}
-
-// ---------------------------------------------------------------------------
-// velocity moments of the markers on the field grid (include/pic1dp_hip.h pic1dp_hip_moments)
-// ---------------------------------------------------------------------------
-int pic1dp_hip_moments(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
-  CHECK_CTX(c);
-  if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "moments: bad species index %d", isp);
-  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "moments: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", which);
-  if ((which & 2) && !c->in.deltaf)
-    return fail(PIC1DP_ERR_ARG, "moments: which = %d asks for the planes of w (which & 2), but a full-f context (deltaf = 0) has no w", which);
-  if (!out) return fail(PIC1DP_ERR_ARG, "moments: null output");
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;   // (as state_digest: a noted push becomes memory; clean: nothing is launched)
-  const int nx = c->in.nx;
-  const Species &S = c->sp[isp];
-  const MomentsPlan plan = moments_plan(nx, which, c->in.deltaf, S.np, c->num_cu);
-  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: moments_plan has no pass for nx %d, which %d", nx, which);
-  if (!c->d_mom) HIP_TRY(c->mem.alloc(&c->d_mom, static_cast<size_t>(8) * nx));
-  if (!c->h_mom) HIP_TRY(c->mem.alloc_pinned(&c->h_mom, static_cast<size_t>(8) * nx));
-  const size_t n = static_cast<size_t>(plan.selected) * nx;
-  HIP_TRY(hipMemsetAsync(c->d_mom, 0, sizeof(double) * n, c->st));
-  const PSet &A = S.set[c->cur];
-  for (int i = 0; i < plan.npass && S.np > 0; ++i) {
-    Span ks(c, kTagMoments, c->stats_on);
-    HIP_TRY(launch_moments(A.x, A.v, S.p, A.w, S.np, c->grid, c->d_mom, plan.pass[i], c->cfg.dyn_tail, c->st));
-    if (int rc = ks.end()) return rc;
-    c->moments_passes++;
-  }
-  HIP_TRY(hipMemcpyAsync(c->h_mom, c->d_mom, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  std::memcpy(out, c->h_mom, sizeof(double) * n);
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// velocity-resolved wave-particle power on the output grid (include/pic1dp_hip.h pic1dp_hip_power)
-// ---------------------------------------------------------------------------
-// the refusals that need no context: which, w of a full-f run, the output grid
-static int power_args(const char *who, int deltaf, int nx_opd, int nv_opd, int32_t which) {
-  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "%s: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", who, which);
-  if ((which & 2) && !deltaf)
-    return fail(PIC1DP_ERR_ARG, "%s: which = %d asks for the plane of w (which & 2), but a full-f context (deltaf = 0) has no w", who, which);
-  if (nx_opd < 1 || nv_opd < 2) return fail(PIC1DP_ERR_ARG, "%s: nx_opd = %d, nv_opd = %d: nx_opd >= 1 and nv_opd >= 2 required", who, nx_opd, nv_opd);
-  return 0;
-}
-
-int pic1dp_hip_power_len(const pic1dp_input *in, int32_t which, int64_t *n) {
-  if (!in || !n) return fail(PIC1DP_ERR_ARG, "power_len: null argument");
-  if (int rc = power_args("power_len", in->deltaf, in->nx_opd, in->nv_opd, which)) return rc;
-  const int64_t nxv = static_cast<int64_t>(in->nx_opd) * in->nv_opd;
-  *n = (which == 3 ? 2 : 1) * (nxv + in->nv_opd + 1);
-  return 0;
-}
-
-int pic1dp_hip_power(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
-  CHECK_CTX(c);
-  const pic1dp_input &in = c->in;
-  if (isp < 0 || isp >= in.nspecies) return fail(PIC1DP_ERR_ARG, "power: bad species index %d", isp);
-  if (int rc = power_args("power", in.deltaf, in.nx_opd, in.nv_opd, which)) return rc;
-  if (!out) return fail(PIC1DP_ERR_ARG, "power: null output");
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;          // (as pic1dp_hip_moments: a noted push becomes memory; clean: nothing is launched)
-  if (int rc = settle_field_view(c)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
-  const Species &S = c->sp[isp];
-  const PowerPlan plan = power_plan(in.nx, in.nx_opd, in.nv_opd, which, in.deltaf, S.np, c->num_cu);
-  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: power_plan has no pass for nx %d, %d x %d, which %d", in.nx, in.nx_opd, in.nv_opd, which);
-  const size_t nxv = static_cast<size_t>(in.nx_opd) * in.nv_opd, nvo = static_cast<size_t>(in.nv_opd);
-  if (!c->d_pow) HIP_TRY(c->mem.alloc(&c->d_pow, 2 * nxv + 2));
-  if (!c->h_pow) HIP_TRY(c->mem.alloc_pinned(&c->h_pow, 2 * nxv + 2));
-  const size_t nsets = static_cast<size_t>(plan.selected), n = nsets * nxv + nsets;   // the planes, then a rest word per set
-  double *d_rest = c->d_pow + nsets * nxv;
-  HIP_TRY(hipMemsetAsync(c->d_pow, 0, sizeof(double) * n, c->st));
-  const PSet &A = S.set[c->cur];
-  for (int i = 0; i < plan.npass && S.np > 0; ++i) {
-    Span ks(c, kTagPower, c->stats_on);
-    HIP_TRY(launch_power(A.x, A.v, S.p, A.w, S.np, c->grid, dist_geom(c), c->d_E, c->d_pow, d_rest, plan.pass[i], c->cfg.dyn_tail, c->st));
-    if (int rc = ks.end()) return rc;
-    c->power_passes++;
-  }
-  HIP_TRY(hipMemcpyAsync(c->h_pow, c->d_pow, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  if (int rc = xchg_check(c)) return rc;
-  // per set: [plane | v-profile = the plane summed over ix ascending | rest]
-  for (size_t j = 0; j < nsets; ++j) {
-    const double *plane = c->h_pow + j * nxv;
-    double *o = out + j * (nxv + nvo + 1);
-    std::memcpy(o, plane, sizeof(double) * nxv);
-    for (size_t iv = 0; iv < nvo; ++iv) {
-      double acc = 0.0;
-      for (int ix = 0; ix < in.nx_opd; ++ix) acc += plane[iv * in.nx_opd + ix];
-      o[nxv + iv] = acc;
-    }
-    o[nxv + nvo] = c->h_pow[nsets * nxv + j];
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// the exact kind of the moments (include/pic1dp_hip.h pic1dp_hip_moments_exact): the same terms in whole
-// quanta, integer sums.  The arithmetic on the host is moments_fx.cpp's.
-// ---------------------------------------------------------------------------
-int pic1dp_hip_moments_quanta(const pic1dp_input *in, int32_t isp, int32_t e[4]) {
-  if (!in || !e) return fail(PIC1DP_ERR_ARG, "moments_quanta: null argument");
-  int32_t cq = 0;
-  if (int rc = pic1dp_hip_charge_quantum(in, isp, &cq)) return rc;
-  if (!moments_fx_quanta(cq, in->v_max, e)) return fail(PIC1DP_ERR_ARG, "moments_quanta: v_max must be positive and finite");
-  return 0;
-}
-
-// the refusals of pic1dp_hip_moments, for the calls of the exact kind
-static int moments_exact_args(const char *who, int nspecies, int deltaf, int32_t isp, int32_t which) {
-  if (isp < 0 || isp >= nspecies) return fail(PIC1DP_ERR_ARG, "%s: bad species index %d", who, isp);
-  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "%s: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", who, which);
-  if ((which & 2) && !deltaf)
-    return fail(PIC1DP_ERR_ARG, "%s: which = %d asks for the planes of w (which & 2), but a full-f context (deltaf = 0) has no w", who, which);
-  return 0;
-}
-
-int pic1dp_hip_moments_limbs_len(int32_t which, int32_t nx, int64_t *n) {
-  if (!n) return fail(PIC1DP_ERR_ARG, "moments_limbs_len: null argument");
-  if (which < 1 || which > 3) return fail(PIC1DP_ERR_ARG, "moments_limbs_len: which = %d, must be 1 (weights p), 2 (weights w) or 3 (both)", which);
-  if (nx < 1) return fail(PIC1DP_ERR_ARG, "moments_limbs_len: nx = %d", nx);
-  *n = static_cast<int64_t>(which == 3 ? 16 : 8) * nx;
-  return 0;
-}
-
-// This context's exact sums of species isp, normalised, in c->h_momfx [sets selected][4][2][nx]: the accumulators zeroed,
-// the plan's passes, one copy, one wait.  Terms that were not summed: counted, PIC1DP_ERR_ARG, nothing handed out.
-static int moments_exact_local(pic1dp_ctx *c, const char *who, int32_t isp, int32_t which) {
-  if (int rc = moments_exact_args(who, c->in.nspecies, c->in.deltaf, isp, which)) return rc;
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  HIP_TRY(hipSetDevice(c->device));
-  int32_t e[4];
-  if (int rc = pic1dp_hip_moments_quanta(&c->in, isp, e)) return rc;
-  if (int rc = materialize(c)) return rc;   // (as pic1dp_hip_moments: a noted push becomes memory; clean: nothing is launched)
-  const int nx = c->in.nx;
-  const Species &S = c->sp[isp];
-  const MomentsPlan plan = moments_plan_exact(nx, which, c->in.deltaf, S.np, c->num_cu);
-  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: moments_plan_exact has no pass for nx %d, which %d", nx, which);
-  const size_t cap = static_cast<size_t>(16) * nx + 8;
-  if (!c->d_momfx) HIP_TRY(c->mem.alloc(&c->d_momfx, cap));
-  if (!c->h_momfx) HIP_TRY(c->mem.alloc_pinned(&c->h_momfx, cap));
-  const size_t n = static_cast<size_t>(plan.selected) * 2 * nx;   // the limbs; the counters lie behind them
-  HIP_TRY(hipMemsetAsync(c->d_momfx, 0, sizeof(long long) * (n + 8), c->st));
-  MomentsFxArgs a{};
-  a.acc = c->d_momfx, a.rej = c->d_momfx + n;
-  for (int k = 0; k < 4; ++k) a.inv_q[k] = std::ldexp(1.0, -e[k]);
-  const PSet &A = S.set[c->cur];
-  for (int i = 0; i < plan.npass && S.np > 0; ++i) {
-    Span ks(c, kTagMomentsExact, c->stats_on);
-    HIP_TRY(launch_moments_exact(A.x, A.v, S.p, A.w, S.np, c->grid, a, plan.pass[i], c->cfg.dyn_tail, c->st));
-    if (int rc = ks.end()) return rc;
-    c->moments_exact_passes++;
-  }
-  HIP_TRY(hipMemcpyAsync(c->h_momfx, c->d_momfx, sizeof(long long) * (n + 8), hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  const long long *rej = c->h_momfx + n;
-  const int nsets = plan.selected / 4;
-  int first = -1;
-  for (int j = 0; j < nsets * 4; ++j) {
-    c->moments_exact_rejected += rej[j];
-    if (rej[j] != 0 && first < 0) first = j;
-  }
-  if (first >= 0) {
-    const bool is_w = which == 2 || first >= 4;
-    return fail(PIC1DP_ERR_ARG,
-                "%s: %lld term(s) of species %d, weight set %s, power v^%d, lay at or beyond 2^44 quanta of 2^%d or were NaN (|p|, |w| "
-                "or |v| far past the bounds the input gives) and were not summed; nothing was handed out",
-                who, rej[first], isp, is_w ? "w" : "p", first & 3, e[first & 3]);
-  }
-  static_assert(sizeof(long long) == sizeof(int64_t), "limbs are 64-bit");
-  moments_fx_normalise(reinterpret_cast<int64_t *>(c->h_momfx), plan.selected, nx);
-  return 0;
-}
-
-int pic1dp_hip_moments_local_exact(pic1dp_ctx *c, int32_t isp, int32_t which, int64_t *limbs) {
-  CHECK_CTX(c);
-  if (int rc = moments_exact_args("moments_local_exact", c->in.nspecies, c->in.deltaf, isp, which)) return rc;
-  if (!limbs) return fail(PIC1DP_ERR_ARG, "moments_local_exact: null output");
-  if (int rc = moments_exact_local(c, "moments_local_exact", isp, which)) return rc;
-  std::memcpy(limbs, c->h_momfx, sizeof(int64_t) * static_cast<size_t>(which == 3 ? 16 : 8) * c->in.nx);
-  return 0;
-}
-
-int pic1dp_hip_moments_convert(const pic1dp_input *in, int32_t isp, int32_t which, const int64_t *limbs, double *out) {
-  if (!in) return fail(PIC1DP_ERR_ARG, "moments_convert: null input");
-  int32_t e[4];
-  if (int rc = pic1dp_hip_moments_quanta(in, isp, e)) return rc;   // (the input's version and species count with it)
-  if (int rc = moments_exact_args("moments_convert", in->nspecies, in->deltaf, isp, which)) return rc;
-  if (!limbs || !out) return fail(PIC1DP_ERR_ARG, "moments_convert: null array");
-  if (in->nx < 1) return fail(PIC1DP_ERR_ARG, "moments_convert: nx = %d", in->nx);
-  moments_fx_convert(e, limbs, which == 3 ? 8 : 4, in->nx, out);
-  return 0;
-}
-
-int pic1dp_hip_moments_exact(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
-  CHECK_CTX(c);
-  if (int rc = moments_exact_args("moments_exact", c->in.nspecies, c->in.deltaf, isp, which)) return rc;
-  if (!out) return fail(PIC1DP_ERR_ARG, "moments_exact: null output");
-  if (int rc = moments_exact_local(c, "moments_exact", isp, which)) return rc;
-  int32_t e[4];
-  if (int rc = pic1dp_hip_moments_quanta(&c->in, isp, e)) return rc;
-  moments_fx_convert(e, reinterpret_cast<const int64_t *>(c->h_momfx), which == 3 ? 8 : 4, c->in.nx, out);
-  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -141,11 +141,11 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
   int *counters[3] = {&c->imerge, &c->iremove, &c->isplit};
   std::vector<double> hist(static_cast<size_t>(ns) * nv), local(nv);
   auto to_device = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    c->opt_pcie_bytes += static_cast<int64_t>(bytes);
+    c->cnt.opt_pcie_bytes += static_cast<int64_t>(bytes);
     return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
   };
   auto to_host = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    c->opt_pcie_bytes += static_cast<int64_t>(bytes);
+    c->cnt.opt_pcie_bytes += static_cast<int64_t>(bytes);
     return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
   };
   for (int kind = 0; kind < 3; ++kind) {
@@ -335,7 +335,7 @@ int optimize_on_device(pic1dp_ctx *c, const bool due[3]) {
       for (int t = 0; t < nthreads; ++t) pool.emplace_back(worker, t);
       for (auto &t : pool) t.join();
     }
-    c->opt_pcie_bytes += pcie_total.load();
+    c->cnt.opt_pcie_bytes += pcie_total.load();
     if (err_rc != 0) return fail(err_rc, "%s", err_msg.c_str());
     t_blocks += ms_since(t_phase);
     threads_used = nthreads;
@@ -464,7 +464,7 @@ static int optimize_on_host(pic1dp_ctx *c, const bool due[3]) {
       toff += na - np;
     }
   }
-  for (int s = 0; s < ns; ++s) c->opt_pcie_bytes += 2 * 32 * c->sp[s].nalloc;
+  for (int s = 0; s < ns; ++s) c->cnt.opt_pcie_bytes += 2 * 32 * c->sp[s].nalloc;
   return 0;
 }
 
@@ -488,7 +488,7 @@ int pic1dp_hip_particle_optimize(pic1dp_ctx *c, int32_t irk, int32_t *flag_optim
     for (int b = 0; b < nb; ++b) sum += c->blk_np[s][b];
     if (sum != c->sp[s].np) return fail(PIC1DP_ERR_STATE, "marker counts per block unknown (uploaded over several blocks)");
   }
-  Span tm(c, PIC1DP_IWT_PARTICLE_OPTIMIZE, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_PARTICLE_OPTIMIZE, c->tm.timers_on);
   c->state_version++;
   HIP_TRY(hipStreamSynchronize(c->st));
   const char *eh = std::getenv("PIC1DP_OPT_HOST");  // (read per event: rare)

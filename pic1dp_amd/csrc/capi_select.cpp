@@ -1,5 +1,5 @@
 // capi_select.cpp -- select and gather markers on the device behind the C ABI (include/pic1dp_hip.h pic1dp_hip_select_count,
-// _select, _gather): passes of their own in the mould of pic1dp_hip_moments, which cache nothing and change
+// _select, _gather): passes of their own in the mould of capi_products.cpp, which cache nothing and change
 // nothing.  Every device buffer of a call -- the chunk counts, the result, a gather's indices -- is taken from the context's
 // owner and given back before the call returns; results cross to the host through the context's pinned staging in slices.
 // The rule on the host and the thinning threshold are select_host.cpp's.
@@ -83,11 +83,8 @@ int select_run(pic1dp_ctx *c, const char *who, int32_t isp, const pic1dp_select 
   CHECK_CTX(c);
   if (!sel || !count) return fail(PIC1DP_ERR_ARG, "%s: null selection or count", who);
   if (max < 0) return fail(PIC1DP_ERR_ARG, "%s: max = %lld is negative", who, (long long)max);
-  if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "%s: bad species index %d", who, isp);
   if (const char *why = select_refusal(*sel)) return fail(PIC1DP_ERR_ARG, "%s: %s", who, why);
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;   // (as pic1dp_hip_moments: a noted push becomes memory; clean: nothing is launched)
+  if (int rc = product_begin(c, who, isp)) return rc;
   const Species &S = c->sp[isp];
   const SelectPlan plan = select_plan(S.np, c->num_cu, c->threads_req, c->bpc_req);
   if (plan.nchunk < 1) {   // no valid marker
@@ -98,12 +95,12 @@ int select_run(pic1dp_ctx *c, const char *who, int32_t isp, const pic1dp_select 
   const SelectArrays arr = current_arrays(c, S);
   CallBuf<unsigned long long> counts(c->mem);
   if (int rc = counts.take(static_cast<size_t>(plan.nchunk) + 1, who, "the chunk counts")) return rc;
-  {
-    Span ks(c, kTagSelect, c->stats_on);
+  {  // (count and scan: one span, one pass)
+    Span ks(c->tm, kTagSelect, c->tm.stats_on);
     HIP_TRY(launch_select_count(arr, S.np, rule, counts.p, plan, c->st));
     HIP_TRY(launch_select_scan(counts.p, plan, c->st));
     if (int rc = ks.end()) return rc;
-    c->select_passes++;
+    c->cnt.select_passes++;
   }
   unsigned long long total = 0;
   if (int rc = words_to_host(c, &total, counts.p + plan.nchunk, 1)) return rc;
@@ -116,12 +113,8 @@ int select_run(pic1dp_ctx *c, const char *who, int32_t isp, const pic1dp_select 
     double *d[5];
     for (int k = 0; k < 5; ++k) d[k] = host[k] ? res.p + static_cast<size_t>(k) * static_cast<size_t>(n) : nullptr;
     const SelectOut out{reinterpret_cast<long long *>(d[0]), d[1], d[2], d[3], d[4]};
-    {
-      Span ks(c, kTagSelect, c->stats_on);
-      HIP_TRY(launch_select_write(arr, S.np, rule, counts.p, n, out, plan, c->st));
-      if (int rc = ks.end()) return rc;
-      c->select_passes++;
-    }
+    auto write = [&](int) { return launch_select_write(arr, S.np, rule, counts.p, n, out, plan, c->st); };
+    if (int rc = run_passes(c, kTagSelect, c->cnt.select_passes, 1, S.np, write)) return rc;
     for (int k = 0; k < 5; ++k)
       if (int rc = words_to_host(c, host[k], d[k], n)) return rc;
   }
@@ -144,18 +137,16 @@ int pic1dp_hip_select(pic1dp_ctx *c, int32_t isp, const pic1dp_select *sel, int6
 
 int pic1dp_hip_gather(pic1dp_ctx *c, int32_t isp, const int64_t *index, int64_t n, double *x, double *v, double *p, double *w) {
   CHECK_CTX(c);
-  if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "gather: bad species index %d", isp);
   if (n < 0) return fail(PIC1DP_ERR_ARG, "gather: n = %lld is negative", (long long)n);
   if (n == 0) return 0;
   if (!index) return fail(PIC1DP_ERR_ARG, "gather: null index array");
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
+  if (int rc = product_check(c, "gather", isp)) return rc;
   const Species &S = c->sp[isp];
   for (int64_t k = 0; k < n; ++k)
     if (index[k] < 0 || index[k] >= S.nalloc)
       return fail(PIC1DP_ERR_ARG, "gather: index[%lld] = %lld lies outside [0, %lld), the slots of species %d", (long long)k,
                   (long long)index[k], (long long)S.nalloc, isp);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;
+  if (int rc = product_begin(c, "gather", isp)) return rc;
   void *const host[4] = {x, v, p, w};
   if (!x && !v && !p && !w) return 0;
   CallBuf<long long> idx(c->mem);
@@ -166,12 +157,8 @@ int pic1dp_hip_gather(pic1dp_ctx *c, int32_t isp, const int64_t *index, int64_t 
   double *d[4];
   for (int k = 0; k < 4; ++k) d[k] = host[k] ? res.p + static_cast<size_t>(k) * static_cast<size_t>(n) : nullptr;
   const SelectOut out{nullptr, d[0], d[1], d[2], d[3]};
-  {
-    Span ks(c, kTagGather, c->stats_on);
-    HIP_TRY(launch_gather(current_arrays(c, S), tail_arrays(S), S.np, idx.p, n, out, c->st));
-    if (int rc = ks.end()) return rc;
-    c->gather_launches++;
-  }
+  auto pass = [&](int) { return launch_gather(current_arrays(c, S), tail_arrays(S), S.np, idx.p, n, out, c->st); };
+  if (int rc = run_passes(c, kTagGather, c->cnt.gather_launches, 1, n, pass)) return rc;
   for (int k = 0; k < 4; ++k)
     if (int rc = words_to_host(c, host[k], d[k], n)) return rc;
   return 0;

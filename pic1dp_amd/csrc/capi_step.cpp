@@ -1,7 +1,7 @@
 // capi_step.cpp -- the hot path behind the C ABI of include/pic1dp_hip.h: the three call sites and their lazy state
 // machine (push / collect_charge / solve_field), the whole-step kernels' sequencing (pic1dp_hip_step), the
 // prediction of the half-step charge, the solve inside the marker launch, and the split-phase deposit.
-// Context, transfers, field access, timers: capi.cpp; launch shapes: launch_policy.cpp; the other units: ctx.hpp.
+// Context, transfers, field access: capi.cpp; timers: capi_timing.cpp; launch shapes: launch_policy.cpp; the other units: ctx.hpp.
 // In order of dependency: predicates and launch shapes, the marker launches, prediction and solve, pic1dp_hip_step, the
 // call sites and what settles their state, the split-phase deposit, pic1dp_hip_check_state.
 // (the entry points are declared extern "C" in include/pic1dp_hip.h; their definitions here inherit that linkage)
@@ -175,11 +175,11 @@ static int enqueue_deposit(pic1dp_ctx *c) {
     const bool exact = c->charge_sum == 1;
     LaunchCfg lc = particle_launch(c, S.np, false, true, exact);
     {
-      pic1dp_ctx::KernelBytes &kb = c->kbytes[kTagDeposit];
+      KernelBytes &kb = c->tm.kbytes[kTagDeposit];
       kb.rd = 16.0, kb.wr = 8.0, kb.carry = 0.0;  // x, q read; wrapped x written
       std::snprintf(kb.name, sizeof kb.name, "%s", exact ? "k_deposit<EXACT>" : "k_deposit");
     }
-    Span ks(c, kTagDeposit, c->stats_on);
+    Span ks(c->tm, kTagDeposit, c->tm.stats_on);
     HIP_TRY(launch_deposit(x, q, S.rho, fx_args(c, s), S.np, c->grid, lc, c->st));
     if (int rc = ks.end()) return rc;
   }
@@ -199,15 +199,15 @@ static int enqueue_push(pic1dp_ctx *c, int irk, bool fused, const double *E = nu
     if (a.np <= 0) continue;
     LaunchCfg lc = particle_launch(c, a.np, true, fused, exact);
     {  // irk 1 reads x, v, p (+ w); irk 2 also the RK base x (+ v) (+ w); both write x (+ v) (+ w)
-      pic1dp_ctx::KernelBytes &kb = c->kbytes[fused ? kTagFused : kTagPush];
+      KernelBytes &kb = c->tm.kbytes[fused ? kTagFused : kTagPush];
       const double pushed = 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0));
       kb.rd = 8.0 * (3 + (c->in.deltaf ? 1 : 0)) + (irk == 2 ? pushed : 0.0);
       kb.wr = pushed;
       kb.carry = 0.0;
       std::snprintf(kb.name, sizeof kb.name, "%s", fused ? (exact ? "k_push<FUSED, EXACT>" : "k_push<FUSED>") : "k_push");
     }
-    Span tm(c, PIC1DP_IWT_PUSH_PARTICLE, c->timers_on);
-    Span ks(c, fused ? kTagFused : kTagPush, c->stats_on);
+    Span tm(c->tm, PIC1DP_IWT_PUSH_PARTICLE, c->tm.timers_on);
+    Span ks(c->tm, fused ? kTagFused : kTagPush, c->tm.stats_on);
     HIP_TRY(launch_push(a, fused, lc, c->st));
     if (int rc = ks.end()) return rc;
     if (int rc = tm.end()) return rc;
@@ -323,7 +323,7 @@ static void wire_tail(pic1dp_ctx *c, StepTail &t, int tail_mode) {
     t.x.ticks = nullptr;  // (the field launch's half of the exchange is the one the attribution times)
   }
   c->tail_done = tail_mode;
-  c->tail_launches++;
+  c->cnt.tail_launches++;
 }
 
 // k_step_full<DIAG> of species s: its histograms and partial sums, its launch shape, what the collector has to know
@@ -375,7 +375,7 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
       return fail(PIC1DP_ERR_STATE, "internal: fused field solve in a launch of %d threads", threads);
     a.fused = c->fuse_args;
     c->fuse_args.on = 0;
-    c->fused_solves++;
+    c->cnt.fused_solves++;
   }
   if (int rc = wire_carry(c, S, a, full, pred)) return rc;
   if (pred) {  // k_step_one: the full step + the prediction of the next first sub-step's charge
@@ -402,7 +402,7 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
     if (int rc = wire_diag(c, s, a, lc)) return rc;
   const int tag = pred ? kTagStepOne : (full ? kTagStepFull : kTagStepHalf);
   {  // the bytes this instantiation moves per marker: x, v, p (+ w) read; x (+ v) (+ w) written by a full step
-    pic1dp_ctx::KernelBytes &kb = c->kbytes[tag];
+    KernelBytes &kb = c->tm.kbytes[tag];
     kb.rd = 8.0 * (3 + (c->in.deltaf ? 1 : 0));
     kb.wr = full ? 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0)) : 0.0;
     kb.carry = 0.0;
@@ -412,8 +412,8 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
                   a.fx.acc ? "<EXACT>" : "", S.sc.one_exp && c->in.deltaf ? " (one-exp -f0'/f0)" : "");
     if (a.fused.on) std::strncat(kb.name, " + field solve", sizeof kb.name - std::strlen(kb.name) - 1);
   }
-  Span tm(c, PIC1DP_IWT_PUSH_PARTICLE, c->timers_on);
-  Span ks(c, tag, c->stats_on);
+  Span tm(c->tm, PIC1DP_IWT_PUSH_PARTICLE, c->tm.timers_on);
+  Span ks(c->tm, tag, c->tm.stats_on);
   HIP_TRY(launch_step(sa, full, lc, c->st));
   if (int rc = ks.end()) return rc;
   return tm.end();
@@ -467,7 +467,7 @@ static int enqueue_field_solve(pic1dp_ctx *c, FieldArgs f, bool with_local, bool
 // the local result of the prediction summed over ranks in d_charge
 static int pred_reduce(pic1dp_ctx *c) {
   if (xchg_active(c)) {
-    Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
+    Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
     XchgArgs x = next_xchg_args(c);
     x.local_in_charge = 1;
     HIP_TRY(launch_charge_exchange(c->fa, x, c->st));
@@ -511,7 +511,7 @@ static int predict_half_field(pic1dp_ctx *c) {
   FieldArgs f = c->fa;
   f.chargeden = c->d_cd_h;
   if (int rc = pred_to_chargeden(c, f)) return rc;
-  Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   f.E = c->d_Ehn;
   f.mode_re = c->d_mode_h;
   f.mode_im = c->d_mode_h + c->in.nmode;
@@ -538,18 +538,18 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
     return fail(PIC1DP_ERR_STATE, "internal: a posted charge nobody waits for");
   if (will_pack) {
     if (tail_done != 1) {  // the species sum and the packing are collect_charge's share of the step (src/pic1dp_interaction.F90:126-127)
-      Span pk(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
+      Span pk(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
       HIP_TRY(launch_charge_pack(c->fa, c->d_pred, c->in.nmode, c->plan.pred_kind, c->d_pack, c->st));
       if (int rc = pk.end()) return rc;
     }
-    Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
+    Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
     ncclResult_t r = rccl().AllReduce(c->d_pack, c->d_pack, c->plan.pack_doubles, ncclDouble, ncclSum, c->comm, c->st);
     if (r != ncclSuccess) return fail(PIC1DP_ERR_COMM, "ncclAllReduce: %s", rccl().GetErrorString(r));
     if (int rc = sp.end()) return rc;
   } else if (multi && !fused_xchg) {
     if (int rc = reduce_charge(c)) return rc;
   }
-  Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   FieldArgs f = c->fa;
   f.E = Eout;
   if (record && c->hist_count < kHistCap) f.history = c->d_hist + c->hist_count++;
@@ -576,7 +576,7 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
     } else if (fused_xchg) {  // ONE exchange: charge2 and the prediction slices travel together
       if (tail_done == 2) {  // ... and this rank's half of it is under way since the marker launch's tail
         x1 = c->tail_x;
-        x1.ticks = c->timers_on ? c->xc.ticks : nullptr;
+        x1.ticks = c->tm.timers_on ? c->xc.ticks : nullptr;
         pa.posted = 1;
       } else {
         x1 = next_xchg_args(c);
@@ -660,7 +660,7 @@ static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
   const bool fused_xchg = multi && xchg_active(c) && dft_paths(c);  // exchange inside the solve's launch
   if (multi && !fused_xchg)
     if (int rc = reduce_charge(c)) return rc;
-  Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   FieldArgs f = c->fa;
   if (record && c->hist_count < kHistCap) f.history = c->d_hist + c->hist_count++;
   if (fused_xchg) {
@@ -960,7 +960,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   if (c->seq == Seq::Push1 && pred_usable(c)) {
     if (int rc = save_step_start_field(c)) return rc;
     if (int rc = set_call_state(c, Seq::Half, Owed::Nothing)) return rc;   // (a stale AdoptHalfField ends here)
-    Span tm(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
+    Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
     if (int rc = pred_to_chargeden(c, c->fa, c->cfg.lazy_calls != 0)) return rc;
     return tm.end();
   }
@@ -970,7 +970,7 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   const bool noted = lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2;
   if (noted)
     if (int rc = deposit_or_step(c)) return rc;
-  Span tm(c, PIC1DP_IWT_COLLECT_CHARGE, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
   if (!noted)
     if (int rc = deposit_or_step(c)) return rc;
   if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
@@ -1034,7 +1034,7 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   HIP_TRY(hipSetDevice(c->device));
   if (c->seq == Seq::HalfPair) {  // the half-step field is solved already (the pair below): nothing to launch
     if (int rc = set_call_state(c, Seq::HalfPairSolved, Owed::Nothing)) return rc;
-    c->call_pair_skips++;
+    c->cnt.call_pair_skips++;
     field_written(c, true);  // from now on field_electric IS the half-step field, as far as anybody can tell
     return 0;
   }
@@ -1042,7 +1042,7 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   // a noted push has to see the field of its own moment
   if (lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2)
     if (int rc = materialize(c)) return rc;
-  Span tm(c, PIC1DP_IWT_FIELD_ELECTRIC, c->timers_on);
+  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   FieldArgs f = c->fa;
   Owed pending = c->owed;  // what collect_charge left to this launch
   if (int rc = set_owed(c, Owed::Nothing)) return rc;

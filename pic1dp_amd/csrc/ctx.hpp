@@ -1,13 +1,15 @@
 // ctx.hpp -- what the translation units behind the C ABI share: the context (one process = one GPU = one HIP stream),
-// the error convention, the event spans, and the internal entry points one unit offers the others.
-//   capi.cpp           context (create: settings -> plan -> tables -> allocate -> self-test), input, transfers, field access, timers and knobs
+// the error convention, and the internal entry points one unit offers the others.
+//   capi.cpp           context (create: settings -> plan -> tables -> allocate -> self-test), input, transfers, field access, knobs
+//   capi_timing.cpp    timers and kernel statistics: switches, reads, reset (timing.hpp: pic1dp_ctx::tm, the event spans)
 //   settings.cpp       what a context takes from the environment, read once (settings.hpp: pic1dp_ctx::cfg; no HIP call)
 //   context_plan.cpp   create()'s decisions as a pure function, and the mode tables (context_plan.hpp: pic1dp_ctx::plan; no HIP call)
 //   device_mem.hpp     the one owner of a context's device and pinned memory (pic1dp_ctx::mem)
 //   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
-//   capi_diag.cpp      diagnostics of output_all; the velocity moments on the field grid (pic1dp_hip_moments, _moments_exact)
+//   capi_diag.cpp      diagnostics of output_all
+//   capi_products.cpp  read-only marker products on demand (pic1dp_hip_moments, _moments_exact, _power); what they share with select and gather
 //   capi_select.cpp    select and gather markers on the device (pic1dp_hip_select_count, _select, _gather); the rule on the
 //                      host and the thinning threshold: select_host.cpp (select_rule.hpp; no HIP call)
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
@@ -35,6 +37,7 @@
 #include "optimize.hpp"
 #include "rccl_dyn.hpp"
 #include "settings.hpp"
+#include "timing.hpp"
 
 using namespace pic1dp;
 
@@ -57,8 +60,6 @@ int fail(int code, const char *fmt, ...);
 
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
-constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kTagSelect = 111, kTagGather = 112, kNumTags = 128;
 constexpr int64_t kHistCap = 1 << 20;
 constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
 constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
@@ -147,10 +148,22 @@ struct DiagSpecies {
   double max_p = 0.0, max_w = 0.0;    // max |p|, |w| as the last pass saw them: the next pass's scales (0: unknown -- doubles)
 };
 
-struct EvPair {
-  hipEvent_t a, b;
-  int tag;
-  bool head;  // one of the first 64 spans of its timer id since the last reset (sampled timers: taken as they are, not scaled)
+// what the context counts for pic1dp_hip_kernel_stats (capi_timing.cpp: the table's rows name these members); nothing reads them to decide
+struct Counters {
+  int64_t diag_passes = 0;                 // separate k_ptcldist passes launched so far (kernel_stats 5)
+  int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field (7)
+  int64_t opt_pcie_bytes = 0;              // bytes marker optimisation events have moved between host and device (8)
+  int64_t tail_launches = 0;               // marker launches that carried a tail so far (10)
+  int64_t call_pair_skips = 0;             // solve_field calls of a half step served without a launch (11)
+  int64_t diag_fx_passes = 0, diag_fx_repeats = 0;   // fixed-point passes so far; passes repeated in doubles after an overflow (12)
+  int64_t dfx_rejected = 0;                // terms the exact passes of the diagnostics did not sum so far (15)
+  int64_t moments_passes = 0;              // k_moments passes launched so far (16)
+  int64_t moments_exact_passes = 0;        // k_moments_exact passes launched so far (17)
+  int64_t moments_exact_rejected = 0;      // terms they did not sum so far (18)
+  int64_t load_passes = 0;                 // k_load passes launched so far (19)
+  int64_t power_passes = 0;                // k_power passes launched so far (20)
+  int64_t select_passes = 0;               // k_select_count and k_select_write passes launched so far (21)
+  int64_t gather_launches = 0;             // k_gather launches so far (22)
 };
 
 }  // namespace pic1dp_host
@@ -162,6 +175,8 @@ struct pic1dp_ctx {
   Settings cfg{};      // the environment as create() found it: constants of the context
   ContextPlan plan{};  // what create() derived from input, layout and settings: constants too (blocks, one-pass kind, sizes)
   DeviceMem mem;       // owns every device and pinned buffer below (allocated at create() or lazily; released by destroy())
+  Timing tm;           // timers and kernel statistics (timing.hpp)
+  Counters cnt;        // what kernel_stats reports besides times
   int device = 0, num_cu = 256;
   hipStream_t st = nullptr;
   int cur = 0;  // which particle set is particle_x/v/w right now
@@ -197,13 +212,11 @@ struct pic1dp_ctx {
   unsigned int *d_ticket = nullptr;  // the tail's arrival counter (zero between launches)
   int tail_done = 0;                 // what the last marker launch's tail did: 0 nothing, 1 packed into d_pack, 2 posted (tail_x)
   XchgArgs tail_x{};                 // tail_done == 2: the exchange the field launch has to finish
-  int64_t tail_launches = 0;         // marker launches that carried a tail so far (kernel_stats 10)
   uint64_t pred_version = 0;       // state_version the accumulators in d_pred belong to (0: none)
   uint64_t eh_version = 0;         // state_version d_Eh has been predicted for (step() path)
   uint64_t field_version = 1, eh_field_version = 0, modes_field_version = 0;  // who wrote d_E last
   double *d_stage = nullptr;  // contiguous staging buffer between host arrays and the tiled marker arrays
   unsigned long long *d_loadmax = nullptr;  // [nspecies][2] bit patterns of max |p|, max |w| of a device load (capi.cpp; allocated at the first one)
-  int64_t load_passes = 0;                 // k_load passes launched so far (kernel_stats 19)
   unsigned long long *d_digest = nullptr;  // [nspecies][4] the state digest's words (capi_checkpoint.cpp; allocated at the first digest)
   double *d_Eh = nullptr;  // field after the first sub-step of the last whole-step call
   // The reference's three call sites at whole-step cost (see "lazy call sites"
@@ -216,7 +229,6 @@ struct pic1dp_ctx {
   // not filled), the "Solved" ones that the host has called solve_field for it -- what it may look at from then on is the
   // half-step field, so every inspection first settles (capi_step.cpp settle_half_pair: copies, memory as eager calls leave it).
   // cfg.call_pair 0: the three launches per step of rounds 2-4.
-  int64_t call_pair_skips = 0;   // solve_field calls of a half step served without a launch (kernel_stats 11)
   // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step): materialize_cd()
   // before anything else looks at charge, chargeden or the accumulators.
   Owed owed = Owed::Nothing;
@@ -252,7 +264,6 @@ struct pic1dp_ctx {
   uint64_t state_version = 1;              // bumped by everything that writes marker arrays
   std::vector<DiagSpecies> diag;           // [nspecies]
   double *d_diag_part = nullptr;           // [nspecies][diag_max_blocks][DIAG_PART] per-workgroup partial sums of the pass
-  int64_t diag_fx_passes = 0, diag_fx_repeats = 0;   // fixed-point passes so far; passes repeated in doubles after an overflow
   int fuse_output = 0;                     // take the diagnostics inside k_step_full on steps output_all follows
   double *d_rec = nullptr;                 // output_all's record gathered on the device (kernels.hpp PackArgs), grow-only
   size_t d_rec_doubles = 0;
@@ -260,25 +271,10 @@ struct pic1dp_ctx {
   size_t h_pin_doubles = 0;                // pageable copies cost a synchronous call each, ~20 us; grow-only, capi_diag.cpp pinned)
   DistGeom dist_geom_v{};                  // output_ptcldist's histogram geometry (capi_diag.cpp dist_geom)
   bool dist_geom_ready = false;
-  int64_t opt_pcie_bytes = 0;              // bytes marker optimisation events have moved between host and device
   std::vector<void *> opt_workers;         // streams and staging of the events' block workers (capi_optimize.cpp OptWorker), kept between events
-  int64_t diag_passes = 0;                 // separate k_ptcldist passes launched so far
-  // pic1dp_hip_moments (capi_diag.cpp): the planes [8][nx] on the device and their pinned copy, allocated at the first call
-  double *d_mom = nullptr, *h_mom = nullptr;
-  int64_t moments_passes = 0;              // k_moments passes launched so far (kernel_stats 16)
-  // pic1dp_hip_moments_exact / _local_exact (capi_diag.cpp): the limbs [8][2][nx] and the 8 counters of terms not summed
-  // on the device, and their pinned copy, allocated at the first call
-  long long *d_momfx = nullptr, *h_momfx = nullptr;
-  int64_t moments_exact_passes = 0;        // k_moments_exact passes launched so far (kernel_stats 17)
-  int64_t moments_exact_rejected = 0;      // terms they did not sum so far (kernel_stats 18)
-  // pic1dp_hip_power (capi_diag.cpp): the planes [2][nx_opd nv_opd] and the two rest words on the device and their pinned
-  // copy, allocated at the first call
-  double *d_pow = nullptr, *h_pow = nullptr;
-  int64_t power_passes = 0;                // k_power passes launched so far (kernel_stats 20)
-  // pic1dp_hip_select_count / _select / _gather (capi_select.cpp): every buffer of theirs lives for the call only
-  int64_t select_passes = 0;               // k_select_count and k_select_write passes launched so far (kernel_stats 21)
-  int64_t gather_launches = 0;             // k_gather launches so far (kernel_stats 22)
-  int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field
+  // the marker products on demand (capi_products.cpp): one device buffer for whichever runs, grow-only, zeroed by every call over what it uses
+  double *d_prod = nullptr;
+  size_t d_prod_words = 0;                 // its capacity in 8-byte words
   int chain_selftest = 0;                  // create()'s verdict on the serial sums through the matrix unit: 1 identical, 0 differs, -1 could not run
   int32_t itime = 0;
   double time = 0.0;
@@ -317,29 +313,8 @@ struct pic1dp_ctx {
   int diag_sum = 0;
   long long *d_dfx = nullptr;                // [nspecies + 1][diag_fx_words]: per species, + the copy summed over ranks
   int dfx_e[8][6] = {{0}};                   // the six log2 quanta per species (pic1dp_hip_diag_quanta)
-  int64_t dfx_rejected = 0;                  // terms the exact passes did not sum so far (kernel_stats 15)
   // launch
   int threads_req = 0, bpc_req = 0;
-  // timing
-  bool timers_on = false, stats_on = false;
-  std::vector<EvPair> evpool;
-  size_t ev_used = 0;
-  double acc_ms[kNumTags] = {0};
-  int64_t acc_n[kNumTags] = {0};
-  // timers (tags < 100) may be SAMPLED: only every timer_every-th block of 64 spans of a tag is bracketed by events (an event pair costs
-  // the stream ~3 us of dependency: 10-28 % of a 70 us step at the reference's default size), the others only counted;
-  // pic1dp_hip_timer_ms scales the sampled time by spans seen / spans timed
-  int timer_every = 1;
-  int64_t span_seen[kNumTags] = {0};
-  // the first block of a timer id (first launches: code loading, cold caches, the run's first step) is always timed and
-  // enters as it is; only the later blocks stand for the ones between them
-  double head_ms[kNumTags] = {0};
-  int64_t head_n[kNumTags] = {0};
-  // what the marker kernel launched last under a tag moves per marker (pic1dp_hip_kernel_bytes)
-  struct KernelBytes {
-    double rd = 0.0, wr = 0.0, carry = 0.0;
-    char name[64] = {0};
-  } kbytes[kNumTags];
 };
 
 namespace pic1dp_host {
@@ -349,71 +324,6 @@ inline bool several_ranks(const pic1dp_ctx *c) { return c->lay.nranks > 1 || c->
 // ... and their charge is summed in FP64 (kind 0 of the charge sum; kind 1 sums exact integers in fx_settle, after which
 // the one-rank path runs)
 inline bool fp64_rank_sum(const pic1dp_ctx *c) { return c->charge_sum == 0 && several_ranks(c); }
-
-inline int ev_resolve(pic1dp_ctx *c) {
-  if (c->ev_used == 0) return 0;
-  HIP_TRY(hipStreamSynchronize(c->st));
-  for (size_t i = 0; i < c->ev_used; ++i) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->evpool[i].a, c->evpool[i].b));
-    if (c->evpool[i].head) {
-      c->head_ms[c->evpool[i].tag] += ms;
-      c->head_n[c->evpool[i].tag] += 1;
-    } else {
-      c->acc_ms[c->evpool[i].tag] += ms;
-      c->acc_n[c->evpool[i].tag] += 1;
-    }
-  }
-  c->ev_used = 0;
-  return 0;
-}
-
-// bracket helper: records a start event on construction (if enabled) and the
-// stop event in end(); pairs are resolved to milliseconds lazily (ev_resolve)
-struct Span {
-  pic1dp_ctx *c;
-  long idx = -1;
-  int rc = 0;
-  Span(pic1dp_ctx *c_, int tag, bool on) : c(c_) {
-    if (!on) return;
-    // sampled timers: blocks of 64 consecutive spans of a timer id are timed, every timer_every-th block -- inside a block
-    // everything is bracketed as with exact timers (a run's output steps, optimisation steps and plain steps enter in
-    // their own proportions), the other blocks are only counted
-    const int64_t seq = tag < 100 ? c->span_seen[tag]++ : 0;
-    if (tag < 100 && ((seq >> 6) % c->timer_every) != 0) return;
-    if (c->ev_used == c->evpool.size() && c->evpool.size() >= (1u << 16)) {
-      // a long run that reads its timers only at the end: fold what has been recorded into
-      // the accumulators (one stream synchronisation per 65 536 spans) and reuse the pool
-      if ((rc = ev_resolve(c)) != 0) return;
-    }
-    if (c->ev_used == c->evpool.size()) {
-      EvPair p{};
-      // timing only (the pairs are read after a stream synchronisation): no system-scope fence at the event -- with it
-      // every bracketed launch pays a write-back of the caches its markers live in (a 70 us step at the reference's default
-      // size: +10-28 %), and the time it reports contains that write-back
-      // (A/B at the reference's default size: profiles/r05/experiments, tools/ab_event_fence.sh of that round)
-      auto make = [](hipEvent_t *e) {
-        if (hipEventCreateWithFlags(e, hipEventDisableSystemFence) == hipSuccess) return true;
-        (void)hipGetLastError();
-        return hipEventCreate(e) == hipSuccess;
-      };
-      if (!make(&p.a) || !make(&p.b)) {
-        rc = fail(PIC1DP_ERR_HIP, "hipEventCreate failed");
-        return;
-      }
-      c->evpool.push_back(p);
-    }
-    idx = static_cast<long>(c->ev_used++);
-    c->evpool[idx].tag = tag;
-    c->evpool[idx].head = tag < 100 && c->timer_every > 1 && seq < 64;
-    if (hipEventRecord(c->evpool[idx].a, c->st) != hipSuccess) rc = fail(PIC1DP_ERR_HIP, "hipEventRecord failed");
-  }
-  int end() {
-    if (idx >= 0 && hipEventRecord(c->evpool[idx].b, c->st) != hipSuccess)
-      return fail(PIC1DP_ERR_HIP, "hipEventRecord failed");
-    return rc;
-  }
-};
 
 // ---- capi.cpp ----
 int ensure_second_set(pic1dp_ctx *c);     // the second slab (RK ping-pong set; re-packing target of the optimiser)
@@ -463,5 +373,19 @@ void diag_note_pass(pic1dp_ctx *c, int isp, int blocks, bool fixed, bool launche
 const DistGeom &dist_geom(pic1dp_ctx *c);
 int pinned(pic1dp_ctx *c, size_t ndoubles, double **out);   // the context's pinned staging with room for ndoubles
 size_t dist_len(const pic1dp_input &in);
+// ---- capi_products.cpp (what every read-only pass over a species' markers begins with and is made of) ----
+int product_begin(pic1dp_ctx *c, const char *who, int32_t isp);   // species index and markers checked, the device current, a noted push in memory; who: for the message
+int product_check(pic1dp_ctx *c, const char *who, int32_t isp);   // ... its refusals alone (gather: what it checks next needs the species)
+// npass launches under one tag, each bracketed and counted; none when the species has no valid marker
+template <class Launch>
+int run_passes(pic1dp_ctx *c, int tag, int64_t &counter, int npass, int64_t np, Launch launch) {
+  for (int i = 0; i < npass && np > 0; ++i) {
+    Span ks(c->tm, tag, c->tm.stats_on);
+    HIP_TRY(launch(i));
+    if (int rc = ks.end()) return rc;
+    counter++;
+  }
+  return 0;
+}
 
 }  // namespace pic1dp_host

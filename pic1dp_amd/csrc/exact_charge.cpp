@@ -55,7 +55,7 @@ FxArgs fx_args(const pic1dp_ctx *c, int isp) {
 int fx_settle(pic1dp_ctx *c) {
   const int ns = c->in.nspecies, nx = c->in.nx;
   if (several_ranks(c)) {
-    Span sp(c, PIC1DP_IWT_MPIALLREDU, c->timers_on);
+    Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
     if (xchg_active(c)) {
       HIP_TRY(launch_fx_exchange(c->d_fx, ns, nx, next_xchg_args(c), c->st));
     } else if (c->comm) {

@@ -1,6 +1,6 @@
 // moments_fx.hpp -- host arithmetic of the exact velocity moments (include/pic1dp_hip.h pic1dp_hip_moments_exact; DESIGN.md
 // 2.15): the quanta from the input's two bounds, the normalisation of the (hi, lo) limbs and their conversion to doubles.
-// No context, no HIP call (moments_fx.cpp): the entry points of capi_diag.cpp share it, and a stand-alone program can run it
+// No context, no HIP call (moments_fx.cpp): the entry points of capi_products.cpp share it, and a stand-alone program can run it
 // under the host's sanitizers.
 #pragma once
 #include <cstddef>

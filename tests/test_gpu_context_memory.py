@@ -39,7 +39,10 @@ def test_every_buffer_is_allocated_and_released(amd, monkeypatch, name, how):
             e.set_diag_sum(how["diag_sum"])
         if "transform" in how:
             e.set_field_transform(how["transform"])  # the FFT plan's tables, adopted
-        e.particle_load()                            # d_stage
+        if name == "register_sums":
+            e.particle_load_device()                 # d_loadmax
+        else:
+            e.particle_load()                        # d_stage
         e.interaction_collect_charge()
         e.field_solve_electric()
         e.step(3)                                    # Species::t2 (the carry), the prediction's buffers
@@ -52,6 +55,12 @@ def test_every_buffer_is_allocated_and_released(amd, monkeypatch, name, how):
         e.step(2)
         scal, field, dists = e.output_all()          # d_dist, d_diag_part (d_dfx), d_rec, h_pin
         assert np.all(np.isfinite(scal)) and np.all(np.isfinite(field["electric"])) and len(dists) == 1
+        for call, which in ((e.moments, 3), (e.moments_exact, 3), (e.power, 3), (e.power, 1), (e.moments, 1)):
+            assert len(call(0, which)) == (2 if which == 3 else 1)   # d_prod: grows twice, is reused at smaller sizes
+        got = e.select(0, v=(0.0, np.inf))           # buffers that live for the call; the result through h_pin
+        assert 0 < got["count"] == got["index"].size < N
+        assert e.gather(0, got["index"][:5])["x"].size == 5
+        assert e.state_digest().shape == (1, 4)      # d_digest
         ix, cnt = e.cell_indices()                   # scratch taken from and returned to the owner within the call
         assert int(cnt.sum()) == N and ix.size == N
         assert np.isfinite(e.field_energy())
