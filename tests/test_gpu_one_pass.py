@@ -18,7 +18,8 @@ N = 200_001
 def engine(amd, monkeypatch, predict, kind=None, npe=1, **kw):
     """kind 1: the prediction as tiles (k_step_one) wherever they fit; kind 2: as six sums (k_step_one<PRIV> in
     thread-private LDS slots where E0, Eh and the tables fit the LDS, else k_step_sums) -- the library's own choice
-    is the sums from nx = 512 up with one kept mode, the tiles below and with two kept modes"""
+    is the sums from nx = 8 up with one kept mode (test_private_sums_at_their_limits), the tiles below and with two or
+    three kept modes"""
     monkeypatch.setenv("PIC1DP_PREDICT", "1" if predict else "0")
     if kind and predict:         # 1: the tiles wherever they fit; 2: the six sums (k_step_one<PRIV> / k_step_sums);
         monkeypatch.setenv("PIC1DP_PRED_KIND", str(kind))      # 3: the six sums in registers (k_step_sums) at any grid

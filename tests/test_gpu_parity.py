@@ -531,20 +531,29 @@ STEP_CASES = [(n, kw, lin) for n, kw in DIST_CASES for lin in (0, 1)] + [
 
 @pytest.mark.parametrize("stream", ["plain", "nt"])
 @pytest.mark.parametrize("name,kw,linear", STEP_CASES, ids=lambda v: str(v) if not isinstance(v, dict) else "")
-def test_whole_step_recompute_equals_substeps(amd, monkeypatch, name, kw, linear, stream):
+def test_whole_step_recompute_equals_substeps(amd, probe, monkeypatch, name, kw, linear, stream):
     """pic1dp_hip_step's default path never stores the half-step state: the
     second kernel recomputes it from the step-start state and field.  Given the
     same two fields it must reproduce the two-sub-step path bit for bit -- in
     both instantiations of the kernels: plain accesses for cache-resident marker
-    counts, non-temporal ones once the marker state outgrows the 256 MiB Infinity
-    Cache (9e6 markers here: the product build has no knob for the threshold; a
-    tuning build's PIC1DP_NT_THRESHOLD_MB reaches them at the small count)."""
+    counts, non-temporal ones once the marker state exceeds the whole-step
+    kernels' threshold of 288 MiB (settings.hpp nt_threshold_full; 9 437 185
+    markers here, the smallest count with 32 n beyond it and an odd one: the
+    product build has no knob for the threshold; a tuning build's
+    PIC1DP_NT_THRESHOLD_MB reaches them at the small count).  On a product
+    build the sub-step kernels of b stay plain at either count
+    (nt_threshold_half: 2 GiB)."""
     n = N_SMALL
     if stream == "nt":
         if amd.tuning_build():
             monkeypatch.setenv("PIC1DP_NT_THRESHOLD_MB", "0")
         else:
-            n = 9_000_000
+            n = 9_437_185
+    # the launch of the whole-step kernels is non-temporal exactly when the state exceeds the threshold (capi_step.cpp plan_step)
+    threshold = probe.host_settings()["nt_threshold_full"]
+    assert (32.0 * n > threshold) == (stream == "nt"), (n, threshold)
+    print("%s: %d B of state against nt_threshold_full = %d B: a %s launch" % (
+        stream, 32 * n, threshold, "non-temporal" if 32.0 * n > threshold else "plain"))
     inp = amd.make_input(nparticle_max=n, nx=96, linear=linear, **kw)
     a, b = amd.Pic1dp(inp), amd.Pic1dp(inp)
     for e in (a, b):
