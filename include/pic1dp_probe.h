@@ -159,6 +159,36 @@ int pic1dp_probe_host_context_plan(const pic1dp_input *in, const pic1dp_layout *
  * nt_threshold_full, diag_fx_margin_w}. */
 int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]);
 
+/* What a time step launches (pic1dp_amd/csrc/step_plan.hpp), on the HOST: step_caps, plan_markers, plan_solve and
+ * plan_whole_step for an input, a layout (plan_context makes the context's plan of them) and this query. */
+typedef struct pic1dp_probe_step_query {
+  /* settings (settings.hpp; nt_threshold_* <= 0: the default) */
+  int32_t fuse_solve, tail_on, call_pair, lazy_calls, predict, carry, osub_req, dyn_tail, dyn_tail_full, pred_kind_req, gcopies_req,
+      one_rank_order;
+  double nt_threshold_half, nt_threshold_full;
+  /* the device and pic1dp_hip_set_launch */
+  int32_t num_cu, threads_req, bpc_req;
+  /* what setters and the communicator change; field_npe 0: the plan's; has_pred < 0: the plan has a one-pass kernel */
+  int32_t charge_sum, diag_sum, fuse_output, step_mode, field_solver, field_transform, comm, xchg, field_npe, chain_mfma, has_pred;
+  int32_t pow2[8], one_exp[8]; /* SpeciesConst of each species */
+  int64_t np[8];               /* valid markers of each species (< 0: the plan's) */
+  /* plan_markers */
+  int32_t full, diag, pred, tail_ok, eh_modes, nt_force;
+  /* plan_solve */
+  int32_t pred_fresh, tail_done, into_E;
+  /* plan_whole_step: StepMoment */
+  int32_t pending, have_eh, steps_left, output_now, output_next, optimize_now, optimize_next;
+} pic1dp_probe_step_query;
+/* out[112] = 13 words of StepCaps {dft_paths, six_sums_one_mode, modes_fit_field_kernel, exp_bearing, step_recompute_ok,
+ * predict_capable, diag_in_step, priv, fuse_capable, lazy_calls_ok, pair_serves_collect, pair_in_solve_field, the plan's
+ * pred_kind}; 12 of MarkerPlan {pred, priv, diag, tail_mode, tail_species, stream_nt, solve_species, solve_fits,
+ * solve_threads, tag, bytes read, bytes written}; 8 x 9 of its species {launched, family, threads, blocks, LDS bytes,
+ * dyn_tail, plain_chunks, carry, tail}; 6 of SolvePlan {refused, reduce_first, pack_reduce, pack_first, launch, with_local};
+ * 9 of WholeStepPlan {substeps, finish_pending, diag, pred, fused_in, adopt_eh, half_pass, half_eh_modes, fuse_out}.
+ * names[s]: what kernel_bytes would report of species s' launch.  Nonzero: null argument, nspecies or nranks out of range. */
+int pic1dp_probe_host_step_plan(const pic1dp_input *in, const pic1dp_layout *lay, const pic1dp_probe_step_query *q, int64_t out[112],
+                                char names[8][64]);
+
 
 /* The launch shape of the on-device particle load's pass over nalloc slots (launch_policy.hpp load_launch), on the HOST:
  * out = {workgroups, threads, non-temporal stores, markers a workgroup takes at a time}.  Workgroup b takes the chunks b,

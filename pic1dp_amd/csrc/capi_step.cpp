@@ -1,46 +1,48 @@
-// capi_step.cpp -- the hot path behind the C ABI of include/pic1dp_hip.h: the three call sites and their lazy state
-// machine (push / collect_charge / solve_field), the whole-step kernels' sequencing (pic1dp_hip_step), the
-// prediction of the half-step charge, the solve inside the marker launch, and the split-phase deposit.
-// Context, transfers, field access: capi.cpp; timers: capi_timing.cpp; launch shapes: launch_policy.cpp; the other units: ctx.hpp.
-// In order of dependency: predicates and launch shapes, the marker launches, prediction and solve, pic1dp_hip_step, the
-// call sites and what settles their state, the split-phase deposit, pic1dp_hip_check_state.
+// capi_step.cpp -- the ACTIONS of the hot path behind the C ABI of include/pic1dp_hip.h: the three call sites and their
+// lazy state machine (push / collect_charge / solve_field), pic1dp_hip_step, the prediction of the half-step charge, the
+// solve inside the marker launch, the split-phase deposit.  What a step launches is DECIDED in step_plan.cpp (pure, pinned
+// on the host): here are the wiring (pointers, versions, counters, spans), the state transitions and the order of enqueues.
+// Launch shapes: launch_policy.cpp; the other units: ctx.hpp.  In order of dependency: facts_of and the currency relations,
+// the marker launches, prediction and solve, pic1dp_hip_step, the call sites, the split-phase deposit, pic1dp_hip_check_state.
 // (the entry points are declared extern "C" in include/pic1dp_hip.h; their definitions here inherit that linkage)
 #include "ctx.hpp"
 
 // ---------------------------------------------------------------------------
-// which path: predicates of the context
+// which path: the plan (step_plan.hpp) and what it is asked with
 // ---------------------------------------------------------------------------
-// The fused and predicted paths -- the pair solves, the solve in a marker launch's prologue (kernels.hpp FusedSolve), the
-// prediction tiles and sums, Eh from its kept modes, the tail, the exchange inside the solve's launch -- reproduce the
-// dense-table solve of the mode-filter solver, and only that: not the finite differences (field_solver 1), not the FFT
-// (field_transform 1), under which every solve goes through enqueue_field_solve.
-static bool dft_paths(const pic1dp_ctx *c) { return c->field_solver == 0 && c->field_transform == 0; }
-// the prediction is the six sums of ONE kept mode (k_step_sums, k_step_one<PRIV>): what the pair solve of the call sites,
-// the fused solve and the tail are written for
-static bool six_sums_one_mode(const pic1dp_ctx *c) { return c->plan.pred_kind == 2 && c->in.nmode == 1; }
-// the kept modes fit the one-workgroup field kernels (the wide kernels take more; no predicted or paired solve there)
-static bool modes_fit_field_kernel(const pic1dp_ctx *c) { return 2 * c->in.nmode <= FIELD_THREADS; }
-// -f0'/f0 of the distribution bears an exp (two-stream2, bump-on-tail)
-static bool exp_bearing(const pic1dp_ctx *c) { return c->in.deltaf && (c->in.iptcldist == 2 || c->in.iptcldist == 3); }
-
 // launch shapes (launch_policy.hpp) for this context
 static LaunchPolicy policy_of(const pic1dp_ctx *c) { return LaunchPolicy{c->num_cu, c->threads_req, c->bpc_req, c->cfg.osub_req}; }
+// THE bridge from the context to the plan: the facts, and the predicates that follow from them.  Taken once per API call
+// (nothing inside a call changes them but an optimisation event: pic1dp_hip_step takes them again behind one)
+struct Step {
+  StepFacts f;
+  StepCaps k;
+};
+static Step facts_of(const pic1dp_ctx *c) {
+  Step s{};
+  StepFacts &f = s.f;
+  f.in = &c->in, f.plan = &c->plan, f.cfg = &c->cfg;
+  f.pol = policy_of(c);
+  f.charge_sum = c->charge_sum, f.diag_sum = c->diag_sum, f.fuse_output = c->fuse_output;
+  f.step_mode = c->step_mode, f.field_solver = c->field_solver, f.field_transform = c->field_transform;
+  f.several_ranks = several_ranks(c), f.xchg_active = xchg_active(c), f.has_comm = c->comm != nullptr;
+  f.field_npe = c->fa.npe, f.chain_mfma = c->fa.chain_mfma;
+  f.has_pred = c->d_pred != nullptr;
+  for (int i = 0; i < c->in.nspecies; ++i) f.np[i] = c->sp[i].np, f.pow2[i] = c->sp[i].sc.pow2, f.one_exp[i] = c->sp[i].sc.one_exp;
+  s.k = step_caps(f);
+  return s;
+}
+// the currency relations between the versions: the prediction in d_pred belongs to the markers as they are ...
+static bool pred_fresh(const pic1dp_ctx *c) { return c->pred_version != 0 && c->pred_version == c->state_version; }
+// ... d_Ehn is the half-step field of the markers and the field as they are
+static bool eh_current(const pic1dp_ctx *c) { return c->eh_version == c->state_version && c->eh_field_version == c->field_version; }
+static void mark_eh_current(pic1dp_ctx *c) {
+  c->eh_version = c->state_version;
+  c->eh_field_version = c->field_version;
+}
 static LaunchCfg particle_launch(const pic1dp_ctx *c, int64_t np, bool with_E, bool with_rho, bool exact = false) {
   return particle_launch(policy_of(c), c->in.nx, np, with_E, with_rho, exact);
 }
-static LaunchCfg step_launch(const pic1dp_ctx *c, int64_t np, bool full) {
-  return step_launch(policy_of(c), c->in.nx, np, full, c->charge_sum == 1);
-}
-// the one-pass kernels (k_step_one, k_step_one<PRIV>, k_step_sums)
-static PredLaunch pred_launch(const pic1dp_ctx *c, int64_t np, bool priv) {
-  return pred_launch(policy_of(c), c->in.nx, c->in.nmode, np, priv, c->plan.pred_kind, exp_bearing(c));
-}
-
-// (kind 1 of the charge sum: its rho tile is twice as large -- up to nx 5080; beyond, the sub-step kernels)
-static bool step_recompute_ok(const pic1dp_ctx *c) {
-  return c->step_mode == 0 && step_lds_bytes(c->in.nx, true, c->charge_sum == 1) <= PARTICLE_LDS_CAP;
-}
-
 // does output_all follow the step that is being taken?  (src/pic1dp.F90:98-107 evaluated one step ahead)
 static bool output_follows_at(const pic1dp_ctx *c, int32_t itime0, double time0) {  // (counters at the start of the step)
   const pic1dp_input &in = c->in;
@@ -51,24 +53,6 @@ static bool output_follows_at(const pic1dp_ctx *c, int32_t itime0, double time0)
 }
 static bool output_follows(const pic1dp_ctx *c) { return output_follows_at(c, c->itime, c->time); }
 
-// One pass per step (kernels_step.hip k_step_one) needs: the mode-filter solver (the kept modes must
-// describe E), few kept modes, and LDS for E0, Eh, the mode tables and the four accumulators
-// (kind 1 of the charge sum: no prediction -- two passes per step)
-static bool predict_capable(const pic1dp_ctx *c) {
-  return c->charge_sum == 0 && c->cfg.predict && c->plan.pred_kind != 0 && c->d_pred && dft_paths(c) && step_recompute_ok(c);
-}
-
-// Does a step that output_all follows take the diagnostics inside its marker kernel (k_step_full<DIAG>)?
-// fuse_output 2: always.  1 (what a host that calls output_all at the reference's cadence asks for): only where the step
-// is not a predicted one-pass step anyway.  Where it is, k_step_full<DIAG> costs the prediction -- the step after the
-// output pays a first-sub-step pass again (k_step_half): 10 steps + output_all at 1e8 markers 10.57 ms against 9.5 for
-// ten plain steps --, whereas k_step_one followed by the diagnostics' own pass (k_ptcldist: it changes no marker, the
-// prediction stays valid) costs that pass alone (profiles/r05/experiments/diag_bench.log).
-// (kind 1 of the charge sum or of the diagnostics sum: never -- the diagnostics keep their own pass and summation)
-static bool diag_in_step(const pic1dp_ctx *c) {
-  return c->charge_sum == 0 && c->diag_sum == 0 && (c->fuse_output == 2 || (c->fuse_output == 1 && !predict_capable(c)));
-}
-
 // the accumulator set the marker kernels deposit into from now on (d_rho_all / d_pred_all hold three)
 static void use_accumulators(pic1dp_ctx *c, int idx) {
   c->acc_idx = idx;
@@ -78,55 +62,24 @@ static void use_accumulators(pic1dp_ctx *c, int idx) {
   if (c->d_pred_all) c->d_pred = c->d_pred_all + static_cast<size_t>(idx) * c->plan.pred_set_doubles;
 }
 
-// the one-pass launch of the first species that has markers -- the one whose prologue would carry a fused solve -- can
-// (launch_policy.hpp fits_fused_solve); *threads: its workgroup size
-static bool fused_solve_launch_fits(const pic1dp_ctx *c, bool priv, int *threads = nullptr) {
-  for (int s = 0; s < c->in.nspecies; ++s) {
-    if (c->sp[s].np <= 0) continue;
-    const PredLaunch pl = pred_launch(c, c->sp[s].np, priv);
-    if (threads) *threads = pl.lc.threads;
-    return fits_fused_solve(pl);
-  }
-  return false;
-}
-
-// One launch per time step (kernels.hpp FusedSolve): may the solve of a step be left to the prologue of the next
-// step's marker launch?  One rank (no charge sum between the launches), the six-sum prediction of one kept mode, the
-// mode-filter solver, and partial chains of an npe-rank order that fit the prologue's scratch.
-// And a grid of at most the resident workgroups: EVERY workgroup runs the solve in its prologue, side by side in
-// one round; in an oversubscribed grid each round pays it again (1e8 markers / nx 1024, four rounds: 0.962 -> 0.990 ms
-// per step, profiles/r04/experiments/ab_fused_solve.log).  What the fusion is worth where it applies: one dependency
-// gap and the field launch's start-up, 1-2 us of a step (the solve itself is a chain of dependent round trips either way).
-static bool fuse_capable(const pic1dp_ctx *c) {
-  if (!(c->cfg.fuse_solve && !several_ranks(c) && six_sums_one_mode(c) && dft_paths(c) && c->fa.npe <= 32 && predict_capable(c)))
-    return false;
-  // ... and serial forward sums that are short enough.  The solve costs inside a marker launch what it costs in its own: a
-  // row of dependent round trips and the chain in the reference's order (12 cycles a term at the marker kernel's
-  // clock).  With a chain of 1024 terms the launch it saves is level or slightly behind (1.25e7 markers / nx 1024:
-  // 0.1471 against 0.1460 ms per step); with 192 terms it is 1 % ahead at 6.4e6 markers and 11 % at 2e5
-  // (profiles/r04/experiments/ab_fused_solve.log, ab_small_knobs.log).  PIC1DP_FUSE_SOLVE=2 fuses whatever the length.
-  // Round 4, later: with the sums through the matrix unit (one-rank order, FieldArgs::chain_mfma: a third of the chain's
-  // time) the fused launch is ahead at nx 1024 too (1.25e7 markers: 0.1395-0.1416 against 0.1420-0.1429 ms per step) and
-  // level to +0.3 % at nx 4096 (ab_fused_solve_mfma_chain.log; left unfused: its kernel stays the plain stream the profiles
-  // price): the length that counts is the chain's cost in terms.
-  const int chain_terms = (c->fa.npe == 1 && c->fa.chain_mfma) ? c->in.nx / 3 : c->in.nx / std::max(1, c->fa.npe);
-  if (c->cfg.fuse_solve != 2 && chain_terms > 1024) return false;
-  return fused_solve_launch_fits(c, c->plan.pred_private && c->threads_req <= 0);  // (the first species launched carries the solve)
-}
-
 // the prediction in d_pred describes the next first sub-step of the markers as they are, and the kept
 // modes describe the field as it is
-static bool pred_usable(const pic1dp_ctx *c) {
-  return c->pred_version != 0 && c->pred_version == c->state_version && c->modes_field_version == c->field_version &&
-         predict_capable(c);
+static bool pred_usable(const pic1dp_ctx *c, const Step &s) {
+  return pred_fresh(c) && c->modes_field_version == c->field_version && s.k.predict_capable;
 }
 
+// both fields in one launch: what every pair solve is handed
+// (cd_h: the tiles' scratch; with the six sums the kept mode's content of the half-step charge density -- what the call
+// sites adopt into field_chargeden when the host's next push(1), collect_charge, solve_field are served from this solve,
+// which they are after a step() as after the call sites' own pair: round 6's fuzz campaign found the stale copy)
+static PairArgs pair_args(const pic1dp_ctx *c) {
+  return PairArgs{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->plan.pred_kind, c->pred_tab, 0};
+}
 // bookkeeping behind a pair solve: field_electric is the new state's field, d_Ehn / d_mode_h the next step's half-step field
 static void pair_solved(pic1dp_ctx *c) {
   field_written(c, true);
   c->pred_version = 0;  // consumed
-  c->eh_version = c->state_version;
-  c->eh_field_version = c->field_version;
+  mark_eh_current(c);
 }
 // d_E0 <- field_electric: the field a noted push(1) saw
 static int save_step_start_field(pic1dp_ctx *c) {
@@ -217,90 +170,25 @@ static int enqueue_push(pic1dp_ctx *c, int irk, bool fused, const double *E = nu
   return 0;
 }
 
-// what the marker launches of one sub-step of the whole-step path do, decided once per call of step_particles
-struct StepPlan {
-  bool pred;         // k_step_one / k_step_sums: the full step + the prediction of the next first sub-step's charge
-  bool priv;         // k_step_one<PRIV>: Eh from its tile
-  bool diag;         // k_step_full<DIAG>: the diagnostics of output_all in the same pass
-  int tail_mode;     // kernels.hpp StepTail: 0 none, 1 packed for one all-reduce, 2 posted into the peers' exchange slots ...
-  int tail_species;  // ... by the launch of this species (the last one that has markers)
-  int stream_nt;     // 1: non-temporal loads and stores
-};
-
-static StepPlan plan_step(const pic1dp_ctx *c, bool full, bool diag, bool pred, bool tail_ok) {
-  StepPlan pl{};
-  if (pred && (!full || diag || !predict_capable(c))) pred = false;
-  pl.priv = c->plan.pred_kind == 2 && c->plan.pred_private && c->threads_req <= 0;  // k_step_one<PRIV>: Eh from its tile
-  if (pred && c->plan.pred_kind == 2 && !pl.priv && c->eh_modes == 0) pred = false;  // k_step_sums forms Eh from its kept mode
-  pl.pred = pred;
-  // the diagnostics of output_all inside k_step_full: when asked for, the LDS holds them, and the
-  // tuning build of the marker loop is the default one
-  if (diag) {
-    const size_t need = step_lds_bytes(c->in.nx, true) +
-                        step_diag_lds_bytes(c->in.nx, c->in.nx_opd, c->in.nv_opd);
-    if (!full || c->in.nx_opd < 1 || c->in.nv_opd < 2 || need > PARTICLE_LDS_CAP) diag = false;
-  }
-  pl.diag = diag;
-  // several ranks, the six sums of one kept mode, the mode-filter solver: the packing of this rank's charge for the sum
-  // over ranks rides in the tail of the last marker launch (RCCL: one all-reduce follows; exchange: posted at once)
-  pl.tail_species = -1;
-  if (tail_ok && pred && c->cfg.tail_on && six_sums_one_mode(c) && dft_paths(c) && several_ranks(c)) {
-    pl.tail_mode = xchg_active(c) ? 2 : (c->comm != nullptr ? 1 : 0);
-    for (int s = 0; s < c->in.nspecies; ++s)
-      if (c->sp[s].np > 0) pl.tail_species = s;
-    if (pl.tail_species < 0) pl.tail_mode = 0;
-  }
-  // x, v, w, p of all species against the 256 MiB Infinity Cache
-  double state_bytes = 0.0;
-  for (int s = 0; s < c->in.nspecies; ++s) state_bytes += 32.0 * static_cast<double>(c->sp[s].np);
-  pl.stream_nt = state_bytes > (full ? c->cfg.nt_threshold_full : c->cfg.nt_threshold_half) ? 1 : 0;
-  if (const char *e = tuning_env("PIC1DP_NT_FORCE")) {  // tuning build only, read per launch (tools/ab_nt.py)
-    const int f = std::atoi(e);
-    if (f == 0) pl.stream_nt = 0;
-    if (f == 1) pl.stream_nt = 1;
-    if (f == 2) pl.stream_nt = full ? 0 : 1;
-    if (f == 3) pl.stream_nt = full ? 1 : 0;
-  }
-  return pl;
-}
-
 static int carry_buffer(pic1dp_ctx *c, Species &S) {
   if (!S.t2) HIP_TRY(c->mem.alloc(&S.t2, static_cast<size_t>(S.nalloc + 2)));
   return 0;
 }
 
 // -f0'/f0 through memory (Species::t2) instead of a second evaluation: from k_step_half to k_step_full of a step, or from
-// one one-pass step to the next
-static int wire_carry(pic1dp_ctx *c, Species &S, StepArgsDev &a, bool full, bool pred) {
-  const uint64_t read_version = full ? c->state_version - 1 : c->state_version;
-  if (!pred) {
-    // a species with general divisor constants and an exp-bearing f0 is FP64-issue-bound: its
-    // -f0'/f0 at the step-start velocity goes from the first kernel to the second through
-    // memory (8 B per marker) instead of being evaluated twice.  Measured at 1e8 markers
-    // (tools/ab_pipe_carry.sh): bump-on-tail with T = 1.3, T2 = 0.7, m = 1.1 8.9e10 -> 9.85e10
-    // updates/s; two-stream2 (one division fewer per exp pair) 1.05e11 either way, so only
-    // bump-on-tail carries.  PIC1DP_CARRY=0 switches it off, 2 also carries for two-stream2.
-    const bool carry2 = c->cfg.carry != 0 && c->in.deltaf && !S.sc.pow2 && !S.sc.one_exp &&
-                        (c->in.iptcldist == 3 || (c->cfg.carry == 2 && c->in.iptcldist == 2));
-    if (!carry2) return 0;
-    if (int rc = carry_buffer(c, S)) return rc;
-    // the second kernel may only load what the first one stored for these very markers
-    if (!full || S.t2_version == read_version) a.t2 = S.t2;
+// one one-pass step to the next (which species carries: step_plan.cpp carry_of).  A launch may only load what an earlier
+// one stored for these very markers
+static int wire_carry(pic1dp_ctx *c, Species &S, StepArgsDev &a, bool full, Carry carry) {
+  if (carry == Carry::None) return 0;
+  if (int rc = carry_buffer(c, S)) return rc;
+  const bool stored = S.t2_version == (full ? c->state_version - 1 : c->state_version);
+  if (carry == Carry::HalfToFull) {
+    if (!full || stored) a.t2 = S.t2;
     if (!full) S.t2_version = c->state_version;
     return 0;
   }
-  // -f0'/f0 at the new velocity is what the NEXT step's recomputation of the half-step state
-  // needs: it goes there through memory (16 B per marker and step; k_step_one 1.45 -> 1.33 ms at
-  // 1e8 markers, tools/ab_pred.sh).  PIC1DP_CARRY=0: evaluated again instead.
-  // Only where -f0'/f0 costs something: two-stream2 and bump-on-tail (two exp and a division);
-  // Maxwellian and two-stream1 evaluate it in one or two operations.
-  // With the one-exp form of -f0'/f0 (device_math.hpp) an evaluation costs about what its 16 B of carry
-  // traffic cost: measured (profiles/r03/experiments/ab_one_exp.log), PIC1DP_CARRY=1 / 0 insists either way.
-  const bool carry_one = c->cfg.carry < 0 ? (S.sc.one_exp ? kCarryOneExpDefault : true) : c->cfg.carry > 0;
-  if (!(exp_bearing(c) && carry_one)) return 0;
-  if (int rc = carry_buffer(c, S)) return rc;
   a.t2 = S.t2;
-  a.t2_mode = S.t2_version == read_version ? 2 : 1;
+  a.t2_mode = stored ? 2 : 1;
   S.t2_version = c->state_version;
   return 0;
 }
@@ -326,14 +214,13 @@ static void wire_tail(pic1dp_ctx *c, StepTail &t, int tail_mode) {
   c->cnt.tail_launches++;
 }
 
-// k_step_full<DIAG> of species s: its histograms and partial sums, its launch shape, what the collector has to know
-static int wire_diag(pic1dp_ctx *c, int s, StepArgsDev &a, LaunchCfg &lc) {
+// k_step_full<DIAG> of species s: its histograms and partial sums, what the collector has to know
+static int wire_diag(pic1dp_ctx *c, int s, StepArgsDev &a, const LaunchCfg &lc) {
   const size_t ntot = dist_len(c->in);
   a.dg = dist_geom(c);
   a.dist_out = c->d_dist + ntot * s;
   a.dist_partial = diag_part_dev(c, s);
   HIP_TRY(hipMemsetAsync(a.dist_out, 0, sizeof(double) * ntot, c->st));
-  lc = step_diag_launch(policy_of(c), c->in.nx, a.np, c->charge_sum == 1, c->in.nx_opd, c->in.nv_opd);
   // the histograms as 64-bit fixed-point sums where the diagnostics' own pass would take them so (capi_diag.cpp
   // diag_fx_bounds; a marker beyond the bounds: the collector repeats in doubles)
   double bp = 0.0, bw = 0.0;
@@ -343,13 +230,14 @@ static int wire_diag(pic1dp_ctx *c, int s, StepArgsDev &a, LaunchCfg &lc) {
 }
 
 // the marker launch of species s
-static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0, const double *Eh, const StepPlan &pl) {
+static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0, const double *Eh, const MarkerPlan &pl) {
   Species &S = c->sp[s];
-  const bool pred = pl.pred;
+  const SpeciesLaunch &L = pl.sp[s];
   StepArgs sa{};
   sa.iptcldist = c->in.iptcldist;
   sa.deltaf = c->in.deltaf;
   sa.linear = c->in.linear;
+  sa.family = L.family;
   StepArgsDev &a = sa.d;
   a.x = S.set[c->cur].x;
   a.v = S.set[c->cur].v;
@@ -364,57 +252,42 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
   a.g = c->grid;
   a.s = S.sc;
   a.nt = pl.stream_nt;
-  // the drawn chunk tail of every whole-step kernel: half a workgroup's chunks, all of them for k_step_full (two passes
-  // per step at 1e8 markers: 0.913 -> 0.898 ms with 16/16 against 8/16, profiles/r05/experiments/ab_dyn_tail_other.log)
-  a.dyn_tail = (full && !pred) ? c->cfg.dyn_tail_full : c->cfg.dyn_tail;
+  a.dyn_tail = L.dyn_tail;
   a.fx = fx_args(c, s);
-  LaunchCfg lc = step_launch(c, S.np, full);
-  if (pred && c->fuse_args.on) {  // this launch's prologue solves the previous step's field (first species launched)
-    int threads = 0;
-    if (!fused_solve_launch_fits(c, pl.priv, &threads))  // what fuse_capable promised (checked at the launch too)
-      return fail(PIC1DP_ERR_STATE, "internal: fused field solve in a launch of %d threads", threads);
+  if (pl.pred && c->fuse_args.on) {  // this launch's prologue solves the previous step's field (first species launched)
+    if (s != pl.solve_species || !pl.solve_fits)  // what fuse_capable promised (checked at the launch too)
+      return fail(PIC1DP_ERR_STATE, "internal: fused field solve in a launch of %d threads", pl.solve_threads);
     a.fused = c->fuse_args;
     c->fuse_args.on = 0;
     c->cnt.fused_solves++;
   }
-  if (int rc = wire_carry(c, S, a, full, pred)) return rc;
-  if (pred) {  // k_step_one: the full step + the prediction of the next first sub-step's charge
+  if (int rc = wire_carry(c, S, a, full, L.carry)) return rc;
+  if (pl.pred) {  // k_step_one: the full step + the prediction of the next first sub-step's charge
+    const bool sums = c->plan.pred_kind == 2;
     a.tabA = c->d_tabA;
     a.tabB = c->d_tabB;
-    a.pred = c->plan.pred_kind == 2 ? c->d_pred  // six sums, all species together (Z folded in)
-                               : c->d_pred + static_cast<size_t>(s) * (1 + 2 * c->in.nmode) * c->in.nx;
+    a.pred = sums ? c->d_pred  // six sums, all species together (Z folded in)
+                  : c->d_pred + static_cast<size_t>(s) * (1 + 2 * c->in.nmode) * c->in.nx;
     a.pred_nm = c->in.nmode;
-    sa.family = c->plan.pred_kind == 2 ? (pl.priv ? StepFamily::PrivateSums : StepFamily::Sums) : StepFamily::Tiles;
     a.fxb = S.fxb;
-    if (c->plan.pred_kind == 2) {
+    if (sums) {
       a.eh_re = c->eh_modes == 2 ? c->d_mode_h : c->fa.mode_re;
       a.eh_im = c->eh_modes == 2 ? c->d_mode_h + 1 : c->fa.mode_im;
     }
-    lc = pred_launch(c, S.np, pl.priv).lc;
-    {  // a non-temporal launch keeps the head of the slab in the Infinity Cache (launch_policy.hpp)
-      int64_t np_all = 0;
-      for (int k = 0; k < c->in.nspecies; ++k) np_all += c->sp[k].np;
-      a.plain_chunks = static_cast<int>(stream_plain_chunks(np_all, S.np, pl.stream_nt != 0));
-    }
-    if (pl.tail_mode != 0 && s == pl.tail_species && !a.fused.on) wire_tail(c, a.tail, pl.tail_mode);
+    a.plain_chunks = static_cast<int>(L.plain_chunks);
+    if (L.tail && !a.fused.on) wire_tail(c, a.tail, pl.tail_mode);
   }
   if (pl.diag)
-    if (int rc = wire_diag(c, s, a, lc)) return rc;
-  const int tag = pred ? kTagStepOne : (full ? kTagStepFull : kTagStepHalf);
-  {  // the bytes this instantiation moves per marker: x, v, p (+ w) read; x (+ v) (+ w) written by a full step
-    KernelBytes &kb = c->tm.kbytes[tag];
-    kb.rd = 8.0 * (3 + (c->in.deltaf ? 1 : 0));
-    kb.wr = full ? 8.0 * (1 + (c->in.linear ? 0 : 1) + (c->in.deltaf ? 1 : 0)) : 0.0;
-    kb.carry = 0.0;
-    if (a.t2) kb.carry = pred ? (a.t2_mode == 2 ? 16.0 : 8.0) : 8.0;  // k_step_one: 8 read (mode 2) + 8 written
-    std::snprintf(kb.name, sizeof kb.name, "%s%s%s", pred ? (c->plan.pred_kind == 2 ? (pl.priv ? "k_step_one<sums>" : "k_step_sums") : "k_step_one")
-                                                          : (full ? (pl.diag ? "k_step_full<DIAG>" : "k_step_full") : "k_step_half"),
-                  a.fx.acc ? "<EXACT>" : "", S.sc.one_exp && c->in.deltaf ? " (one-exp -f0'/f0)" : "");
-    if (a.fused.on) std::strncat(kb.name, " + field solve", sizeof kb.name - std::strlen(kb.name) - 1);
+    if (int rc = wire_diag(c, s, a, L.lc)) return rc;
+  {  // what this instantiation moves per marker (k_step_one's carry: 8 read when loaded + 8 written)
+    KernelBytes &kb = c->tm.kbytes[pl.tag];
+    kb.rd = pl.rd, kb.wr = pl.wr;
+    kb.carry = a.t2 ? carry_bytes(L.carry, a.t2_mode == 2) : 0.0;
+    std::snprintf(kb.name, sizeof kb.name, "%s%s", L.name, a.fused.on ? " + field solve" : "");
   }
   Span tm(c->tm, PIC1DP_IWT_PUSH_PARTICLE, c->tm.timers_on);
-  Span ks(c->tm, tag, c->tm.stats_on);
-  HIP_TRY(launch_step(sa, full, lc, c->st));
+  Span ks(c->tm, pl.tag, c->tm.stats_on);
+  HIP_TRY(launch_step(sa, full, L.lc, c->st));
   if (int rc = ks.end()) return rc;
   return tm.end();
 }
@@ -424,17 +297,18 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
 // full = true: the caller has bumped state_version for this step; the state the kernel READS is version - 1
 // tail_ok (the step() path on several ranks): the last species' launch may pack / post this rank's charge in its tail
 // (kernels.hpp StepTail) -- c->tail_done tells solve_phase what it did
-static int step_particles(pic1dp_ctx *c, bool full, const double *E0, const double *Eh, bool diag = false, bool pred = false,
-                          bool tail_ok = false) {
+static int step_particles(pic1dp_ctx *c, const Step &s, bool full, const double *E0, const double *Eh, bool diag = false,
+                          bool pred = false, bool tail_ok = false) {
   c->tail_done = 0;
-  const StepPlan pl = plan_step(c, full, diag, pred, tail_ok);
+  const char *nt = tuning_env("PIC1DP_NT_FORCE");  // tuning build only, read per launch (tools/ab_nt.py)
+  const MarkerPlan pl = plan_markers(s.f, s.k, full, diag, pred, tail_ok, c->eh_modes, nt ? std::atoi(nt) : -1);
   if (pl.pred && c->pred_version != 0)  // a prediction nobody used: the accumulators start from zero
     HIP_TRY(hipMemsetAsync(c->d_pred, 0, sizeof(double) * c->plan.pred_set_doubles, c->st));
   if (pl.diag)
     if (int rc = diag_buffers(c)) return rc;
-  for (int s = 0; s < c->in.nspecies; ++s)
-    if (c->sp[s].np > 0)
-      if (int rc = launch_step_species(c, s, full, E0, Eh, pl)) return rc;
+  for (int i = 0; i < c->in.nspecies; ++i)
+    if (pl.sp[i].launched)
+      if (int rc = launch_step_species(c, i, full, E0, Eh, pl)) return rc;
   if (c->fuse_args.on) return fail(PIC1DP_ERR_STATE, "internal: a fused field solve found no marker launch to run in");
   if (pl.pred) c->pred_version = c->state_version;
   return 0;
@@ -480,12 +354,12 @@ static int pred_reduce(pic1dp_ctx *c) {
 // Tiles: combined locally, summed over ranks, scaled.  Six sums: summed over ranks, then the kept mode's
 // content of that charge density -- all the solve looks at (k_pred_chargeden).
 // defer (call sites, f = c->fa): leave the scaling of the summed charge to the solve_field that follows (Owed)
-static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = false) {
+static int pred_to_chargeden(pic1dp_ctx *c, const Step &s, const FieldArgs &f, bool defer = false) {
   c->pred_version = 0;  // consumed: the accumulators are zero again afterwards
   const bool multi = several_ranks(c);
   if (c->plan.pred_kind == 2) {
     if (f.chargeden == c->d_chargeden) c->cd_kept_mode_only = true;
-    if (defer && !multi && dft_paths(c) && f.tab_lds)  // the sums' combination, chargeden and the solve in the
+    if (defer && !multi && s.k.dft_paths && f.tab_lds)  // the sums' combination, chargeden and the solve in the
       return set_owed(c, Owed::PredSums);               // launch of the solve_field that follows
     if (!multi) {
       HIP_TRY(launch_pred_chargeden(f, c->pred_tab, c->d_pred, nullptr, c->st));
@@ -496,7 +370,7 @@ static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = fal
     HIP_TRY(launch_pred_chargeden(f, c->pred_tab, nullptr, c->d_charge, c->st));
     return 0;
   }
-  if (defer && !multi && dft_paths(c) && modes_fit_field_kernel(c))
+  if (defer && !multi && s.k.dft_paths && s.k.modes_fit_field_kernel)
     return set_owed(c, Owed::PredTiles);  // all of it in the launch of the solve_field that follows
   HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
   if (multi)
@@ -507,54 +381,45 @@ static int pred_to_chargeden(pic1dp_ctx *c, const FieldArgs &f, bool defer = fal
 }
 
 // step() path: Eh of the NEXT step from the prediction, right after the field of the new state is solved
-static int predict_half_field(pic1dp_ctx *c) {
+static int predict_half_field(pic1dp_ctx *c, const Step &s) {
   FieldArgs f = c->fa;
   f.chargeden = c->d_cd_h;
-  if (int rc = pred_to_chargeden(c, f)) return rc;
+  if (int rc = pred_to_chargeden(c, s, f)) return rc;
   Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   f.E = c->d_Ehn;
   f.mode_re = c->d_mode_h;
   f.mode_im = c->d_mode_h + c->in.nmode;
   f.history = nullptr;
   HIP_TRY(launch_field_solve(f, false, true, c->st));
-  c->eh_version = c->state_version;
-  c->eh_field_version = c->field_version;
+  mark_eh_current(c);
   return tm.end();
 }
 
-// charge sum over ranks and field solve(s) behind the marker kernel(s) of a sub-step of the whole-step path
-static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
+// charge sum over ranks and field solve(s) behind the marker kernel(s) of a sub-step: what plan_solve says, enqueued
+static int solve_phase(pic1dp_ctx *c, const Step &s, double *Eout, bool record, bool pred) {
   if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
     if (int rc = fx_settle(c)) return rc;
-  const bool multi = fp64_rank_sum(c);
-  const bool fused_xchg = multi && xchg_active(c) && dft_paths(c);  // exchange inside the solve's launch
-  // RCCL path of a one-pass step: everything the two charge sums of the step need in one all-reduce
-  const bool will_pack = pred && c->pred_version == c->state_version && multi && !fused_xchg && c->comm != nullptr &&
-                         !xchg_active(c) && dft_paths(c) && modes_fit_field_kernel(c) && Eout == c->d_E;
   const int tail_done = c->tail_done;  // what the marker launch's tail has done already (kernels.hpp StepTail)
   c->tail_done = 0;
-  if (tail_done == 1 && !will_pack) return fail(PIC1DP_ERR_STATE, "internal: a packed charge nobody reduces");
-  if (tail_done == 2 && !(fused_xchg && pred && c->pred_version == c->state_version))
-    return fail(PIC1DP_ERR_STATE, "internal: a posted charge nobody waits for");
-  if (will_pack) {
-    if (tail_done != 1) {  // the species sum and the packing are collect_charge's share of the step (src/pic1dp_interaction.F90:126-127)
+  const SolvePlan sp = plan_solve(s.f, s.k, pred && pred_fresh(c), tail_done, Eout == c->d_E);
+  if (sp.refused) return fail(PIC1DP_ERR_STATE, sp.refused == 1 ? "internal: a packed charge nobody reduces" : "internal: a posted charge nobody waits for");
+  if (sp.pack_reduce) {  // RCCL path of a one-pass step: everything the two charge sums of the step need in one all-reduce
+    if (sp.pack_first) {  // the species sum and the packing are collect_charge's share of the step (src/pic1dp_interaction.F90:126-127)
       Span pk(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
       HIP_TRY(launch_charge_pack(c->fa, c->d_pred, c->in.nmode, c->plan.pred_kind, c->d_pack, c->st));
       if (int rc = pk.end()) return rc;
     }
-    Span sp(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
+    Span ar(c->tm, PIC1DP_IWT_MPIALLREDU, c->tm.timers_on);
     ncclResult_t r = rccl().AllReduce(c->d_pack, c->d_pack, c->plan.pack_doubles, ncclDouble, ncclSum, c->comm, c->st);
     if (r != ncclSuccess) return fail(PIC1DP_ERR_COMM, "ncclAllReduce: %s", rccl().GetErrorString(r));
-    if (int rc = sp.end()) return rc;
-  } else if (multi && !fused_xchg) {
+    if (int rc = ar.end()) return rc;
+  } else if (sp.reduce_first) {
     if (int rc = reduce_charge(c)) return rc;
   }
   Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   FieldArgs f = c->fa;
   f.E = Eout;
   if (record && c->hist_count < kHistCap) f.history = c->d_hist + c->hist_count++;
-  // one-pass step on one rank or with the exchange: both fields (the new state's, and the next step's
-  // half-step field from the prediction) in ONE launch
   if (c->fused_dirty >= 0) {  // the set the last fused launch read: no launch follows that would zero it
     HIP_TRY(hipMemsetAsync(c->d_rho_all + static_cast<size_t>(c->fused_dirty) * c->plan.rho_set_doubles, 0,
                            sizeof(double) * c->plan.rho_set_doubles, c->st));
@@ -562,87 +427,89 @@ static int solve_phase(pic1dp_ctx *c, double *Eout, bool record, bool pred) {
                            sizeof(double) * c->plan.pred_set_doubles, c->st));
     c->fused_dirty = -1;
   }
-  const bool pair = pred && c->pred_version == c->state_version && (!multi || fused_xchg || will_pack) &&
-                    dft_paths(c) && modes_fit_field_kernel(c) && Eout == c->d_E;
-  if (pair) {
-    // (cd_h: the tiles' scratch; with the six sums the kept mode's content of the half-step charge density -- what the call
-    // sites adopt into field_chargeden when the host's next push(1), collect_charge, solve_field are served from this solve,
-    // which they are after a step() as after the call sites' own pair: round 6's fuzz campaign found the stale copy)
-    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->plan.pred_kind, c->pred_tab, 0};
-    XchgArgs x1;
-    const XchgArgs *xchg = nullptr;
-    if (will_pack) {  // both charge sums of the step came in ONE all-reduce (pack_doubles)
-      pa.pack = c->d_pack;
-    } else if (fused_xchg) {  // ONE exchange: charge2 and the prediction slices travel together
-      if (tail_done == 2) {  // ... and this rank's half of it is under way since the marker launch's tail
+  switch (sp.launch) {
+    case SolveLaunch::Plain:
+      if (int rc = enqueue_field_solve(c, f, sp.with_local, false)) return rc;
+      break;
+    case SolveLaunch::Exchange:
+      HIP_TRY(launch_field_solve_xchg(f, next_xchg_args(c), c->st));
+      break;
+    default: {  // both fields (the new state's, and the next step's half-step field from the prediction) in ONE launch
+      PairArgs pa = pair_args(c);
+      XchgArgs x1;
+      const XchgArgs *xchg = nullptr;
+      if (sp.launch == SolveLaunch::PairPacked) {  // both charge sums of the step came in ONE all-reduce (pack_doubles)
+        pa.pack = c->d_pack;
+      } else if (sp.launch == SolveLaunch::PairPosted) {  // this rank's half of the exchange is under way since the marker launch's tail
         x1 = c->tail_x;
         x1.ticks = c->tm.timers_on ? c->xc.ticks : nullptr;
         pa.posted = 1;
-      } else {
+        xchg = &x1;
+      } else if (sp.launch == SolveLaunch::PairExchange) {  // ONE exchange: charge2 and the prediction slices travel together
         x1 = next_xchg_args(c);
+        xchg = &x1;
       }
-      xchg = &x1;
+      HIP_TRY(launch_field_solve_pair(f, pa, xchg, c->st));
+      pair_solved(c);
+      return tm.end();
     }
-    HIP_TRY(launch_field_solve_pair(f, pa, xchg, c->st));
-    pair_solved(c);
-    return tm.end();
-  }
-  if (fused_xchg) {
-    HIP_TRY(launch_field_solve_xchg(f, next_xchg_args(c), c->st));
-  } else if (int rc = enqueue_field_solve(c, f, !multi, false)) {
-    return rc;
   }
   if (Eout == c->d_E) field_written(c, true);
   return tm.end();
 }
 
 // the solve of a step whose marker launch left it pending, in a launch of its own after all
-static int finish_pending_solve(pic1dp_ctx *c) {
+static int finish_pending_solve(pic1dp_ctx *c, const Step &s) {
   c->fused_pending = false;
-  return solve_phase(c, c->d_E, true, true);
+  return solve_phase(c, s, c->d_E, true, true);
+}
+
+// the previous step's marker launch left its solve (field of the state the markers are in, Eh of this step) to the next
+// launch's prologue: what that prologue has to solve, the accumulators' rotation, and what the dedicated launch would
+// have recorded
+static void wire_fused_solve(pic1dp_ctx *c) {
+  FusedSolve &fs = c->fuse_args;
+  fs = FusedSolve{};
+  fs.on = 1;
+  fs.f = c->fa;  // rho_sp: the set the previous launch deposited into
+  if (c->hist_count < kHistCap) fs.f.history = c->d_hist + c->hist_count++;
+  fs.pt = c->pred_tab;
+  fs.pred_in = c->d_pred;
+  fs.E_h = c->d_Eh;
+  fs.mode_h = c->d_mode_h;
+  const int read = c->acc_idx, dirty = c->fused_dirty;
+  fs.zero_rho = c->d_rho_all + static_cast<size_t>(dirty >= 0 ? dirty : read) * c->plan.rho_set_doubles;
+  fs.zero_rho_n = dirty >= 0 ? static_cast<int64_t>(c->plan.rho_set_doubles) : 0;
+  fs.zero_pred = dirty >= 0 ? c->d_pred_all + static_cast<size_t>(dirty) * c->plan.pred_set_doubles
+                            : c->d_pred_all + static_cast<size_t>((read + 2) % 3) * c->plan.pred_set_doubles;  // (zero already)
+  use_accumulators(c, (read + 1) % 3);  // zero: nobody has deposited into it since it was last zeroed
+  c->fused_dirty = read;
+  c->fused_pending = false;
+  // what the dedicated launch would have recorded: E and its kept mode are the new state's, Eh is this step's
+  field_written(c, true);
+  c->pred_version = 0;
+  c->eh_modes = 2;
 }
 
 // sub-step of the whole-step path: particle kernel(s), charge, field into Eout
-// fused_in: the previous step's marker launch left its solve (field of the state the markers are in, Eh of this step)
-// to this launch's prologue; fuse_out: this step's solve is left to the next launch likewise (fused_pending)
-static int step_phase(pic1dp_ctx *c, bool full, double *Eout, bool record, bool diag = false, bool pred = false,
+// fused_in: this launch's prologue solves the previous step's field; fuse_out: this step's solve is left to the next
+// launch likewise (fused_pending)
+static int step_phase(pic1dp_ctx *c, const Step &s, bool full, double *Eout, bool record, bool diag = false, bool pred = false,
                       bool fused_in = false, bool fuse_out = false) {
   if (full) c->state_version++;
-  if (fused_in) {
-    FusedSolve &fs = c->fuse_args;
-    fs = FusedSolve{};
-    fs.on = 1;
-    fs.f = c->fa;  // rho_sp: the set the previous launch deposited into
-    if (c->hist_count < kHistCap) fs.f.history = c->d_hist + c->hist_count++;
-    fs.pt = c->pred_tab;
-    fs.pred_in = c->d_pred;
-    fs.E_h = c->d_Eh;
-    fs.mode_h = c->d_mode_h;
-    const int read = c->acc_idx, dirty = c->fused_dirty;
-    fs.zero_rho = c->d_rho_all + static_cast<size_t>(dirty >= 0 ? dirty : read) * c->plan.rho_set_doubles;
-    fs.zero_rho_n = dirty >= 0 ? static_cast<int64_t>(c->plan.rho_set_doubles) : 0;
-    fs.zero_pred = dirty >= 0 ? c->d_pred_all + static_cast<size_t>(dirty) * c->plan.pred_set_doubles
-                              : c->d_pred_all + static_cast<size_t>((read + 2) % 3) * c->plan.pred_set_doubles;  // (zero already)
-    use_accumulators(c, (read + 1) % 3);  // zero: nobody has deposited into it since it was last zeroed
-    c->fused_dirty = read;
-    c->fused_pending = false;
-    // what the dedicated launch would have recorded: E and its kept mode are the new state's, Eh is this step's
-    field_written(c, true);
-    c->pred_version = 0;
-    c->eh_modes = 2;
-  }
-  if (int rc = step_particles(c, full, c->d_E, c->d_Eh, diag, pred, /*tail_ok=*/full && Eout == c->d_E)) return rc;
-  if (fuse_out && pred && c->pred_version == c->state_version) {
+  if (fused_in) wire_fused_solve(c);
+  if (int rc = step_particles(c, s, full, c->d_E, c->d_Eh, diag, pred, /*tail_ok=*/full && Eout == c->d_E)) return rc;
+  if (fuse_out && pred && pred_fresh(c)) {
     c->fused_pending = true;
     return 0;
   }
-  return solve_phase(c, Eout, record, pred);
+  return solve_phase(c, s, Eout, record, pred);
 }
 
 // ---------------------------------------------------------------------------
 // whole steps and sub-steps in one call
 // ---------------------------------------------------------------------------
-static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
+static int substep_impl(pic1dp_ctx *c, const Step &s, int irk, bool record) {
   c->cd_kept_mode_only = false;
   c->cd_version++;
   if (irk == 2 && optimize_due_any(c)) {
@@ -654,22 +521,8 @@ static int substep_impl(pic1dp_ctx *c, int irk, bool record) {
   } else if (int rc = enqueue_push(c, irk, true)) {
     return rc;
   }
-  if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
-    if (int rc = fx_settle(c)) return rc;
-  const bool multi = fp64_rank_sum(c);
-  const bool fused_xchg = multi && xchg_active(c) && dft_paths(c);  // exchange inside the solve's launch
-  if (multi && !fused_xchg)
-    if (int rc = reduce_charge(c)) return rc;
-  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
-  FieldArgs f = c->fa;
-  if (record && c->hist_count < kHistCap) f.history = c->d_hist + c->hist_count++;
-  if (fused_xchg) {
-    HIP_TRY(launch_field_solve_xchg(f, next_xchg_args(c), c->st));
-  } else if (int rc = enqueue_field_solve(c, f, !multi, false)) {
-    return rc;
-  }
-  field_written(c, true);
-  return tm.end();
+  // (no prediction: reduce, then the plain solve or the exchange's; nothing of a fused launch or a tail is left over here)
+  return solve_phase(c, s, c->d_E, record, false);
 }
 
 int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
@@ -680,58 +533,52 @@ int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
     c->cd_kept_mode_only = false;
     c->cd_version++;
   }
-  const bool recompute = step_recompute_ok(c);
+  Step s = facts_of(c);
   for (int it = 0; it < nsteps; ++it) {
-    // a step in which a marker optimisation is due goes through the sub-steps
-    if (recompute && !optimize_due_any(c)) {
-      // E0 = d_E stays untouched until the second solve overwrites it
-      // Eh of this step: predicted by the previous step's kernel (one pass per step), or from a
-      // first-sub-step pass over the markers
-      const bool pc = predict_capable(c);
-      // the host can only call output_all after the last step of this call
-      const bool diag = diag_in_step(c) && it == nsteps - 1 && output_follows(c);
-      const bool pred = pc && !diag;
-      // the previous step left its solve to this step's marker launch (one launch per step, kernels.hpp FusedSolve)
-      const bool fused_in = c->fused_pending && pred && fuse_capable(c);
-      if (c->fused_pending && !fused_in)
-        if (int rc = finish_pending_solve(c)) return rc;
-      if (!fused_in) {
-        const bool have_eh = pc && c->eh_version == c->state_version && c->eh_field_version == c->field_version;
-        if (have_eh) {
-          std::swap(c->d_Eh, c->d_Ehn);  // d_Eh: the half-step field of the step being taken
-          c->eh_modes = 2;               // its kept modes: d_mode_h
-        } else if (int rc = step_phase(c, false, c->d_Eh, false)) {
-          return rc;
-        } else {
-          c->eh_modes = dft_paths(c) ? 1 : 0;  // that solve left them in fa.mode_re / mode_im
-        }
-      }
-      // may the NEXT step's launch take this step's solve?  Only if that step will be an ordinary predicted one (the
-      // step after an output, an optimisation step or the last step of the call need the field in memory first)
-      bool fuse_out = false;
-      if (pred && it + 1 < nsteps && fuse_capable(c)) {
-        const bool next_diag = diag_in_step(c) && it + 1 == nsteps - 1 && output_follows_at(c, c->itime + 1, c->time + c->in.dt);
-        bool due[3];
-        optimize_due_at(c, c->time + c->in.dt, due);
-        fuse_out = !next_diag && !(due[0] || due[1] || due[2]);
-      }
-      if (int rc = step_phase(c, true, c->d_E, true, diag, pred, fused_in, fuse_out)) return rc;
-      if (pred && !c->fused_pending && c->pred_version == c->state_version)  // not already turned into Eh by the paired solve
-        if (int rc = predict_half_field(c)) return rc;
-    } else {
-      if (c->fused_pending)
-        if (int rc = finish_pending_solve(c)) return rc;
-      if (int rc = substep_impl(c, 1, false)) return rc;
+    StepMoment m{};
+    m.pending = c->fused_pending;
+    m.have_eh = eh_current(c);
+    m.steps_left = nsteps - it;
+    m.output_now = output_follows(c);
+    m.output_next = output_follows_at(c, c->itime + 1, c->time + c->in.dt);
+    m.optimize_now = optimize_due_any(c);
+    bool due[3];
+    optimize_due_at(c, c->time + c->in.dt, due);
+    m.optimize_next = due[0] || due[1] || due[2];
+    WholeStepPlan w = plan_whole_step(s.f, s.k, m);
+    if (w.finish_pending) {  // (its pair solve may leave the Eh of this step: asked again)
+      if (int rc = finish_pending_solve(c, s)) return rc;
+      m.pending = false;
+      m.have_eh = eh_current(c);
+      w = plan_whole_step(s.f, s.k, m);
+    }
+    if (w.substeps) {
+      const bool event = m.optimize_now;
+      if (int rc = substep_impl(c, s, 1, false)) return rc;
       HIP_TRY(hipMemcpyAsync(c->d_Eh, c->d_E, sizeof(double) * c->in.nx, hipMemcpyDeviceToDevice, c->st));
-      if (int rc = substep_impl(c, 2, true)) return rc;
+      if (int rc = substep_impl(c, s, 2, true)) return rc;
+      if (event) s = facts_of(c);  // (the event changed the marker counts)
+    } else {
+      // E0 = d_E stays untouched until the second solve overwrites it
+      if (w.adopt_eh) {
+        std::swap(c->d_Eh, c->d_Ehn);  // d_Eh: the half-step field of the step being taken
+        c->eh_modes = 2;               // its kept modes: d_mode_h
+      } else if (w.half_pass) {
+        if (int rc = step_phase(c, s, false, c->d_Eh, false)) return rc;
+        c->eh_modes = w.half_eh_modes;
+      }
+      if (int rc = step_phase(c, s, true, c->d_E, true, w.diag, w.pred, w.fused_in, w.fuse_out)) return rc;
+      if (w.pred && !c->fused_pending && pred_fresh(c))  // not already turned into Eh by the paired solve
+        if (int rc = predict_half_field(c, s)) return rc;
     }
     c->itime += 1;                  // src/pic1dp.F90:92
     c->time = c->time + c->in.dt;   // :93
   }
   if (c->fused_pending)  // (the last step of a call never leaves its solve pending; a safety net)
-    if (int rc = finish_pending_solve(c)) return rc;
+    if (int rc = finish_pending_solve(c, s)) return rc;
   return 0;
 }
+
 
 // ---------------------------------------------------------------------------
 // the call sites and what settles their state
@@ -837,10 +684,6 @@ int pic1dp_host::require_loaded(pic1dp_ctx *c) {
 // memory is bit for bit what the eager calls would have left; results of the lazy
 // path itself are the whole-step path's (tests: test_lazy_call_sites_*).
 // ---------------------------------------------------------------------------
-static bool lazy_ok(const pic1dp_ctx *c) {
-  return c->cfg.lazy_calls && step_recompute_ok(c) && !optimize_due_any(c);
-}
-
 // wrap of x stored back, as the deposit of collect_charge does, charge discarded
 static int enqueue_wrap_only(pic1dp_ctx *c) {
   for (int s = 0; s < c->in.nspecies; ++s) {
@@ -911,27 +754,27 @@ int pic1dp_host::materialize(pic1dp_ctx *c) {
 
 // the deposit of collect_charge / charge_local into the species accumulators:
 // the whole-step kernel of a noted push, or the plain wrap + deposit
-static int deposit_or_step(pic1dp_ctx *c) {
+static int deposit_or_step(pic1dp_ctx *c, const Step &s) {
   if (c->seq == Seq::Push1) {
     if (int rc = save_step_start_field(c)) return rc;
-    if (int rc = step_particles(c, false, c->d_E, c->d_Eh)) return rc;
+    if (int rc = step_particles(c, s, false, c->d_E, c->d_Eh)) return rc;
     return set_seq(c, Seq::Half);
   }
   if (lz_of(c->seq) == LZ_PUSH2) {
     if (c->seq == Seq::Push2Pair)  // (push(2) without the solve_field of the half step: it sees the old field)
       if (int rc = settle_half_pair(c)) return rc;
     c->state_version++;
-    const bool diag = diag_in_step(c) && output_follows(c);
+    const bool diag = s.k.diag_in_step && output_follows(c);
     if (c->seq == Seq::Push2PairSolved) {  // the half-step field came out of the previous step's pair solve: E0 is still in d_E
       std::swap(c->d_Eh, c->d_Ehn);
       c->eh_modes = 2;  // its kept mode: d_mode_h
-      if (int rc = step_particles(c, true, c->d_E, c->d_Eh, diag, !diag)) return rc;
+      if (int rc = step_particles(c, s, true, c->d_E, c->d_Eh, diag, !diag)) return rc;
       c->e_step_start = true;  // (field_electric: still the step-start field -- the solve_field that follows overwrites it)
       return set_seq(c, Seq::Clean);
     }
     // Eh = d_E: the kept modes describe it when the mode-filter solve wrote it last
-    c->eh_modes = (dft_paths(c) && c->modes_field_version == c->field_version) ? 1 : 0;
-    if (int rc = step_particles(c, true, c->d_E0, c->d_E, diag, !diag)) return rc;
+    c->eh_modes = (s.k.dft_paths && c->modes_field_version == c->field_version) ? 1 : 0;
+    if (int rc = step_particles(c, s, true, c->d_E0, c->d_E, diag, !diag)) return rc;
     return set_seq(c, Seq::Clean);
   }
   if (int rc = materialize(c)) return rc;
@@ -941,6 +784,7 @@ static int deposit_or_step(pic1dp_ctx *c) {
 int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   CHECK_CTX(c);
   if (int rc = require_loaded_keep_lazy(c)) return rc;
+  const Step s = facts_of(c);
   c->cd_version++;
   // a whole-step kernel run for a noted push is booked under "push particle"
   // (step_particles); "collect charge" then covers the reduction and scaling only
@@ -951,17 +795,16 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   // after a noted push(1) whose half-step FIELD the previous solve_field has already solved (the pair, below): nothing
   // to launch at all
   // (the six sums of one kept mode: with the tiles collect_charge owes the host the whole half-step charge density)
-  if (c->seq == Seq::Push1 && c->cfg.call_pair && c->cfg.lazy_calls && !several_ranks(c) && predict_capable(c) &&
-      six_sums_one_mode(c) && c->eh_version == c->state_version && c->eh_field_version == c->field_version) {
+  if (c->seq == Seq::Push1 && s.k.pair_serves_collect && eh_current(c)) {
     c->cd_kept_mode_only = true;  // (field_chargeden is not the half step's: asking for it rebuilds, get_field)
     c->adopt_cd_version = c->cd_version;
     return set_call_state(c, Seq::HalfPair, Owed::AdoptHalfField);  // what the solve_field that follows has to do: adopt the half-step field
   }
-  if (c->seq == Seq::Push1 && pred_usable(c)) {
+  if (c->seq == Seq::Push1 && pred_usable(c, s)) {
     if (int rc = save_step_start_field(c)) return rc;
     if (int rc = set_call_state(c, Seq::Half, Owed::Nothing)) return rc;   // (a stale AdoptHalfField ends here)
     Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
-    if (int rc = pred_to_chargeden(c, c->fa, c->cfg.lazy_calls != 0)) return rc;
+    if (int rc = pred_to_chargeden(c, s, c->fa, c->cfg.lazy_calls != 0)) return rc;
     return tm.end();
   }
   c->cd_kept_mode_only = false;  // a deposit follows: the whole vector again
@@ -969,10 +812,10 @@ int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
     if (int rc = set_owed(c, Owed::Nothing)) return rc;
   const bool noted = lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2;
   if (noted)
-    if (int rc = deposit_or_step(c)) return rc;
+    if (int rc = deposit_or_step(c, s)) return rc;
   Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
   if (!noted)
-    if (int rc = deposit_or_step(c)) return rc;
+    if (int rc = deposit_or_step(c, s)) return rc;
   if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
     if (int rc = fx_settle(c)) return rc;
   const bool multi = fp64_rank_sum(c);
@@ -1042,6 +885,7 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   // a noted push has to see the field of its own moment
   if (lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2)
     if (int rc = materialize(c)) return rc;
+  const Step s = facts_of(c);
   Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   FieldArgs f = c->fa;
   Owed pending = c->owed;  // what collect_charge left to this launch
@@ -1051,18 +895,16 @@ int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   // One rank, behind the collect_charge of push(2) whose kernel has predicted the next half-step charge: BOTH fields in
   // one launch, as pic1dp_hip_step solves them -- the next step's push(1), collect_charge, solve_field then launch nothing
   // and a time step through the three call sites is two launches (round 5; three and a copy before)
-  if (pending == Owed::SumScale && c->cfg.call_pair && c->cfg.lazy_calls && dft_paths(c) && c->seq == Seq::Clean && pred_usable(c) &&
-      six_sums_one_mode(c)) {
-    PairArgs pa{c->d_pred, c->d_Ehn, c->d_mode_h, c->d_cd_h, nullptr, c->plan.pred_kind, c->pred_tab, 0};
-    HIP_TRY(launch_field_solve_pair(f, pa, nullptr, c->st));
+  if (pending == Owed::SumScale && s.k.pair_in_solve_field && c->seq == Seq::Clean && pred_usable(c, s)) {
+    HIP_TRY(launch_field_solve_pair(f, pair_args(c), nullptr, c->st));
     pair_solved(c);
     return tm.end();
   }
   if (pending == Owed::AdoptHalfField) {  // (the fast path above was left by an inspection in between: the field is adopted by copying)
     if (int rc = adopt_half_field(c)) return rc;
-  } else if (pending == Owed::PredTiles && dft_paths(c)) {
+  } else if (pending == Owed::PredTiles && s.k.dft_paths) {
     HIP_TRY(launch_field_solve_pred(f, c->d_pred, c->in.nmode, c->st));
-  } else if (pending == Owed::PredSums && dft_paths(c)) {
+  } else if (pending == Owed::PredSums && s.k.dft_paths) {
     HIP_TRY(launch_field_solve_pred_sums(f, c->pred_tab, c->d_pred, c->st));
   } else {
     if (pending == Owed::PredSums) HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, c->d_pred, nullptr, c->st));
@@ -1077,7 +919,7 @@ int pic1dp_hip_push(pic1dp_ctx *c, int32_t irk) {
   CHECK_CTX(c);
   if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
   if (int rc = require_loaded_keep_lazy(c)) return rc;
-  if (irk == 1 && c->seq == Seq::Clean && lazy_ok(c)) return set_seq(c, Seq::Push1);
+  if (irk == 1 && c->seq == Seq::Clean && lazy_ok(facts_of(c).k, optimize_due_any(c))) return set_seq(c, Seq::Push1);
   if (irk == 2 && lz_of(c->seq) == LZ_HALF) return set_seq(c, push2_noted(c->seq));
   if (int rc = materialize(c)) return rc;
   return enqueue_push(c, irk, false);
@@ -1087,7 +929,7 @@ int pic1dp_hip_substep(pic1dp_ctx *c, int32_t irk) {
   CHECK_CTX(c);
   if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
   if (int rc = require_loaded(c)) return rc;
-  return substep_impl(c, irk, false);
+  return substep_impl(c, facts_of(c), irk, false);
 }
 
 int pic1dp_hip_set_step_mode(pic1dp_ctx *c, int32_t mode) {
@@ -1100,7 +942,7 @@ int pic1dp_hip_set_step_mode(pic1dp_ctx *c, int32_t mode) {
 int pic1dp_hip_predict_kind(pic1dp_ctx *c, int32_t *kind) {
   CHECK_CTX(c);
   if (!kind) return fail(PIC1DP_ERR_ARG, "null argument");
-  *kind = predict_capable(c) ? c->plan.pred_kind : 0;
+  *kind = facts_of(c).k.predict_capable ? c->plan.pred_kind : 0;
   return 0;
 }
 
@@ -1151,11 +993,12 @@ int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
   if (!charge2) return fail(PIC1DP_ERR_ARG, "null array");
   if (c->charge_sum == 1) return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_local_exact");
   if (int rc = require_loaded_keep_lazy(c)) return rc;
+  const Step s = facts_of(c);
   if (pair_of(c->seq) && c->seq != Seq::Push2PairSolved)  // out of sequence (as in collect_charge): memory as the eager calls leave it
     if (int rc = settle_half_pair(c)) return rc;
   if (c->owed == Owed::AdoptHalfField)   // (left over by a pair settled before its solve_field: void now)
     if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  if (c->seq == Seq::Push1 && pred_usable(c)) {  // predicted by the previous step's kernel: no marker pass
+  if (c->seq == Seq::Push1 && pred_usable(c, s)) {  // predicted by the previous step's kernel: no marker pass
     if (int rc = save_step_start_field(c)) return rc;
     if (int rc = set_seq(c, Seq::Half)) return rc;
     if (c->plan.pred_kind == 2) {  // the six sums in charge2[0..5], zeros behind: the host's sum over ranks sums them
@@ -1167,7 +1010,7 @@ int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
     c->pred_version = 0;
   } else {
     c->cd_kept_mode_only = false;
-    if (int rc = deposit_or_step(c)) return rc;
+    if (int rc = deposit_or_step(c, s)) return rc;
     HIP_TRY(launch_charge_local(c->fa, c->st));
   }
   HIP_TRY(hipStreamSynchronize(c->st));
@@ -1203,7 +1046,7 @@ int pic1dp_hip_charge_local_exact(pic1dp_ctx *c, int64_t *limbs) {
   if (c->charge_sum != 1) return fail(PIC1DP_ERR_STATE, "charge_local_exact needs the exact charge sum (set_charge_sum(1))");
   if (int rc = require_loaded_keep_lazy(c)) return rc;
   c->cd_kept_mode_only = false;
-  if (int rc = deposit_or_step(c)) return rc;
+  if (int rc = deposit_or_step(c, facts_of(c))) return rc;
   const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
   HIP_TRY(launch_fx_normalise(c->d_fx, c->in.nspecies, c->in.nx, c->st));
   HIP_TRY(hipMemcpyAsync(limbs, c->d_fx, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->st));
@@ -1249,6 +1092,8 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   // occur (ctx.hpp kCallStateLegal): what used to be a dozen relations between lz, cd_lazy, half_pair and half_solved
   // checked here cannot be violated any more.  What is left relates the state to the CONTEXT it is held in:
   const bool one_rank = !several_ranks(c);
+  const Step s = facts_of(c);
+  const bool six_sums_one_mode = s.k.six_sums_one_mode;
   INVARIANT(kCallStateLegal[static_cast<int>(c->seq)][static_cast<int>(c->owed)]);
   INVARIANT(c->seq == Seq::Clean || (c->cfg.lazy_calls && c->loaded));    // a push is only noted by the lazy call sites
   INVARIANT(c->owed == Owed::Nothing || c->cfg.lazy_calls);
@@ -1259,8 +1104,8 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT(c->charge_sum == 0 || (c->owed != Owed::PredTiles && c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField &&
                                    !pair_of(c->seq)));
   INVARIANT(c->owed != Owed::PredTiles || c->plan.pred_kind == 1);
-  INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || six_sums_one_mode(c));
-  INVARIANT(!pair_of(c->seq) || (c->cfg.call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
+  INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || six_sums_one_mode);
+  INVARIANT(!pair_of(c->seq) || (s.f.cfg->call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
   INVARIANT(!c->cd_kept_mode_only || c->plan.pred_kind == 2);
   // an owed adoption is current: made for the field_chargeden the eager calls hold now (and, by kCallStateLegal, while the
   // markers still stand at the half step)

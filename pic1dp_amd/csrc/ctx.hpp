@@ -5,7 +5,8 @@
 //   settings.cpp       what a context takes from the environment, read once (settings.hpp: pic1dp_ctx::cfg; no HIP call)
 //   context_plan.cpp   create()'s decisions as a pure function, and the mode tables (context_plan.hpp: pic1dp_ctx::plan; no HIP call)
 //   device_mem.hpp     the one owner of a context's device and pinned memory (pic1dp_ctx::mem)
-//   capi_step.cpp      the hot path: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
+//   capi_step.cpp      the hot path's actions: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
+//   step_plan.cpp      the hot path's decisions: which marker kernel, carry, streaming, fused solve, tail, field launch (step_plan.hpp: no context, no HIP call)
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
 //   capi_diag.cpp      diagnostics of output_all
@@ -37,6 +38,7 @@
 #include "optimize.hpp"
 #include "rccl_dyn.hpp"
 #include "settings.hpp"
+#include "step_plan.hpp"
 #include "timing.hpp"
 
 using namespace pic1dp;
@@ -61,8 +63,6 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int64_t kHistCap = 1 << 20;
-constexpr bool kCarryOneExpDefault = false;  // k_step_one with the one-exp form of -f0'/f0: carry it (72 B) or evaluate it again (56 B)
-constexpr int FIELD_THREADS = 256;  // the one-workgroup field kernels' thread count (kernels_field.hip keeps its own copy): they take 2 * nmode <= this
 // ---------------------------------------------------------------------------
 // The call sites' state (capi_step.cpp "lazy call sites").  Two variables, each an enum, and a table of
 // the pairs that can occur -- until round 6 this was lz, half_pair, half_solved and cd_lazy, 4 x 2 x 2 x 6 combinations of
@@ -253,7 +253,7 @@ struct pic1dp_ctx {
   int field_solver = 0;    // 0 the reference's mode-filter DFT solve, 1 finite-difference tridiagonal (opt-in)
   // how the mode-filter solve computes its DFT (pic1dp_hip_set_field_transform; kernels_fft.hip): 0 the dense tables, the
   // reference's sums; 1 the FFT (plan built at the first switch).  Transform 1 runs none of the fused or predicted paths
-  // (capi_step.cpp dft_paths).
+  // (step_plan.hpp StepCaps::dft_paths).
   int field_transform = 0;
   FftArgs fft{};
   double *d_fft_tw = nullptr;

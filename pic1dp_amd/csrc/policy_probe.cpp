@@ -1,13 +1,15 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_step_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
+#include <cstdio>
 
 #include "../../include/pic1dp_probe.h"
 #include "context_plan.hpp"
 #include "field_lds.hpp"
 #include "launch_policy.hpp"
+#include "step_plan.hpp"
 
 using namespace pic1dp;
 
@@ -159,5 +161,56 @@ extern "C" int pic1dp_probe_host_settings(int32_t iv[15], double dv[3]) {
                          s.chain_selftest_verbose};
   for (int i = 0; i < 15; ++i) iv[i] = v[i];
   dv[0] = s.nt_threshold_half, dv[1] = s.nt_threshold_full, dv[2] = s.diag_fx_margin_w;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_step_plan(const pic1dp_input *in, const pic1dp_layout *lay, const pic1dp_probe_step_query *q,
+                                           int64_t out[112], char names[8][64]) {
+  if (!in || !lay || !q || !out || !names || in->nspecies < 1 || in->nspecies > PIC1DP_MAX_SPECIES || lay->nranks < 1) return 1;
+  Settings cfg;
+  cfg.fuse_solve = q->fuse_solve, cfg.tail_on = q->tail_on, cfg.call_pair = q->call_pair, cfg.lazy_calls = q->lazy_calls;
+  cfg.predict = q->predict, cfg.carry = q->carry, cfg.osub_req = q->osub_req, cfg.dyn_tail = q->dyn_tail, cfg.dyn_tail_full = q->dyn_tail_full;
+  cfg.pred_kind_req = q->pred_kind_req, cfg.gcopies_req = accepted_gcopies(q->gcopies_req), cfg.field_one_rank_order = q->one_rank_order;
+  if (q->nt_threshold_half > 0.0) cfg.nt_threshold_half = q->nt_threshold_half;
+  if (q->nt_threshold_full > 0.0) cfg.nt_threshold_full = q->nt_threshold_full;
+  const ContextPlan plan = plan_context(*in, *lay, cfg);
+  StepFacts f{};
+  f.in = in, f.plan = &plan, f.cfg = &cfg;
+  f.pol = LaunchPolicy{q->num_cu, q->threads_req, q->bpc_req, cfg.osub_req};
+  f.charge_sum = q->charge_sum, f.diag_sum = q->diag_sum, f.fuse_output = q->fuse_output;
+  f.step_mode = q->step_mode, f.field_solver = q->field_solver, f.field_transform = q->field_transform;
+  f.several_ranks = lay->nranks > 1 || q->comm != 0, f.xchg_active = q->xchg != 0, f.has_comm = q->comm != 0;
+  f.field_npe = q->field_npe > 0 ? q->field_npe : plan.field_npe, f.chain_mfma = q->chain_mfma;
+  f.has_pred = q->has_pred < 0 ? plan.pred_kind != 0 : q->has_pred != 0;
+  for (int s = 0; s < in->nspecies; ++s)
+    f.np[s] = q->np[s] < 0 ? plan.np[s] : q->np[s], f.pow2[s] = q->pow2[s] != 0, f.one_exp[s] = q->one_exp[s] != 0;
+  const StepCaps k = step_caps(f);
+  const MarkerPlan m = plan_markers(f, k, q->full != 0, q->diag != 0, q->pred != 0, q->tail_ok != 0, q->eh_modes, q->nt_force);
+  const SolvePlan sp = plan_solve(f, k, q->pred_fresh != 0, q->tail_done, q->into_E != 0);
+  const StepMoment mo{q->pending != 0, q->have_eh != 0, q->steps_left, q->output_now != 0, q->output_next != 0, q->optimize_now != 0,
+                      q->optimize_next != 0};
+  const WholeStepPlan w = plan_whole_step(f, k, mo);
+  int64_t *o = out;
+  for (int64_t v : {int64_t(k.dft_paths), int64_t(k.six_sums_one_mode), int64_t(k.modes_fit_field_kernel), int64_t(k.exp_bearing),
+                    int64_t(k.step_recompute_ok), int64_t(k.predict_capable), int64_t(k.diag_in_step), int64_t(k.priv),
+                    int64_t(k.fuse_capable), int64_t(k.lazy_calls_ok), int64_t(k.pair_serves_collect), int64_t(k.pair_in_solve_field),
+                    int64_t(plan.pred_kind)})
+    *o++ = v;
+  for (int64_t v : {int64_t(m.pred), int64_t(m.priv), int64_t(m.diag), int64_t(m.tail_mode), int64_t(m.tail_species), int64_t(m.stream_nt),
+                    int64_t(m.solve_species), int64_t(m.solve_fits), int64_t(m.solve_threads), int64_t(m.tag), int64_t(m.rd), int64_t(m.wr)})
+    *o++ = v;
+  for (int s = 0; s < 8; ++s) {
+    const SpeciesLaunch &L = m.sp[s];
+    for (int64_t v : {int64_t(L.launched), int64_t(L.family), int64_t(L.lc.threads), int64_t(L.lc.blocks), int64_t(L.lc.lds), int64_t(L.dyn_tail),
+                      L.plain_chunks, int64_t(L.carry), int64_t(L.tail)})
+      *o++ = v;
+    std::snprintf(names[s], 64, "%s", L.name);
+  }
+  for (int64_t v : {int64_t(sp.refused), int64_t(sp.reduce_first), int64_t(sp.pack_reduce), int64_t(sp.pack_first), int64_t(sp.launch),
+                    int64_t(sp.with_local)})
+    *o++ = v;
+  for (int64_t v : {int64_t(w.substeps), int64_t(w.finish_pending), int64_t(w.diag), int64_t(w.pred), int64_t(w.fused_in), int64_t(w.adopt_eh),
+                    int64_t(w.half_pass), int64_t(w.half_eh_modes), int64_t(w.fuse_out)})
+    *o++ = v;
   return 0;
 }

@@ -27,6 +27,21 @@ class LaunchQuery(C.Structure):
                                                        "exp_bearing", "nx_opd", "nv_opd")]
 
 
+STEP_QUERY_SETTINGS = ("fuse_solve", "tail_on", "call_pair", "lazy_calls", "predict", "carry", "osub_req", "dyn_tail", "dyn_tail_full",
+                       "pred_kind_req", "gcopies_req", "one_rank_order")
+STEP_QUERY_KNOBS = ("charge_sum", "diag_sum", "fuse_output", "step_mode", "field_solver", "field_transform", "comm", "xchg", "field_npe",
+                    "chain_mfma", "has_pred")
+STEP_QUERY_CALLS = ("full", "diag", "pred", "tail_ok", "eh_modes", "nt_force", "pred_fresh", "tail_done", "into_E", "pending", "have_eh",
+                    "steps_left", "output_now", "output_next", "optimize_now", "optimize_next")
+
+
+class StepQuery(C.Structure):
+    """struct pic1dp_probe_step_query: settings, device, knobs, species facts, and the arguments of the three plans"""
+    _fields_ = ([(n, C.c_int32) for n in STEP_QUERY_SETTINGS] + [("nt_threshold_half", C.c_double), ("nt_threshold_full", C.c_double)] +
+                [(n, C.c_int32) for n in ("num_cu", "threads_req", "bpc_req") + STEP_QUERY_KNOBS] +
+                [("pow2", C.c_int32 * 8), ("one_exp", C.c_int32 * 8), ("np", C.c_int64 * 8)] + [(n, C.c_int32) for n in STEP_QUERY_CALLS])
+
+
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 _I32 = C.POINTER(C.c_int32)
@@ -59,6 +74,7 @@ SIGNATURES = {
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
+    "pic1dp_probe_host_step_plan": [C.c_void_p, C.c_void_p, C.POINTER(StepQuery), _I64, C.c_void_p],
     "pic1dp_probe_host_load_launch": [C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_plain_chunks": [C.c_int64, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_write_stream": [C.c_int32, C.c_int64, C.c_int32, _D],
@@ -324,6 +340,38 @@ def host_settings():
     if load().pic1dp_probe_host_settings(iv, dv) != 0:
         raise ValueError("pic1dp_probe_host_settings")
     return dict(list(zip(SETTINGS_INTS, iv)) + list(zip(SETTINGS_DOUBLES, dv)))
+
+
+STEP_CAPS = ("dft_paths", "six_sums_one_mode", "modes_fit_field_kernel", "exp_bearing", "step_recompute_ok", "predict_capable",
+             "diag_in_step", "priv", "fuse_capable", "lazy_calls_ok", "pair_serves_collect", "pair_in_solve_field", "pred_kind")
+STEP_MARKERS = ("pred", "priv", "diag", "tail_mode", "tail_species", "stream_nt", "solve_species", "solve_fits", "solve_threads", "tag",
+                "rd", "wr")
+STEP_SPECIES = ("launched", "family", "threads", "blocks", "lds", "dyn_tail", "plain_chunks", "carry", "tail")
+STEP_SOLVE = ("refused", "reduce_first", "pack_reduce", "pack_first", "launch", "with_local")
+STEP_WHOLE = ("substeps", "finish_pending", "diag", "pred", "fused_in", "adopt_eh", "half_pass", "half_eh_modes", "fuse_out")
+STEP_QUERY_DEFAULTS = dict(fuse_solve=1, tail_on=1, call_pair=1, lazy_calls=1, predict=1, carry=-1, dyn_tail=8, dyn_tail_full=16,
+                           num_cu=256, has_pred=-1, nt_force=-1, full=1, into_E=1, steps_left=1)
+
+
+def host_step_plan(inp, nranks=1, npe=0, rank=0, np_=None, pow2=None, one_exp=None, **query):
+    """what a time step would launch (csrc/step_plan.hpp), on the host: dict(caps, markers -- with one dict per species
+    under "species", name included --, solve, whole) of integers.  query: the fields of StepQuery (the settings at their
+    defaults, 256 CUs, a full step into field_electric, the last step of its call unless given); np_ / pow2 / one_exp: per
+    species (the plan's marker counts, 0, 0)"""
+    from ._lib import Layout
+    lay = Layout(rank, nranks, npe, -1)
+    q = StepQuery(**dict(STEP_QUERY_DEFAULTS, **query))
+    for s in range(8):
+        q.np[s] = -1 if np_ is None or s >= len(np_) else int(np_[s])
+        q.pow2[s] = 0 if pow2 is None or s >= len(pow2) else int(pow2[s])
+        q.one_exp[s] = 0 if one_exp is None or s >= len(one_exp) else int(one_exp[s])
+    out, names = (C.c_int64 * 112)(), ((C.c_char * 64) * 8)()
+    if load().pic1dp_probe_host_step_plan(C.addressof(inp), C.addressof(lay), C.byref(q), out, C.addressof(names)) != 0:
+        raise ValueError("pic1dp_probe_host_step_plan: bad argument")
+    v = list(out)
+    caps, markers = dict(zip(STEP_CAPS, v[:13])), dict(zip(STEP_MARKERS, v[13:25]))
+    markers["species"] = [dict(zip(STEP_SPECIES, v[25 + 9 * s:34 + 9 * s]), name=names[s].value.decode()) for s in range(inp.nspecies)]
+    return dict(caps=caps, markers=markers, solve=dict(zip(STEP_SOLVE, v[97:103])), whole=dict(zip(STEP_WHOLE, v[103:112])))
 
 
 def host_load_launch(nalloc, num_cu=256):
