@@ -666,8 +666,8 @@ int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, d
  *   - The arithmetic is plain IEEE, every product and sum rounded on its own.  A non-finite term makes its bin non-finite;
  *     there is no counter and no trap.
  *   - The sums are FP64 and their order is free: the result is defined up to that order.  With n_b terms in a bin (or in
- *     rest) and B workgroups, |result - exact sum| <= (n_b + B) 2^-53 sum |terms| to first order.  There is no exact
- *     (integer) kind of these planes.
+ *     rest) and B workgroups, |result - exact sum| <= (n_b + B) 2^-53 sum |terms| to first order.  The exact
+ *     (integer) kind of these planes is an entry point of its own: pic1dp_hip_power_exact below.
  *   - Normalisation.  The sums are raw and LOCAL to the context: the sum over ranks is an element-wise addition by the
  *     host; no communicator is used.  Z_s * t is the rate at which the field does work on that marker's share of f (q = p)
  *     or delta f (q = w); 2 (Z / m) sum t_w is the part of d/dt sum v^2 w that comes from the acceleration at fixed weights.
@@ -684,6 +684,53 @@ int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, d
  * straight in memory. */
 int pic1dp_hip_power(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
 int pic1dp_hip_power_len(const pic1dp_input *in, int32_t which, int64_t *n);   /* host only */
+
+/* ---- exact, order-independent wave-particle power ---------------------------------
+ * The planes above with integer sums: fixed by the input, the markers and the field alone, independent of launch shape,
+ * storage order of the markers, number of passes and split over ranks.  The exactness is in the entry points, not in a mode:
+ * set_diag_sum and set_charge_sum do not affect these calls, and the checkpoint carries nothing of them.
+ *   Terms.  The very terms of pic1dp_hip_power, bit for bit: px = wrap(x), (ix, wl) = locate(px), e = E[ix] * wl;
+ *     e = e + E[ir] * (1.0 - wl), c = v * e, t_q = c * q.  A marker with bins contributes the four products w00 * t_q ...
+ *     w11 * t_q of the output grid's stencil with its edge rules; a marker with |v| >= v_max contributes t_q to rest[q].
+ *     Tail slots do not count.
+ *   Scale.  A term t becomes n = rint(t 2^-e), one rounding to nearest even, with
+ *         e = max(kb + kvm + kE - 40, -1000)        one e for p and w, the planes and rest,
+ *     kb = ceil(log2 B_s), B_s the bound of pic1dp_hip_charge_quantum (kb = charge_quantum + 52), kvm = ceil(log2 v_max),
+ *     kE = ceil(log2 max_ix |E[ix]|) over the field pic1dp_hip_get_field would return at that moment, kE = 0 for a field of
+ *     zeros (all terms are then +-0 and all limbs 0).  The clamp keeps 2^e and 2^-e normal doubles for a subnormal field.
+ *     The quantum follows the field of the call: max |E| is found on the device, and e is handed out with the limbs.
+ *     At the bounds |q| <= B_s, |v| <= v_max, |e| <= max |E| a binned term is at most 2^40 (1 + a few ulp) quanta.  A term of
+ *     2^44 quanta or more, or a NaN, is not summed: it is counted, per weight set, separately for bins and for rest.
+ *     A field with an infinity or a NaN is PIC1DP_ERR_ARG ("field not finite"); no marker is read.
+ *   Sums.  The integers are summed exactly -- in the LDS, across workgroups, across passes, and across ranks by the host.
+ *     Each bin's total, and each rest total, is converted to double once (round to nearest even) and multiplied by 2^e.  The
+ *     v-profile is the exact integer sum over ix of the plane's bins, converted once -- not the sum of the converted doubles.
+ *   Limbs.  Per selected weight set j, in output order (p first), power_limbs_len / nsets int64 words:
+ *         [hi plane: nv_opd * nx_opd | lo plane: nv_opd * nx_opd | rest hi | rest lo]
+ *     a total is hi 2^32 + lo quanta, the plane's index is iv * nx_opd + ix.  What power_local_exact hands out is NORMALISED,
+ *     0 <= lo < 2^32: the limbs are fixed by the markers and the field.  What power_convert accepts need not be:
+ *     element-wise sums over ranks (MPI_Allreduce of MPI_INT64_T) are accepted as they are.
+ *   Ranks.  The field is bit-identical on all ranks, so e is too: the host checks that the ranks' e agree, adds the limbs
+ *     and converts once.
+ * power_quantum: e of a species from the input and max |E| -- the rule above.  max_abs_E negative, infinite or NaN:
+ *   PIC1DP_ERR_ARG.  Host only.
+ * power_limbs_len: *n = nsets * (2 * nx_opd * nv_opd + 2).  Host only.
+ * power_local_exact: this context's exact sums as limbs, and the call's e.  Validation, the rule for a noted push and
+ *   "between time steps nothing changes" are those of pic1dp_hip_power.  No communicator is used.
+ * power_convert: limbs and e -> out, laid out as pic1dp_hip_power lays it out.  Host only.
+ * power_exact: power_local_exact followed by power_convert, for one rank.
+ *   - Terms that were not summed: the call returns PIC1DP_ERR_ARG naming the species, the weight set, bins or rest and the
+ *     count, and writes nothing to the caller's buffers.  The next call starts from zero counters: a counted error path, no
+ *     trap.  Markers the call cannot sum are the caller's to fix; pic1dp_hip_power is unaffected.
+ *   - which & 2 on a full-f context or input, an unknown `which`, an unknown species, a null pointer, and nx_opd < 1 or
+ *     nv_opd < 2 are PIC1DP_ERR_ARG.
+ * Cost: pic1dp_hip_power's passes (the planes are 64-bit words, byte for byte the doubles' size), on the grid of the exact
+ * kinds: one workgroup per 2^17 markers, at most one per CU. */
+int pic1dp_hip_power_quantum(const pic1dp_input *in, int32_t ispecies, double max_abs_E, int32_t *log2_quantum);   /* host only */
+int pic1dp_hip_power_limbs_len(const pic1dp_input *in, int32_t which, int64_t *n);                                 /* host only */
+int pic1dp_hip_power_local_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, int64_t *limbs, int32_t *log2_quantum);
+int pic1dp_hip_power_convert(const pic1dp_input *in, int32_t which, int32_t log2_quantum, const int64_t *limbs, double *out);   /* host only */
+int pic1dp_hip_power_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
 
 /* ---- select and gather markers on the device: phase-space samples and tracers ----------
  * pic1dp_hip_select hands out the markers of one species that lie in a window of (x, v), thinned by a hash of their global
@@ -917,9 +964,16 @@ int pic1dp_hip_get_stream(pic1dp_ctx *ctx, void **stream);
  * marker selected, or every output pointer NULL), 0 for a species without valid markers -- *ms = their accumulated device
  * milliseconds while kernel stats were enabled;
  * which = 22: *launches = launches of pic1dp_hip_gather (k_gather, one per call with n > 0) so far, *ms = their accumulated
- * device milliseconds while kernel stats were enabled */
+ * device milliseconds while kernel stats were enabled.
+ * The rows end at 22: the exact power's passes are reported by pic1dp_hip_power_exact_stats below. */
 int pic1dp_hip_kernel_stats(pic1dp_ctx *ctx, int32_t which, double *ms,
                             int64_t *launches);
+/* the exact power (pic1dp_hip_power_exact / _power_local_exact): *passes = passes of k_power_exact that swept markers so far (a
+ * call refused for a field that is not finite counts none), *ms = the accumulated device milliseconds of the passes launched
+ * while kernel stats were enabled, *rejected = terms those passes did not sum so far (2^44 quanta or more, or NaN; each call
+ * that met some returned PIC1DP_ERR_ARG).  Any of the three pointers may be null.  (Not rows of pic1dp_hip_kernel_stats: its
+ * range 0..22 is part of what callers rely on.) */
+int pic1dp_hip_power_exact_stats(pic1dp_ctx *ctx, double *ms, int64_t *passes, int64_t *rejected);
 int pic1dp_hip_kernel_stats_enable(pic1dp_ctx *ctx, int32_t on);
 /* what the marker kernel launched last under `which` (numbering of kernel_stats; not 5)
  * moves per marker and launch, in bytes: read_bytes (x, v, p (+ w); the RK base as well

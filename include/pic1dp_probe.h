@@ -136,6 +136,10 @@ int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, int32_t delt
  * out holds 4 + 8 * 2 words.  Nonzero: null argument. */
 int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
                                  int32_t num_cu, int64_t out[20]);
+/* ... and of one pic1dp_hip_power_exact call (launch_policy.hpp power_plan_exact): the same words; only `blocks` differs,
+ * max(1, min(num_cu, ceil(np / 2^17))). */
+int pic1dp_probe_host_power_plan_exact(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
+                                       int32_t num_cu, int64_t out[20]);
 
 /* The count and write passes of a selection over np valid markers (launch_policy.hpp select_plan), on the HOST: out = {pairs
  * of a chunk, chunks, workgroups, threads, non-temporal loads, threads of the prefix sum's one workgroup}.  Chunk c holds the

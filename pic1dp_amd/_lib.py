@@ -181,6 +181,12 @@ SIGNATURES = {
     "pic1dp_hip_moments_exact": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_power": [_P, C.c_int32, C.c_int32, _P],
     "pic1dp_hip_power_len": [_INP, C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_power_quantum": [_INP, C.c_int32, C.c_double, C.POINTER(C.c_int32)],
+    "pic1dp_hip_power_limbs_len": [_INP, C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_power_local_exact": [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)],
+    "pic1dp_hip_power_convert": [_INP, C.c_int32, C.c_int32, _P, _P],
+    "pic1dp_hip_power_exact": [_P, C.c_int32, C.c_int32, _P],
+    "pic1dp_hip_power_exact_stats": [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "pic1dp_hip_select_count": [_P, C.c_int32, C.POINTER(Select), C.POINTER(C.c_int64)],
     "pic1dp_hip_select": [_P, C.c_int32, C.POINTER(Select), C.c_int64, C.POINTER(C.c_int64), _P, _P, _P, _P, _P],
     "pic1dp_hip_gather": [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P],

@@ -1,9 +1,11 @@
 // capi_products.cpp -- the read-only marker products computed on demand behind the C ABI of include/pic1dp_hip.h: the velocity
-// moments on the field grid (pic1dp_hip_moments), their exact kind (2.15) and the wave-particle power on the
-// output grid (2.17).  Passes of their own that cache nothing and change nothing, all of one shape: refusals, product_begin,
-// the plan, prod_buffers, run_passes, prod_fetch, the product's own arithmetic on the host (how to add one).
+// moments on the field grid (pic1dp_hip_moments), their exact kind (2.15), the wave-particle power on the
+// output grid (2.17) and its exact kind (2.19).  Passes of their own that cache nothing and change nothing, all of one shape:
+// refusals, product_begin, the plan, prod_buffers, run_passes, prod_fetch, the product's own arithmetic on the host (DESIGN.md 1:
+// how to add one).
 #include "ctx.hpp"
 #include "moments_fx.hpp"
+#include "power_fx.hpp"
 
 namespace pic1dp_host {
 
@@ -97,6 +99,75 @@ int moments_exact_local(pic1dp_ctx *c, const char *who, int32_t isp, int32_t whi
   return 0;
 }
 
+// e_base = kb + kvm - 40 of a species, from the input alone
+int power_exact_base(const char *who, const pic1dp_input &in, int32_t isp, int32_t *e_base) {
+  int32_t cq = 0;
+  if (int rc = pic1dp_hip_charge_quantum(&in, isp, &cq)) return rc;   // (the input's version and species index with it)
+  if (!power_fx_base(cq, in.v_max, e_base)) return fail(PIC1DP_ERR_ARG, "%s: v_max must be positive and finite", who);
+  return 0;
+}
+
+// this context's exact power sums of species isp, normalised, in the pinned staging (*limbs) [sets][2 nxv + 2], and the call's e;
+// a field that is not finite, terms not summed: PIC1DP_ERR_ARG
+int power_exact_local(pic1dp_ctx *c, const char *who, int32_t isp, int32_t which, const void *out, int64_t **limbs, int32_t *e) {
+  CHECK_CTX(c);
+  const pic1dp_input &in = c->in;
+  if (int rc = power_refusal(who, in, which)) return rc;
+  if (!out || !e) return fail(PIC1DP_ERR_ARG, "%s: null output", who);
+  if (isp < 0 || isp >= in.nspecies) return fail(PIC1DP_ERR_ARG, "%s: bad species index %d", who, isp);
+  int32_t e_base = 0;
+  if (int rc = power_exact_base(who, in, isp, &e_base)) return rc;
+  if (int rc = product_begin(c, who, isp)) return rc;
+  if (int rc = settle_field_view(c)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
+  const Species &S = c->sp[isp];
+  const PowerPlan plan = power_plan_exact(in.nx, in.nx_opd, in.nv_opd, which, in.deltaf, S.np, c->num_cu);
+  if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: power_plan_exact has no pass for nx %d, %d x %d, which %d", in.nx, in.nx_opd, in.nv_opd, which);
+  const size_t nsets = static_cast<size_t>(plan.selected), n = nsets * power_fx_set_words(in.nx_opd, in.nv_opd);
+  // behind the limbs: [4] terms not summed (per set: bins, rest), [3] e, the non-finite flag, the bits of max |E|, [1]
+  // padding; a species without markers launches nothing: the field itself travels in their place
+  const size_t nx = static_cast<size_t>(in.nx), words = n + 8 + (S.np > 0 ? 0 : nx);
+  double *h = nullptr;
+  if (int rc = prod_buffers(c, words, &h)) return rc;
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int64_t) == sizeof(double), "limbs are 64-bit words");
+  PowerFxArgs a{};
+  a.acc = reinterpret_cast<long long *>(c->d_prod), a.rej = a.acc + n, a.scale = a.rej + 4, a.e_base = e_base;
+  const PSet &A = S.set[c->cur];
+  auto pass = [&](int i) {
+    return launch_power_exact(A.x, A.v, S.p, A.w, S.np, c->grid, dist_geom(c), c->d_E, a, plan.pass[i], c->cfg.dyn_tail, c->st);
+  };
+  int64_t launched = 0;   // (counted once the field is known to be finite: other passes sweep no marker)
+  if (int rc = run_passes(c, kTagPowerExact, launched, plan.npass, S.np, pass)) return rc;
+  if (S.np <= 0) HIP_TRY(hipMemcpyAsync(c->d_prod + n + 8, c->d_E, sizeof(double) * nx, hipMemcpyDeviceToDevice, c->st));
+  if (int rc = prod_fetch(c, words, h)) return rc;
+  if (int rc = xchg_check(c)) return rc;
+  *limbs = reinterpret_cast<int64_t *>(h);
+  const int64_t *rej = *limbs + n, *scale = rej + 4;
+  bool finite = scale[1] == 0;
+  int32_t e_call = static_cast<int32_t>(scale[0]);
+  if (S.np <= 0) {   // the device's rule on the host (power_fx_quantum: the two agree at every double)
+    double mx = 0.0;
+    for (size_t i = 0; i < nx && finite; ++i) {
+      finite = std::isfinite(h[n + 8 + i]);
+      mx = std::fmax(mx, std::fabs(h[n + 8 + i]));
+    }
+    if (finite) power_fx_quantum(e_base, mx, &e_call);
+  }
+  if (!finite) return fail(PIC1DP_ERR_ARG, "%s: field not finite: field_electric holds an infinity or a NaN; no marker was read, nothing was handed out", who);
+  c->cnt.power_exact_passes += launched;
+  for (size_t j = 0; j < nsets; ++j) c->cnt.power_exact_rejected += rej[2 * j] + rej[2 * j + 1];
+  for (size_t j = 0; j < 2 * nsets; ++j)
+    if (rej[j] != 0) {
+      const bool is_w = which == 2 || j >= 2;
+      return fail(PIC1DP_ERR_ARG,
+                  "%s: %lld term(s) of species %d, weight set %s, %s, lay at or beyond 2^44 quanta of 2^%d or were NaN (|p|, |w| or |v| "
+                  "far past the bounds the input gives) and were not summed; nothing was handed out",
+                  who, static_cast<long long>(rej[j]), isp, is_w ? "w" : "p", (j & 1) ? "rest" : "bins", e_call);
+    }
+  power_fx_normalise(*limbs, plan.selected, in.nx_opd, in.nv_opd);
+  *e = e_call;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -165,6 +236,47 @@ int pic1dp_hip_power(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
     }
     o[nxv + nvo] = h[nsets * nxv + j];
   }
+  return 0;
+}
+
+// ---- the exact kind of the power: the same terms in whole quanta 2^e, e from max |E| of the call (the arithmetic on the host: power_fx.cpp) ----
+int pic1dp_hip_power_quantum(const pic1dp_input *in, int32_t isp, double max_abs_E, int32_t *e) {
+  if (!in || !e) return fail(PIC1DP_ERR_ARG, "power_quantum: null argument");
+  int32_t e_base = 0;
+  if (int rc = power_exact_base("power_quantum", *in, isp, &e_base)) return rc;
+  if (!power_fx_quantum(e_base, max_abs_E, e)) return fail(PIC1DP_ERR_ARG, "power_quantum: field not finite: max_abs_E must be finite and not negative");
+  return 0;
+}
+
+int pic1dp_hip_power_limbs_len(const pic1dp_input *in, int32_t which, int64_t *n) {
+  if (!in || !n) return fail(PIC1DP_ERR_ARG, "power_limbs_len: null argument");
+  if (int rc = power_refusal("power_limbs_len", *in, which)) return rc;
+  *n = static_cast<int64_t>(which == 3 ? 2 : 1) * static_cast<int64_t>(power_fx_set_words(in->nx_opd, in->nv_opd));
+  return 0;
+}
+
+int pic1dp_hip_power_local_exact(pic1dp_ctx *c, int32_t isp, int32_t which, int64_t *limbs, int32_t *e) {
+  int64_t *h = nullptr;
+  int32_t e_call = 0;
+  if (int rc = power_exact_local(c, "power_local_exact", isp, which, limbs, &h, e ? &e_call : nullptr)) return rc;
+  std::memcpy(limbs, h, sizeof(int64_t) * (which == 3 ? 2 : 1) * power_fx_set_words(c->in.nx_opd, c->in.nv_opd));
+  *e = e_call;
+  return 0;
+}
+
+int pic1dp_hip_power_convert(const pic1dp_input *in, int32_t which, int32_t e, const int64_t *limbs, double *out) {
+  if (!in) return fail(PIC1DP_ERR_ARG, "power_convert: null input");
+  if (int rc = power_refusal("power_convert", *in, which)) return rc;
+  if (!limbs || !out) return fail(PIC1DP_ERR_ARG, "power_convert: null array");
+  power_fx_convert(e, limbs, which == 3 ? 2 : 1, in->nx_opd, in->nv_opd, out);
+  return 0;
+}
+
+int pic1dp_hip_power_exact(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
+  int64_t *h = nullptr;
+  int32_t e = 0;
+  if (int rc = power_exact_local(c, "power_exact", isp, which, out, &h, &e)) return rc;
+  power_fx_convert(e, h, which == 3 ? 2 : 1, c->in.nx_opd, c->in.nv_opd, out);
   return 0;
 }
 

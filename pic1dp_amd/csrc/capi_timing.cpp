@@ -156,6 +156,16 @@ int pic1dp_hip_kernel_stats(pic1dp_ctx *c, int32_t which, double *ms, int64_t *l
   return 0;
 }
 
+// the exact power's passes are not a row of kernel_stats (its rows end at 22): an entry point of their own
+int pic1dp_hip_power_exact_stats(pic1dp_ctx *c, double *ms, int64_t *passes, int64_t *rejected) {
+  CHECK_CTX(c);
+  if (int rc = ev_resolve(c->tm)) return rc;
+  if (ms) *ms = c->tm.acc_ms[kTagPowerExact];
+  if (passes) *passes = c->cnt.power_exact_passes;
+  if (rejected) *rejected = c->cnt.power_exact_rejected;
+  return 0;
+}
+
 int pic1dp_hip_kernel_bytes(pic1dp_ctx *c, int32_t which, double *read_bytes, double *written_bytes, double *carry_bytes,
                             char *name, int32_t name_len) {
   CHECK_CTX(c);

@@ -148,7 +148,7 @@ struct DiagSpecies {
   double max_p = 0.0, max_w = 0.0;    // max |p|, |w| as the last pass saw them: the next pass's scales (0: unknown -- doubles)
 };
 
-// what the context counts for pic1dp_hip_kernel_stats (capi_timing.cpp: the table's rows name these members); nothing reads them to decide
+// what the context counts for pic1dp_hip_kernel_stats (capi_timing.cpp: the table's rows name these members) and pic1dp_hip_power_exact_stats; nothing reads them to decide
 struct Counters {
   int64_t diag_passes = 0;                 // separate k_ptcldist passes launched so far (kernel_stats 5)
   int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field (7)
@@ -164,6 +164,8 @@ struct Counters {
   int64_t power_passes = 0;                // k_power passes launched so far (20)
   int64_t select_passes = 0;               // k_select_count and k_select_write passes launched so far (21)
   int64_t gather_launches = 0;             // k_gather launches so far (22)
+  int64_t power_exact_passes = 0;          // k_power_exact passes that swept markers so far (pic1dp_hip_power_exact_stats)
+  int64_t power_exact_rejected = 0;        // terms they did not sum so far (the same)
 };
 
 }  // namespace pic1dp_host

@@ -1,6 +1,6 @@
 // device_sweep.hpp -- the one sweep of the off-path marker kernels over a workgroup's rows of marker pairs (k_ptcldist,
-// k_ptcldist_exact: kernels_diag.hip; k_moments, k_moments_exact: kernels_moments.hip), and the window rule of the two
-// exact kernels around it.  The rows and the drawn chunks themselves are device_math.hpp's (pair_rows, draw_chunk): the
+// k_ptcldist_exact: kernels_diag.hip; k_moments, k_moments_exact: kernels_moments.hip; k_power, k_power_exact:
+// kernels_power.hip), and the window rule of the exact kernels around it.  The rows and the drawn chunks themselves are device_math.hpp's (pair_rows, draw_chunk): the
 // step kernels use them too.
 #pragma once
 #include "device_math.hpp"
@@ -58,8 +58,11 @@ __device__ __forceinline__ void pair_sweep(const double *x, const double *v, con
 // DIAG_FX_WINDOW_TRIPS trips of 2 x 1024 markers and that marker, or DIAG_FX_WINDOW_TRIPS - 1 dealt and as many drawn
 // trips: fewer than 2^17 markers.  A marker adds at most 4 terms to a word in the histograms (its four corners in one
 // bin), at most 2 in the moments (nx = 1: ix == ir), each below 2^44 quanta (DIAG_FX_LIMIT): fewer than 2^19 terms, the
-// word stays below 2^63 in magnitude in the histograms and below 2^62 in the moments.  The cap, the cadence and the place
-// of the odd marker carry this bound together: change none of them alone.
+// word stays below 2^63 in magnitude in the histograms and below 2^62 in the moments.  The exact power (device_power.hpp
+// pfx_*) is the histograms' case: at most 4 terms of a marker in one word (nx_opd = 1 with the top v row keeping the marker),
+// 4 x 2^17 x 2^44 = 2^63 -- the STRICT inequality in the marker count is what keeps the word inside.  Its rest sums take one
+// term per marker: a thread's register sum and the workgroup's LDS word of a window stay below 2^17 x 2^44 = 2^61.  The cap,
+// the cadence and the place of the odd marker carry these bounds together: change none of them alone.
 // The dealt trips are the same number for every thread of a workgroup, so window_due is uniform over it and the barriers
 // a kernel puts around its flush inside the sweep are met by all.
 __device__ __forceinline__ PairRows window_rows(PairRows rows) {

@@ -642,6 +642,40 @@ hipError_t launch_moments_exact(const double *x, const double *v, const double *
 hipError_t launch_power(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
                         const DistGeom &dg, const double *E, double *planes, double *rest, const PowerPass &ps, int dyn_tail,
                         hipStream_t st);
+// The exact kind of the power (kernels_power.hip k_power_exact; the definition: include/pic1dp_hip.h pic1dp_hip_power_exact;
+// DESIGN.md 2.19).  The quantum 2^e follows the field: e = max(e_base + kE, POWER_FX_MIN_E), kE = ceil(log2 max |E|) (0 for
+// a field of zeros), which every workgroup takes from the E tile it stages -- a maximum, so the same bits everywhere.
+// |x| of a double as its bit pattern orders as an unsigned integer, and a pattern of POWER_FX_NONFINITE or more is an
+// infinity or a NaN: one integer maximum is the scale and the flag.
+constexpr int POWER_FX_MIN_E = -1000;   // 2^e and 2^-e stay normal doubles for a subnormal field
+constexpr unsigned long long POWER_FX_NONFINITE = 0x7ff0000000000000ull;
+// ceil(log2 b) of a positive finite double from its bits (sign cleared): fx_limbs.hpp ceil_log2 at every such double
+// (tests/power_fx_check.cpp holds the two together)
+__host__ __device__ inline int fx_ceil_log2_bits(unsigned long long bits) {
+  const int ex = static_cast<int>(bits >> 52);
+  const unsigned long long m = bits & 0xfffffffffffffull;
+  if (ex != 0) return ex - 1023 + (m != 0ull ? 1 : 0);
+  const int top = 63 - __builtin_clzll(m);           // subnormal: b = m 2^-1074, m != 0
+  return top - 1074 + ((m & (m - 1ull)) != 0ull ? 1 : 0);
+}
+// e of a call from e_base = kb + kvm - 40 and the bits of max |E| (finite)
+__host__ __device__ inline int power_fx_exponent(int e_base, unsigned long long max_bits) {
+  const int e = e_base + (max_bits != 0ull ? fx_ceil_log2_bits(max_bits) : 0);
+  return e > POWER_FX_MIN_E ? e : POWER_FX_MIN_E;
+}
+// acc: the call's limbs, per selected weight set [hi plane nx_opd nv_opd | lo plane | rest hi | rest lo]; rej: [sets
+// selected][2] terms not summed (bins, rest); scale: [3] e, the non-finite flag, the bits of max |E| -- written by workgroup 0
+// of every pass (the same values).  All zeroed by the caller before a call's passes; launch_power_exact moves acc and rej to
+// the pass's first weight set.  A non-finite field: the pass sweeps no marker.
+struct PowerFxArgs {
+  long long *acc, *rej, *scale;
+  int e_base;
+};
+inline size_t power_fx_set_words(int nxo, int nvo) { return 2 * static_cast<size_t>(nxo) * nvo + 2; }
+// ps: a pass of power_plan_exact (its bytes are the tile and the planes as 64-bit words)
+hipError_t launch_power_exact(const double *x, const double *v, const double *p, const double *w, int64_t np, const GridConst &g,
+                              const DistGeom &dg, const double *E, const PowerFxArgs &a, const PowerPass &ps, int dyn_tail,
+                              hipStream_t st);
 // The state digest of one species (kernels_digest.hip; the definition: include/pic1dp_hip.h pic1dp_hip_state_digest).
 // Array k (0 x, 1 v, 2 w, 3 p): slot i < np is read from cur[k] (the current particle set), slot i >= np from first[k]
 // (set 0, where the tail slots live); out[k] += sum of the mixed words of slots [0, nalloc) (64-bit integer atomics).

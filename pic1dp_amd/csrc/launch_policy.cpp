@@ -207,6 +207,13 @@ PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int6
   return m;
 }
 
+PowerPlan power_plan_exact(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu) {
+  PowerPlan m = power_plan(nx, nx_opd, nv_opd, which, deltaf, np, num_cu);   // (a 64-bit word per (set, bin): the bytes are the doubles')
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(num_cu, (np + (int64_t{1} << 17) - 1) >> 17));   // moments_plan_exact's rule
+  for (int i = 0; i < m.npass; ++i) m.pass[i].blocks = static_cast<int>(blocks);
+  return m;
+}
+
 SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req) {
   SelectPlan s{};
   s.chunk_pairs = SELECT_CHUNK_PAIRS;

@@ -87,6 +87,10 @@ MomentsPlan moments_plan_exact(int nx, int which, int deltaf, int64_t np, int nu
 // w asked of a full-f run (deltaf = 0), nx < 1, nx_opd < 1, nv_opd < 2, or a tile beyond the cap (no context has such a grid).
 constexpr size_t power_tile_bytes(int nx) { return (sizeof(double) * (static_cast<size_t>(nx) + 1) + 15) & ~static_cast<size_t>(15); }
 PowerPlan power_plan(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu);
+// The passes of pic1dp_hip_power_exact (k_power_exact): passes, bytes (the tile, and one 64-bit word per set and bin), NT,
+// weight sets and first sets are power_plan's; the grid is max(1, min(num_cu, ceil(np / 2^17))) workgroups, the rule of
+// the exact diagnostics and the exact moments.
+PowerPlan power_plan_exact(int nx, int nx_opd, int nv_opd, int which, int deltaf, int64_t np, int num_cu);
 
 // ---- select and gather markers (kernels_select.hip; include/pic1dp_hip.h pic1dp_hip_select) ----
 // The count pass and the write pass of a selection over np valid markers, one shape for both: chunks of SELECT_CHUNK_PAIRS

@@ -97,11 +97,9 @@ extern "C" int pic1dp_probe_host_moments_plan_exact(int32_t nx, int32_t which, i
   return moments_plan_words(moments_plan_exact(nx, which, deltaf, np, num_cu), out);
 }
 
-extern "C" int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
-                                            int32_t num_cu, int64_t out[20]) {
+static int power_plan_words(const PowerPlan &m, int64_t out[20]) {
   if (!out) return 1;
   for (int i = 0; i < 20; ++i) out[i] = 0;
-  const PowerPlan m = power_plan(nx, nx_opd, nv_opd, which, deltaf, np, num_cu);
   out[0] = m.npass, out[1] = m.selected, out[2] = static_cast<int64_t>(m.tile), out[3] = static_cast<int64_t>(m.plane);
   for (int i = 0; i < m.npass; ++i) {
     const PowerPass &ps = m.pass[i];
@@ -110,6 +108,16 @@ extern "C" int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t 
     for (int k = 0; k < 8; ++k) out[4 + 8 * i + k] = v[k];
   }
   return 0;
+}
+
+extern "C" int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
+                                            int32_t num_cu, int64_t out[20]) {
+  return power_plan_words(power_plan(nx, nx_opd, nv_opd, which, deltaf, np, num_cu), out);
+}
+
+extern "C" int pic1dp_probe_host_power_plan_exact(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
+                                                  int32_t num_cu, int64_t out[20]) {
+  return power_plan_words(power_plan_exact(nx, nx_opd, nv_opd, which, deltaf, np, num_cu), out);
 }
 
 extern "C" int pic1dp_probe_host_select_plan(int64_t np, int32_t num_cu, int32_t threads_req, int32_t bpc_req, int64_t out[6]) {

@@ -183,16 +183,38 @@ class Pic1dp:
         of work on the marker's share of f or delta f."""
         n = C.c_int64()
         check(self.L.pic1dp_hip_power_len(C.byref(self.inp), int(which), C.byref(n)))
-        nxo, nvo = self.inp.nx_opd, self.inp.nv_opd
-        per = nxo * nvo + nvo + 1
         out = np.zeros(n.value)
         check(self.L.pic1dp_hip_power(self._ctx, int(ispecies), int(which), _ptr(out)))
-        names = [name for bit, name in ((1, "total"), (2, "pertb")) if which & bit]
-        res = {}
-        for j, name in enumerate(names):
-            o = out[j * per:(j + 1) * per]
-            res[name] = {"xv": o[:nxo * nvo].reshape(nvo, nxo).copy(), "v": o[nxo * nvo:nxo * nvo + nvo].copy(), "rest": float(o[-1])}
-        return res
+        return _split_power(out, self.inp, which)
+
+    # -- exact, order-independent wave-particle power (DESIGN.md 2.19) -------------
+    def power_exact(self, ispecies=0, which=3):
+        """power() with integer sums (include/pic1dp_hip.h pic1dp_hip_power_exact): every term rounded once to whole quanta
+        2^e, e from the input and max |E| of the call (power_quantum), the integers summed exactly, every bin converted
+        once, "v" the exact integer row sums.  The same dict as power(); fixed by the input, the markers and the field
+        alone.  Pic1dpError if the field is not finite, or naming species, weight set and bins or rest if a term lay at or
+        beyond 2^44 quanta (power_exact_stats counts them)."""
+        n = C.c_int64()
+        check(self.L.pic1dp_hip_power_len(C.byref(self.inp), int(which), C.byref(n)))
+        out = np.zeros(n.value)
+        check(self.L.pic1dp_hip_power_exact(self._ctx, int(ispecies), int(which), _ptr(out)))
+        return _split_power(out, self.inp, which)
+
+    def power_exact_stats(self):
+        """(device ms of the exact power's passes while kernel stats were enabled, passes that swept markers so far, terms
+        they did not sum so far) -- pic1dp_hip_power_exact_stats; kernel_stats has no row for them"""
+        ms, n, rej = C.c_double(), C.c_int64(), C.c_int64()
+        check(self.L.pic1dp_hip_power_exact_stats(self._ctx, C.byref(ms), C.byref(n), C.byref(rej)))
+        return ms.value, n.value, rej.value
+
+    def power_local_exact(self, ispecies=0, which=3):
+        """(limbs, log2_quantum): this context's exact sums as int64 limbs of shape (nsets, 2 nx_opd nv_opd + 2) -- per set
+        [hi plane | lo plane | rest hi | rest lo], normalised (0 <= lo < 2^32), a total is hi 2^32 + lo quanta -- and the e of
+        the call.  Ranks: check that e agrees, add the limbs element by element, then power_convert"""
+        limbs = np.zeros((2 if which == 3 else 1, power_limbs_len(self.inp, which) // (2 if which == 3 else 1)), dtype=np.int64)
+        e = C.c_int32()
+        check(self.L.pic1dp_hip_power_local_exact(self._ctx, int(ispecies), int(which), _ptr(limbs), C.byref(e)))
+        return limbs, e.value
 
     # -- select and gather markers on the GPU (DESIGN.md 2.18) --------------------
     def _selection(self, ispecies, x, v, fraction, key, origin):
@@ -742,6 +764,46 @@ def moments_convert(inp, limbs, which=3, ispecies=0):
     check(_lib.load().pic1dp_hip_moments_convert(C.byref(inp), int(ispecies), int(which), _ptr(a), _ptr(out)))
     names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
     return {n: out[j] for j, n in enumerate(names)}
+
+
+def _split_power(out, inp, which):
+    """the dict of Pic1dp.power() from its flat output"""
+    nxo, nvo = inp.nx_opd, inp.nv_opd
+    per = nxo * nvo + nvo + 1
+    names = [name for bit, name in ((1, "total"), (2, "pertb")) if which & bit]
+    res = {}
+    for j, name in enumerate(names):
+        o = out[j * per:(j + 1) * per]
+        res[name] = {"xv": o[:nxo * nvo].reshape(nvo, nxo).copy(), "v": o[nxo * nvo:nxo * nvo + nvo].copy(), "rest": float(o[-1])}
+    return res
+
+
+def power_quantum(inp, max_abs_E, ispecies=0):
+    """e = max(kb + ceil(log2 v_max) + kE - 40, -1000), the log2 quantum of the exact power of a species, from the input and
+    max |E| (no device); kb = charge_quantum + 52, kE = ceil(log2 max_abs_E), 0 for a field of zeros"""
+    e = C.c_int32()
+    check(_lib.load().pic1dp_hip_power_quantum(C.byref(inp), int(ispecies), float(max_abs_E), C.byref(e)))
+    return e.value
+
+
+def power_limbs_len(inp, which):
+    """int64 words of the limbs of the exact power: 2 nx_opd nv_opd + 2 per selected weight set"""
+    n = C.c_int64()
+    check(_lib.load().pic1dp_hip_power_limbs_len(C.byref(inp), int(which), C.byref(n)))
+    return n.value
+
+
+def power_convert(inp, limbs, log2_quantum, which=3):
+    """the dict of Pic1dp.power() from limbs (nsets, 2 nx_opd nv_opd + 2) as power_local_exact returns them, or their
+    element-wise sum over ranks (lo need not be normalised), and the ranks' common log2_quantum (no context, no device)"""
+    a = np.ascontiguousarray(limbs, dtype=np.int64)
+    if a.size != power_limbs_len(inp, which):
+        raise ValueError("limbs must have 2 * nx_opd * nv_opd + 2 entries per selected weight set")
+    n = C.c_int64()
+    check(_lib.load().pic1dp_hip_power_len(C.byref(inp), int(which), C.byref(n)))
+    out = np.zeros(n.value)
+    check(_lib.load().pic1dp_hip_power_convert(C.byref(inp), int(which), int(log2_quantum), _ptr(a), _ptr(out)))
+    return _split_power(out, inp, which)
 
 
 def host_digest(a):

@@ -145,6 +145,57 @@ interface
     integer(c_int64_t), intent(out) :: n
     integer(c_int) :: ierr
   end function pic1dp_hip_power_len
+  ! the exact kind: limbs(2 * nx_opd * nv_opd + 2, sets selected) int64 -- per set [hi plane | lo plane | rest hi | rest lo] --
+  ! and the call's log2_quantum, the same on every rank; the host adds the limbs over ranks (MPI_INT64_T), then converts
+  function pic1dp_hip_power_quantum(inp, ispecies, max_abs_e, log2_quantum) bind(C, name="pic1dp_hip_power_quantum") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies
+    real(c_double), value :: max_abs_e
+    integer(c_int32_t), intent(out) :: log2_quantum
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_quantum
+  function pic1dp_hip_power_limbs_len(inp, which, n) bind(C, name="pic1dp_hip_power_limbs_len") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_limbs_len
+  function pic1dp_hip_power_local_exact(ctx, ispecies, which, limbs, log2_quantum) bind(C, name="pic1dp_hip_power_local_exact") &
+      result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(inout) :: limbs(*)
+    integer(c_int32_t), intent(inout) :: log2_quantum
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_local_exact
+  function pic1dp_hip_power_convert(inp, which, log2_quantum, limbs, out) bind(C, name="pic1dp_hip_power_convert") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: which
+    integer(c_int32_t), value :: log2_quantum
+    integer(c_int64_t), intent(in) :: limbs(*)
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_convert
+  function pic1dp_hip_power_exact(ctx, ispecies, which, out) bind(C, name="pic1dp_hip_power_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies
+    integer(c_int32_t), value :: which
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_exact
+  function pic1dp_hip_power_exact_stats(ctx, ms, passes, rejected) bind(C, name="pic1dp_hip_power_exact_stats") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    real(c_double), intent(out) :: ms
+    integer(c_int64_t), intent(out) :: passes, rejected
+    integer(c_int) :: ierr
+  end function pic1dp_hip_power_exact_stats
   ! select and gather markers on the device: the valid markers inside the window, thinned by a hash of their global index, in
   ! ascending logical index (0-based, as the C side counts); count = the number selected, the first min(count, nmax) are
   ! written.  Arrays not wanted: pass c_null_ptr through the type(c_ptr) arguments

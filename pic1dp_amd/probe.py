@@ -70,6 +70,7 @@ SIGNATURES = {
     "pic1dp_probe_host_moments_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_moments_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_power_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_power_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_select_plan": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
@@ -266,6 +267,16 @@ def host_power_plan(nx, nx_opd, nv_opd, which, deltaf, np_, num_cu):
     out = (C.c_int64 * 20)()
     if load().pic1dp_probe_host_power_plan(int(nx), int(nx_opd), int(nv_opd), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
         raise ValueError("pic1dp_probe_host_power_plan")
+    return dict(selected=out[1], tile=out[2], plane=out[3],
+                passes=[dict(zip(POWER_PASS_FIELDS, out[4 + 8 * i:12 + 8 * i])) for i in range(out[0])])
+
+
+def host_power_plan_exact(nx, nx_opd, nv_opd, which, deltaf, np_, num_cu):
+    """the passes of one power_exact call (csrc/launch_policy.hpp power_plan_exact), as host_power_plan returns them: the
+    same passes, bytes, NT and sets; blocks = max(1, min(num_cu, ceil(np / 2^17)))"""
+    out = (C.c_int64 * 20)()
+    if load().pic1dp_probe_host_power_plan_exact(int(nx), int(nx_opd), int(nv_opd), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_power_plan_exact")
     return dict(selected=out[1], tile=out[2], plane=out[3],
                 passes=[dict(zip(POWER_PASS_FIELDS, out[4 + 8 * i:12 + 8 * i])) for i in range(out[0])])
 
