@@ -453,7 +453,10 @@ int pic1dp_hip_ptcldist(pic1dp_ctx *ctx, int32_t ispecies, int32_t finish,
  * three times and more per record).  scalars: [2 + 3 nspecies]; electric, chargeden: [nx]; mode_re, mode_im:
  * [nmode]; dist: [nspecies][3 nx_opd nv_opd + 3 nv_opd] = markr_xv | total_xv | pertb_xv | markr_v | total_v |
  * pertb_v of each species in turn.  Any pointer but scalars may be NULL.  On several ranks the call composes the
- * separate ones (RCCL communicator: they reduce; no communicator: an error, as pic1dp_hip_ptcldist). */
+ * separate ones (RCCL communicator: they reduce; no communicator: an error, as pic1dp_hip_ptcldist).
+ * When the call may come: anywhere in a time step (a noted push becomes memory first; chargeden is field_chargeden as it
+ * stands, the kept mode's content only where pic1dp_hip_chargeden_state says so) but not between charge_local and
+ * charge_reduced: PIC1DP_ERR_STATE there, nothing written, the pending deposit untouched. */
 int pic1dp_hip_output_all(pic1dp_ctx *ctx, double *scalars, int32_t nscalars, double *electric, double *chargeden,
                           double *mode_re, double *mode_im, double *dist);
 /* ---- split-phase diagnostics for a host that owns the reductions (MPI) ----
@@ -599,7 +602,14 @@ int pic1dp_hip_host_digest(const double *a, int64_t n, uint64_t *out);
  * When the call may come.  Between time steps it launches its own passes and nothing else and changes nothing: markers,
  * fields, the one-pass prediction, a pending fused solve and cached diagnostics survive (the rule of
  * pic1dp_hip_state_digest).  Inside a time step (a push noted) it first puts the noted push into memory, as every entry point
- * outside the sequence does; the moments are those of the memory eager calls would hold.
+ * outside the sequence does; the moments are those of the memory eager calls would hold.  Between charge_local and
+ * charge_reduced (or their _exact pair), and with a half-step field waiting for the solve_field that adopts it, the call is
+ * served as pic1dp_hip_particles_download is served there: from the markers as eager calls would hold them at that point (a
+ * noted push becomes memory), and the charge_reduced or solve_field that follows does what it does after eager calls.  The
+ * same holds for moments_exact / moments_local_exact, power and its exact kinds, select, select_count,
+ * gather and state_digest; pic1dp_hip_output_all, which hands out field_chargeden, returns PIC1DP_ERR_STATE while a
+ * charge_local is pending, as energy_sums, output_scalars and ptcldist do.  (tests/test_gpu_call_sequences.py calls every one
+ * of them at every boundary of the reference's six calls and between charge_local and charge_reduced.)
  * Cost: one pass over x, v and p and / or w (24 or 32 B per marker) while the selected planes fit a workgroup's LDS (all
  * eight up to nx 2400); four planes per pass up to nx 4800 (which = 3: two passes), two per pass beyond (four, or two). */
 int pic1dp_hip_moments(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, double *out);
@@ -678,7 +688,8 @@ int pic1dp_hip_moments_exact(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, d
  * When the call may come.  The rule of pic1dp_hip_moments, and pic1dp_hip_get_field's for the field.  Between time steps it
  * launches its own passes and nothing else and changes nothing: markers, fields, the one-pass prediction, the fused solve
  * and cached diagnostics survive.  Inside a time step (a push noted) the noted push becomes memory first; markers and field
- * are then those eager call sites would hold.
+ * are then those eager call sites would hold.  Between charge_local and charge_reduced: as pic1dp_hip_moments, with the
+ * field pic1dp_hip_get_field shows there.
  * Cost: one pass over x, v and p and / or w (24 or 32 B per marker) while the E tile (8 (nx + 1) B) and the selected planes
  * fit a workgroup's LDS (150 KiB); one pass per set where only one plane fits; planes that do not fit at all are summed
  * straight in memory. */
@@ -824,8 +835,15 @@ typedef struct pic1dp_checkpoint_info {
  *   x, v, w, p in logical order (untiled); field_electric, field_chargeden, the kept modes; the energy history; the
  *   events' counters and every owned block's generator; the prediction tiles' fixed-point bounds; the diagnostics
  *   pass's scales; the digests of the marker sections and one checksum over the rest.
- *   Only between time steps: with a push noted or a charge_local pending it returns PIC1DP_ERR_STATE and creates no
- *   file.  What collect_charge left to the next solve_field is settled first.  The markers cross in chunks through
+ *   Only between time steps: inside one, or with a charge_local pending, it returns PIC1DP_ERR_STATE and creates no
+ *   file; the context goes on as if the call had not come.  "Inside a time step" is decided by the calls alone, the same
+ *   with lazy and with eager call sites: push(1) and push(2) open their sub-step, the collect_charge (or charge_reduced)
+ *   and the solve_field that follow move on, and the time step is over behind the solve_field of the second sub-step --
+ *   so the write is refused after each of the first five of the reference's six calls push(1), collect_charge,
+ *   solve_field, push(2), collect_charge, solve_field (the file carries no RK backup for a push(2), and behind the second
+ *   collect_charge the field of the new state is still to be solved).  substep(1) leaves the context inside a time
+ *   step; substep(2), step, a particle load, an upload and checkpoint_read leave it between two.
+ *   What collect_charge left to the next solve_field is settled first.  The markers cross in chunks through
  *   the context's pinned staging; the file appears under its name only when it is complete.
  *   Afterwards everything the file does NOT carry -- the one-pass prediction, the predicted half-step field, cached
  *   diagnostics, the accumulator sets, the call sites' state -- is put into the one defined state that

@@ -650,6 +650,7 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   c->rng_ready = true;
   diag_void_bounds(c);  // (new markers)
   c->cur = 0;
+  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   c->itime = 0;
   c->time = 0.0;
@@ -706,6 +707,7 @@ int pic1dp_hip_particle_load_device(pic1dp_ctx *c, int32_t kind) {
   c->rng_ready = true;
   diag_void_bounds(c);  // (new markers)
   c->cur = 0;
+  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   c->itime = 0;
   c->time = 0.0;
@@ -776,6 +778,7 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
   if (c->plan.nblk == 1) c->blk_np[isp][0] = np;
   c->rng_ready = false;  // the host's loader owns the random stream now
   diag_void_bounds(c);
+  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   return 0;
 }

@@ -125,6 +125,9 @@ int pic1dp_hip_checkpoint_write(pic1dp_ctx *c, const char *path) {
   if (c->charge_pending) return fail(PIC1DP_ERR_STATE, "checkpoint_write: charge_local is waiting for charge_reduced");
   if (lz_of(c->seq) != LZ_CLEAN)
     return fail(PIC1DP_ERR_STATE, "checkpoint_write: a push is noted -- checkpoints are written between time steps only");
+  if (c->call_phase != 0)   // (eager call sites note no push, and behind the second collect_charge nothing is noted either)
+    return fail(PIC1DP_ERR_STATE, "checkpoint_write: call %d of the six of a time step was the last -- checkpoints are written between time steps only",
+                c->call_phase);
   if (c->fused_pending) return fail(PIC1DP_ERR_STATE, "internal: checkpoint_write with a fused solve pending");
   HIP_TRY(hipSetDevice(c->device));
   if (int rc = settle_step_start_field(c)) return rc;

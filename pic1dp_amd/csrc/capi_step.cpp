@@ -532,6 +532,7 @@ int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
   if (nsteps > 0) {  // every step ends with the deposit of the new state
     c->cd_kept_mode_only = false;
     c->cd_version++;
+    c->call_phase = 0;
   }
   Step s = facts_of(c);
   for (int it = 0; it < nsteps; ++it) {
@@ -630,6 +631,7 @@ int pic1dp_host::reset_derived_state(pic1dp_ctx *c) {
   c->cd_version++;
   c->adopt_cd_version = 0;
   c->charge_pending = c->charge_pending_pred = false;
+  c->call_phase = 0;
   for (Species &S : c->sp) S.t2_version = 0;
   for (DiagSpecies &D : c->diag) {
     D.version = 0;
@@ -650,6 +652,18 @@ int pic1dp_host::reset_derived_state(pic1dp_ctx *c) {
   HIP_TRY(hipMemsetAsync(c->d_Eh, 0, sizeof(double) * c->in.nx, c->st));
   HIP_TRY(hipStreamSynchronize(c->st));
   return 0;
+}
+
+// ctx.hpp call_phase: a push opens its sub-step wherever the host stood; a collected charge (collect_charge, charge_reduced)
+// and a solved field move on only from the call they follow in the reference's order -- a second collect_charge or
+// solve_field of the same sub-step stays where it is
+static void call_phase_push(pic1dp_ctx *c, int irk) { c->call_phase = irk == 1 ? 1 : 4; }
+static void call_phase_collect(pic1dp_ctx *c) {
+  if (c->call_phase == 1 || c->call_phase == 4) c->call_phase++;
+}
+static void call_phase_solve(pic1dp_ctx *c) {
+  if (c->call_phase == 2) c->call_phase = 3;
+  else if (c->call_phase == 5) c->call_phase = 0;
 }
 
 // checks only: for the call sites that take part in the lazy scheme themselves
@@ -784,6 +798,7 @@ static int deposit_or_step(pic1dp_ctx *c, const Step &s) {
 int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   CHECK_CTX(c);
   if (int rc = require_loaded_keep_lazy(c)) return rc;
+  call_phase_collect(c);
   const Step s = facts_of(c);
   c->cd_version++;
   // a whole-step kernel run for a noted push is booked under "push particle"
@@ -872,9 +887,16 @@ int pic1dp_hip_set_field_transform(pic1dp_ctx *c, int32_t transform) {
   return 0;
 }
 
+static int solve_field_call(pic1dp_ctx *c);
 int pic1dp_hip_solve_field(pic1dp_ctx *c) {
   CHECK_CTX(c);
   HIP_TRY(hipSetDevice(c->device));
+  if (int rc = solve_field_call(c)) return rc;
+  call_phase_solve(c);   // (only a solve_field that was served moves the record on)
+  return 0;
+}
+
+static int solve_field_call(pic1dp_ctx *c) {
   if (c->seq == Seq::HalfPair) {  // the half-step field is solved already (the pair below): nothing to launch
     if (int rc = set_call_state(c, Seq::HalfPairSolved, Owed::Nothing)) return rc;
     c->cnt.call_pair_skips++;
@@ -919,17 +941,21 @@ int pic1dp_hip_push(pic1dp_ctx *c, int32_t irk) {
   CHECK_CTX(c);
   if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
   if (int rc = require_loaded_keep_lazy(c)) return rc;
-  if (irk == 1 && c->seq == Seq::Clean && lazy_ok(facts_of(c).k, optimize_due_any(c))) return set_seq(c, Seq::Push1);
-  if (irk == 2 && lz_of(c->seq) == LZ_HALF) return set_seq(c, push2_noted(c->seq));
-  if (int rc = materialize(c)) return rc;
-  return enqueue_push(c, irk, false);
+  int rc;
+  if (irk == 1 && c->seq == Seq::Clean && lazy_ok(facts_of(c).k, optimize_due_any(c))) rc = set_seq(c, Seq::Push1);
+  else if (irk == 2 && lz_of(c->seq) == LZ_HALF) rc = set_seq(c, push2_noted(c->seq));
+  else if ((rc = materialize(c)) == 0) rc = enqueue_push(c, irk, false);
+  if (rc == 0) call_phase_push(c, irk);   // (a push that failed has opened nothing)
+  return rc;
 }
 
 int pic1dp_hip_substep(pic1dp_ctx *c, int32_t irk) {
   CHECK_CTX(c);
   if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
   if (int rc = require_loaded(c)) return rc;
-  return substep_impl(c, facts_of(c), irk, false);
+  if (int rc = substep_impl(c, facts_of(c), irk, false)) return rc;
+  c->call_phase = irk == 1 ? 3 : 0;   // (push, collect_charge and solve_field of the sub-step in one)
+  return 0;
 }
 
 int pic1dp_hip_set_step_mode(pic1dp_ctx *c, int32_t mode) {
@@ -1027,6 +1053,7 @@ int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpy(c->d_charge, charge1, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
   c->charge_pending = false;
+  call_phase_collect(c);
   c->cd_version++;
   if (c->charge_pending_pred) {  // what came back are the summed prediction sums
     c->charge_pending_pred = false;
@@ -1066,6 +1093,7 @@ int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *c, const int64_t *limbs) {
   const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
   HIP_TRY(hipMemcpy(c->d_fx, limbs, sizeof(int64_t) * n, hipMemcpyHostToDevice));
   c->charge_pending = false;
+  call_phase_collect(c);
   c->cd_version++;
   HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st));
   if (c->cfg.lazy_calls) return set_owed(c, Owed::SumScale);
@@ -1113,6 +1141,9 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT(!c->e_step_start || (c->seq == Seq::Clean && c->eh_modes == 2));   // (the half-step field: d_Eh / d_mode_h)
   // whole-step path: nothing of a step() is left over between calls
   INVARIANT(!c->fused_pending);
+  // the call record: a noted push lies inside a time step (checkpoint_write goes by the record alone)
+  INVARIANT(c->call_phase >= 0 && c->call_phase <= 5);
+  INVARIANT(lz_of(c->seq) == LZ_CLEAN || c->call_phase != 0);
   INVARIANT(c->fuse_args.on == 0);
   INVARIANT(c->fused_dirty == -1);
   INVARIANT(c->tail_done == 0);

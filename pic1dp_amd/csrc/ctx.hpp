@@ -189,6 +189,10 @@ struct pic1dp_ctx {
   int imerge = 0, iremove = 0, isplit = 0;        // particle_imerge / _iremove / _isplit
   bool loaded = false;
   bool charge_pending = false;  // charge_local ran, waiting for charge_reduced
+  // Where the host stands in the reference's six calls push(1), collect_charge, solve_field, push(2), collect_charge,
+  // solve_field, by the calls alone (eager call sites note no push, and after the second collect_charge nothing is noted
+  // either): 0 between time steps, 1 ... 5 after the first ... fifth call.  Read by checkpoint_write only (capi_step.cpp call_phase_*).
+  int call_phase = 0;
   // field
   double *d_rho_sp = nullptr, *d_charge = nullptr, *d_chargeden = nullptr, *d_E = nullptr;
   // The species accumulators and the six sums of the prediction exist three times (kernels.hpp FusedSolve): d_rho_sp /
