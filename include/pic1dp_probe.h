@@ -64,6 +64,12 @@ int pic1dp_probe_host_diag_div(double lx, int32_t nxo, double vmax, int32_t nvo,
 int pic1dp_probe_host_optimize(int32_t kind, int32_t typeremove, int32_t nx, int32_t nv, int32_t split_ngroup, double threshold,
                                uint64_t seed, int64_t np, int64_t nalloc, int64_t *mismatches, int64_t *np_after);
 
+/* (ix[i], wl[i]) = cell and left weight of position x[i] as the marker kernels' locate gives them, n <= 2^20 host
+ * arrays, for a grid of nx cells over lx.  form 0: x / lx in five operations; form 1: in two operations where the host
+ * proves them for this lx (GridConst::mul2), else five again.  *two_ops: 1 when the run took the two operations. */
+int pic1dp_probe_locate(int32_t device, double lx, int32_t nx, int32_t form, const double *x, int32_t *ix, double *wl, int64_t n,
+                        int32_t *two_ops);
+
 /* y[i] = exp(x[i]) as the marker kernels evaluate it (pexp; host arrays) */
 int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n);
 

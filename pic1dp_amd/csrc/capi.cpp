@@ -339,11 +339,8 @@ static int create_filled(pic1dp_ctx *c) {
   c->blk_np = P.blk_np;
   c->blk_rng.resize(P.nblk);
   c->imerge = P.imerge, c->iremove = P.iremove, c->isplit = P.isplit;
-  c->grid.lx = in.lx;
-  c->grid.dnx = static_cast<double>(nx);
+  c->grid = make_grid_const(in.lx, nx);
   c->grid.dt_full = in.dt;
-  c->grid.nx = nx;
-  c->grid.rlx = 1.0 / in.lx;
   c->grid.gcopies = P.gcopies;
   c->grid.gstride = P.gstride;
   c->sp.resize(ns);

@@ -275,6 +275,16 @@ static int launch_step_species(pic1dp_ctx *c, int s, bool full, const double *E0
       a.eh_im = c->eh_modes == 2 ? c->d_mode_h + 1 : c->fa.mode_im;
     }
     a.plain_chunks = static_cast<int>(L.plain_chunks);
+#ifdef PIC1DP_TUNING
+    a.plain_every = 0;
+    if (const char *e = tuning_env("PIC1DP_PLAIN_ROWS"))
+      if (std::atoi(e) != 0 && a.plain_chunks > 0) {  // the same share of the state as whole rows, evenly through the sweep
+        const int64_t stride = static_cast<int64_t>(L.lc.blocks) * L.lc.threads;
+        const int64_t rows = ((S.np >> 1) + stride - 1) / stride;
+        const int64_t plain_rows = std::max<int64_t>(1, static_cast<int64_t>(a.plain_chunks) * 64 / stride);
+        a.plain_every = static_cast<int>(std::max<int64_t>(1, (rows + plain_rows - 1) / plain_rows));
+      }
+#endif
     if (L.tail && !a.fused.on) wire_tail(c, a.tail, pl.tail_mode);
   }
   if (pl.diag)

@@ -175,9 +175,19 @@ __device__ __forceinline__ double div_lx(double x, const GridConst &g) {
 // subnormals included) any quotient within a few ulp gives s < 2^-490, hence ix = 0 and wl = 1 exactly
 // as the IEEE quotient does; NaN stays NaN and folds to cell 0 below like NaN / lx; |x| > 2^500 would
 // index outside the grid in the reference and folds to cell 0 here either way.
+// TWO = false: an instance that has no scalar registers left for the second form keeps the five operations (k_step_one)
+template <bool TWO = true>
 __device__ __forceinline__ double div_lx_unchecked(double x, const GridConst &g) {
 #if !PIC1DP_FAST_DIV
   return x / g.lx;
+#endif
+#if PIC1DP_TRIMS
+  // Two operations where the host has PROVEN them for this lx (GridConst::mul2; const_mul.cpp decides it exactly from
+  // the continued fraction of 1/lx): q = RN(yh x + RN(yl x)) = RN(x / lx) for every double in the no-underflow range,
+  // and outside it the argument above holds for this form as well (|q| < 2^-490 -> cell 0, wl = 1).  The flag is a
+  // kernel argument: a scalar branch, the same for every wave of a run.
+  if constexpr (TWO)
+    if (g.mul2) return fma(g.rlx, x, g.rlx_lo * x);
 #endif
   const double y = g.rlx;
   const double q0 = x * y;
@@ -186,11 +196,21 @@ __device__ __forceinline__ double div_lx_unchecked(double x, const GridConst &g)
   const double r1 = fma(-g.lx, q1, x);
   return fma(r1, y, q1);
 }
+template <bool TWO = true>
 __device__ __forceinline__ void locate(double x, const GridConst &g, int &ix, double &wl) {
-  const double s = div_lx_unchecked(x, g) * g.dnx;
+  const double s = div_lx_unchecked<TWO>(x, g) * g.dnx;
+#if PIC1DP_TRIMS
+  // Positions reaching locate are >= 0 (or -0, or NaN), hence s >= 0: the conversion truncates to the cell floor(s)
+  // names, and s - floor(s) is exact and IS the hardware's fraction (v_fract_f64; its clamp below 1 only acts on
+  // negative arguments).  -0: cell 0, fraction +0 either way; x = lx: s = nx, fraction 0, folded below; NaN: cell 0 and
+  // wl = NaN either way.  One operation fewer than floor / convert / subtract.
+  ix = static_cast<int>(s);
+  wl = 1.0 - __builtin_amdgcn_fract(s);
+#else
   const double fl = floor(s);
   ix = static_cast<int>(fl);
   wl = 1.0 - (s - fl);
+#endif
   // memory safety only (x + lx may round to lx; NaN): fold to cell 0
   if (static_cast<unsigned>(ix) >= static_cast<unsigned>(g.nx)) ix = 0;
 }
@@ -419,9 +439,12 @@ struct One {
 // src/pic1dp_interaction.F90:261-338.  T2MODE: 0 evaluate tmp2 = -f0'/f0(v); 1 evaluate it and
 // hand it out through t2io; 2 take it from t2io (the whole-step kernels can carry it from the
 // first sub-step's kernel to the second's instead of evaluating it twice, see k_step_half)
+// dtz: dt Z from the host, read by the unit-species instances only (POW2 = 2 implies |Z| = 1, SpeciesConst::zunit): with
+// |Z| = 1 the reference's trailing "* Z" flips a sign or does nothing, a sign passes through every rounding exactly, and
+// RN((-a) b) = -RN(a b) -- so (dt Z) tmp1 tmp2 has the bits of dt tmp1 tmp2 Z, one multiplication fewer (two per push)
 template <int DIST, int MODE, int POW2, int T2MODE, class D>
 __device__ __forceinline__ One push_core(double v, double w, double p, double xb, double vb, double wb, double e,
-                                         double dt, const SpeciesConst &s, D &dv, double *t2io) {
+                                         double dt, const SpeciesConst &s, D &dv, double *t2io, double dtz) {
   One o;
   o.x = xb + dt * v;                     // :261
   o.w = w;
@@ -439,13 +462,19 @@ __device__ __forceinline__ One push_core(double v, double w, double p, double xb
       // division by a general mass may be the product with its reciprocal (one operation instead of five)
       o.w = wb + (dt * tmp1 * tmp2 * s.Z) * s.r_m;
     } else {
-      o.w = wb + divc<POW2>(dt * tmp1 * tmp2 * s.Z, s.m, s.r_m, dv);  // :329
+      if constexpr (POW2 == 2 && PIC1DP_TRIMS != 0)  // |Z| = 1: the trailing factor only sets the sign, dtz = dt Z carries it
+        o.w = wb + dtz * tmp1 * tmp2;
+      else
+        o.w = wb + divc<POW2>(dt * tmp1 * tmp2 * s.Z, s.m, s.r_m, dv);  // :329
     }
   }
   if constexpr (MODE == MODE_DF_LIN) {
     o.v = v;
   } else {
-    o.v = vb + divc<POW2>(dt * e * s.Z, s.m, s.r_m, dv);  // :336
+    if constexpr (POW2 == 2 && PIC1DP_TRIMS != 0)
+      o.v = vb + dtz * e;
+    else
+      o.v = vb + divc<POW2>(dt * e * s.Z, s.m, s.r_m, dv);  // :336
   }
   return o;
 }
@@ -467,24 +496,24 @@ __device__ __forceinline__ double field_at(const ModeField &m, int i) {
   return e;
 }
 
-template <int DIST, int MODE, int POW2, int T2MODE = 0, class FS = const double *>
+template <int DIST, int MODE, int POW2, int T2MODE = 0, bool TWO = true, class FS = const double *>
 __device__ __forceinline__ One push_one(double x, double v, double w, double p, double xb,
-                                        double vb, double wb, const FS &sE, double dt,
+                                        double vb, double wb, const FS &sE, double dt, double dtz,
                                         const GridConst &g, const SpeciesConst &s, double *t2io = nullptr) {
   int ix;
   double wl;
-  locate(x, g, ix, wl);
+  locate<TWO>(x, g, ix, wl);
   double e = field_at(sE, ix) * wl;                // :254
   e = e + field_at(sE, ix + 1) * (1.0 - wl);       // :257 (cell nx holds E[0])
   if constexpr (POW2 == 0) {
     if (s.fastc) {
       DivFast dv;
-      const One o = push_core<DIST, MODE, POW2, T2MODE>(v, w, p, xb, vb, wb, e, dt, s, dv, t2io);
+      const One o = push_core<DIST, MODE, POW2, T2MODE>(v, w, p, xb, vb, wb, e, dt, s, dv, t2io, dtz);
       if (dv.ok()) return o;
     }
   }
   DivTrue dv;
-  return push_core<DIST, MODE, POW2, T2MODE>(v, w, p, xb, vb, wb, e, dt, s, dv, t2io);
+  return push_core<DIST, MODE, POW2, T2MODE>(v, w, p, xb, vb, wb, e, dt, s, dv, t2io, dtz);
 }
 
 // Kind 1 of the charge sum (kernels.hpp FxArgs): the workgroup's LDS tile holds two u64 words per cell, (lo, hi) at
@@ -511,13 +540,13 @@ __device__ __forceinline__ void rho_add(const RhoFx &r, int i, double c) {
 
 // wrap + linear deposit of one marker into the LDS copy of rho (R: double *, or RhoFx in kind 1),
 // src/pic1dp_interaction.F90:102-113; returns the wrapped position
-template <class R>
+template <bool TWO = true, class R>
 __device__ __forceinline__ double deposit_one(double x, double q, const R &sR, const GridConst &g, int *ix_out = nullptr,
                                               double *wl_out = nullptr) {
   const double px = wrap(x, g.lx);
   int ix;
   double wl;
-  locate(px, g, ix, wl);
+  locate<TWO>(px, g, ix, wl);
   if (ix_out) {  // cell and left weight of the wrapped position, for a caller that gathers there next
     *ix_out = ix;
     *wl_out = wl;

@@ -1,8 +1,12 @@
 // hostcheck.cpp -- div_lx's and div_const's algorithm with the host's FMA (libm fma is exact) against the true
 // quotient: create() vouches for a species' divisor constants with host_divc_check before it enables the fast form.
+// Also make_grid_const: the grid constants with the verdict of const_mul_decide -- here because this is the host unit
+// that the product, the probe library and the stand-alone checks (tests/const_mul_check.cpp) all link, and const_mul.cpp
+// stays free of the kernels' header.
 #include <cmath>
 
 #include "check_values.hpp"
+#include "const_mul.hpp"
 #include "kernels.hpp"
 
 namespace pic1dp {
@@ -61,6 +65,22 @@ int64_t host_diag_div_check(double lx, int nxo, double vmax, int nvo, uint64_t s
     if (std::memcmp(&q, &b, 8) != 0) ++bad;
   }
   return bad;
+}
+
+// the grid constants of a context: the reciprocal of lx, and -- where const_mul_decide proves it for this lx -- the
+// low part and the flag of the two-operation quotient (device_math.hpp locate); not proven: five operations
+GridConst make_grid_const(double lx, int nx) {
+  GridConst g{};
+  g.lx = lx;
+  g.dnx = static_cast<double>(nx);
+  g.nx = nx;
+  g.rlx = 1.0 / lx;
+  const ConstMul cm = const_mul_decide(lx);
+  g.mul2 = cm.proven;
+  g.rlx_lo = cm.proven ? cm.lo : 0.0;
+  if (!PIC1DP_TRIMS) g.mul2 = 0;
+  if (const char *e = tuning_env("PIC1DP_MUL2")) g.mul2 = g.mul2 && std::atoi(e) != 0;
+  return g;
 }
 
 // the histogram geometry of output_ptcldist with its two constant divisors prepared (kernels.hpp DistGeom)

@@ -21,6 +21,11 @@ inline const char *tuning_env(const char *name) { return std::getenv(name); }
 #else
 inline const char *tuning_env(const char *) { return nullptr; }
 #endif
+// -DPIC1DP_TRIMS=0 (A/B builds, tools/ab_trims.py): the shared per-marker functions without the result-preserving strength
+// reductions of DESIGN.md 2.1 -- the five-operation x / lx always, locate through floor, the charge as a trailing factor
+#ifndef PIC1DP_TRIMS
+#define PIC1DP_TRIMS 1
+#endif
 #if defined(PIC1DP_TUNE_STAMPS) && !defined(PIC1DP_TUNING)
 #error "-DPIC1DP_TUNE_STAMPS instruments the marker kernels: it belongs to a tuning build (-DPIC1DP_TUNING), never to the product"
 #endif
@@ -41,6 +46,7 @@ struct SpeciesConst {
   double r_m, r_T, r_tm, r_tm2, r_two_tm, r_two_tm2, r_stm, r_stm2;
   int pow2;             // 1: all divisors above are powers of two
   int unit;             // 1: m = T = T2 = 1 (T/m = sqrt(T/m) = 1, 2T/m = 2): divisions vanish
+  int zunit;            // 1: |Z| = 1 -- with unit, the whole-step kernels' unit instances take dt Z from the host (StepArgsDev::dtz_*)
   int fastc;            // 1: a/c by reciprocal + two FMA corrections for all eight divisors (host-verified)
   // one-exp form of -f0'/f0 (device_math.hpp dlnf0_one_exp; iptcldist 2 and 3): L(v) = (fq2 v + fq1) v + fq0 is
   // the log of the ratio of the two Maxwellians, tmp2 = (fm1 v + fm0) + (fd1 v + fd0) tanh(L / 2)
@@ -58,7 +64,10 @@ SpeciesConst make_species_const(const SpeciesInput &in, int species_index);
 struct GridConst {
   double lx, dnx, dt_full;
   double rlx;    // RN(1/lx), for the exact division by the constant lx
+  double rlx_lo; // RN(1/lx - rlx): the low part of the two-operation quotient (const_mul.hpp)
   int nx;
+  int mul2;      // 1: the host has PROVEN fma(rlx, x, RN(rlx_lo x)) = RN(x / lx) for every x (const_mul_decide);
+                 // 0: locate divides in Markstein's five operations
   int gcopies, gstride;  // copies of the species accumulators in memory (power of two) and doubles between them:
                          // workgroup b flushes into copy b % gcopies (fewer atomics per address), the field
                          // kernels add the copies up
@@ -184,6 +193,9 @@ struct DistGeom {
   int vfast;
 };
 DistGeom make_dist_geom(double lx, double vmax, int nxo, int nvo);
+// lx, nx, dnx, rlx and the two-operation quotient's decision (const_mul.hpp) as create() fills them; dt_full and the
+// accumulator copies are the caller's (hostcheck.cpp)
+GridConst make_grid_const(double lx, int nx);
 // scales of the histograms' 64-bit fixed-point sums in a workgroup's LDS copy (device_diag.hpp): plane k (markers, p, w)
 // is summed as RN(term * sc[k]); a |p| / |w| beyond bound[k] makes the pass say so instead (the host repeats it in doubles)
 struct DistScale {
@@ -373,6 +385,7 @@ struct StepArgsDev {
   double *rho;         // this species' charge accumulator
   int64_t np;
   double dt_half, dt_full;
+  double dtz_half, dtz_full;   // dt_half Z, dt_full Z (launch_step): the unit instances' step constants with the charge folded in
   GridConst g;
   SpeciesConst s;
   int nt;              // 1: non-temporal loads/stores (state larger than the Infinity Cache)
@@ -403,6 +416,9 @@ struct StepArgsDev {
   double *fxb;                  // Tiles: [2] device bounds on |q|, |c| of this species, for the tiles' fixed-point sums
   double fx_markers, fx_cap;    // ... the most markers one workgroup of this launch takes, and 2^61 over it (launch_step)
   FxArgs fx;                    // kind 1 of the charge sum (k_step_half / k_step_full<EXACT>): the exact accumulators (acc null: rho)
+#ifdef PIC1DP_TUNING       // tuning build, PIC1DP_PLAIN_ROWS=1 (k_step_one): > 0: every plain_every-th grid-stride row is plain instead
+  int plain_every;          // of the first plain_chunks chunks -- the same share of the state, spread over the launch
+#endif
 #ifdef PIC1DP_TUNE_STAMPS  // tuning build (tools/stamp_probe.sh): [gridDim][8] wall-clock stamps of the phases of a workgroup
   unsigned long long *stamps;
 #endif

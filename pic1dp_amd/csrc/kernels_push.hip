@@ -53,8 +53,8 @@ __global__ void __launch_bounds__(1024) k_push(const PushArgs a) {
       if constexpr (PUSH_V) VB = ld2(bv2 + o);
       if constexpr (HAS_W) WB = ld2(bw2 + o);
     }
-    One o0 = push_one<DIST, MODE, POW2>(X.x, V.x, W.x, P.x, XB.x, VB.x, WB.x, sE, a.dt, a.g, a.s);
-    One o1 = push_one<DIST, MODE, POW2>(X.y, V.y, W.y, P.y, XB.y, VB.y, WB.y, sE, a.dt, a.g, a.s);
+    One o0 = push_one<DIST, MODE, POW2>(X.x, V.x, W.x, P.x, XB.x, VB.x, WB.x, sE, a.dt, a.dt * a.s.Z, a.g, a.s);
+    One o1 = push_one<DIST, MODE, POW2>(X.y, V.y, W.y, P.y, XB.y, VB.y, WB.y, sE, a.dt, a.dt * a.s.Z, a.g, a.s);
     if constexpr (FUSED) {
       o0.x = deposit_one(o0.x, HAS_W ? o0.w : P.x, sR, a.g);
       o1.x = deposit_one(o1.x, HAS_W ? o1.w : P.y, sR, a.g);
@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(1024) k_push(const PushArgs a) {
       if constexpr (PUSH_V) vb = a.base.v[i];
       if constexpr (HAS_W) wb = a.base.w[i];
     }
-    One o = push_one<DIST, MODE, POW2>(x, v, w, p, xb, vb, wb, sE, a.dt, a.g, a.s);
+    One o = push_one<DIST, MODE, POW2>(x, v, w, p, xb, vb, wb, sE, a.dt, a.dt * a.s.Z, a.g, a.s);
     if constexpr (FUSED) o.x = deposit_one(o.x, HAS_W ? o.w : p, sR, a.g);
     a.dst.x[i] = o.x;
     if constexpr (PUSH_V) a.dst.v[i] = o.v;

@@ -123,10 +123,10 @@ __global__ void __launch_bounds__(1024) k_step_half(const StepArgsDev a) {
     double2 W = make_double2(0.0, 0.0);
     if constexpr (HAS_W) W = ld2t<NT>(w2 + o);
     double t0 = 0.0, t1 = 0.0;
-    const One h0 = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(X.x, V.x, W.x, P.x, X.x, V.x, W.x, sE, a.dt_half, a.g, a.s, &t0);
+    const One h0 = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(X.x, V.x, W.x, P.x, X.x, V.x, W.x, sE, a.dt_half, a.dtz_half, a.g, a.s, &t0);
     deposit_one(h0.x, HAS_W ? h0.w : P.x, sR, a.g);
     PAIR_FENCE();
-    const One h1 = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(X.y, V.y, W.y, P.y, X.y, V.y, W.y, sE, a.dt_half, a.g, a.s, &t1);
+    const One h1 = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(X.y, V.y, W.y, P.y, X.y, V.y, W.y, sE, a.dt_half, a.dtz_half, a.g, a.s, &t1);
     deposit_one(h1.x, HAS_W ? h1.w : P.y, sR, a.g);
     if constexpr (CARRY) st2t<NT>(reinterpret_cast<double2 *>(a.t2) + j, t0, t1);
   }
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(1024) k_step_half(const StepArgsDev a) {
     const double x = a.x[i], v = a.v[i], p = a.p[i];
     const double w = HAS_W ? a.w[i] : 0.0;
     double t0 = 0.0;
-    const One h = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(x, v, w, p, x, v, w, sE, a.dt_half, a.g, a.s, &t0);
+    const One h = push_one<DIST, MODE, POW2, CARRY ? 1 : 0>(x, v, w, p, x, v, w, sE, a.dt_half, a.dtz_half, a.g, a.s, &t0);
     if constexpr (CARRY) a.t2[a.np - 1] = t0;
     deposit_one(h.x, HAS_W ? h.w : p, sR, a.g);
   }
@@ -147,17 +147,17 @@ __global__ void __launch_bounds__(1024) k_step_half(const StepArgsDev a) {
 }
 
 // one marker through the second half of the time step
-template <int DIST, int MODE, int POW2, bool CARRY = false, class FH = const double *, class R = double *>
+template <int DIST, int MODE, int POW2, bool CARRY = false, bool TWO = true, class FH = const double *, class R = double *>
 __device__ __forceinline__ One step_full_one(double x, double v, double w, double p, const double *sE0,
                                              const FH &sEh, const R &sR, const StepArgsDev &a, double t2 = 0.0,
                                              int *ix_out = nullptr, double *wl_out = nullptr) {
   constexpr bool HAS_W = (MODE != MODE_FULLF);
   // sub-step 1 again (identical arithmetic), with the wrap the deposit applied
-  One h = push_one<DIST, MODE, POW2, CARRY ? 2 : 0>(x, v, w, p, x, v, w, sE0, a.dt_half, a.g, a.s, &t2);
+  One h = push_one<DIST, MODE, POW2, CARRY ? 2 : 0, TWO>(x, v, w, p, x, v, w, sE0, a.dt_half, a.dtz_half, a.g, a.s, &t2);
   h.x = wrap(h.x, a.g.lx);
   // sub-step 2: derivatives at the half-step state, base = step-start state
-  One n = push_one<DIST, MODE, POW2>(h.x, h.v, h.w, p, x, v, w, sEh, a.dt_full, a.g, a.s);
-  n.x = deposit_one(n.x, HAS_W ? n.w : p, sR, a.g, ix_out, wl_out);
+  One n = push_one<DIST, MODE, POW2, 0, TWO>(h.x, h.v, h.w, p, x, v, w, sEh, a.dt_full, a.dtz_full, a.g, a.s);
+  n.x = deposit_one<TWO>(n.x, HAS_W ? n.w : p, sR, a.g, ix_out, wl_out);
   return n;
 }
 
@@ -630,7 +630,9 @@ __device__ __forceinline__ double pred_one_private(const One &n, double p, int i
   const double *hl = sAB + 2 * ih;                // [A B] of cell ih, then of cell ih + 1 (cell nx: the guard, = cell 0)
   const double2 ul = *reinterpret_cast<const double2 *>(hl), ur = *reinterpret_cast<const double2 *>(hl + 2);
   const double Ah = fma(ur.x, wr, ul.x * wh), Bh = fma(ur.y, wr, ul.y * wh);  // projection weights of the deposit at x'
-  const double q = a.s.Z * (MODE == MODE_FULLF ? p : n.w);
+  // (a unit species, |Z| = 1: the sign is applied ONCE to the workgroup's sums 0 and 3 instead, k_step_one's reduction --
+  // every term and every partial sum changes its sign with Z and nothing else, the same bits)
+  const double q = (POW2 == 2 && PIC1DP_TRIMS != 0 ? 1.0 : a.s.Z) * (MODE == MODE_FULLF ? p : n.w);
   lds_add(sS, q * Ah);
   lds_add(sS + 3 * stride, q * Bh);
   if constexpr (MODE != MODE_FULLF) {
@@ -765,6 +767,10 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
   constexpr bool PUSH_V = (MODE != MODE_DF_LIN);
   constexpr bool CARRY_IN = (T2 == 2) && HAS_W;
   constexpr bool CARRY_OUT = (T2 != 0) && HAS_W;
+  // x / lx in two operations where the host proves them (device_math.hpp) -- except in the private-sum instances of a
+  // power-of-two species: they sit at the scalar-register limit, and the second form's flag and low part cost the one-exp
+  // unit two vector registers in scratch.  They keep the five operations: the same bits.
+  constexpr bool TWO_OPS = !(PRIV && POW2 == 1);
   const int64_t npair = a.np >> 1;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   double2 *x2 = reinterpret_cast<double2 *>(a.x);
@@ -786,6 +792,9 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
     drawn_total = drawn_rows * static_cast<int>(blockDim.x >> 6);
   }
   int64_t j = first + threadIdx.x;
+#ifdef PIC1DP_TUNING
+  int row = 0;
+#endif
   for (int k = 0;; ++k, j += stride) {
     if (k >= dealt) {
       int c = 0;
@@ -794,10 +803,20 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
       if (c >= drawn_total) break;
       const int waves = static_cast<int>(blockDim.x >> 6);
       j = first + static_cast<int64_t>(dealt + c / waves) * stride + (c % waves) * 64 + (threadIdx.x & 63);
+#ifdef PIC1DP_TUNING
+      row = dealt + c / waves;
+#endif
     }
     if (j >= npair) continue;
     const int64_t o = tidx2(j);
+#ifdef PIC1DP_TUNING
+    // PIC1DP_PLAIN_ROWS=1 (measured and kept out of the product): the cached share as every m-th grid-stride
+    // ROW -- the gridDim blockDim pairs all workgroups take together -- instead of the slab's head
+    if (k < dealt) row = k;
+    const bool plain = NT && a.plain_every > 0 ? row % a.plain_every == 0 : chunk_plain<NT>(j, a);
+#else
     const bool plain = chunk_plain<NT>(j, a);
+#endif
     double2 X, V, P, W = make_double2(0.0, 0.0), T = make_double2(0.0, 0.0);
     ld_marker_rows<NT, HAS_W>(plain, x2, v2, w2, p2, o, X, V, W, P);
     if constexpr (CARRY_IN) T = ld2t<NT>(t2 + j);
@@ -805,14 +824,14 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
     double l0, l1;
     // the two markers of a pair one after the other (PAIR_FENCE): interleaving their four exp chains
     // costs more registers than six waves per SIMD leave
-    const One n0 = step_full_one<DIST, MODE, POW2, CARRY_IN>(X.x, V.x, W.x, P.x, sE0, sEh, sR, a, T.x, &i0, &l0);
+    const One n0 = step_full_one<DIST, MODE, POW2, CARRY_IN, TWO_OPS>(X.x, V.x, W.x, P.x, sE0, sEh, sR, a, T.x, &i0, &l0);
     double u0, u1;
     if constexpr (PRIV)
       u0 = priv_sums<DIST, MODE, POW2, NM>(n0, P.x, i0, l0, sAB, sP + threadIdx.x, a);
     else
       u0 = pred_one<DIST, MODE, POW2, NM>(n0, P.x, i0, l0, sAB, sP, a, fx);
     PAIR_FENCE();
-    const One n1 = step_full_one<DIST, MODE, POW2, CARRY_IN>(X.y, V.y, W.y, P.y, sE0, sEh, sR, a, T.y, &i1, &l1);
+    const One n1 = step_full_one<DIST, MODE, POW2, CARRY_IN, TWO_OPS>(X.y, V.y, W.y, P.y, sE0, sEh, sR, a, T.y, &i1, &l1);
     if constexpr (PRIV)
       u1 = priv_sums<DIST, MODE, POW2, NM>(n1, P.y, i1, l1, sAB, sP + threadIdx.x, a);
     else
@@ -825,7 +844,7 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
     const double w = HAS_W ? a.w[i] : 0.0, p = a.p[i];
     int ic;
     double lc;
-    const One n = step_full_one<DIST, MODE, POW2, CARRY_IN>(a.x[i], a.v[i], w, p, sE0, sEh, sR, a,
+    const One n = step_full_one<DIST, MODE, POW2, CARRY_IN, TWO_OPS>(a.x[i], a.v[i], w, p, sE0, sEh, sR, a,
                                                             CARRY_IN ? a.t2[a.np - 1] : 0.0, &ic, &lc);
     a.x[i] = n.x;
     if constexpr (PUSH_V) a.v[i] = n.v;
@@ -855,6 +874,8 @@ __global__ void __launch_bounds__(1024) PIC1DP_SIX_WAVES k_step_one(const StepAr
 #pragma unroll
       for (int j = 0; j < PRIV_THREADS / 64; ++j) t += s[64 * j];
       for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+      if constexpr (POW2 == 2 && PIC1DP_TRIMS != 0)   // the charge of a unit species (pred_one_private): sums 0 and 3 carry q = Z w
+        if (wave == 0 || wave == 3) t *= a.s.Z;
       if (lane == 0) glb_add(a.pred + (blockIdx.x % PRED_SUM_COPIES) * 8 + wave, t);
     }
     STAMP(a, 5);
@@ -1245,7 +1266,9 @@ hipError_t launch_step_d(const StepArgs &a, bool full, const LaunchCfg &lc, hipS
     return pow2 ? launch_step_dmp<DIST, MODE_DF_LIN, 1>(a, full, lc, st)
                 : launch_step_dmp<DIST, MODE_DF_LIN, 0>(a, full, lc, st);
   }
-  if (d.s.unit) return launch_step_dmp<DIST, MODE_DF_NL, 2>(a, full, lc, st);
+  // (the unit instances fold the charge into the step constants: |Z| = 1 as well; a unit species of another charge takes the
+  // power-of-two instances, the same bits -- every a * (1/c) there is a * 1 or a * 0.5)
+  if (d.s.unit && (d.s.zunit || !PIC1DP_TRIMS)) return launch_step_dmp<DIST, MODE_DF_NL, 2>(a, full, lc, st);
   if constexpr (DIST == 2 || DIST == 3)
     if (carry) return launch_step_dmp<DIST, MODE_DF_NL, 0, true>(a, full, lc, st);
   return pow2 ? launch_step_dmp<DIST, MODE_DF_NL, 1>(a, full, lc, st)

@@ -263,6 +263,18 @@ __global__ void k_fx_raise_events(double *bound, const unsigned *noted, const do
   for (int64_t i = 0; i < n; ++i) fx_raise(bound, noted[i], start[i]);
 }
 
+// locate on its own, as every marker kernel calls it: cell and left weight of n positions
+__global__ void __launch_bounds__(256) k_locate_array(const GridConst g, const double *x, int32_t *ix, double *wl, int64_t n) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    int c;
+    double l;
+    locate(x[i], g, c, l);
+    ix[i] = c;
+    wl[i] = l;
+  }
+}
+
 // the push's transcendental on its own (tests bound it against libm)
 __global__ void __launch_bounds__(256) k_exp_array(const double *x, double *y, int64_t n) {
   exp_table_init();
@@ -620,6 +632,29 @@ int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n) {
   PROBE_TRY(launch_exp_array(dx, dx + n, n, nullptr));
   PROBE_TRY(hipDeviceSynchronize());
   PROBE_TRY(hipMemcpy(y, dx + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pic1dp_probe_locate(int32_t device, double lx, int32_t nx, int32_t form, const double *x, int32_t *ix, double *wl, int64_t n,
+                        int32_t *two_ops) {
+  if (!x || !ix || !wl || !two_ops || n < 0 || n > (1ll << 20) || !(lx > 0.0) || nx < 1 || form < 0 || form > 1)
+    return pfail("bad argument");
+  GridConst g = make_grid_const(lx, nx);
+  if (form == 0) g.mul2 = 0;   // the five operations whatever the host has proven
+  *two_ops = g.mul2;
+  if (n == 0) return 0;
+  PROBE_TRY(hipSetDevice(device));
+  DevBuf d;
+  PROBE_TRY(hipMalloc(&d.p, (2 * sizeof(double) + sizeof(int32_t)) * static_cast<size_t>(n)));
+  double *dx = static_cast<double *>(d.p), *dw = dx + n;
+  int32_t *di = reinterpret_cast<int32_t *>(dw + n);
+  PROBE_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  const int blocks = static_cast<int>(std::min<int64_t>(1024, (n + 255) / 256));
+  hipLaunchKernelGGL(k_locate_array, dim3(blocks), dim3(256), 0, nullptr, g, dx, di, dw, n);
+  PROBE_TRY(hipGetLastError());
+  PROBE_TRY(hipDeviceSynchronize());
+  PROBE_TRY(hipMemcpy(ix, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(wl, dw, sizeof(double) * n, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -10,6 +10,8 @@ hipError_t launch_step(StepArgs a, bool full, const LaunchCfg &lc, hipStream_t s
   StepArgsDev &d = a.d;
   d.snx = d.g.dnx / d.g.lx;
   d.pred_k = d.dt_half * d.s.Z / d.s.m;
+  d.dtz_half = d.dt_half * d.s.Z;
+  d.dtz_full = d.dt_full * d.s.Z;
   {  // rows of pairs a workgroup takes (static grid stride; the drawn chunks are its own rows), two markers a pair
     const int64_t npair = d.np >> 1, stride = static_cast<int64_t>(lc.blocks) * lc.threads;
     // (at least 4096: a term times its scale then stays below 2^49, inside the 2^51 the conversion's magic number covers)

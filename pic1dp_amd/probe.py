@@ -60,6 +60,7 @@ SIGNATURES = {
     "pic1dp_probe_host_diag_div": [C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_uint64, _I64],
     "pic1dp_probe_host_optimize": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_int64,
                                    C.c_int64, _I64, _I64],
+    "pic1dp_probe_locate": [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _I32],
     "pic1dp_probe_exp": [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64],
     "pic1dp_probe_fx_raise": [C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, _D],
     "pic1dp_probe_species_const": [_SP, _I32, _I32, _I32, _I32, _D],
@@ -178,6 +179,18 @@ def div_const_mismatches(divisor, n, seed, device=0, host=False):
     else:
         _check(L.pic1dp_probe_div_const(device, divisor, n, seed, C.byref(m)))
     return m.value
+
+
+def locate(x, lx, nx, form, device=0):
+    """(ix, wl, two_ops): the marker kernels' locate on the positions x (at most 2^20); form 0 divides by lx in five
+    operations, form 1 in two where the host proves them for lx (two_ops tells)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    ix = np.empty(x.size, dtype=np.int32)
+    wl = np.empty(x.size, dtype=np.float64)
+    two = C.c_int32(-1)
+    _check(load().pic1dp_probe_locate(device, float(lx), int(nx), int(form), x.ctypes.data_as(C.c_void_p),
+                                      ix.ctypes.data_as(C.c_void_p), wl.ctypes.data_as(C.c_void_p), x.size, C.byref(two)))
+    return ix, wl, two.value
 
 
 def device_exp(x, device=0):
