@@ -812,6 +812,80 @@ int pic1dp_hip_host_select(const pic1dp_input *in, const pic1dp_select *sel, con
                            int64_t max, int64_t *count, int64_t *index);          /* host only, no device */
 int pic1dp_hip_select_thin(double fraction, uint64_t *thin);                      /* host only */
 
+/* ---- exact phase-space histogram on a caller-chosen window and grid ----------------------
+ * pic1dp_hip_zoom counts the markers of one species, and sums their p and w, on a cell-centred grid of nxb x nvb cells laid
+ * over a window of (wrapped x, v) the caller chooses -- the picture pic1dp_hip_ptcldist draws on the input's fixed grid,
+ * zoomed to where the physics is.  There is one kind only: exact.  A term is the marker's own p or w (no interpolation
+ * weight), rounded once to whole quanta and summed as integers, so the result does not depend on launch shape, marker order,
+ * the number of passes or the split over ranks. */
+typedef struct pic1dp_zoom {
+  double x_lo, x_hi;     /* window in the WRAPPED position px; x_lo > x_hi straddles the periodic boundary */
+  double v_lo, v_hi;     /* window in v, v_lo < v_hi */
+  int32_t nxb, nvb;      /* cells across the window */
+} pic1dp_zoom;
+/* which is a mask: 1 markr (the count of markers), 2 total (sum p), 4 pertb (sum w); the selected planes come in that order.
+ * The rule.  It applies to every valid marker i < np of the species, on the state a pic1dp_hip_particles_download at that
+ * moment would return.  Every operation is one IEEE operation; none of them has the shape of an FMA.
+ *     px   = wrap(x)                                   the deposit's wrap, exactly as pic1dp_hip_select uses it; not stored back
+ *     in_x = x_lo <= px && px < x_hi                   when x_lo <= x_hi
+ *     in_x = px >= x_lo || px < x_hi                   when x_lo >  x_hi
+ *     in_v = v_lo <= v && v < v_hi
+ *     Lw   = x_hi - x_lo            (x_lo <= x_hi)     Lw = (x_hi + lx) - x_lo    (x_lo > x_hi)          host, once
+ *     sx   = (double)nxb / Lw       sv = (double)nvb / (v_hi - v_lo)                                     host, once
+ *     d    = px - x_lo;  if (d < 0) d = d + lx
+ *     ix   = (int)(d * sx);         if (ix > nxb - 1) ix = nxb - 1
+ *     jv   = (int)((v - v_lo) * sv); if (jv > nvb - 1) jv = nvb - 1
+ *     cell = jv * nxb + ix
+ *   - A marker with in_x && in_v adds terms to its cell: 1 to markr, p to total, w to pertb.  A marker outside the window
+ *     adds nothing.  A NaN px or v is never inside the window.  Tail slots (i >= np) do not count.
+ *   - The clamp is reachable at the upper edge of either axis (the product may round up to nxb or nvb just below the bound);
+ *     the overshoot is one cell.  An inside marker never gives a negative index: d and v - v_lo are not negative.
+ * Argument checks (PIC1DP_ERR_ARG, nothing written): the bounds finite, 0 <= x_lo, x_hi <= lx, v_lo < v_hi (stricter than
+ *   pic1dp_hip_select: a grid needs a finite extent); v_hi - v_lo, sx and sv finite (so the window x_lo = lx, x_hi = 0, whose
+ *   extent is zero although px == lx would lie in it, is refused); 1 <= nxb, nvb <= 4096 and
+ *   nxb * nvb <= 2^20; which in 1..7; which & 4 on a full-f context or input (deltaf = 0); an unknown species; a null
+ *   pointer.  x_lo == x_hi is legal and is the empty window: all zeros, and no marker is read.
+ * Sums.  markr is a plain integer count: its quantum is one.  A term t of total or pertb becomes n = rint(t 2^-e), e =
+ *   pic1dp_hip_diag_quanta's entry 1 (total) or 2 (pertb) of the species, kb - 40, from the input alone -- what
+ *   pic1dp_hip_diag_quantise(t, e, 0, &n) hands out.  A term of 2^44 quanta or more, or a NaN, is not summed but counted,
+ *   per plane: the call returns PIC1DP_ERR_ARG naming the species, the plane and the count, nothing is written to the
+ *   caller's buffer, and the next call starts from zero counters.  Each plane judges its own term: a marker whose p is
+ *   rejected still counts in markr.  The integers are summed exactly -- in a workgroup's LDS, across workgroups, across
+ *   passes, and by the host across ranks.
+ * Limbs: limbs[((j * 2 + h) * nvb + jv) * nxb + ix], j counting the selected planes, h = 0 the hi limb, h = 1 the lo limb;
+ *   a cell's total is hi * 2^32 + lo quanta.  pic1dp_hip_zoom_local_exact hands out normalised limbs (0 <= lo < 2^32), so
+ *   the limbs are fixed by the markers; pic1dp_hip_zoom_convert accepts element-wise sums over ranks as they are.
+ *   out[(j * nvb + jv) * nxb + ix] is the total converted to double once (round to nearest even) times 2^e.  The sums are
+ *   raw and local to the context: no communicator is used, and there are no bin widths -- dividing by
+ *   (Lw / nxb) * ((v_hi - v_lo) / nvb) gives a density, which is the caller's line, as with pic1dp_hip_power.
+ * pic1dp_hip_zoom_len / _zoom_limbs_len: nplanes * nxb * nvb doubles of out / twice as many limbs.  Host only.
+ * pic1dp_hip_host_zoom: the rule and the sums on HOST arrays of np valid markers (p read where which & 2, w where which & 4):
+ *   the normalised limbs of the terms summed, and rejected[3], the terms not summed per plane markr, total, pertb (it
+ *   returns 0 with them counted: the caller sees both).  Host only, no device, no context.
+ * pic1dp_hip_zoom_stats: the passes that swept markers so far, their device milliseconds while kernel stats were enabled,
+ *   and the terms not summed so far (pic1dp_hip_kernel_stats keeps its rows 0..22).
+ * When the call may come.  The rule of pic1dp_hip_moments.  Between time steps it launches its own passes and nothing else
+ *   and changes nothing: markers, fields, the one-pass prediction, a pending fused solve, cached diagnostics and the state
+ *   digest survive.  Inside a time step (a push noted) the noted push becomes memory first.  pic1dp_hip_set_diag_sum and
+ *   pic1dp_hip_set_charge_sum do not affect it, and the checkpoint carries nothing of it.
+ * Memory.  The device rows (16 B per plane and cell: up to 6 x 8 MiB) and the three counters live for the call only, as
+ *   pic1dp_hip_select's buffers do: the context's standing allocation does not grow.  An allocation that fails is
+ *   PIC1DP_ERR_NOMEM.  The transfer to the host goes through the context's pinned staging in slices of at most 32 MiB.
+ * Cost.  Planes of up to 19 200 words (150 KiB of a workgroup's LDS; 64 x 64 x 3 fits) take one pass over x, v and the
+ *   weights asked for.  A larger grid is cut into bands of whole v rows, one pass each, whose per-marker test begins with
+ *   v: a pass over a band the marker is not in costs its loads, two compares and a product.  Beyond the plan's pass cap
+ *    one pass adds every term straight into the global rows with two 64-bit atomics. */
+int pic1dp_hip_zoom_len(const pic1dp_zoom *z, int32_t which, int64_t *n);        /* host only: nplanes * nxb * nvb     */
+int pic1dp_hip_zoom_limbs_len(const pic1dp_zoom *z, int32_t which, int64_t *n);  /* host only: 2 * nplanes * nxb * nvb */
+int pic1dp_hip_zoom_local_exact(pic1dp_ctx *ctx, int32_t ispecies, const pic1dp_zoom *z, int32_t which, int64_t *limbs);
+int pic1dp_hip_zoom_convert(const pic1dp_input *in, int32_t ispecies, const pic1dp_zoom *z, int32_t which,
+                            const int64_t *limbs, double *out);                  /* host only */
+int pic1dp_hip_zoom(pic1dp_ctx *ctx, int32_t ispecies, const pic1dp_zoom *z, int32_t which, double *out);
+int pic1dp_hip_host_zoom(const pic1dp_input *in, int32_t ispecies, const pic1dp_zoom *z, int32_t which, const double *x,
+                         const double *v, const double *p, const double *w, int64_t np, int64_t *limbs,
+                         int64_t rejected[3]);                                   /* host only: the rule on HOST arrays */
+int pic1dp_hip_zoom_stats(pic1dp_ctx *ctx, double *ms, int64_t *passes, int64_t *rejected);
+
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
   int32_t format_version;

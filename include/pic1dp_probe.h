@@ -147,6 +147,14 @@ int pic1dp_probe_host_power_plan(int32_t nx, int32_t nx_opd, int32_t nv_opd, int
 int pic1dp_probe_host_power_plan_exact(int32_t nx, int32_t nx_opd, int32_t nv_opd, int32_t which, int32_t deltaf, int64_t np,
                                        int32_t num_cu, int64_t out[20]);
 
+/* The passes of one pic1dp_hip_zoom call (launch_policy.hpp zoom_plan), on the HOST: out[0] = passes (0: arguments out of
+ * range, pertb asked of a full-f run), out[1] = planes selected, out[2] = the library's pass cap (kZoomPassCap), then per
+ * pass i eight words at out[3 + 8 i]: {blocks, threads, non-temporal loads, dynamic LDS bytes, the planes' mask, band in LDS
+ * (1) or every row straight in memory (0), first v row, rows}.  pass_cap <= 0: the library's.  out holds 3 + 8 * 64 words.
+ * Nonzero: null argument. */
+int pic1dp_probe_host_zoom_plan(int32_t nxb, int32_t nvb, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
+                                int32_t pass_cap, int64_t out[515]);
+
 /* The count and write passes of a selection over np valid markers (launch_policy.hpp select_plan), on the HOST: out = {pairs
  * of a chunk, chunks, workgroups, threads, non-temporal loads, threads of the prefix sum's one workgroup}.  Chunk c holds the
  * logical pairs [c * pairs, min((c + 1) * pairs, np / 2)), and the odd last marker (np odd) belongs to the last chunk; np = 0:

@@ -82,6 +82,12 @@ class Select(C.Structure):
                 ("thin", C.c_uint64), ("key", C.c_uint64), ("origin", C.c_int64)]
 
 
+class Zoom(C.Structure):
+    """struct pic1dp_zoom: a window of (wrapped x, v) and the cells across it"""
+    _fields_ = [("x_lo", C.c_double), ("x_hi", C.c_double), ("v_lo", C.c_double), ("v_hi", C.c_double),
+                ("nxb", C.c_int32), ("nvb", C.c_int32)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _INP = C.POINTER(Input)
@@ -192,6 +198,13 @@ SIGNATURES = {
     "pic1dp_hip_gather": [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P],
     "pic1dp_hip_host_select": [_INP, C.POINTER(Select), _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _P],
     "pic1dp_hip_select_thin": [C.c_double, C.POINTER(C.c_uint64)],
+    "pic1dp_hip_zoom_len": [C.POINTER(Zoom), C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_zoom_limbs_len": [C.POINTER(Zoom), C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_zoom_local_exact": [_P, C.c_int32, C.POINTER(Zoom), C.c_int32, _P],
+    "pic1dp_hip_zoom_convert": [_INP, C.c_int32, C.POINTER(Zoom), C.c_int32, _P, _P],
+    "pic1dp_hip_zoom": [_P, C.c_int32, C.POINTER(Zoom), C.c_int32, _P],
+    "pic1dp_hip_host_zoom": [_INP, C.c_int32, C.POINTER(Zoom), C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P],
+    "pic1dp_hip_zoom_stats": [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

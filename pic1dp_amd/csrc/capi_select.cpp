@@ -2,7 +2,8 @@
 // _select, _gather): passes of their own in the mould of capi_products.cpp, which cache nothing and change
 // nothing.  Every device buffer of a call -- the chunk counts, the result, a gather's indices -- is taken from the context's
 // owner and given back before the call returns; results cross to the host through the context's pinned staging in slices.
-// The rule on the host and the thinning threshold are select_host.cpp's.
+// The rule on the host and the thinning threshold are select_host.cpp's; the call's buffers and the sliced transfer (CallBuf,
+// words_to_host) are ctx.hpp's, shared with capi_zoom.cpp.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -10,43 +11,6 @@
 
 namespace {
 
-constexpr int64_t kSliceWords = static_cast<int64_t>(4) << 20;  // 32 MiB of pinned staging per transfer, as the checkpoint's
-
-// a device buffer that lives for one call
-template <class T>
-struct CallBuf {
-  DeviceMem &mem;
-  T *p = nullptr;
-  explicit CallBuf(DeviceMem &m) : mem(m) {}
-  CallBuf(const CallBuf &) = delete;
-  CallBuf &operator=(const CallBuf &) = delete;
-  ~CallBuf() {
-    if (p) mem.release(&p);
-  }
-  // 0, or PIC1DP_ERR_NOMEM / PIC1DP_ERR_HIP with the message set
-  int take(size_t n, const char *who, const char *what) {
-    const hipError_t e = mem.alloc(&p, n);
-    if (e == hipSuccess) return 0;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
-      return fail(PIC1DP_ERR_NOMEM, "%s: no device memory for %s (%zu bytes)", who, what, n * sizeof(T));
-    return fail(PIC1DP_ERR_HIP, "%s: allocating %s failed: %s", who, what, hipGetErrorString(e));
-  }
-};
-
-// n 8-byte words from the device to the host through the pinned staging, slice by slice
-int words_to_host(pic1dp_ctx *c, void *host, const void *dev, int64_t n) {
-  if (n <= 0 || !host) return 0;
-  double *h = nullptr;
-  if (int rc = pinned(c, static_cast<size_t>(std::min(n, kSliceWords)), &h)) return rc;
-  for (int64_t done = 0; done < n; done += kSliceWords) {
-    const int64_t m = std::min(kSliceWords, n - done);
-    HIP_TRY(hipMemcpyAsync(h, static_cast<const double *>(dev) + done, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    std::memcpy(static_cast<double *>(host) + done, h, sizeof(double) * m);
-  }
-  return 0;
-}
 // ... and from the host to the device
 int words_to_device(pic1dp_ctx *c, void *dev, const void *host, int64_t n) {
   if (n <= 0) return 0;

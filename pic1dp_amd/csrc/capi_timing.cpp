@@ -166,6 +166,16 @@ int pic1dp_hip_power_exact_stats(pic1dp_ctx *c, double *ms, int64_t *passes, int
   return 0;
 }
 
+// ... and so are the zoom's
+int pic1dp_hip_zoom_stats(pic1dp_ctx *c, double *ms, int64_t *passes, int64_t *rejected) {
+  CHECK_CTX(c);
+  if (int rc = ev_resolve(c->tm)) return rc;
+  if (ms) *ms = c->tm.acc_ms[kTagZoom];
+  if (passes) *passes = c->cnt.zoom_passes;
+  if (rejected) *rejected = c->cnt.zoom_rejected;
+  return 0;
+}
+
 int pic1dp_hip_kernel_bytes(pic1dp_ctx *c, int32_t which, double *read_bytes, double *written_bytes, double *carry_bytes,
                             char *name, int32_t name_len) {
   CHECK_CTX(c);

@@ -13,11 +13,13 @@
 //   capi_products.cpp  read-only marker products on demand (pic1dp_hip_moments, _moments_exact, _power); what they share with select and gather
 //   capi_select.cpp    select and gather markers on the device (pic1dp_hip_select_count, _select, _gather); the rule on the
 //                      host and the thinning threshold: select_host.cpp (select_rule.hpp; no HIP call)
+//   capi_zoom.cpp      the exact phase-space histogram on a caller's window and grid (pic1dp_hip_zoom; its host arithmetic: zoom_fx.cpp, no HIP call)
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
 //   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -148,7 +150,7 @@ struct DiagSpecies {
   double max_p = 0.0, max_w = 0.0;    // max |p|, |w| as the last pass saw them: the next pass's scales (0: unknown -- doubles)
 };
 
-// what the context counts for pic1dp_hip_kernel_stats (capi_timing.cpp: the table's rows name these members) and pic1dp_hip_power_exact_stats; nothing reads them to decide
+// what the context counts for pic1dp_hip_kernel_stats (capi_timing.cpp: the table's rows name these members), pic1dp_hip_power_exact_stats and pic1dp_hip_zoom_stats; nothing reads them to decide
 struct Counters {
   int64_t diag_passes = 0;                 // separate k_ptcldist passes launched so far (kernel_stats 5)
   int64_t fused_solves = 0;                // marker launches whose prologue solved the previous step's field (7)
@@ -166,6 +168,8 @@ struct Counters {
   int64_t gather_launches = 0;             // k_gather launches so far (22)
   int64_t power_exact_passes = 0;          // k_power_exact passes that swept markers so far (pic1dp_hip_power_exact_stats)
   int64_t power_exact_rejected = 0;        // terms they did not sum so far (the same)
+  int64_t zoom_passes = 0;                 // k_zoom passes that swept markers so far (pic1dp_hip_zoom_stats)
+  int64_t zoom_rejected = 0;               // terms they did not sum so far (the same)
 };
 
 }  // namespace pic1dp_host
@@ -390,6 +394,45 @@ int run_passes(pic1dp_ctx *c, int tag, int64_t &counter, int npass, int64_t np, 
     HIP_TRY(launch(i));
     if (int rc = ks.end()) return rc;
     counter++;
+  }
+  return 0;
+}
+
+// ---- what the calls with buffers of their own share (capi_select.cpp, capi_zoom.cpp) ----
+constexpr int64_t kSliceWords = static_cast<int64_t>(4) << 20;  // 32 MiB of pinned staging per transfer, as the checkpoint's
+
+// a device buffer that lives for one call (capi_select.cpp, capi_zoom.cpp): taken from the context's owner, given back when it goes out of scope
+template <class T>
+struct CallBuf {
+  DeviceMem &mem;
+  T *p = nullptr;
+  explicit CallBuf(DeviceMem &m) : mem(m) {}
+  CallBuf(const CallBuf &) = delete;
+  CallBuf &operator=(const CallBuf &) = delete;
+  ~CallBuf() {
+    if (p) mem.release(&p);
+  }
+  // 0, or PIC1DP_ERR_NOMEM / PIC1DP_ERR_HIP with the message set
+  int take(size_t n, const char *who, const char *what) {
+    const hipError_t e = mem.alloc(&p, n);
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
+      return fail(PIC1DP_ERR_NOMEM, "%s: no device memory for %s (%zu bytes)", who, what, n * sizeof(T));
+    return fail(PIC1DP_ERR_HIP, "%s: allocating %s failed: %s", who, what, hipGetErrorString(e));
+  }
+};
+
+// n 8-byte words from the device to the host through the pinned staging, slice by slice
+inline int words_to_host(pic1dp_ctx *c, void *host, const void *dev, int64_t n) {
+  if (n <= 0 || !host) return 0;
+  double *h = nullptr;
+  if (int rc = pinned(c, static_cast<size_t>(std::min(n, kSliceWords)), &h)) return rc;
+  for (int64_t done = 0; done < n; done += kSliceWords) {
+    const int64_t m = std::min(kSliceWords, n - done);
+    HIP_TRY(hipMemcpyAsync(h, static_cast<const double *>(dev) + done, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    std::memcpy(static_cast<double *>(host) + done, h, sizeof(double) * m);
   }
   return 0;
 }

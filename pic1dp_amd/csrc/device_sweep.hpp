@@ -1,6 +1,6 @@
 // device_sweep.hpp -- the one sweep of the off-path marker kernels over a workgroup's rows of marker pairs (k_ptcldist,
 // k_ptcldist_exact: kernels_diag.hip; k_moments, k_moments_exact: kernels_moments.hip; k_power, k_power_exact:
-// kernels_power.hip), and the window rule of the exact kernels around it.  The rows and the drawn chunks themselves are device_math.hpp's (pair_rows, draw_chunk): the
+// kernels_power.hip; k_zoom: kernels_zoom.hip), and the window rule of the exact kernels around it.  The rows and the drawn chunks themselves are device_math.hpp's (pair_rows, draw_chunk): the
 // step kernels use them too.
 #pragma once
 #include "device_math.hpp"
@@ -61,7 +61,9 @@ __device__ __forceinline__ void pair_sweep(const double *x, const double *v, con
 // word stays below 2^63 in magnitude in the histograms and below 2^62 in the moments.  The exact power (device_power.hpp
 // pfx_*) is the histograms' case: at most 4 terms of a marker in one word (nx_opd = 1 with the top v row keeping the marker),
 // 4 x 2^17 x 2^44 = 2^63 -- the STRICT inequality in the marker count is what keeps the word inside.  Its rest sums take one
-// term per marker: a thread's register sum and the workgroup's LDS word of a window stay below 2^17 x 2^44 = 2^61.  The cap,
+// term per marker: a thread's register sum and the workgroup's LDS word of a window stay below 2^17 x 2^44 = 2^61.  The zoomed
+// histogram (device_zoom.hpp; k_zoom) is the same case: one term per marker into a word of its plane, each below 2^44 quanta
+// (markr: 1), fewer than 2^17 markers between two flushes -- a word stays below 2^61; its bounds need no new argument.  The cap,
 // the cadence and the place of the odd marker carry these bounds together: change none of them alone.
 // The dealt trips are the same number for every thread of a workgroup, so window_due is uniform over it and the barriers
 // a kernel puts around its flush inside the sweep are met by all.

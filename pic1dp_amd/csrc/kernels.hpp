@@ -763,6 +763,42 @@ hipError_t launch_select_write(const SelectArrays &a, int64_t np, const SelectRu
 hipError_t launch_gather(const SelectArrays &cur, const SelectArrays &tail, int64_t np, const long long *index, int64_t n,
                          const SelectOut &out, hipStream_t st);
 
+// ---- the exact phase-space histogram on a caller's window and grid (kernels_zoom.hip; the definition: include/pic1dp_hip.h
+// pic1dp_hip_zoom) ----
+constexpr int ZOOM_MAX_BINS = 4096, ZOOM_MAX_CELLS = 1 << 20;
+// the window and its grid as the rule takes them (pic1dp_zoom and lx; zoom_fx.cpp zoom_geom fills it on the host, once):
+// Lw = x_hi - x_lo, or (x_hi + lx) - x_lo where straddle (x_lo > x_hi); sx = nxb / Lw, sv = nvb / (v_hi - v_lo)
+struct ZoomGeom {
+  double lx, x_lo, x_hi, v_lo, v_hi, sx, sv;
+  int nxb, nvb, straddle;
+};
+// One pass of pic1dp_hip_zoom over a species' markers (launch_policy.hpp zoom_plan; kernels_zoom.hip k_zoom): the planes
+// `planes` (bit 0 markr, 1 total, 2 pertb) of the band of whole v rows [first_row, first_row + rows), one signed 64-bit word
+// per (plane, cell) in the workgroup's LDS (lds), or every row straight in memory
+struct ZoomPass {
+  int blocks, threads;
+  bool nt;          // non-temporal marker loads
+  size_t bytes;     // dynamic LDS: the band's words where lds, else 0
+  bool lds;
+  int planes;       // the mask of the pass's planes
+  int first_row, rows;
+};
+constexpr int ZOOM_MAX_PASSES = 64;
+struct ZoomPlan {
+  int selected;     // planes asked for: 1 ... 3
+  int npass;        // 0: arguments out of range
+  ZoomPass pass[ZOOM_MAX_PASSES];
+};
+// The call's device rows.  acc: [planes selected][2][nvb][nxb] -- per plane the hi rows, then the lo rows, the layout the
+// limbs are handed out in; rej: [3] terms not summed (2^44 quanta or more, NaN) per plane markr, total, pertb.  Zeroed by the
+// caller before a call's passes.  inv_q: 2^-e of total and of pertb (pic1dp_hip_diag_quanta's entries 1 and 2).
+struct ZoomArgs {
+  long long *acc, *rej;
+  double inv_q_p, inv_q_w;
+};
+hipError_t launch_zoom(const double *x, const double *v, const double *p, const double *w, int64_t np, const ZoomGeom &zg,
+                       int which, const ZoomArgs &a, const ZoomPass &ps, int dyn_tail, hipStream_t st);
+
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

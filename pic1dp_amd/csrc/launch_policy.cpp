@@ -214,6 +214,32 @@ PowerPlan power_plan_exact(int nx, int nx_opd, int nv_opd, int which, int deltaf
   return m;
 }
 
+ZoomPlan zoom_plan(int nxb, int nvb, int which, int deltaf, int64_t np, int num_cu, int pass_cap) {
+  ZoomPlan m{};
+  if (which < 1 || which > 7 || ((which & 4) && !deltaf) || nxb < 1 || nvb < 1 || nxb > ZOOM_MAX_BINS || nvb > ZOOM_MAX_BINS ||
+      static_cast<int64_t>(nxb) * nvb > ZOOM_MAX_CELLS)
+    return m;
+  m.selected = (which & 1) + ((which >> 1) & 1) + ((which >> 2) & 1);
+  const int cap_words = static_cast<int>(kDiagLdsCap / sizeof(long long));
+  const int rows_fit = cap_words / (m.selected * nxb);   // >= 1: a row of three planes is at most 12 288 words
+  const int bands = (nvb + rows_fit - 1) / rows_fit;
+  const bool lds = bands <= std::max(1, std::min(pass_cap, ZOOM_MAX_PASSES));
+  m.npass = lds ? bands : 1;
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(num_cu, (np + (int64_t{1} << 17) - 1) >> 17));   // moments_plan_exact's rule
+  for (int i = 0; i < m.npass; ++i) {
+    ZoomPass &ps = m.pass[i];
+    ps.lds = lds;
+    ps.planes = which;
+    ps.first_row = lds ? i * rows_fit : 0;
+    ps.rows = lds ? std::min(rows_fit, nvb - ps.first_row) : nvb;
+    ps.bytes = lds ? sizeof(long long) * static_cast<size_t>(m.selected) * ps.rows * nxb : 0;
+    ps.threads = 1024;
+    ps.blocks = static_cast<int>(blocks);
+    ps.nt = 8.0 * (2 + ((which >> 1) & 1) + ((which >> 2) & 1)) * static_cast<double>(np) > 288.0 * 1048576.0;
+  }
+  return m;
+}
+
 SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req) {
   SelectPlan s{};
   s.chunk_pairs = SELECT_CHUNK_PAIRS;

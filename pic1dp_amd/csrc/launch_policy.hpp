@@ -104,6 +104,22 @@ PowerPlan power_plan_exact(int nx, int nx_opd, int nv_opd, int which, int deltaf
 // once x and v (16 B per marker) exceed the threshold of diag_launch.  The prefix sum runs in one workgroup of 1024.
 SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req);
 
+// ---- the exact phase-space histogram on a caller's window and grid (kernels_zoom.hip; include/pic1dp_hip.h pic1dp_hip_zoom) ----
+// The passes of one call: which (bit 0 markr, 1 total, 2 pertb) selects n planes of nvb rows of nxb cells, one signed 64-bit
+// word per (plane, cell) in a workgroup's LDS, kDiagLdsCap / 8 = 19 200 words at most.  Every pass holds ALL selected planes
+// of a band of whole v rows: a row of all three is at most 3 x 4096 = 12 288 words, so it always fits, and a pass per group
+// of planes would sweep x and v once more for the same rows.  With R = 19 200 / (n nxb) rows a pass:
+//   nvb <= R                        : one pass, every row (LDS)
+//   ceil(nvb / R) <= kZoomPassCap   : that many band passes, R rows each, the last the remainder (LDS)
+//   else                            : one pass, the terms straight into the global (hi, lo) rows (bytes 0)
+// pass_cap: kZoomPassCap, the measured crossover -- at 1e8 markers four band passes take 2.31 ms, the pass into memory 2.6 ms
+// whatever the grid, eight band passes 4.34 ms; a measurement varies it (tools/zoom_bench.py).
+// One workgroup of 1024 threads per CU, the exact kinds' grid max(1, min(num_cu, ceil(np / 2^17))); non-temporal loads once
+// the arrays a pass reads (x, v and p and / or w) exceed the threshold of diag_launch.  npass = 0: which outside 1..7, pertb
+// asked of a full-f run (deltaf = 0), nxb or nvb outside 1..4096, more than 2^20 cells.
+constexpr int kZoomPassCap = 4;
+ZoomPlan zoom_plan(int nxb, int nvb, int which, int deltaf, int64_t np, int num_cu, int pass_cap = kZoomPassCap);
+
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
 // (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs

@@ -120,6 +120,20 @@ extern "C" int pic1dp_probe_host_power_plan_exact(int32_t nx, int32_t nx_opd, in
   return power_plan_words(power_plan_exact(nx, nx_opd, nv_opd, which, deltaf, np, num_cu), out);
 }
 
+extern "C" int pic1dp_probe_host_zoom_plan(int32_t nxb, int32_t nvb, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
+                                           int32_t pass_cap, int64_t out[515]) {
+  if (!out) return 1;
+  const ZoomPlan m = zoom_plan(nxb, nvb, which, deltaf, np, num_cu, pass_cap > 0 ? pass_cap : kZoomPassCap);
+  for (int i = 0; i < 515; ++i) out[i] = 0;
+  out[0] = m.npass, out[1] = m.selected, out[2] = kZoomPassCap;
+  for (int i = 0; i < m.npass; ++i) {
+    const ZoomPass &ps = m.pass[i];
+    const int64_t v[8] = {ps.blocks, ps.threads, ps.nt, static_cast<int64_t>(ps.bytes), ps.planes, ps.lds, ps.first_row, ps.rows};
+    for (int k = 0; k < 8; ++k) out[3 + 8 * i + k] = v[k];
+  }
+  return 0;
+}
+
 extern "C" int pic1dp_probe_host_select_plan(int64_t np, int32_t num_cu, int32_t threads_req, int32_t bpc_req, int64_t out[6]) {
   if (!out) return 1;
   const SelectPlan s = select_plan(np, num_cu, threads_req, bpc_req);

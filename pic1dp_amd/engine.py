@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Input, Layout, Pic1dpError, Select, check  # noqa: F401
+from ._lib import Input, Layout, Pic1dpError, Select, Zoom, check  # noqa: F401
 
 
 def make_input(**kw):
@@ -215,6 +215,36 @@ class Pic1dp:
         e = C.c_int32()
         check(self.L.pic1dp_hip_power_local_exact(self._ctx, int(ispecies), int(which), _ptr(limbs), C.byref(e)))
         return limbs, e.value
+
+    # -- exact phase-space histogram on a caller-chosen window and grid --
+    def zoom(self, ispecies=0, x=None, v=None, bins=(64, 64), which=7):
+        """the markers of a species counted, and their p and w summed, on a cell-centred grid of bins = (nxb, nvb) cells over
+        the window x = (lo, hi) of the wrapped position (lo > hi: across the periodic boundary; None: the whole box) and
+        v = (lo, hi) (None: [-v_max, v_max)), on the GPU (include/pic1dp_hip.h pic1dp_hip_zoom).  which: a mask of 1 markr,
+        2 total, 4 pertb.  Returns a dict of the planes asked for as (nvb, nxb) arrays, plus x_edges (nxb + 1, running past
+        lx where the window straddles) and v_edges (nvb + 1).  Exact: every term rounded once to whole quanta and summed as
+        integers, so the result is fixed by the input and the markers alone.  The sums are raw and local to this context;
+        divide by the cell's area for a density.  Pic1dpError naming species and plane if a term lay at or beyond 2^44
+        quanta (zoom_stats counts them)."""
+        z = make_zoom(self.inp, x, v, bins)
+        out = np.zeros((_zoom_planes(which),) + _zoom_shape(z))
+        check(self.L.pic1dp_hip_zoom(self._ctx, int(ispecies), C.byref(z), int(which), _ptr(out)))
+        return _split_zoom(out, self.inp, z, which)
+
+    def zoom_local_exact(self, ispecies=0, x=None, v=None, bins=(64, 64), which=7):
+        """this context's exact sums as int64 limbs of shape (nplanes, 2, nvb, nxb): [j, 0] the hi limb, [j, 1] the lo limb,
+        normalised (0 <= lo < 2^32); a cell's total is hi 2^32 + lo quanta.  Ranks: add element by element, then zoom_convert"""
+        z = make_zoom(self.inp, x, v, bins)
+        limbs = np.zeros((_zoom_planes(which), 2) + _zoom_shape(z), dtype=np.int64)
+        check(self.L.pic1dp_hip_zoom_local_exact(self._ctx, int(ispecies), C.byref(z), int(which), _ptr(limbs)))
+        return limbs
+
+    def zoom_stats(self):
+        """(device ms of the zoom's passes while kernel stats were enabled, passes that swept markers so far, terms they did
+        not sum so far) -- pic1dp_hip_zoom_stats; kernel_stats has no row for them"""
+        ms, n, rej = C.c_double(), C.c_int64(), C.c_int64()
+        check(self.L.pic1dp_hip_zoom_stats(self._ctx, C.byref(ms), C.byref(n), C.byref(rej)))
+        return ms.value, n.value, rej.value
 
     # -- select and gather markers on the GPU (DESIGN.md 2.18) --------------------
     def _selection(self, ispecies, x, v, fraction, key, origin):
@@ -820,6 +850,72 @@ def select_thin(fraction):
     t = C.c_uint64()
     check(_lib.load().pic1dp_hip_select_thin(float(fraction), C.byref(t)))
     return int(t.value)
+
+
+ZOOM_PLANES = ("markr", "total", "pertb")
+
+
+def _zoom_planes(which):
+    if not 1 <= int(which) <= 7:
+        raise Pic1dpError(1, "zoom: which = %d, must be a mask of 1 (markr), 2 (total) and 4 (pertb)" % which)
+    return bin(int(which)).count("1")
+
+
+def _zoom_shape(z):
+    """(nvb, nxb), or (0, 0) for a grid the library will refuse (nothing of that size is allocated for the refusal)"""
+    ok = 1 <= z.nxb <= 4096 and 1 <= z.nvb <= 4096 and z.nxb * z.nvb <= 2**20
+    return (z.nvb, z.nxb) if ok else (0, 0)
+
+
+def make_zoom(inp, x=None, v=None, bins=(64, 64)):
+    """struct pic1dp_zoom from windows (lo, hi) and bins = (nxb, nvb); x=None: the whole box, v=None: [-v_max, v_max)"""
+    x = (0.0, inp.lx) if x is None else x
+    v = (-inp.v_max, inp.v_max) if v is None else v
+    return Zoom(float(x[0]), float(x[1]), float(v[0]), float(v[1]), int(bins[0]), int(bins[1]))
+
+
+def _split_zoom(out, inp, z, which):
+    res = {name: out[j] for j, name in enumerate(n for k, n in enumerate(ZOOM_PLANES) if which & (1 << k))}
+    lw = (z.x_hi + inp.lx) - z.x_lo if z.x_lo > z.x_hi else z.x_hi - z.x_lo
+    res["x_edges"] = z.x_lo + lw * np.arange(z.nxb + 1) / z.nxb
+    res["v_edges"] = z.v_lo + (z.v_hi - z.v_lo) * np.arange(z.nvb + 1) / z.nvb
+    return res
+
+
+def zoom_len(x, v, bins, which=7):
+    """doubles pic1dp_hip_zoom hands out for this window, grid and mask: nplanes * nxb * nvb (host only)"""
+    z, n = Zoom(float(x[0]), float(x[1]), float(v[0]), float(v[1]), int(bins[0]), int(bins[1])), C.c_int64()
+    check(_lib.load().pic1dp_hip_zoom_len(C.byref(z), int(which), C.byref(n)))
+    return n.value
+
+
+def zoom_convert(inp, limbs, x=None, v=None, bins=(64, 64), which=7, ispecies=0):
+    """limbs of zoom_local_exact (or their element-wise sum over ranks) -> the dict zoom() returns: every cell's integer
+    total converted once (host only, no device)"""
+    z = make_zoom(inp, x, v, bins)
+    a = np.ascontiguousarray(limbs, dtype=np.int64)
+    m = C.c_int64()
+    check(_lib.load().pic1dp_hip_zoom_limbs_len(C.byref(z), int(which), C.byref(m)))
+    if a.size != m.value:
+        raise ValueError("limbs: %d words, %d expected" % (a.size, m.value))
+    out = np.zeros((_zoom_planes(which),) + _zoom_shape(z))
+    check(_lib.load().pic1dp_hip_zoom_convert(C.byref(inp), int(ispecies), C.byref(z), int(which), _ptr(a), _ptr(out)))
+    return _split_zoom(out, inp, z, which)
+
+
+def host_zoom(inp, xs, vs, ps=None, ws=None, x=None, v=None, bins=(64, 64), which=7, ispecies=0):
+    """the zoom's rule and sums on host arrays of valid markers (include/pic1dp_hip.h pic1dp_hip_host_zoom; no device):
+    (limbs of shape (nplanes, 2, nvb, nxb), normalised, of the terms summed; rejected[3], the terms not summed per plane)"""
+    z = make_zoom(inp, x, v, bins)
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (xs, vs, ps, ws)]
+    n = arrs[0].size
+    if any(a is not None and a.size != n for a in arrs):
+        raise ValueError("the marker arrays must have one length")
+    limbs = np.zeros((_zoom_planes(which), 2) + _zoom_shape(z), dtype=np.int64)
+    rej = np.zeros(3, dtype=np.int64)
+    check(_lib.load().pic1dp_hip_host_zoom(C.byref(inp), int(ispecies), C.byref(z), int(which), *[None if a is None else _ptr(a) for a in arrs],
+                                           n, _ptr(limbs), _ptr(rej)))
+    return limbs, rej
 
 
 def make_select(x=(-np.inf, np.inf), v=(-np.inf, np.inf), fraction=1.0, key=0, origin=0, thin=None):

@@ -70,6 +70,11 @@ type, bind(C) :: pic1dp_select_t
   real(c_double) :: x_lo, x_hi, v_lo, v_hi
   integer(c_int64_t) :: thin, key, origin
 end type pic1dp_select_t
+! struct pic1dp_zoom: a window of (wrapped x, v) and the cells across it (x_lo > x_hi: across the periodic boundary)
+type, bind(C) :: pic1dp_zoom_t
+  real(c_double) :: x_lo, x_hi, v_lo, v_hi
+  integer(c_int32_t) :: nxb, nvb
+end type pic1dp_zoom_t
 
 interface
   ! state digest, checkpoint and restart (include/pic1dp_hip.h; file names are C strings: trim(name) // c_null_char)
@@ -242,6 +247,68 @@ interface
     integer(c_int64_t), intent(out) :: thin
     integer(c_int) :: ierr
   end function pic1dp_hip_select_thin
+  ! the exact phase-space histogram on a caller-chosen window and grid: which is a mask of 1 (markr), 2 (total), 4 (pertb);
+  ! out(nxb, nvb, planes selected), limbs(nxb, nvb, 2, planes selected) with (:, :, 1, j) the hi and (:, :, 2, j) the lo limb.
+  ! Ranks: zoom_local_exact, add the limbs element by element (MPI_SUM on MPI_INTEGER8), zoom_convert once
+  function pic1dp_hip_zoom_len(z, which, n) bind(C, name="pic1dp_hip_zoom_len") result(ierr)
+    import
+    type(pic1dp_zoom_t), intent(in) :: z
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom_len
+  function pic1dp_hip_zoom_limbs_len(z, which, n) bind(C, name="pic1dp_hip_zoom_limbs_len") result(ierr)
+    import
+    type(pic1dp_zoom_t), intent(in) :: z
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom_limbs_len
+  function pic1dp_hip_zoom_local_exact(ctx, ispecies, z, which, limbs) bind(C, name="pic1dp_hip_zoom_local_exact") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_zoom_t), intent(in) :: z
+    integer(c_int64_t), intent(inout) :: limbs(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom_local_exact
+  function pic1dp_hip_zoom_convert(inp, ispecies, z, which, limbs, out) bind(C, name="pic1dp_hip_zoom_convert") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_zoom_t), intent(in) :: z
+    integer(c_int64_t), intent(in) :: limbs(*)
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom_convert
+  function pic1dp_hip_zoom(ctx, ispecies, z, which, out) bind(C, name="pic1dp_hip_zoom") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_zoom_t), intent(in) :: z
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom
+  ! the rule on host arrays; p / w not wanted (their plane not selected): c_null_ptr
+  function pic1dp_hip_host_zoom(inp, ispecies, z, which, x, v, p, w, np, limbs, rejected) bind(C, name="pic1dp_hip_host_zoom") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_zoom_t), intent(in) :: z
+    real(c_double), intent(in) :: x(*), v(*)
+    type(c_ptr), value :: p, w
+    integer(c_int64_t), value :: np
+    integer(c_int64_t), intent(inout) :: limbs(*)
+    integer(c_int64_t), intent(out) :: rejected(3)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_host_zoom
+  function pic1dp_hip_zoom_stats(ctx, ms, passes, rejected) bind(C, name="pic1dp_hip_zoom_stats") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    real(c_double), intent(out) :: ms
+    integer(c_int64_t), intent(out) :: passes, rejected
+    integer(c_int) :: ierr
+  end function pic1dp_hip_zoom_stats
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

@@ -73,6 +73,7 @@ SIGNATURES = {
     "pic1dp_probe_host_power_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_power_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_select_plan": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _I64],
+    "pic1dp_probe_host_zoom_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
@@ -292,6 +293,19 @@ def host_power_plan_exact(nx, nx_opd, nv_opd, which, deltaf, np_, num_cu):
         raise ValueError("pic1dp_probe_host_power_plan_exact")
     return dict(selected=out[1], tile=out[2], plane=out[3],
                 passes=[dict(zip(POWER_PASS_FIELDS, out[4 + 8 * i:12 + 8 * i])) for i in range(out[0])])
+
+
+ZOOM_PASS_FIELDS = ("blocks", "threads", "nt", "bytes", "planes", "lds", "first_row", "rows")
+
+
+def host_zoom_plan(nxb, nvb, which, deltaf, np_, num_cu, pass_cap=0):
+    """the passes of one zoom call (csrc/launch_policy.hpp zoom_plan), on the host: dict(selected, pass_cap, passes) with one
+    dict of ZOOM_PASS_FIELDS per pass (planes: bit 0 markr, 1 total, 2 pertb; lds: the band's words in the workgroup's LDS,
+    0: every row straight in memory); pass_cap=0: the library's; no pass: arguments out of range"""
+    out = (C.c_int64 * 515)()
+    if load().pic1dp_probe_host_zoom_plan(int(nxb), int(nvb), int(which), int(deltaf), int(np_), int(num_cu), int(pass_cap), out) != 0:
+        raise ValueError("pic1dp_probe_host_zoom_plan")
+    return dict(selected=out[1], pass_cap=out[2], passes=[dict(zip(ZOOM_PASS_FIELDS, out[3 + 8 * i:11 + 8 * i])) for i in range(out[0])])
 
 
 SELECT_PLAN_FIELDS = ("chunk_pairs", "nchunk", "blocks", "threads", "nt", "scan_threads")
