@@ -207,6 +207,19 @@ typedef struct pic1dp_probe_step_query {
 int pic1dp_probe_host_step_plan(const pic1dp_input *in, const pic1dp_layout *lay, const pic1dp_probe_step_query *q, int64_t out[112],
                                 char names[8][64]);
 
+/* What a call of the call sites' lazy state machine enqueues and which state follows (pic1dp_amd/csrc/call_plan.hpp), on
+ * the HOST: plan_call for
+ *   state[9]   = CallState {seq, owed, e_step_start, cd_kept_mode_only, adopt_current, charge_pending, charge_pending_pred,
+ *                call_phase, eh_modes},
+ *   moment[14] = CallMoment {lazy_calls, call_pair, loaded, several_ranks, fp64_rank_sum, charge_sum, pred_kind, tab_lds,
+ *                field_differs, pred_usable, eh_current, modes_current, optimize_due_any, output_follows},
+ *   caps[8]    = the StepCaps it reads {dft_paths, six_sums_one_mode, modes_fit_field_kernel, predict_capable, diag_in_step,
+ *                lazy_calls_ok, pair_serves_collect, pair_in_solve_field}
+ * and a kind of call (the index of enum Call).  out[64] = {refusal, refused_after, the refused pair's seq and owed, the 9
+ * words of the state that follows, the number n of actions, n x {action, argument}}, zeros behind; out[63]: 1 where
+ * call_state_invariants holds of the state that follows under this moment and these caps.  Nonzero: null argument or no such
+ * kind of call. */
+int pic1dp_probe_host_call_plan(const int32_t state[9], const int32_t moment[14], const int32_t caps[8], int32_t call, int32_t out[64]);
 
 /* The launch shape of the on-device particle load's pass over nalloc slots (launch_policy.hpp load_launch), on the HOST:
  * out = {workgroups, threads, non-temporal stores, markers a workgroup takes at a time}.  Workgroup b takes the chunks b,

@@ -593,12 +593,8 @@ int pic1dp_hip_set_seed_offset(pic1dp_ctx *c, int32_t offset) {
 
 int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   CHECK_CTX(c);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize_cd(c)) return rc;  // deposits of the old markers are consumed, not mixed with the new ones
-  if (c->owed == Owed::AdoptHalfField)        // a half-step field waiting to be adopted: field_chargeden becomes the half-step
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;  // charge density the eager collect_charge left (markers still there)
+  if (int rc = call_site(c, Call::ReplaceMarkers)) return rc;  // what the old markers still owe is settled; a noted push of them is void
   HIP_TRY(hipStreamSynchronize(c->st));  // kernels of an earlier run may still be writing the arrays
-  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;  // a noted push of markers that are about to be replaced is void
   c->state_version++;
   const pic1dp_input &in = c->in;
   const int ns = in.nspecies;
@@ -647,7 +643,6 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   c->rng_ready = true;
   diag_void_bounds(c);  // (new markers)
   c->cur = 0;
-  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   c->itime = 0;
   c->time = 0.0;
@@ -667,11 +662,8 @@ int pic1dp_hip_particle_load_device(pic1dp_ctx *c, int32_t kind) {
     if (int rc = init_block_rng(in, P.blk0 + b + c->seed_offset, rng[b])) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if (!c->d_loadmax) HIP_TRY(c->mem.alloc(&c->d_loadmax, 2 * static_cast<size_t>(PIC1DP_MAX_SPECIES)));  // (the last thing that can refuse)
-  if (int rc = materialize_cd(c)) return rc;  // deposits of the old markers are consumed, not mixed with the new ones
-  if (c->owed == Owed::AdoptHalfField)
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;
+  if (int rc = call_site(c, Call::ReplaceMarkers)) return rc;  // what the old markers still owe is settled; a noted push of them is void
   HIP_TRY(hipStreamSynchronize(c->st));  // kernels of an earlier run may still be writing the arrays
-  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;
   c->state_version++;
   const int ns = in.nspecies;
   HIP_TRY(hipMemsetAsync(c->d_loadmax, 0, sizeof(unsigned long long) * 2 * PIC1DP_MAX_SPECIES, c->st));
@@ -704,7 +696,6 @@ int pic1dp_hip_particle_load_device(pic1dp_ctx *c, int32_t kind) {
   c->rng_ready = true;
   diag_void_bounds(c);  // (new markers)
   c->cur = 0;
-  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   c->itime = 0;
   c->time = 0.0;
@@ -744,10 +735,7 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
   if (!x || !v || !p || !w) return fail(PIC1DP_ERR_ARG, "null array");
   if (n != S.nalloc) return fail(PIC1DP_ERR_ARG, "n = %lld but this process owns %lld slots", (long long)n, (long long)S.nalloc);
   if (np < 0 || np > n) return fail(PIC1DP_ERR_ARG, "np out of range");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize_cd(c)) return rc;   // (first: what collect_charge left pending is settled before the sequence is left)
-  if (c->loaded)
-    if (int rc = materialize(c)) return rc;
+  if (int rc = call_site(c, Call::UploadMarkers)) return rc;   // (what collect_charge left pending is settled, a noted push in memory: the sequence is left)
   HIP_TRY(hipStreamSynchronize(c->st));
   c->state_version++;
   // an upload (re)starts from set 0 for every species: slots beyond np live there
@@ -775,7 +763,6 @@ int pic1dp_hip_particles_upload(pic1dp_ctx *c, int32_t isp, const double *x, con
   if (c->plan.nblk == 1) c->blk_np[isp][0] = np;
   c->rng_ready = false;  // the host's loader owns the random stream now
   diag_void_bounds(c);
-  c->call_phase = 0;   // (new markers: between time steps)
   c->loaded = true;
   return 0;
 }
@@ -786,8 +773,7 @@ int pic1dp_hip_particles_download(pic1dp_ctx *c, int32_t isp, double *x, double 
   if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "bad species index");
   Species &S = c->sp[isp];
   if (n != S.nalloc) return fail(PIC1DP_ERR_ARG, "n = %lld but this process owns %lld slots", (long long)n, (long long)S.nalloc);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;
+  if (int rc = call_site(c, Call::ReadMarkers)) return rc;
   HIP_TRY(hipStreamSynchronize(c->st));
   const PSet &A = S.set[c->cur];
   const int64_t np = S.np;
@@ -810,8 +796,7 @@ int pic1dp_hip_particles_download_bak(pic1dp_ctx *c, int32_t isp, double *xb, do
   if (isp < 0 || isp >= c->in.nspecies) return fail(PIC1DP_ERR_ARG, "bad species index");
   Species &S = c->sp[isp];
   if (n != S.nalloc) return fail(PIC1DP_ERR_ARG, "n does not match the owned slots");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;
+  if (int rc = call_site(c, Call::ReadMarkers)) return rc;
   if (!S.slab[1]) return fail(PIC1DP_ERR_STATE, "no RK backup exists before the first push / substep call");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->st));
@@ -895,20 +880,9 @@ int pic1dp_hip_steps_to_output(pic1dp_ctx *c, int32_t *nsteps) {
 // ---------------------------------------------------------------------------
 // field access
 // ---------------------------------------------------------------------------
-int pic1dp_hip_chargeden_state(pic1dp_ctx *c, int32_t *kept_mode_only) {
-  CHECK_CTX(c);
-  if (!kept_mode_only) return fail(PIC1DP_ERR_ARG, "null output");
-  *kept_mode_only = c->cd_kept_mode_only ? 1 : 0;
-  return 0;
-}
-
 int pic1dp_hip_get_field(pic1dp_ctx *c, double *E, double *cd, double *re, double *im) {
   CHECK_CTX(c);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = settle_field_view(c)) return rc;
-  if (int rc = materialize_cd(c)) return rc;
-  if (cd && c->cd_kept_mode_only)
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;
+  if (int rc = call_site(c, cd ? Call::GetFieldCd : Call::GetField)) return rc;
   // the four small vectors through the pinned staging, on the engine's stream, ONE wait (four synchronous copies from
   // pageable memory cost ~55 us: tools/output_host_cost.py)
   const size_t nx = c->in.nx, nm = c->in.nmode;
@@ -930,11 +904,7 @@ int pic1dp_hip_get_field(pic1dp_ctx *c, double *E, double *cd, double *re, doubl
 int pic1dp_hip_set_electric(pic1dp_ctx *c, const double *E) {
   CHECK_CTX(c);
   if (!E) return fail(PIC1DP_ERR_ARG, "null array");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = settle_step_start_field(c)) return rc;   // (the kept modes stay the half step's, as after eager calls)
-  if (int rc = settle_half_pair(c)) return rc;   // (d_E0 keeps the step-start field a noted push(1) saw)
-  if (lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2)
-    if (int rc = materialize(c)) return rc;
+  if (int rc = call_site(c, Call::WriteElectric)) return rc;   // (a noted push sees the field of its own moment first)
   HIP_TRY(hipStreamSynchronize(c->st));
   HIP_TRY(hipMemcpy(c->d_E, E, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
   field_written(c, false);
@@ -944,25 +914,16 @@ int pic1dp_hip_set_electric(pic1dp_ctx *c, const double *E) {
 int pic1dp_hip_set_chargeden(pic1dp_ctx *c, const double *cd) {
   CHECK_CTX(c);
   if (!cd) return fail(PIC1DP_ERR_ARG, "null array");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize_cd(c)) return rc;  // pending deposits are consumed, then overwritten
-  // a half-step field waiting to be adopted, or adopted as far as the host can tell but not yet copied (Seq::*PairSolved): memory
-  // first becomes what the eager calls leave -- the adoption writes field_chargeden too --, then the host's vector rules
-  if (int rc = settle_half_pair(c)) return rc;
-  if (c->owed == Owed::AdoptHalfField)
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  c->cd_version++;
+  if (int rc = call_site(c, Call::WriteChargeden)) return rc;  // (pending deposits are consumed, an adoption made or dropped: then the host's vector rules)
   HIP_TRY(hipStreamSynchronize(c->st));
   HIP_TRY(hipMemcpy(c->d_chargeden, cd, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
-  c->cd_kept_mode_only = false;
   return 0;
 }
 
 int pic1dp_hip_field_energy(pic1dp_ctx *c, double *energy) {
   CHECK_CTX(c);
   if (!energy) return fail(PIC1DP_ERR_ARG, "null output");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = settle_field_view(c)) return rc;
+  if (int rc = call_site(c, Call::ReadField)) return rc;
   double *slot = c->d_scratch + kEnergyBlocks * 3;
   HIP_TRY(launch_field_energy(c->d_E, c->in.nx, c->in.lx, static_cast<double>(c->in.nx), slot, c->st));
   double *h = nullptr;

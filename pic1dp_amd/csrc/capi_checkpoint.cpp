@@ -113,27 +113,17 @@ int pic1dp_hip_state_digest(pic1dp_ctx *c, uint64_t *out) {
   CHECK_CTX(c);
   if (!out) return fail(PIC1DP_ERR_ARG, "null output");
   if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = materialize(c)) return rc;   // (as particles_download: a noted push becomes memory; clean: nothing is launched)
+  if (int rc = call_site(c, Call::ReadMarkers)) return rc;   // (as particles_download: a noted push becomes memory; clean: nothing is launched)
   return device_digests(c, out);
 }
 
 int pic1dp_hip_checkpoint_write(pic1dp_ctx *c, const char *path) {
   CHECK_CTX(c);
   if (!path || !*path) return fail(PIC1DP_ERR_ARG, "checkpoint_write: no file name");
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  if (c->charge_pending) return fail(PIC1DP_ERR_STATE, "checkpoint_write: charge_local is waiting for charge_reduced");
-  if (lz_of(c->seq) != LZ_CLEAN)
-    return fail(PIC1DP_ERR_STATE, "checkpoint_write: a push is noted -- checkpoints are written between time steps only");
-  if (c->call_phase != 0)   // (eager call sites note no push, and behind the second collect_charge nothing is noted either)
-    return fail(PIC1DP_ERR_STATE, "checkpoint_write: call %d of the six of a time step was the last -- checkpoints are written between time steps only",
-                c->call_phase);
   if (c->fused_pending) return fail(PIC1DP_ERR_STATE, "internal: checkpoint_write with a fused solve pending");
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = settle_step_start_field(c)) return rc;
-  if (int rc = materialize_cd(c)) return rc;
-  if (c->cd_kept_mode_only)
-    return fail(PIC1DP_ERR_STATE, "checkpoint_write: field_chargeden holds a half step's kept mode only -- checkpoints are written between time steps only");
+  // between time steps only (no particles, a charge or a push pending, a call of the six the last: refused); what the
+  // step's end still owes is settled; a half step's kept mode alone in field_chargeden: refused behind that
+  if (int rc = call_site(c, Call::Checkpoint)) return rc;
   HIP_TRY(hipStreamSynchronize(c->st));
   if (int rc = xchg_check(c)) return rc;
 

@@ -554,11 +554,7 @@ int pic1dp_hip_output_all(pic1dp_ctx *c, double *scalars, int32_t nscal, double 
     }
     return 0;
   }
-  if (int rc = require_loaded(c)) return rc;
-  if (int rc = settle_field_view(c)) return rc;
-  if (int rc = materialize_cd(c)) return rc;
-  if (cd && c->cd_kept_mode_only)
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;
+  if (int rc = call_site(c, cd ? Call::OutputAllCd : Call::OutputAll)) return rc;
   if (int rc = diag_buffers(c)) return rc;
   const RecordLayout L(c);
   double *h = nullptr;
@@ -599,8 +595,8 @@ int pic1dp_hip_diag_quantise(double term, int32_t log2_quantum, int32_t kinetic,
 int pic1dp_hip_set_diag_sum(pic1dp_ctx *c, int32_t kind) {
   CHECK_CTX(c);
   if (kind != 0 && kind != 1) return fail(PIC1DP_ERR_ARG, "diagnostics sum must be 0 (FP64 and per-pass fixed point) or 1 (exact)");
-  if (c->seq != Seq::Clean || c->owed != Owed::Nothing || c->charge_pending || c->fused_pending)
-    return fail(PIC1DP_ERR_STATE, "set_diag_sum while a push, a charge or a solve is pending: call it between time steps");
+  if (c->fused_pending) return fail(PIC1DP_ERR_STATE, "set_diag_sum while a push, a charge or a solve is pending: call it between time steps");
+  if (int rc = call_site(c, Call::BetweenSteps, "set_diag_sum")) return rc;
   if (kind == 1)
     for (int s = 0; s < c->in.nspecies; ++s)
       if (int rc = pic1dp_hip_diag_quanta(&c->in, s, c->dfx_e[s])) return rc;

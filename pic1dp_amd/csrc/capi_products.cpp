@@ -17,8 +17,7 @@ int product_check(pic1dp_ctx *c, const char *who, int32_t isp) {
 
 int product_begin(pic1dp_ctx *c, const char *who, int32_t isp) {
   if (int rc = product_check(c, who, isp)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  return materialize(c);   // (as state_digest: a noted push becomes memory; clean: nothing is launched)
+  return call_site(c, Call::ReadMarkers);   // (as state_digest: a noted push becomes memory; clean: nothing is launched)
 }
 
 }  // namespace pic1dp_host
@@ -118,7 +117,7 @@ int power_exact_local(pic1dp_ctx *c, const char *who, int32_t isp, int32_t which
   int32_t e_base = 0;
   if (int rc = power_exact_base(who, in, isp, &e_base)) return rc;
   if (int rc = product_begin(c, who, isp)) return rc;
-  if (int rc = settle_field_view(c)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
+  if (int rc = call_site(c, Call::ReadField)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
   const Species &S = c->sp[isp];
   const PowerPlan plan = power_plan_exact(in.nx, in.nx_opd, in.nv_opd, which, in.deltaf, S.np, c->num_cu);
   if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: power_plan_exact has no pass for nx %d, %d x %d, which %d", in.nx, in.nx_opd, in.nv_opd, which);
@@ -208,7 +207,7 @@ int pic1dp_hip_power(pic1dp_ctx *c, int32_t isp, int32_t which, double *out) {
   if (int rc = power_refusal("power", in, which)) return rc;
   if (!out) return fail(PIC1DP_ERR_ARG, "power: null output");
   if (int rc = product_begin(c, "power", isp)) return rc;
-  if (int rc = settle_field_view(c)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
+  if (int rc = call_site(c, Call::ReadField)) return rc;    // (as pic1dp_hip_get_field: d_E is field_electric)
   const Species &S = c->sp[isp];
   const PowerPlan plan = power_plan(in.nx, in.nx_opd, in.nv_opd, which, in.deltaf, S.np, c->num_cu);
   if (plan.npass < 1) return fail(PIC1DP_ERR_STATE, "internal: power_plan has no pass for nx %d, %d x %d, which %d", in.nx, in.nx_opd, in.nv_opd, which);

@@ -1,10 +1,15 @@
-// capi_step.cpp -- the ACTIONS of the hot path behind the C ABI of include/pic1dp_hip.h: the three call sites and their
-// lazy state machine (push / collect_charge / solve_field), pic1dp_hip_step, the prediction of the half-step charge, the
-// solve inside the marker launch, the split-phase deposit.  What a step launches is DECIDED in step_plan.cpp (pure, pinned
-// on the host): here are the wiring (pointers, versions, counters, spans), the state transitions and the order of enqueues.
-// Launch shapes: launch_policy.cpp; the other units: ctx.hpp.  In order of dependency: facts_of and the currency relations,
-// the marker launches, prediction and solve, pic1dp_hip_step, the call sites, the split-phase deposit, pic1dp_hip_check_state.
+// capi_step.cpp -- the ACTIONS of the hot path behind the C ABI of include/pic1dp_hip.h: the three call sites (push /
+// collect_charge / solve_field), pic1dp_hip_step, the prediction of the half-step charge, the solve inside the marker launch,
+// the split-phase deposit.  What a step launches is DECIDED in step_plan.cpp, what a call of the call sites' lazy state
+// machine enqueues and which state follows in call_plan.cpp (both pure, pinned on the host): here are the wiring (pointers,
+// versions, counters, spans), the bridges from the context to the plans (facts_of; call_state_of, call_moment_of) and the one
+// executor that walks a call's plan through the enqueue helpers and stores the state (run_call).
+// Launch shapes: launch_policy.cpp; the other units: ctx.hpp.  In order of dependency: the bridges and the currency
+// relations, the marker launches, prediction and solve, pic1dp_hip_step, the call sites' executor and entry points, the
+// split-phase deposit, pic1dp_hip_check_state.
 // (the entry points are declared extern "C" in include/pic1dp_hip.h; their definitions here inherit that linkage)
+#include <optional>
+
 #include "ctx.hpp"
 
 // ---------------------------------------------------------------------------
@@ -66,6 +71,30 @@ static void use_accumulators(pic1dp_ctx *c, int idx) {
 // modes describe the field as it is
 static bool pred_usable(const pic1dp_ctx *c, const Step &s) {
   return pred_fresh(c) && c->modes_field_version == c->field_version && s.k.predict_capable;
+}
+
+// THE bridge from the context to the call sites' plan (call_plan.hpp): what the machine remembers ...
+static CallState call_state_of(const pic1dp_ctx *c) {
+  CallState s;
+  s.seq = c->seq, s.owed = c->owed;
+  s.e_step_start = c->e_step_start, s.cd_kept_mode_only = c->cd_kept_mode_only;
+  s.adopt_current = c->owed == Owed::AdoptHalfField && c->adopt_cd_version == c->cd_version;
+  s.charge_pending = c->charge_pending, s.charge_pending_pred = c->charge_pending_pred;
+  s.call_phase = static_cast<int8_t>(c->call_phase), s.eh_modes = static_cast<int8_t>(c->eh_modes);
+  return s;
+}
+// ... and what a decision looks at besides (the clock's two questions only for the calls that ask them)
+static CallMoment call_moment_of(const pic1dp_ctx *c, const Step &s, Call call, bool field_differs = false) {
+  CallMoment m;
+  m.lazy_calls = c->cfg.lazy_calls != 0, m.call_pair = c->cfg.call_pair != 0, m.loaded = c->loaded;
+  m.several_ranks = several_ranks(c), m.fp64_rank_sum = fp64_rank_sum(c);
+  m.charge_sum = c->charge_sum, m.pred_kind = c->plan.pred_kind, m.tab_lds = c->fa.tab_lds != 0;
+  m.field_differs = field_differs;
+  m.pred_usable = pred_usable(c, s), m.eh_current = eh_current(c);
+  m.modes_current = c->modes_field_version == c->field_version;
+  m.optimize_due_any = call == Call::Push1 && optimize_due_any(c);
+  m.output_follows = (call == Call::CollectCharge || call == Call::ChargeLocal || call == Call::ChargeLocalExact) && output_follows(c);
+  return m;
 }
 
 // both fields in one launch: what every pair solve is handed
@@ -330,7 +359,6 @@ static int step_particles(pic1dp_ctx *c, const Step &s, bool full, const double 
 // d_E has been written: by the mode-filter solve (the kept modes describe it) or by something else
 void pic1dp_host::field_written(pic1dp_ctx *c, bool by_solve) {
   c->field_version++;
-  c->e_step_start = false;  // (every writer writes the whole of field_electric; set_electric settles the kept modes first)
   if (by_solve && c->field_solver == 0) c->modes_field_version = c->field_version;
 }
 
@@ -360,41 +388,62 @@ static int pred_reduce(pic1dp_ctx *c) {
   return allreduce_charge(c);
 }
 
-// prediction -> chargeden of the next first sub-step (f.chargeden: field_chargeden, or a scratch vector).
-// Tiles: combined locally, summed over ranks, scaled.  Six sums: summed over ranks, then the kept mode's
-// content of that charge density -- all the solve looks at (k_pred_chargeden).
-// defer (call sites, f = c->fa): leave the scaling of the summed charge to the solve_field that follows (Owed)
-static int pred_to_chargeden(pic1dp_ctx *c, const Step &s, const FieldArgs &f, bool defer = false) {
-  c->pred_version = 0;  // consumed: the accumulators are zero again afterwards
-  const bool multi = several_ranks(c);
-  if (c->plan.pred_kind == 2) {
-    if (f.chargeden == c->d_chargeden) c->cd_kept_mode_only = true;
-    if (defer && !multi && s.k.dft_paths && f.tab_lds)  // the sums' combination, chargeden and the solve in the
-      return set_owed(c, Owed::PredSums);               // launch of the solve_field that follows
-    if (!multi) {
-      HIP_TRY(launch_pred_chargeden(f, c->pred_tab, c->d_pred, nullptr, c->st));
-      return 0;
-    }
-    HIP_TRY(launch_pred_to_charge(c->fa, c->d_pred, c->st));
-    if (int rc = pred_reduce(c)) return rc;
-    HIP_TRY(launch_pred_chargeden(f, c->pred_tab, nullptr, c->d_charge, c->st));
-    return 0;
+// one action of a plan (call_plan.hpp Act), through the helpers above.  f: the field arguments the charge-density and solve
+// launches take -- c->fa at the call sites, a copy aimed at scratch vectors on the step path
+static int enqueue_wrap_only(pic1dp_ctx *c);
+static int adopt_half_field(pic1dp_ctx *c);
+static int run_act(pic1dp_ctx *c, const Step &s, Act act, int arg, const FieldArgs &f) {
+  const size_t nx = c->in.nx;
+  switch (act) {
+    case Act::SaveStepStartField: return save_step_start_field(c);
+    case Act::AdoptHalfField: return adopt_half_field(c);
+    case Act::AdoptHalfModes: return adopt_half_modes(c);
+    case Act::CopyEhToE: HIP_TRY(hipMemcpyAsync(c->d_E, c->d_Eh, sizeof(double) * nx, hipMemcpyDeviceToDevice, c->st)); return 0;
+    case Act::PushEager1: return enqueue_push(c, 1, false);
+    case Act::PushEager1FromE0: return enqueue_push(c, 1, false, c->d_E0);
+    case Act::PushEager2: return enqueue_push(c, 2, false);
+    case Act::WrapOnly: return enqueue_wrap_only(c);
+    case Act::Deposit: return enqueue_deposit(c);
+    case Act::HalfPass: return step_particles(c, s, false, c->d_E, c->d_Eh);
+    case Act::SwapEh: std::swap(c->d_Eh, c->d_Ehn); return 0;  // d_Eh: the half-step field of the step being taken
+    case Act::FullPass:
+      c->eh_modes = arg >> kFullEhModesShift;
+      return step_particles(c, s, true, (arg & kFullE0Saved) ? c->d_E0 : c->d_E, (arg & kFullEhIsE) ? c->d_E : c->d_Eh,
+                            (arg & kFullDiag) != 0, (arg & kFullPred) != 0);
+    case Act::FxSettle: return fx_settle(c);
+    case Act::ReduceCharge: return reduce_charge(c);
+    case Act::Chargeden: HIP_TRY(launch_chargeden(f, false, c->st)); return 0;
+    case Act::ChargedenSum: HIP_TRY(launch_chargeden(f, true, c->st)); return 0;
+    case Act::PredChargeden: HIP_TRY(launch_pred_chargeden(f, c->pred_tab, c->d_pred, nullptr, c->st)); return 0;
+    case Act::PredChargedenSummed: HIP_TRY(launch_pred_chargeden(f, c->pred_tab, nullptr, c->d_charge, c->st)); return 0;
+    case Act::PredCombine: HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st)); return 0;
+    case Act::PredToCharge: HIP_TRY(launch_pred_to_charge(c->fa, c->d_pred, c->st)); return 0;
+    case Act::PredReduce: return pred_reduce(c);
+    case Act::ChargeLocal: HIP_TRY(launch_charge_local(c->fa, c->st)); return 0;
+    case Act::FxToRho: HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st)); return 0;
+    case Act::SolvePair: HIP_TRY(launch_field_solve_pair(f, pair_args(c), nullptr, c->st)); return 0;
+    case Act::SolvePredTiles: HIP_TRY(launch_field_solve_pred(f, c->d_pred, c->in.nmode, c->st)); return 0;
+    case Act::SolvePredSums: HIP_TRY(launch_field_solve_pred_sums(f, c->pred_tab, c->d_pred, c->st)); return 0;
+    case Act::SolvePlain: return enqueue_field_solve(c, f, (arg & 1) != 0, (arg & 2) != 0);
+    case Act::StateVersion: c->state_version++; return 0;
+    case Act::CdVersion: c->cd_version++; return 0;
+    case Act::FieldWrittenBySolve: field_written(c, true); return 0;
+    case Act::CallPairSkip: c->cnt.call_pair_skips++; return 0;
+    case Act::PredConsumed: c->pred_version = 0; return 0;  // the accumulators are zero again afterwards
+    case Act::MarkEhCurrent: mark_eh_current(c); return 0;
+    default: return fail(PIC1DP_ERR_STATE, "internal: action %d of a call plan has no executor", static_cast<int>(act));
   }
-  if (defer && !multi && s.k.dft_paths && s.k.modes_fit_field_kernel)
-    return set_owed(c, Owed::PredTiles);  // all of it in the launch of the solve_field that follows
-  HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
-  if (multi)
-    if (int rc = pred_reduce(c)) return rc;
-  if (defer) return set_owed(c, Owed::Scale);
-  HIP_TRY(launch_chargeden(f, false, c->st));
-  return 0;
 }
 
 // step() path: Eh of the NEXT step from the prediction, right after the field of the new state is solved
 static int predict_half_field(pic1dp_ctx *c, const Step &s) {
   FieldArgs f = c->fa;
   f.chargeden = c->d_cd_h;
-  if (int rc = pred_to_chargeden(c, s, f)) return rc;
+  // prediction -> chargeden of the next first sub-step, into the scratch vector: tiles combined locally, summed over ranks,
+  // scaled; six sums summed over ranks, then the kept mode's content of that charge density -- all the solve looks at
+  const PredPlan pp = plan_pred_chargeden(call_moment_of(c, s, Call::WholeSteps), s.k, /*defer=*/false);
+  for (int i = 0; i < pp.n; ++i)
+    if (int rc = run_act(c, s, pp.act[i], 0, f)) return rc;
   Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
   f.E = c->d_Ehn;
   f.mode_re = c->d_mode_h;
@@ -519,9 +568,8 @@ static int step_phase(pic1dp_ctx *c, const Step &s, bool full, double *Eout, boo
 // ---------------------------------------------------------------------------
 // whole steps and sub-steps in one call
 // ---------------------------------------------------------------------------
+static int run_call(pic1dp_ctx *c, const Step &s, Call call, const char *who = nullptr, bool field_differs = false);
 static int substep_impl(pic1dp_ctx *c, const Step &s, int irk, bool record) {
-  c->cd_kept_mode_only = false;
-  c->cd_version++;
   if (irk == 2 && optimize_due_any(c)) {
     // src/pic1dp.F90:80-88: push, particle_optimize, collect_charge -- the pushed
     // state has to exist in memory for the host-side optimisation
@@ -538,13 +586,8 @@ static int substep_impl(pic1dp_ctx *c, const Step &s, int irk, bool record) {
 int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
   CHECK_CTX(c);
   if (nsteps < 0) return fail(PIC1DP_ERR_ARG, "nsteps < 0");
-  if (int rc = require_loaded(c)) return rc;
-  if (nsteps > 0) {  // every step ends with the deposit of the new state
-    c->cd_kept_mode_only = false;
-    c->cd_version++;
-    c->call_phase = 0;
-  }
   Step s = facts_of(c);
+  if (int rc = run_call(c, s, nsteps > 0 ? Call::WholeSteps : Call::Markers)) return rc;  // (every step ends with the deposit of the new state)
   for (int it = 0; it < nsteps; ++it) {
     StepMoment m{};
     m.pending = c->fused_pending;
@@ -592,26 +635,25 @@ int pic1dp_hip_step(pic1dp_ctx *c, int32_t nsteps) {
 
 
 // ---------------------------------------------------------------------------
-// the call sites and what settles their state
+// Lazy call sites.  The reference driver calls push(irk), collect_charge,
+// solve_field per sub-step (src/pic1dp.F90:80-89).  Run one kernel per call, that
+// sequence streams 136 B + 2 x 24 B per marker and step; the whole-step kernels
+// need 88 B.  So push() only notes the request and the collect_charge() that
+// follows runs k_step_half (after push(1): deposit of the half-step state,
+// nothing stored) or k_step_full (after push(2): the whole RK2 step in place).
+//   LZ_CLEAN --push(1)--> LZ_PUSH1 --collect--> LZ_HALF --push(2)--> LZ_PUSH2 --collect--> LZ_CLEAN
+// Memory then lags behind what the reference would hold (the half-step state is
+// never written).  Every other entry point that looks at or changes markers,
+// accumulators or the field a noted push depends on first asks for its kind of
+// call (call_plan.hpp Call), whose plan runs the ordinary kernels (k_push with the
+// right field, wrap) so that memory is bit for bit what the eager calls would have
+// left; results of the lazy path itself are the whole-step path's (tests:
+// test_lazy_call_sites_*).  WHAT a call enqueues and which state follows is
+// plan_call's answer (call_plan.cpp); here is the executor.
 // ---------------------------------------------------------------------------
-// field_chargeden (and d_charge, and zeroed accumulators) as collect_charge would have left them at once
-int pic1dp_host::materialize_cd(pic1dp_ctx *c) {
-  const Owed pending = c->owed;
-  if (pending == Owed::AdoptHalfField) return 0;  // (a half-step FIELD waiting to be adopted by solve_field: no charge to settle)
-  if (pending == Owed::Nothing) return 0;
-  if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  if (pending == Owed::PredSums) {  // the six sums of a predicted push(1): the kept mode's content of chargeden, directly
-    HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, c->d_pred, nullptr, c->st));
-    return 0;
-  }
-  if (pending == Owed::PredTiles) HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
-  HIP_TRY(launch_chargeden(c->fa, pending == Owed::SumScale, c->st));
-  return 0;
-}
-
-// THE place the call sites' state is written: a pair that cannot occur (ctx.hpp kCallStateLegal) is an internal error
+// THE place the call sites' state is written: a pair that cannot occur (call_plan.hpp kCallStateLegal) is an internal error
 // here, at the call that would have produced it, instead of a wrong field some calls later
-int pic1dp_host::set_call_state(pic1dp_ctx *c, Seq seq, Owed owed) {
+static int set_call_state(pic1dp_ctx *c, Seq seq, Owed owed) {
   if (seq >= Seq::N || owed >= Owed::N || !kCallStateLegal[static_cast<int>(seq)][static_cast<int>(owed)])
     return fail(PIC1DP_ERR_STATE, "internal: call-site state (%d, %d) cannot occur (from (%d, %d))", static_cast<int>(seq),
                 static_cast<int>(owed), static_cast<int>(c->seq), static_cast<int>(c->owed));
@@ -620,8 +662,15 @@ int pic1dp_host::set_call_state(pic1dp_ctx *c, Seq seq, Owed owed) {
   c->owed = owed;
   return 0;
 }
-int pic1dp_host::set_seq(pic1dp_ctx *c, Seq seq) { return set_call_state(c, seq, c->owed); }
-int pic1dp_host::set_owed(pic1dp_ctx *c, Owed owed) { return set_call_state(c, c->seq, owed); }
+// ... and what the machine remembers beside the pair (the executor's store)
+static int store_call_state(pic1dp_ctx *c, const CallState &n) {
+  if (int rc = set_call_state(c, n.seq, n.owed)) return rc;
+  c->e_step_start = n.e_step_start, c->cd_kept_mode_only = n.cd_kept_mode_only;
+  c->adopt_cd_version = n.adopt_current ? c->cd_version : 0;  // (an adoption holds while cd_version stays where it is)
+  c->charge_pending = n.charge_pending, c->charge_pending_pred = n.charge_pending_pred;
+  c->call_phase = n.call_phase, c->eh_modes = n.eh_modes;
+  return 0;
+}
 
 // What a checkpoint does not carry, in a defined state: call sites Clean with nothing owed; the markers count as changed
 // (state_version), so no prediction, no predicted half-step field, no carried -f0'/f0 and no cached diagnostics belong to
@@ -629,19 +678,13 @@ int pic1dp_host::set_owed(pic1dp_ctx *c, Owed owed) { return set_call_state(c, c
 // one-pass kernels may build Eh from); every accumulator set and the exact accumulators zero, set 0 the current one;
 // nothing of a fused solve or a tail left over.  The step after it takes two passes.
 int pic1dp_host::reset_derived_state(pic1dp_ctx *c) {
-  if (int rc = set_call_state(c, Seq::Clean, Owed::Nothing)) return rc;
+  c->cd_version++;
+  if (int rc = store_call_state(c, CallState{})) return rc;
   c->state_version++;
   c->pred_version = c->eh_version = 0;
   c->eh_field_version = 0;
   c->field_version++;
   c->modes_field_version = 0;
-  c->eh_modes = 0;
-  c->e_step_start = false;
-  c->cd_kept_mode_only = false;
-  c->cd_version++;
-  c->adopt_cd_version = 0;
-  c->charge_pending = c->charge_pending_pred = false;
-  c->call_phase = 0;
   for (Species &S : c->sp) S.t2_version = 0;
   for (DiagSpecies &D : c->diag) {
     D.version = 0;
@@ -664,50 +707,6 @@ int pic1dp_host::reset_derived_state(pic1dp_ctx *c) {
   return 0;
 }
 
-// ctx.hpp call_phase: a push opens its sub-step wherever the host stood; a collected charge (collect_charge, charge_reduced)
-// and a solved field move on only from the call they follow in the reference's order -- a second collect_charge or
-// solve_field of the same sub-step stays where it is
-static void call_phase_push(pic1dp_ctx *c, int irk) { c->call_phase = irk == 1 ? 1 : 4; }
-static void call_phase_collect(pic1dp_ctx *c) {
-  if (c->call_phase == 1 || c->call_phase == 4) c->call_phase++;
-}
-static void call_phase_solve(pic1dp_ctx *c) {
-  if (c->call_phase == 2) c->call_phase = 3;
-  else if (c->call_phase == 5) c->call_phase = 0;
-}
-
-// checks only: for the call sites that take part in the lazy scheme themselves
-static int require_loaded_keep_lazy(pic1dp_ctx *c) {
-  if (!c->loaded) return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
-  if (c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_local is waiting for charge_reduced");
-  hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return fail(PIC1DP_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-  if (int rc = settle_step_start_field(c)) return rc;   // (a push or a step reads field_electric)
-  return materialize_cd(c);
-}
-
-// every other entry point that reads or writes markers or charge accumulators:
-// memory first becomes what the eager calls would have left
-int pic1dp_host::require_loaded(pic1dp_ctx *c) {
-  if (int rc = require_loaded_keep_lazy(c)) return rc;
-  return materialize(c);
-}
-
-// ---------------------------------------------------------------------------
-// Lazy call sites.  The reference driver calls push(irk), collect_charge,
-// solve_field per sub-step (src/pic1dp.F90:80-89).  Run one kernel per call, that
-// sequence streams 136 B + 2 x 24 B per marker and step; the whole-step kernels
-// need 88 B.  So push() only notes the request and the collect_charge() that
-// follows runs k_step_half (after push(1): deposit of the half-step state,
-// nothing stored) or k_step_full (after push(2): the whole RK2 step in place).
-//   LZ_CLEAN --push(1)--> LZ_PUSH1 --collect--> LZ_HALF --push(2)--> LZ_PUSH2 --collect--> LZ_CLEAN
-// Memory then lags behind what the reference would hold (the half-step state is
-// never written).  Every other entry point that looks at or changes markers,
-// accumulators or the field a noted push depends on first calls materialize(),
-// which runs the ordinary kernels (k_push with the right field, wrap) so that
-// memory is bit for bit what the eager calls would have left; results of the lazy
-// path itself are the whole-step path's (tests: test_lazy_call_sites_*).
-// ---------------------------------------------------------------------------
 // wrap of x stored back, as the deposit of collect_charge does, charge discarded
 static int enqueue_wrap_only(pic1dp_ctx *c) {
   for (int s = 0; s < c->in.nspecies; ++s) {
@@ -720,138 +719,108 @@ static int enqueue_wrap_only(pic1dp_ctx *c) {
   return 0;
 }
 
-// Call sites (ctx.hpp Seq, the Pair states): the half-step field the pair solve left in d_Ehn / d_mode_h, and the step-start
-// field still in field_electric, put where the eager calls would have them -- d_E0 <- E, and, once the host has called
-// solve_field for the half step, E <- the half-step field with its kept modes.  Everything that looks at the field, or
-// leaves the sequence push(1), collect_charge, solve_field, push(2), collect_charge, comes through here first.
-int pic1dp_host::settle_half_pair(pic1dp_ctx *c) {
-  if (!pair_of(c->seq)) return 0;
-  if (int rc = save_step_start_field(c)) return rc;
-  const bool solved = solved_of(c->seq);
-  if (int rc = set_seq(c, unpaired(c->seq))) return rc;
-  // solve_field has been called for the half step: field_electric has to BE the half-step field now (field_version was
-  // bumped when it was called); not yet called: it stays owed (AdoptHalfField) and copies when it comes
-  if (solved) return adopt_half_field(c);
-  return 0;
-}
-// for readers of the field only: nothing to do until the host has called solve_field for the half step -- until then
-// field_electric is the step-start field, which is what d_E holds
-int pic1dp_host::settle_field_view(pic1dp_ctx *c) {
-  if (int rc = settle_step_start_field(c)) return rc;
-  return solved_of(c->seq) ? settle_half_pair(c) : 0;
-}
-// field_electric and its kept modes as the eager calls leave them after push(2), collect_charge of a pair-solved step: the
-// half-step field (the whole-step kernel read the step-start field from field_electric; d_Eh / d_mode_h hold the half step's)
-int pic1dp_host::settle_step_start_field(pic1dp_ctx *c) {
-  if (!c->e_step_start) return 0;
-  c->e_step_start = false;
-  HIP_TRY(hipMemcpyAsync(c->d_E, c->d_Eh, sizeof(double) * c->in.nx, hipMemcpyDeviceToDevice, c->st));
-  return adopt_half_modes(c);
-}
 // field_electric and its kept modes <- the half-step field the pair solve left in d_Ehn / d_mode_h, and field_chargeden
 // <- the kept mode's content of the half-step charge density it left in d_cd_h (what collect_charge leaves there when it
 // is served from the six sums, Owed::PredSums): a solve_field that solves from field_chargeden again reproduces the half-step
 // field, as it does after eager calls
-int pic1dp_host::adopt_half_field(pic1dp_ctx *c) {
+static int adopt_half_field(pic1dp_ctx *c) {
   const size_t nx = c->in.nx;
   HIP_TRY(hipMemcpyAsync(c->d_chargeden, c->d_cd_h, sizeof(double) * nx, hipMemcpyDeviceToDevice, c->st));
   HIP_TRY(hipMemcpyAsync(c->d_E, c->d_Ehn, sizeof(double) * nx, hipMemcpyDeviceToDevice, c->st));
   return adopt_half_modes(c);
 }
 
-int pic1dp_host::materialize(pic1dp_ctx *c) {
-  if (int rc = settle_half_pair(c)) return rc;
-  const int lz = lz_of(c->seq);
-  if (lz == LZ_CLEAN) return 0;
-  // a half-step field waits to be adopted: it was solved from the half-step charge density, which leaves with the markers'
-  // half-step state -- that state is deposited for real on its way into memory (what the eager collect_charge left in
-  // field_chargeden), and the solve_field that follows solves from it (a step or substep in between overwrote d_Ehn / d_cd_h)
-  if (c->owed == Owed::AdoptHalfField) return rebuild_half_step_chargeden(c);
-  if (int rc = set_seq(c, Seq::Clean)) return rc;
-  if (lz == LZ_PUSH1) return enqueue_push(c, 1, false);           // the field has not changed since
-  // LZ_HALF / LZ_PUSH2: push(1) saw d_E0; its deposit wrapped x
-  if (int rc = enqueue_push(c, 1, false, c->d_E0)) return rc;
-  if (int rc = enqueue_wrap_only(c)) return rc;
-  if (lz == LZ_PUSH2) return enqueue_push(c, 2, false);
-  return 0;
+// what a refusal of the plan says (the texts the entry points had)
+static int refusal_error(const pic1dp_ctx *c, const CallPlan &p, const char *who) {
+  who = who ? who : "the call";
+  switch (p.refusal) {
+    case Refusal::NotLoaded: return fail(PIC1DP_ERR_STATE, "no particles: call particle_load or particles_upload first");
+    case Refusal::ChargeWaiting: return fail(PIC1DP_ERR_STATE, "charge_local is waiting for charge_reduced");
+    case Refusal::IllegalState:
+      return fail(PIC1DP_ERR_STATE, "internal: call-site state (%d, %d) cannot occur (from (%d, %d))", static_cast<int>(p.bad_seq),
+                  static_cast<int>(p.bad_owed), static_cast<int>(c->seq), static_cast<int>(c->owed));
+    case Refusal::EagerNoted: return fail(PIC1DP_ERR_STATE, "internal: a push noted by eager call sites");
+    case Refusal::WantsExactLocal:
+      return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_local_exact");
+    case Refusal::WantsExactReduced:
+      return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_reduced_exact");
+    case Refusal::NeedsExactSum: return fail(PIC1DP_ERR_STATE, "%s needs the exact charge sum (set_charge_sum(1))", who);
+    case Refusal::ReducedWithoutLocal:
+      return fail(PIC1DP_ERR_STATE, "%s without charge_local%s", who, c->charge_sum == 1 ? "_exact" : "");
+    case Refusal::NotBetweenSteps:
+      return fail(PIC1DP_ERR_STATE, "%s while a push, a charge or a solve is pending: call it between time steps", who);
+    case Refusal::CheckpointChargeWaiting:
+      return fail(PIC1DP_ERR_STATE, "checkpoint_write: charge_local is waiting for charge_reduced");
+    case Refusal::CheckpointPushNoted:
+      return fail(PIC1DP_ERR_STATE, "checkpoint_write: a push is noted -- checkpoints are written between time steps only");
+    case Refusal::CheckpointInsideStep:
+      return fail(PIC1DP_ERR_STATE, "checkpoint_write: call %d of the six of a time step was the last -- checkpoints are written between time steps only",
+                  c->call_phase);
+    case Refusal::CheckpointKeptMode:
+      return fail(PIC1DP_ERR_STATE, "checkpoint_write: field_chargeden holds a half step's kept mode only -- checkpoints are written between time steps only");
+    default: return fail(PIC1DP_ERR_STATE, "internal: a call plan of more than %d actions", kMaxActs);
+  }
 }
 
-// the deposit of collect_charge / charge_local into the species accumulators:
-// the whole-step kernel of a noted push, or the plain wrap + deposit
-static int deposit_or_step(pic1dp_ctx *c, const Step &s) {
-  if (c->seq == Seq::Push1) {
-    if (int rc = save_step_start_field(c)) return rc;
-    if (int rc = step_particles(c, s, false, c->d_E, c->d_Eh)) return rc;
-    return set_seq(c, Seq::Half);
-  }
-  if (lz_of(c->seq) == LZ_PUSH2) {
-    if (c->seq == Seq::Push2Pair)  // (push(2) without the solve_field of the half step: it sees the old field)
-      if (int rc = settle_half_pair(c)) return rc;
-    c->state_version++;
-    const bool diag = s.k.diag_in_step && output_follows(c);
-    if (c->seq == Seq::Push2PairSolved) {  // the half-step field came out of the previous step's pair solve: E0 is still in d_E
-      std::swap(c->d_Eh, c->d_Ehn);
-      c->eh_modes = 2;  // its kept mode: d_mode_h
-      if (int rc = step_particles(c, s, true, c->d_E, c->d_Eh, diag, !diag)) return rc;
-      c->e_step_start = true;  // (field_electric: still the step-start field -- the solve_field that follows overwrites it)
-      return set_seq(c, Seq::Clean);
+// THE executor: the call's plan, its actions in order through the helpers and the timer spans, then the state that follows.
+// (a whole-step kernel run for a noted push books itself under "push particle", step_particles; the span the plan opens
+// around the rest of a collect_charge covers the reduction and scaling only)
+static int plan_of(const pic1dp_ctx *c, const Step &s, Call call, const char *who, bool field_differs, CallPlan *p) {
+  *p = plan_call(call_state_of(c), call_moment_of(c, s, call, field_differs), s.k, call);
+  return p->refusal != Refusal::None && !p->refused_after ? refusal_error(c, *p, who) : 0;
+}
+static int run_plan(pic1dp_ctx *c, const Step &s, const CallPlan &p, const char *who) {
+  HIP_TRY(hipSetDevice(c->device));
+  std::optional<Span> span;
+  for (int i = 0; i < p.n; ++i) {
+    int rc = 0;
+    switch (p.act[i]) {
+      case Act::SpanCollect: span.emplace(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on); break;
+      case Act::SpanField: span.emplace(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on); break;
+      case Act::SpanEnd: rc = span->end(); break;
+      default: rc = run_act(c, s, p.act[i], p.arg[i], c->fa);
     }
-    // Eh = d_E: the kept modes describe it when the mode-filter solve wrote it last
-    c->eh_modes = (s.k.dft_paths && c->modes_field_version == c->field_version) ? 1 : 0;
-    if (int rc = step_particles(c, s, true, c->d_E0, c->d_E, diag, !diag)) return rc;
-    return set_seq(c, Seq::Clean);
+    if (rc) return rc;
   }
-  if (int rc = materialize(c)) return rc;
-  return enqueue_deposit(c);
+  if (int rc = store_call_state(c, p.next)) return rc;
+  return p.refused_after ? refusal_error(c, p, who) : 0;
+}
+static int run_call(pic1dp_ctx *c, const Step &s, Call call, const char *who, bool field_differs) {
+  CallPlan p;
+  if (int rc = plan_of(c, s, call, who, field_differs, &p)) return rc;
+  return run_plan(c, s, p, who);
+}
+// what the other units ask for (ctx.hpp)
+int pic1dp_host::call_site(pic1dp_ctx *c, Call call, const char *who, bool field_differs) {
+  return run_call(c, facts_of(c), call, who, field_differs);
+}
+int pic1dp_host::require_loaded(pic1dp_ctx *c) { return call_site(c, Call::Markers); }
+
+// ---------------------------------------------------------------------------
+// the call sites: check the arguments, name the call, execute
+// ---------------------------------------------------------------------------
+int pic1dp_hip_push(pic1dp_ctx *c, int32_t irk) {
+  CHECK_CTX(c);
+  if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
+  return run_call(c, facts_of(c), irk == 1 ? Call::Push1 : Call::Push2);
 }
 
 int pic1dp_hip_collect_charge(pic1dp_ctx *c) {
   CHECK_CTX(c);
-  if (int rc = require_loaded_keep_lazy(c)) return rc;
-  call_phase_collect(c);
+  return run_call(c, facts_of(c), Call::CollectCharge);
+}
+
+int pic1dp_hip_solve_field(pic1dp_ctx *c) {
+  CHECK_CTX(c);
+  return run_call(c, facts_of(c), Call::SolveField);
+}
+
+int pic1dp_hip_substep(pic1dp_ctx *c, int32_t irk) {
+  CHECK_CTX(c);
+  if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
   const Step s = facts_of(c);
-  c->cd_version++;
-  // a whole-step kernel run for a noted push is booked under "push particle"
-  // (step_particles); "collect charge" then covers the reduction and scaling only
-  // after a noted push(1) whose charge the previous step's kernel has predicted (k_step_one): no
-  // pass over the markers at all -- combine, reduce, scale
-  if (pair_of(c->seq) && c->seq != Seq::Push2PairSolved)  // out of sequence: memory as the eager calls leave it
-    if (int rc = settle_half_pair(c)) return rc;
-  // after a noted push(1) whose half-step FIELD the previous solve_field has already solved (the pair, below): nothing
-  // to launch at all
-  // (the six sums of one kept mode: with the tiles collect_charge owes the host the whole half-step charge density)
-  if (c->seq == Seq::Push1 && s.k.pair_serves_collect && eh_current(c)) {
-    c->cd_kept_mode_only = true;  // (field_chargeden is not the half step's: asking for it rebuilds, get_field)
-    c->adopt_cd_version = c->cd_version;
-    return set_call_state(c, Seq::HalfPair, Owed::AdoptHalfField);  // what the solve_field that follows has to do: adopt the half-step field
-  }
-  if (c->seq == Seq::Push1 && pred_usable(c, s)) {
-    if (int rc = save_step_start_field(c)) return rc;
-    if (int rc = set_call_state(c, Seq::Half, Owed::Nothing)) return rc;   // (a stale AdoptHalfField ends here)
-    Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
-    if (int rc = pred_to_chargeden(c, s, c->fa, c->cfg.lazy_calls != 0)) return rc;
-    return tm.end();
-  }
-  c->cd_kept_mode_only = false;  // a deposit follows: the whole vector again
-  if (c->owed == Owed::AdoptHalfField)   // (left over by an inspection that settled a pair before its solve_field: void now)
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  const bool noted = lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2;
-  if (noted)
-    if (int rc = deposit_or_step(c, s)) return rc;
-  Span tm(c->tm, PIC1DP_IWT_COLLECT_CHARGE, c->tm.timers_on);
-  if (!noted)
-    if (int rc = deposit_or_step(c, s)) return rc;
-  if (c->charge_sum == 1)  // exact sums over ranks, into the species accumulators: what follows is the one-rank path
-    if (int rc = fx_settle(c)) return rc;
-  const bool multi = fp64_rank_sum(c);
-  if (multi)
-    if (int rc = reduce_charge(c)) return rc;
-  if (c->cfg.lazy_calls) {  // the species sum (one rank) and the scaling: in the launch of the solve_field that follows
-    if (int rc = set_owed(c, multi ? Owed::Scale : Owed::SumScale)) return rc;
-  } else {
-    HIP_TRY(launch_chargeden(c->fa, !multi, c->st));
-  }
-  return tm.end();
+  if (int rc = run_call(c, s, irk == 1 ? Call::Substep1 : Call::Substep2)) return rc;
+  return substep_impl(c, s, irk, false);
 }
 
 int pic1dp_hip_set_field_solver(pic1dp_ctx *c, int32_t kind) {
@@ -859,11 +828,7 @@ int pic1dp_hip_set_field_solver(pic1dp_ctx *c, int32_t kind) {
   if (kind != 0 && kind != 1) return fail(PIC1DP_ERR_ARG, "field solver must be 0 (reference mode filter) or 1 (finite differences)");
   if (kind == 1 && (c->in.nx < 3 || c->in.nx > 4096))
     return fail(PIC1DP_ERR_ARG, "the finite-difference solver needs 3 <= nx <= 4096");
-  if (c->owed == Owed::AdoptHalfField && kind != c->field_solver) {  // a half-step field of the OTHER solver waits to be adopted:
-    HIP_TRY(hipSetDevice(c->device));                                // the half-step charge is deposited for real instead
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  }
+  if (int rc = call_site(c, Call::SwitchField, nullptr, kind != c->field_solver)) return rc;
   c->field_solver = kind;
   return 0;
 }
@@ -889,82 +854,8 @@ int pic1dp_hip_set_field_transform(pic1dp_ctx *c, int32_t transform) {
     if (!had_idx) c->mem.adopt(c->d_fft_idx);
     HIP_TRY(e);
   }
-  if (c->owed == Owed::AdoptHalfField && transform != c->field_transform) {  // a half-step field of the OTHER transform waits
-    if (int rc = rebuild_half_step_chargeden(c)) return rc;                // to be adopted: the half-step charge is deposited
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;                    // for real instead
-  }
+  if (int rc = call_site(c, Call::SwitchField, nullptr, transform != c->field_transform)) return rc;
   c->field_transform = transform;
-  return 0;
-}
-
-static int solve_field_call(pic1dp_ctx *c);
-int pic1dp_hip_solve_field(pic1dp_ctx *c) {
-  CHECK_CTX(c);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int rc = solve_field_call(c)) return rc;
-  call_phase_solve(c);   // (only a solve_field that was served moves the record on)
-  return 0;
-}
-
-static int solve_field_call(pic1dp_ctx *c) {
-  if (c->seq == Seq::HalfPair) {  // the half-step field is solved already (the pair below): nothing to launch
-    if (int rc = set_call_state(c, Seq::HalfPairSolved, Owed::Nothing)) return rc;
-    c->cnt.call_pair_skips++;
-    field_written(c, true);  // from now on field_electric IS the half-step field, as far as anybody can tell
-    return 0;
-  }
-  if (int rc = settle_half_pair(c)) return rc;
-  // a noted push has to see the field of its own moment
-  if (lz_of(c->seq) == LZ_PUSH1 || lz_of(c->seq) == LZ_PUSH2)
-    if (int rc = materialize(c)) return rc;
-  const Step s = facts_of(c);
-  Span tm(c->tm, PIC1DP_IWT_FIELD_ELECTRIC, c->tm.timers_on);
-  FieldArgs f = c->fa;
-  Owed pending = c->owed;  // what collect_charge left to this launch
-  if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  if (pending == Owed::AdoptHalfField && c->adopt_cd_version != c->cd_version)  // (made for a charge density since overwritten:
-    pending = Owed::Nothing;                                                     // check_state refuses that state; a safety net)
-  // One rank, behind the collect_charge of push(2) whose kernel has predicted the next half-step charge: BOTH fields in
-  // one launch, as pic1dp_hip_step solves them -- the next step's push(1), collect_charge, solve_field then launch nothing
-  // and a time step through the three call sites is two launches (round 5; three and a copy before)
-  if (pending == Owed::SumScale && s.k.pair_in_solve_field && c->seq == Seq::Clean && pred_usable(c, s)) {
-    HIP_TRY(launch_field_solve_pair(f, pair_args(c), nullptr, c->st));
-    pair_solved(c);
-    return tm.end();
-  }
-  if (pending == Owed::AdoptHalfField) {  // (the fast path above was left by an inspection in between: the field is adopted by copying)
-    if (int rc = adopt_half_field(c)) return rc;
-  } else if (pending == Owed::PredTiles && s.k.dft_paths) {
-    HIP_TRY(launch_field_solve_pred(f, c->d_pred, c->in.nmode, c->st));
-  } else if (pending == Owed::PredSums && s.k.dft_paths) {
-    HIP_TRY(launch_field_solve_pred_sums(f, c->pred_tab, c->d_pred, c->st));
-  } else {
-    if (pending == Owed::PredSums) HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, c->d_pred, nullptr, c->st));
-    if (pending == Owed::PredTiles) HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
-    if (int rc = enqueue_field_solve(c, f, pending == Owed::SumScale, pending == Owed::Nothing || pending == Owed::PredSums)) return rc;
-  }
-  field_written(c, true);
-  return tm.end();
-}
-
-int pic1dp_hip_push(pic1dp_ctx *c, int32_t irk) {
-  CHECK_CTX(c);
-  if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
-  if (int rc = require_loaded_keep_lazy(c)) return rc;
-  int rc;
-  if (irk == 1 && c->seq == Seq::Clean && lazy_ok(facts_of(c).k, optimize_due_any(c))) rc = set_seq(c, Seq::Push1);
-  else if (irk == 2 && lz_of(c->seq) == LZ_HALF) rc = set_seq(c, push2_noted(c->seq));
-  else if ((rc = materialize(c)) == 0) rc = enqueue_push(c, irk, false);
-  if (rc == 0) call_phase_push(c, irk);   // (a push that failed has opened nothing)
-  return rc;
-}
-
-int pic1dp_hip_substep(pic1dp_ctx *c, int32_t irk) {
-  CHECK_CTX(c);
-  if (irk != 1 && irk != 2) return fail(PIC1DP_ERR_ARG, "irk must be 1 or 2");
-  if (int rc = require_loaded(c)) return rc;
-  if (int rc = substep_impl(c, facts_of(c), irk, false)) return rc;
-  c->call_phase = irk == 1 ? 3 : 0;   // (push, collect_charge and solve_field of the sub-step in one)
   return 0;
 }
 
@@ -989,35 +880,10 @@ int pic1dp_hip_set_output_fusion(pic1dp_ctx *c, int32_t on) {
   return 0;
 }
 
-// field_chargeden as the reference holds it between the sub-steps, when the collect_charge after a noted push(1)
-// was served from the six sums (the kept mode's content only): the half-step state is pushed into memory after all
-// (as every inspection of a noted push does) and deposited for real.  One rank only -- on several ranks the
-// reduction is a collective that an inspection on one of them must not start: there chargeden keeps the kept
-// mode's content (include/pic1dp_hip.h says so).  The field solved from either is the same to rounding: the
-// solve only looks at the kept mode.
-int pic1dp_host::rebuild_half_step_chargeden(pic1dp_ctx *c) {
-  // the flag is cleared only when the vector has actually been rebuilt: on several ranks, or when the
-  // markers have left the half-step state through calls outside the sequence, chargeden keeps the kept mode's
-  // content and pic1dp_hip_chargeden_state says so
-  if (several_ranks(c)) return 0;
-  if (lz_of(c->seq) != LZ_HALF && lz_of(c->seq) != LZ_PUSH2) return 0;
-  if (int rc = settle_half_pair(c)) return rc;
-  // the vector becomes the whole half-step charge density, and a solve from it is what the eager solve_field does: a half-step
-  // field owed for adoption is dropped (its copy of the kept mode's content would overwrite the whole vector, flag "full")
-  if (c->owed == Owed::AdoptHalfField)
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  const bool push2_was_noted = lz_of(c->seq) == LZ_PUSH2;
-  if (int rc = enqueue_push(c, 1, false, c->d_E0)) return rc;
-  if (int rc = set_seq(c, Seq::Clean)) return rc;  // memory now holds the half-step state (x not yet wrapped): the deposit wraps and stores it
-  if (int rc = enqueue_deposit(c)) return rc;
-  if (c->charge_sum == 1)
-    if (int rc = fx_settle(c)) return rc;
-  HIP_TRY(launch_chargeden(c->fa, true, c->st));
-  c->cd_kept_mode_only = false;
-  // a push(2) that had been noted: memory as the eager calls would have left it (the field it sees, d_E, is the one
-  // solve_field wrote after the half step)
-  if (push2_was_noted)
-    if (int rc = enqueue_push(c, 2, false)) return rc;
+int pic1dp_hip_chargeden_state(pic1dp_ctx *c, int32_t *kept_mode_only) {
+  CHECK_CTX(c);
+  if (!kept_mode_only) return fail(PIC1DP_ERR_ARG, "null output");
+  *kept_mode_only = call_state_of(c).cd_kept_mode_only ? 1 : 0;
   return 0;
 }
 
@@ -1027,88 +893,48 @@ int pic1dp_host::rebuild_half_step_chargeden(pic1dp_ctx *c) {
 int pic1dp_hip_charge_local(pic1dp_ctx *c, double *charge2) {
   CHECK_CTX(c);
   if (!charge2) return fail(PIC1DP_ERR_ARG, "null array");
-  if (c->charge_sum == 1) return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_local_exact");
-  if (int rc = require_loaded_keep_lazy(c)) return rc;
-  const Step s = facts_of(c);
-  if (pair_of(c->seq) && c->seq != Seq::Push2PairSolved)  // out of sequence (as in collect_charge): memory as the eager calls leave it
-    if (int rc = settle_half_pair(c)) return rc;
-  if (c->owed == Owed::AdoptHalfField)   // (left over by a pair settled before its solve_field: void now)
-    if (int rc = set_owed(c, Owed::Nothing)) return rc;
-  if (c->seq == Seq::Push1 && pred_usable(c, s)) {  // predicted by the previous step's kernel: no marker pass
-    if (int rc = save_step_start_field(c)) return rc;
-    if (int rc = set_seq(c, Seq::Half)) return rc;
-    if (c->plan.pred_kind == 2) {  // the six sums in charge2[0..5], zeros behind: the host's sum over ranks sums them
-      HIP_TRY(launch_pred_to_charge(c->fa, c->d_pred, c->st));
-      c->charge_pending_pred = true;
-    } else {
-      HIP_TRY(launch_pred_combine(c->fa, c->d_pred, c->in.nmode, c->st));
-    }
-    c->pred_version = 0;
-  } else {
-    c->cd_kept_mode_only = false;
-    if (int rc = deposit_or_step(c, s)) return rc;
-    HIP_TRY(launch_charge_local(c->fa, c->st));
-  }
+  if (int rc = run_call(c, facts_of(c), Call::ChargeLocal)) return rc;
   HIP_TRY(hipStreamSynchronize(c->st));
   HIP_TRY(hipMemcpy(charge2, c->d_charge, sizeof(double) * c->in.nx, hipMemcpyDeviceToHost));
-  c->charge_pending = true;
   return 0;
 }
 
 int pic1dp_hip_charge_reduced(pic1dp_ctx *c, const double *charge1) {
   CHECK_CTX(c);
   if (!charge1) return fail(PIC1DP_ERR_ARG, "null array");
-  if (c->charge_sum == 1) return fail(PIC1DP_ERR_STATE, "exact charge sum: a sum of doubles over ranks cannot be exact; use charge_reduced_exact");
-  if (!c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_reduced without charge_local");
+  const Step s = facts_of(c);
+  CallPlan p;
+  if (int rc = plan_of(c, s, Call::ChargeReduced, "charge_reduced", false, &p)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpy(c->d_charge, charge1, sizeof(double) * c->in.nx, hipMemcpyHostToDevice));
-  c->charge_pending = false;
-  call_phase_collect(c);
-  c->cd_version++;
-  if (c->charge_pending_pred) {  // what came back are the summed prediction sums
-    c->charge_pending_pred = false;
-    c->cd_kept_mode_only = true;
-    HIP_TRY(launch_pred_chargeden(c->fa, c->pred_tab, nullptr, c->d_charge, c->st));
-    return 0;
-  }
-  if (c->cfg.lazy_calls) return set_owed(c, Owed::Scale);
-  HIP_TRY(launch_chargeden(c->fa, false, c->st));
-  return 0;
+  return run_plan(c, s, p, "charge_reduced");
 }
 
 // kind 1 of the charge sum: the split phase with integers (include/pic1dp_hip.h has the layout)
 int pic1dp_hip_charge_local_exact(pic1dp_ctx *c, int64_t *limbs) {
   CHECK_CTX(c);
   if (!limbs) return fail(PIC1DP_ERR_ARG, "null array");
-  if (c->charge_sum != 1) return fail(PIC1DP_ERR_STATE, "charge_local_exact needs the exact charge sum (set_charge_sum(1))");
-  if (int rc = require_loaded_keep_lazy(c)) return rc;
-  c->cd_kept_mode_only = false;
-  if (int rc = deposit_or_step(c, facts_of(c))) return rc;
+  const Step s = facts_of(c);
+  if (int rc = run_call(c, s, Call::ChargeLocalExact, "charge_local_exact")) return rc;
   const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
   HIP_TRY(launch_fx_normalise(c->d_fx, c->in.nspecies, c->in.nx, c->st));
   HIP_TRY(hipMemcpyAsync(limbs, c->d_fx, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->st));
   HIP_TRY(hipMemsetAsync(c->d_fx, 0, sizeof(int64_t) * n, c->st));
   HIP_TRY(hipStreamSynchronize(c->st));
   if (int rc = fx_check(c)) return rc;  // (a contribution left out: no charge to hand out)
-  c->charge_pending = true;
-  return 0;
+  return run_call(c, s, Call::ChargeExactHandedOut);
 }
 
 int pic1dp_hip_charge_reduced_exact(pic1dp_ctx *c, const int64_t *limbs) {
   CHECK_CTX(c);
   if (!limbs) return fail(PIC1DP_ERR_ARG, "null array");
-  if (c->charge_sum != 1) return fail(PIC1DP_ERR_STATE, "charge_reduced_exact needs the exact charge sum (set_charge_sum(1))");
-  if (!c->charge_pending) return fail(PIC1DP_ERR_STATE, "charge_reduced_exact without charge_local_exact");
+  const Step s = facts_of(c);
+  CallPlan p;
+  if (int rc = plan_of(c, s, Call::ChargeReducedExact, "charge_reduced_exact", false, &p)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = 2 * static_cast<size_t>(c->in.nspecies) * c->in.nx;
   HIP_TRY(hipMemcpy(c->d_fx, limbs, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-  c->charge_pending = false;
-  call_phase_collect(c);
-  c->cd_version++;
-  HIP_TRY(launch_fx_to_rho(c->d_fx, c->fa.rho_sp, c->in.nspecies, c->in.nx, c->fx_q, c->st));
-  if (c->cfg.lazy_calls) return set_owed(c, Owed::SumScale);
-  HIP_TRY(launch_chargeden(c->fa, true, c->st));
-  return 0;
+  return run_plan(c, s, p, "charge_reduced_exact");
 }
 
 // ---------------------------------------------------------------------------
@@ -1124,36 +950,22 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   do {                                                                                                    \
     if (!(cond))                                                                                          \
       return fail(PIC1DP_ERR_STATE, "state invariant violated: %s (call-site state %d, owed %d)", #cond, \
-                  static_cast<int>(c->seq), static_cast<int>(c->owed));                                   \
+                  static_cast<int>(st.seq), static_cast<int>(st.owed));                                   \
   } while (0)
   // The call sites' state is one (Seq, Owed) pair written by set_call_state alone, which refuses the pairs that cannot
-  // occur (ctx.hpp kCallStateLegal): what used to be a dozen relations between lz, cd_lazy, half_pair and half_solved
-  // checked here cannot be violated any more.  What is left relates the state to the CONTEXT it is held in:
-  const bool one_rank = !several_ranks(c);
+  // occur (call_plan.hpp kCallStateLegal): what used to be a dozen relations between lz, cd_lazy, half_pair and half_solved
+  // checked here cannot be violated any more.  What relates the parts of the state to each other and to the context it is
+  // held in is call_state_invariants' (pure: the host walk of tests/call_plan_check.cpp asks it too); what relates it to the
+  // versions follows here
   const Step s = facts_of(c);
-  const bool six_sums_one_mode = s.k.six_sums_one_mode;
-  INVARIANT(kCallStateLegal[static_cast<int>(c->seq)][static_cast<int>(c->owed)]);
-  INVARIANT(c->seq == Seq::Clean || (c->cfg.lazy_calls && c->loaded));    // a push is only noted by the lazy call sites
-  INVARIANT(c->owed == Owed::Nothing || c->cfg.lazy_calls);
-  INVARIANT(c->owed < Owed::SumScale || one_rank || c->charge_sum == 1);  // species sum / prediction left to solve_field: one rank
-                                                                      // (or exact sums, already summed over ranks)
-  // kind 1 of the charge sum: no prediction pending, no tiles, sums or half-step field owed
-  INVARIANT(c->charge_sum == 0 || c->pred_version == 0);
-  INVARIANT(c->charge_sum == 0 || (c->owed != Owed::PredTiles && c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField &&
-                                   !pair_of(c->seq)));
-  INVARIANT(c->owed != Owed::PredTiles || c->plan.pred_kind == 1);
-  INVARIANT((c->owed != Owed::PredSums && c->owed != Owed::AdoptHalfField && !pair_of(c->seq)) || six_sums_one_mode);
-  INVARIANT(!pair_of(c->seq) || (s.f.cfg->call_pair && c->eh_version == c->state_version));   // the field in d_Ehn belongs to the state in memory
-  INVARIANT(!c->cd_kept_mode_only || c->plan.pred_kind == 2);
-  // an owed adoption is current: made for the field_chargeden the eager calls hold now (and, by kCallStateLegal, while the
-  // markers still stand at the half step)
-  INVARIANT(c->owed != Owed::AdoptHalfField || c->adopt_cd_version == c->cd_version);
-  INVARIANT(!c->e_step_start || (c->seq == Seq::Clean && c->eh_modes == 2));   // (the half-step field: d_Eh / d_mode_h)
+  const CallState st = call_state_of(c);
+  if (const char *broken = call_state_invariants(st, call_moment_of(c, s, Call::N), s.k))
+    return fail(PIC1DP_ERR_STATE, "state invariant violated: %s (call-site state %d, owed %d)", broken, static_cast<int>(st.seq),
+                static_cast<int>(st.owed));
+  INVARIANT(c->charge_sum == 0 || c->pred_version == 0);   // kind 1 of the charge sum: no prediction pending
+  INVARIANT(!pair_of(st.seq) || c->eh_version == c->state_version);   // the field in d_Ehn belongs to the state in memory
   // whole-step path: nothing of a step() is left over between calls
   INVARIANT(!c->fused_pending);
-  // the call record: a noted push lies inside a time step (checkpoint_write goes by the record alone)
-  INVARIANT(c->call_phase >= 0 && c->call_phase <= 5);
-  INVARIANT(lz_of(c->seq) == LZ_CLEAN || c->call_phase != 0);
   INVARIANT(c->fuse_args.on == 0);
   INVARIANT(c->fused_dirty == -1);
   INVARIANT(c->tail_done == 0);
@@ -1163,12 +975,10 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   INVARIANT(c->eh_version <= c->state_version);
   INVARIANT(c->eh_field_version <= c->field_version);
   INVARIANT(c->modes_field_version <= c->field_version);
-  INVARIANT(c->eh_modes >= 0 && c->eh_modes <= 2);
   for (int s = 0; s < c->in.nspecies; ++s) {
     INVARIANT(c->diag[s].version <= c->state_version);
     INVARIANT(c->sp[s].t2_version <= c->state_version);
   }
-  INVARIANT(!c->charge_pending_pred || c->charge_pending);
   if (!deep) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->st));
@@ -1192,7 +1002,7 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
   for (int k = 0; k < 3; ++k) {
     const bool nz = nonzero(h, k * c->plan.rho_set_doubles, c->plan.rho_set_doubles);
     if (k != c->acc_idx) INVARIANT(!nz && "a species accumulator set that is not the current one holds deposits");
-    else if (c->owed != Owed::SumScale && c->owed != Owed::PredTiles && !c->charge_pending) INVARIANT(!nz && "deposits nobody is going to sum");
+    else if (st.owed != Owed::SumScale && st.owed != Owed::PredTiles && !st.charge_pending) INVARIANT(!nz && "deposits nobody is going to sum");
   }
   if (c->d_pred_all && c->plan.pred_set_doubles) {
     h.assign(3 * c->plan.pred_set_doubles, 0.0);
@@ -1200,7 +1010,7 @@ int pic1dp_hip_check_state(pic1dp_ctx *c, int32_t deep) {
     for (int k = 0; k < 3; ++k) {
       const bool nz = nonzero(h, k * c->plan.pred_set_doubles, c->plan.pred_set_doubles);
       if (k != c->acc_idx) INVARIANT(!nz && "a prediction accumulator set that is not the current one holds sums");
-      else if (c->pred_version == 0 && c->owed != Owed::PredTiles && c->owed != Owed::PredSums && !c->charge_pending)
+      else if (c->pred_version == 0 && st.owed != Owed::PredTiles && st.owed != Owed::PredSums && !st.charge_pending)
         INVARIANT(!nz && "prediction sums that belong to no state");
     }
   }

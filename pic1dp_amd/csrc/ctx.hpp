@@ -5,7 +5,8 @@
 //   settings.cpp       what a context takes from the environment, read once (settings.hpp: pic1dp_ctx::cfg; no HIP call)
 //   context_plan.cpp   create()'s decisions as a pure function, and the mode tables (context_plan.hpp: pic1dp_ctx::plan; no HIP call)
 //   device_mem.hpp     the one owner of a context's device and pinned memory (pic1dp_ctx::mem)
-//   capi_step.cpp      the hot path's actions: the three call sites and their lazy state machine, pic1dp_hip_step, the prediction
+//   capi_step.cpp      the hot path's actions: the three call sites, the executor of their lazy state machine (call_site), pic1dp_hip_step, the prediction
+//   call_plan.cpp      the call sites' decisions: for a kind of call arriving in a state, what is enqueued in which order and which state follows (call_plan.hpp: no context, no HIP call)
 //   step_plan.cpp      the hot path's decisions: which marker kernel, carry, streaming, fused solve, tail, field launch (step_plan.hpp: no context, no HIP call)
 //   launch_policy.cpp  the launch shapes of the marker kernels and of the diagnostics passes (launch_policy.hpp: no context, no HIP call)
 //   capi_comm.cpp      RCCL communicator, the one-hop exchange's set-up, the charge sum over ranks
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "../../include/pic1dp_hip.h"
+#include "call_plan.hpp"
 #include "context_plan.hpp"
 #include "device_mem.hpp"
 #include "kernels.hpp"
@@ -65,67 +67,6 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int64_t kHistCap = 1 << 20;
-// ---------------------------------------------------------------------------
-// The call sites' state (capi_step.cpp "lazy call sites").  Two variables, each an enum, and a table of
-// the pairs that can occur -- until round 6 this was lz, half_pair, half_solved and cd_lazy, 4 x 2 x 2 x 6 combinations of
-// which 20 are legal, policed from outside by pic1dp_hip_check_state; now an illegal one cannot be stored (set_call_state).
-//
-// Seq: where the host stands in the reference's sequence push(1), collect_charge, solve_field, push(2), collect_charge,
-// solve_field of a time step (src/pic1dp.F90:79-90), and -- the "Pair" states, one rank, six sums -- whether the half
-// step is being served from the PREVIOUS step's pair solve: the half-step field then lies in d_Ehn / d_mode_h,
-// field_electric still holds the step-start field, d_E0 is not filled.
-enum class Seq : uint8_t {
-  Clean,            // memory is what eager calls would have left; nothing noted
-  Push1,            // push(1) noted
-  Half,             // ... and its collect_charge served (k_step_half ran, or the prediction was taken); the half-step markers are not in memory
-  HalfPair,         // Half, served from the pair solve: nothing was launched; the host has not yet called solve_field for the half step
-  HalfPairSolved,   // ... and now it has: what it may SEE from here on is the half-step field (every reader settles first)
-  Push2,            // push(2) noted after Half
-  Push2Pair,        // push(2) noted after HalfPair (the host skipped the half step's solve_field: it pushes with the old field)
-  Push2PairSolved,  // push(2) noted after HalfPairSolved: the next collect_charge runs k_step_one with E0 = field_electric, Eh = d_Ehn
-  N
-};
-// Owed: what collect_charge has left to the launch of the solve_field that follows (one launch less per sub-step)
-enum class Owed : uint8_t {
-  Nothing,         // field_chargeden is current
-  Scale,           // d_charge holds the summed charge1: the scaling into chargeden
-  SumScale,        // (one rank) the species accumulators hold the deposits: species sum + scaling -- with a usable six-sum prediction: the pair solve
-  PredTiles,       // (one rank, tiles) the prediction accumulators hold the half-step charge as coefficients: combine + sum + scale
-  PredSums,        // (one rank, six sums) the kept mode's content of chargeden follows from the six sums
-  AdoptHalfField,  // nothing to launch: field_electric / its kept mode / chargeden <- what the pair solve left in d_Ehn / d_mode_h / d_cd_h
-  N
-};
-enum { LZ_CLEAN = 0, LZ_PUSH1, LZ_HALF, LZ_PUSH2 };   // the four positions of the sequence (Seq without the pair's colours)
-constexpr int lz_of(Seq s) {
-  return s == Seq::Clean ? LZ_CLEAN : s == Seq::Push1 ? LZ_PUSH1 : (s == Seq::Half || s == Seq::HalfPair || s == Seq::HalfPairSolved) ? LZ_HALF : LZ_PUSH2;
-}
-constexpr bool pair_of(Seq s) { return s == Seq::HalfPair || s == Seq::HalfPairSolved || s == Seq::Push2Pair || s == Seq::Push2PairSolved; }
-constexpr bool solved_of(Seq s) { return s == Seq::HalfPairSolved || s == Seq::Push2PairSolved; }
-// the same position with the pair settled (settle_half_pair: memory as the eager calls leave it)
-constexpr Seq unpaired(Seq s) { return lz_of(s) == LZ_HALF ? Seq::Half : lz_of(s) == LZ_PUSH2 ? Seq::Push2 : s; }
-// push(2) noted at a half step
-constexpr Seq push2_noted(Seq s) { return s == Seq::HalfPair ? Seq::Push2Pair : s == Seq::HalfPairSolved ? Seq::Push2PairSolved : Seq::Push2; }
-// Which (Seq, Owed) pairs occur.  Scale / SumScale: right behind a collect_charge (every other call that looks at the
-// charge settles it first, materialize_cd).  PredTiles / PredSums: behind the collect_charge of a noted push(1) -- and
-// still owed after a look at the MARKERS has put the half-step state into memory (particles_download materialises the
-// markers, not the charge: Clean with a prediction owed; the fuzz campaign of round 6 found that one, 5 seeds in 4 500).
-// AdoptHalfField is set with HalfPair and outlives it when a look at the field settles the pair before solve_field came
-// (the field is then adopted by copying); it ends with the solve_field of the half step, hence never with a Solved state.
-// It is made for the half-step charge density, so it never outlives the half step: whatever puts the markers into memory
-// while it is owed deposits that charge density for real instead (materialize -> rebuild_half_step_chargeden) -- never
-// Clean or Push1 -- and whatever writes field_chargeden drops it (cd_version, pic1dp_hip_check_state).
-constexpr bool kCallStateLegal[static_cast<int>(Seq::N)][static_cast<int>(Owed::N)] = {
-    //                   Nothing Scale  SumScale PredTiles PredSums Adopt
-    /* Clean           */ {true, true,  true,    true,     true,    false},
-    /* Push1           */ {true, false, false,   false,    false,   false},
-    /* Half            */ {true, true,  true,    true,     true,    true},
-    /* HalfPair        */ {false, false, false,  false,    false,   true},
-    /* HalfPairSolved  */ {true, false, false,   false,    false,   false},
-    /* Push2           */ {true, false, false,   false,    false,   true},
-    /* Push2Pair       */ {false, false, false,  false,    false,   true},
-    /* Push2PairSolved */ {true, false, false,   false,    false,   false},
-};
-
 struct Species {
   int64_t nalloc = 0, np = 0;
   PSet set[2] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
@@ -195,7 +136,7 @@ struct pic1dp_ctx {
   bool charge_pending = false;  // charge_local ran, waiting for charge_reduced
   // Where the host stands in the reference's six calls push(1), collect_charge, solve_field, push(2), collect_charge,
   // solve_field, by the calls alone (eager call sites note no push, and after the second collect_charge nothing is noted
-  // either): 0 between time steps, 1 ... 5 after the first ... fifth call.  Read by checkpoint_write only (capi_step.cpp call_phase_*).
+  // either): 0 between time steps, 1 ... 5 after the first ... fifth call.  Read by checkpoint_write's plan only (call_plan.cpp Call::Checkpoint).
   int call_phase = 0;
   // field
   double *d_rho_sp = nullptr, *d_charge = nullptr, *d_chargeden = nullptr, *d_E = nullptr;
@@ -237,25 +178,27 @@ struct pic1dp_ctx {
   // prediction into d_Ehn / d_mode_h.  The next push(1) / collect_charge / solve_field then launch nothing: the
   // "Pair" states of Seq say that the half-step field lies in d_Ehn (field_electric still holds the step-start field, d_E0 is
   // not filled), the "Solved" ones that the host has called solve_field for it -- what it may look at from then on is the
-  // half-step field, so every inspection first settles (capi_step.cpp settle_half_pair: copies, memory as eager calls leave it).
+  // half-step field, so every inspection first settles (call_plan.cpp settle_half_pair: copies, memory as eager calls leave it).
   // cfg.call_pair 0: the three launches per step of rounds 2-4.
-  // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step): materialize_cd()
-  // before anything else looks at charge, chargeden or the accumulators.
+  // collect_charge leaves its last step to the solve_field that follows (one launch less per sub-step): settled (call_plan.cpp
+  // materialize_cd) before anything else looks at charge, chargeden or the accumulators.
+  // The machine's variables -- seq, owed, e_step_start, cd_kept_mode_only, adopt_cd_version, charge_pending[_pred], call_phase,
+  // eh_modes -- are read by capi_step.cpp's bridge (call_state_of) and written by its store alone: every other unit asks call_site().
   Owed owed = Owed::Nothing;
   // field_chargeden holds only the kept mode's content of the half-step charge density (collect_charge after a
   // noted push(1) served from the six sums, pred_kind 2): all solve_field looks at, but not what the reference
-  // holds there.  get_field rebuilds the full vector on one rank (rebuild_half_step_chargeden); cleared by
+  // holds there.  get_field rebuilds the full vector on one rank (call_plan.cpp rebuild_half_step_chargeden); cleared by
   // everything that writes field_chargeden.
   bool cd_kept_mode_only = false;
   // field_chargeden as the eager calls leave it changes with every collect_charge, charge_reduced, set_chargeden, substep and
   // step: cd_version counts those calls, adopt_cd_version is its value when the collect_charge set AdoptHalfField -- the
   // adoption stands for a solve from THAT charge density and only holds while the two agree
   uint64_t cd_version = 1, adopt_cd_version = 0;
-  Seq seq = Seq::Clean;          // written by set_call_state only (capi_step.cpp)
+  Seq seq = Seq::Clean;          // (call_plan.hpp) written by set_call_state only (capi_step.cpp)
   // The collect_charge of a push(2) noted after a pair-solved half step (Push2PairSolved) runs the whole step with
   // E0 = field_electric and leaves field_electric holding the STEP-START field, the kept modes too: the solve_field that
   // follows overwrites both.  Everything that reads them before it first copies the half-step field (d_Eh / d_mode_h) in
-  // -- what the eager calls hold there (settle_step_start_field).
+  // -- what the eager calls hold there (call_plan.cpp settle_step_start_field).
   bool e_step_start = false;
   double *d_E0 = nullptr;        // field the noted push(1) saw
   double *d_rho_dummy = nullptr; // accumulator of a wrap-only deposit
@@ -339,19 +282,13 @@ inline bool fp64_rank_sum(const pic1dp_ctx *c) { return c->charge_sum == 0 && se
 int ensure_second_set(pic1dp_ctx *c);     // the second slab (RK ping-pong set; re-packing target of the optimiser)
 int put_range(pic1dp_ctx *c, double *arr, int64_t off, const double *host, int64_t cnt);
 int get_range(pic1dp_ctx *c, const double *arr, int64_t off, double *host, int64_t cnt);
-// ---- capi_step.cpp (the hot path and the state machine of the lazy call sites) ----
-int require_loaded(pic1dp_ctx *c);        // markers loaded, no charge_local pending; memory as eager calls would have left it
-int materialize(pic1dp_ctx *c);           // a noted push becomes memory
-int materialize_cd(pic1dp_ctx *c);        // what collect_charge left to the next solve_field becomes field_chargeden
-int rebuild_half_step_chargeden(pic1dp_ctx *c);  // the whole vector where only the kept mode's content was formed
+// ---- capi_step.cpp (the hot path and the executor of the lazy call sites' state machine) ----
+// THE entry of everything that intrudes on the call sites' sequence: the plan of this kind of call (call_plan.hpp Call) in
+// the state the context is in, its actions enqueued, the state that follows stored; a refusal is the error returned.
+// who: the caller's name where the refusal's message names it; field_differs: Call::SwitchField's question
+int call_site(pic1dp_ctx *c, Call call, const char *who = nullptr, bool field_differs = false);
+int require_loaded(pic1dp_ctx *c);        // call_site(Call::Markers): markers loaded, no charge_local pending; memory as eager calls would have left it
 void field_written(pic1dp_ctx *c, bool by_solve);  // d_E changed: versions, what a noted push may still assume
-int set_call_state(pic1dp_ctx *c, Seq seq, Owed owed);  // the one writer of the call sites' state: refuses pairs that cannot occur
-int set_seq(pic1dp_ctx *c, Seq seq);
-int set_owed(pic1dp_ctx *c, Owed owed);
-int settle_half_pair(pic1dp_ctx *c);      // call sites: the half-step field the pair solve left aside becomes field_electric (ctx.hpp half_pair)
-int settle_field_view(pic1dp_ctx *c);     // ... for readers of the field only
-int settle_step_start_field(pic1dp_ctx *c);  // field_electric <- the half-step field the second collect_charge left aside (e_step_start)
-int adopt_half_field(pic1dp_ctx *c);
 // Everything a checkpoint file does not carry put into ONE defined state: checkpoint_write and
 // checkpoint_read both end here, so the writing context and one restored from its file continue identically
 int reset_derived_state(pic1dp_ctx *c);

@@ -111,9 +111,8 @@ int pic1dp_hip_charge_quantum(const pic1dp_input *in, int32_t ispecies, int32_t 
 int pic1dp_hip_set_charge_sum(pic1dp_ctx *c, int32_t kind) {
   CHECK_CTX(c);
   if (kind != 0 && kind != 1) return fail(PIC1DP_ERR_ARG, "charge sum must be 0 (FP64 atomics) or 1 (exact)");
-  if (c->seq != Seq::Clean || c->owed != Owed::Nothing || c->charge_pending || c->fused_pending)
-    return fail(PIC1DP_ERR_STATE, "set_charge_sum while a push, a charge or a solve is pending: call it between time steps");
-  HIP_TRY(hipSetDevice(c->device));
+  if (c->fused_pending) return fail(PIC1DP_ERR_STATE, "set_charge_sum while a push, a charge or a solve is pending: call it between time steps");
+  if (int rc = call_site(c, Call::BetweenSteps, "set_charge_sum")) return rc;
   if (kind == 1) {
     for (int s = 0; s < c->in.nspecies; ++s) {
       int32_t e = 0;

@@ -1,11 +1,12 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py, tests/test_step_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_step_plan_host.py, tests/test_call_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 #include <cstdio>
 
 #include "../../include/pic1dp_probe.h"
+#include "call_plan.hpp"
 #include "context_plan.hpp"
 #include "field_lds.hpp"
 #include "launch_policy.hpp"
@@ -234,5 +235,32 @@ extern "C" int pic1dp_probe_host_step_plan(const pic1dp_input *in, const pic1dp_
   for (int64_t v : {int64_t(w.substeps), int64_t(w.finish_pending), int64_t(w.diag), int64_t(w.pred), int64_t(w.fused_in), int64_t(w.adopt_eh),
                     int64_t(w.half_pass), int64_t(w.half_eh_modes), int64_t(w.fuse_out)})
     *o++ = v;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_call_plan(const int32_t st[9], const int32_t mo[14], const int32_t caps[8], int32_t call, int32_t out[64]) {
+  if (!st || !mo || !caps || !out || call < 0 || call >= static_cast<int>(Call::N)) return 1;
+  CallState s;
+  s.seq = static_cast<Seq>(st[0]), s.owed = static_cast<Owed>(st[1]);
+  s.e_step_start = st[2] != 0, s.cd_kept_mode_only = st[3] != 0, s.adopt_current = st[4] != 0;
+  s.charge_pending = st[5] != 0, s.charge_pending_pred = st[6] != 0;
+  s.call_phase = static_cast<int8_t>(st[7]), s.eh_modes = static_cast<int8_t>(st[8]);
+  CallMoment m;
+  m.lazy_calls = mo[0] != 0, m.call_pair = mo[1] != 0, m.loaded = mo[2] != 0, m.several_ranks = mo[3] != 0, m.fp64_rank_sum = mo[4] != 0;
+  m.charge_sum = mo[5], m.pred_kind = mo[6], m.tab_lds = mo[7] != 0;
+  m.field_differs = mo[8] != 0, m.pred_usable = mo[9] != 0, m.eh_current = mo[10] != 0, m.modes_current = mo[11] != 0;
+  m.optimize_due_any = mo[12] != 0, m.output_follows = mo[13] != 0;
+  StepCaps k{};
+  k.dft_paths = caps[0] != 0, k.six_sums_one_mode = caps[1] != 0, k.modes_fit_field_kernel = caps[2] != 0, k.predict_capable = caps[3] != 0;
+  k.diag_in_step = caps[4] != 0, k.lazy_calls_ok = caps[5] != 0, k.pair_serves_collect = caps[6] != 0, k.pair_in_solve_field = caps[7] != 0;
+  const CallPlan p = plan_call(s, m, k, static_cast<Call>(call));
+  for (int i = 0; i < 64; ++i) out[i] = 0;
+  const CallState &n = p.next;
+  const int32_t head[14] = {static_cast<int32_t>(p.refusal), p.refused_after, static_cast<int32_t>(p.bad_seq), static_cast<int32_t>(p.bad_owed),
+                            static_cast<int32_t>(n.seq), static_cast<int32_t>(n.owed), n.e_step_start, n.cd_kept_mode_only, n.adopt_current,
+                            n.charge_pending, n.charge_pending_pred, n.call_phase, n.eh_modes, p.n};
+  for (int i = 0; i < 14; ++i) out[i] = head[i];
+  for (int i = 0; i < p.n; ++i) out[14 + 2 * i] = static_cast<int32_t>(p.act[i]), out[15 + 2 * i] = p.arg[i];
+  out[63] = call_state_invariants(n, m, k) == nullptr;
   return 0;
 }

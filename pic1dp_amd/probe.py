@@ -78,6 +78,7 @@ SIGNATURES = {
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
     "pic1dp_probe_host_settings": [_I32, _D],
     "pic1dp_probe_host_step_plan": [C.c_void_p, C.c_void_p, C.POINTER(StepQuery), _I64, C.c_void_p],
+    "pic1dp_probe_host_call_plan": [_I32, _I32, _I32, C.c_int32, _I32],
     "pic1dp_probe_host_load_launch": [C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_plain_chunks": [C.c_int64, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_write_stream": [C.c_int32, C.c_int64, C.c_int32, _D],
@@ -410,6 +411,49 @@ def host_step_plan(inp, nranks=1, npe=0, rank=0, np_=None, pow2=None, one_exp=No
     caps, markers = dict(zip(STEP_CAPS, v[:13])), dict(zip(STEP_MARKERS, v[13:25]))
     markers["species"] = [dict(zip(STEP_SPECIES, v[25 + 9 * s:34 + 9 * s]), name=names[s].value.decode()) for s in range(inp.nspecies)]
     return dict(caps=caps, markers=markers, solve=dict(zip(STEP_SOLVE, v[97:103])), whole=dict(zip(STEP_WHOLE, v[103:112])))
+
+
+CALL_STATE = ("seq", "owed", "e_step_start", "cd_kept_mode_only", "adopt_current", "charge_pending", "charge_pending_pred", "call_phase",
+              "eh_modes")
+CALL_MOMENT = ("lazy_calls", "call_pair", "loaded", "several_ranks", "fp64_rank_sum", "charge_sum", "pred_kind", "tab_lds",
+               "field_differs", "pred_usable", "eh_current", "modes_current", "optimize_due_any", "output_follows")
+CALL_CAPS = ("dft_paths", "six_sums_one_mode", "modes_fit_field_kernel", "predict_capable", "diag_in_step", "lazy_calls_ok",
+             "pair_serves_collect", "pair_in_solve_field")
+CALL_MOMENT_DEFAULTS = dict(lazy_calls=1, call_pair=1, loaded=1)
+
+
+# call_plan.hpp enum Call and enum Act, in order
+CALL_KINDS = ("push1", "push2", "collect_charge", "charge_local", "charge_reduced", "charge_local_exact", "charge_exact_handed_out",
+              "charge_reduced_exact", "solve_field", "markers", "read_markers", "whole_steps", "substep1", "substep2", "read_field",
+              "get_field", "get_field_cd", "output_all", "output_all_cd", "write_electric", "write_chargeden", "replace_markers",
+              "upload_markers", "switch_field", "between_steps", "checkpoint")
+CALL_ACTS = ("save_step_start_field", "adopt_half_field", "adopt_half_modes", "copy_eh_to_e", "push_eager_1", "push_eager_1_from_e0",
+             "push_eager_2", "wrap_only", "deposit", "half_pass", "swap_eh", "full_pass", "fx_settle", "reduce_charge", "chargeden",
+             "chargeden_sum", "pred_chargeden", "pred_chargeden_summed", "pred_combine", "pred_to_charge", "pred_reduce", "charge_local",
+             "fx_to_rho", "solve_pair", "solve_pred_tiles", "solve_pred_sums", "solve_plain", "state_version", "cd_version",
+             "field_written_by_solve", "call_pair_skip", "pred_consumed", "mark_eh_current", "span_collect", "span_field", "span_end")
+
+
+def host_call_plan(call, state=None, moment=None, caps=None):
+    """what a call of the call sites' state machine enqueues and which state follows (csrc/call_plan.hpp plan_call), on the
+    host: dict(refusal, refused_after, bad=(seq, owed), next=the state that follows, acts=[(name, argument)],
+    invariants_hold).  call: its name (CALL_KINDS) or index; state / moment / caps: dicts of the fields of CALL_STATE /
+    CALL_MOMENT / CALL_CAPS that are not 0 (moment: lazy call sites with the pair, markers loaded unless given)"""
+    calls, acts = CALL_KINDS, CALL_ACTS
+    idx = calls.index(call) if isinstance(call, str) else int(call)
+    moment = dict(CALL_MOMENT_DEFAULTS, **(moment or {}))
+    for given, known in ((state or {}, CALL_STATE), (moment, CALL_MOMENT), (caps or {}, CALL_CAPS)):
+        if set(given) - set(known):
+            raise ValueError("unknown fields %r" % sorted(set(given) - set(known)))
+    st = (C.c_int32 * 9)(*[int((state or {}).get(n, 0)) for n in CALL_STATE])
+    mo = (C.c_int32 * 14)(*[int(moment.get(n, 0)) for n in CALL_MOMENT])
+    ca = (C.c_int32 * 8)(*[int((caps or {}).get(n, 0)) for n in CALL_CAPS])
+    out = (C.c_int32 * 64)()
+    if load().pic1dp_probe_host_call_plan(st, mo, ca, idx, out) != 0:
+        raise ValueError("pic1dp_probe_host_call_plan: no such kind of call")
+    v = list(out)
+    return dict(refusal=v[0], refused_after=v[1], bad=(v[2], v[3]), next=dict(zip(CALL_STATE, v[4:13])),
+                acts=[(acts[v[14 + 2 * i]], v[15 + 2 * i]) for i in range(v[13])], invariants_hold=v[63])
 
 
 def host_load_launch(nalloc, num_cu=256):

@@ -18,7 +18,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKLOADS = {"headline": [], "c2": ["--config", "c2"], "share": ["--particles", "12500000"]}
+WORKLOADS = {"headline": [], "c2": ["--config", "c2"], "share": ["--particles", "12500000"],
+             # through the three call sites per sub-step (round 31: what a call's plan costs the host)
+             "c2_calls": ["--config", "c2", "--unfused"], "small_calls": ["--unfused", "--particles", "200000"]}
 
 
 def find(d, key):
