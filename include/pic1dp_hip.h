@@ -886,6 +886,60 @@ int pic1dp_hip_host_zoom(const pic1dp_input *in, int32_t ispecies, const pic1dp_
                          int64_t rejected[3]);                                   /* host only: the rule on HOST arrays */
 int pic1dp_hip_zoom_stats(pic1dp_ctx *ctx, double *ms, int64_t *passes, int64_t *rejected);
 
+/* ---- Fourier-Hermite spectrum of f and delta f, summed on the matrix unit ----------------
+ * pic1dp_hip_hermite(ctx, ispecies, which, h, out): the Hermite spectrum of the Fourier modes of one species' markers,
+ * g_{k,n} = sum_i q_i psi_n(u_i) exp(-i k x_i) -- the measure of phase mixing (Landau damping, bump-on-tail): |g_{k,n}|^2
+ * against n is the free-energy spectrum of mode k, its front moves as n ~ (k v_t t)^2, its floor is the marker noise.
+ * Evaluated per marker it is unbiased and needs no velocity grid.  It is a matrix product over the marker index,
+ * G[n][c] = sum_i Psi[n][i] Y[i][c], and is summed by the FP64 matrix unit (v_mfma_f64_16x16x4_f64). */
+typedef struct pic1dp_hermite {
+  int32_t nherm, nmodes;   /* Hermite rows n = 0 .. nherm - 1; Fourier modes listed in modes[0 .. nmodes) */
+  int32_t modes[8];
+  double v0, vt;           /* u = (v - v0) / vt */
+} pic1dp_hermite;
+/*   - which is 1 (weights p: total f), 2 (weights w: delta f) or 3 (both, p first).
+ *   - 1 <= nherm <= 256; 1 <= nmodes and nsets * nmodes <= 8 (sixteen columns); the modes distinct, 0 <= m <= nx / 2; vt
+ *     finite and > 0, v0 finite.  Anything else is PIC1DP_ERR_ARG, and so are which & 2 on a full-f context (deltaf = 0), an
+ *     unknown species and a null pointer; nothing is written then.
+ *   - out[((j * nmodes + a) * 2 + t) * nherm + n], j the selected weight set, a the index into modes, t = 0 the cos sum C,
+ *     1 the sin sum S.  pic1dp_hip_hermite_len(h, which, &n): n = nsets * nmodes * 2 * nherm.  Host only (the modes are
+ *     not held against nx there).
+ * For every valid marker i < np of the species, on the state a pic1dp_hip_particles_download at that moment would return:
+ *     px = wrap(x)                                   the deposit's wrap (src/pic1dp_interaction.F90:102-104), NOT stored back
+ *     u  = (v - v0) * ivt                            ivt = 1.0 / vt, computed once on the host
+ *     psi_0 = 1;  psi_1 = u;  psi_(n+1) = (u * psi_n) * ra[n] - psi_(n-1) * rb[n]
+ *         ra[n] = 1.0 / sqrt((double)(n + 1)),  rb[n] = sqrt((double)n) / sqrt((double)(n + 1)), IEEE sqrt and division
+ *         (pic1dp_hip_hermite_tables hands them out); every product and the difference rounded on their own.  These are the
+ *         orthonormal probabilists' Hermite polynomials: the integral of psi_m psi_n exp(-u^2 / 2) / sqrt(2 pi) is delta_mn.
+ *     theta = kk[a] * px                             kk[a] = 2.0 * pi / lx * (double)modes[a], the loader's expression
+ *     (s, c) = sincos(theta)                         the device library's
+ *     y_cos = q * c;  y_sin = q * s                  q = p and / or w
+ *     out[j][a][0][n] += psi_n * y_cos;  out[j][a][1][n] += psi_n * y_sin
+ *   - g_{k,n} = C - i S is the coefficient of exp(+i k x) psi_n(u) exp(-u^2 / 2) / sqrt(2 pi) in the species' f (q = p) or
+ *     delta f (q = w).  For mode 0 the sin row is exactly 0.
+ *   - Tail slots (i >= np) do not count, whatever they hold (a NaN included).
+ *   - The sums are FP64; their order, and whether a product is fused into its addition, are free.  With n_p valid markers, T
+ *     the float64 terms psi_n * y and B the partial sums the launch merges (pic1dp_probe_host_hermite_plan says how many):
+ *     |out - exact sum T| <= (n_p + B + 16) 2^-53 sum |T| (1 + 2^-20); the 16 covers sincos within 4 ulp and the two products.
+ *     A non-finite marker makes sums non-finite; there is no counter and no trap.
+ *   - Normalisation.  The sums are raw and LOCAL to the context: the sum over ranks is an element-wise addition by the host.
+ *   - pic1dp_hip_set_diag_sum and pic1dp_hip_set_charge_sum do not affect the call, and the checkpoint carries nothing of it.
+ * When the call may come.  The rule of pic1dp_hip_moments.  Between time steps it launches its own pass and nothing else and
+ * changes nothing; inside a time step (a push noted) the noted push becomes memory first.
+ * Memory.  4 KiB of tables and 32 KiB of sums on the device, allocated at the first call and kept by the context.
+ * Cost: one pass over x, v and p and / or w (24 or 32 B per marker), nmodes sincos per marker, and one matrix instruction
+ * per marker and 64 Hermite rows (nherm is rounded up to 64, 128 or 256 rows of work).
+ * pic1dp_hip_host_hermite: the same terms on HOST arrays of np valid markers (p read where which & 1, w where which & 2), with
+ *   the host library's sincos, summed in marker order in doubles.  Host only, no device, no context.
+ * pic1dp_hip_hermite_stats: the passes launched so far and their device milliseconds while kernel stats were enabled
+ *   (pic1dp_hip_kernel_stats keeps its rows 0..22). */
+int pic1dp_hip_hermite_len(const pic1dp_hermite *h, int32_t which, int64_t *n);      /* host only */
+int pic1dp_hip_hermite(pic1dp_ctx *ctx, int32_t ispecies, int32_t which, const pic1dp_hermite *h, double *out);
+int pic1dp_hip_host_hermite(const pic1dp_input *in, int32_t ispecies, int32_t which, const pic1dp_hermite *h,
+                            int64_t np, const double *x, const double *v, const double *p, const double *w, double *out);  /* host only */
+int pic1dp_hip_hermite_tables(int32_t nherm, double *ra, double *rb);                /* host only */
+int pic1dp_hip_hermite_stats(pic1dp_ctx *ctx, double *ms, int64_t *passes);
+
 /* what pic1dp_hip_checkpoint_info reports of a file besides the input */
 typedef struct pic1dp_checkpoint_info {
   int32_t format_version;

@@ -155,6 +155,15 @@ int pic1dp_probe_host_power_plan_exact(int32_t nx, int32_t nx_opd, int32_t nv_op
 int pic1dp_probe_host_zoom_plan(int32_t nxb, int32_t nvb, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
                                 int32_t pass_cap, int64_t out[515]);
 
+/* The pass of one pic1dp_hip_hermite call (launch_policy.hpp hermite_plan), on the HOST: out = {workgroups (0: arguments out
+ * of range, w asked of a full-f run), threads, non-temporal loads, dynamic LDS bytes, blocks of sixteen Hermite rows in the
+ * accumulators (4, 8 or 16), the partial sums the launch merges into one output word}.  Nonzero: null argument. */
+int pic1dp_probe_host_hermite_plan(int32_t nherm, int32_t nmodes, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
+                                   int64_t out[6]);
+/* The device's Hermite recurrence alone (device_hermite.hpp herm_all, what k_hermite runs), on the current device:
+ * out[i * nherm + k] = psi_k(u[i]), i < n, k < nherm <= 256. */
+int pic1dp_probe_hermite(const double *u, int64_t n, int32_t nherm, double *out);
+
 /* The count and write passes of a selection over np valid markers (launch_policy.hpp select_plan), on the HOST: out = {pairs
  * of a chunk, chunks, workgroups, threads, non-temporal loads, threads of the prefix sum's one workgroup}.  Chunk c holds the
  * logical pairs [c * pairs, min((c + 1) * pairs, np / 2)), and the odd last marker (np odd) belongs to the last chunk; np = 0:

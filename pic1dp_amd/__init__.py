@@ -10,8 +10,8 @@ from . import _lib
 
 _lib.load()  # fail loudly, now, if the HIP library is absent
 
-from ._lib import Input, Layout, Pic1dpError, Select, Zoom  # noqa: E402,F401
-from .engine import Pic1dp, charge_quantum, checkpoint_info, checkpoint_verify, host_digest, host_select, load_origin, load_uniforms, device_count, diag_convert, diag_quanta, diag_quantise, field_transform_supported, make_input, moments_convert, moments_limbs_len, moments_quanta, power_convert, power_limbs_len, power_quantum, select_thin, tuning_build, host_zoom, make_zoom, zoom_convert, zoom_len  # noqa: E402,F401
+from ._lib import Input, Layout, Pic1dpError, Hermite, Select, Zoom  # noqa: E402,F401
+from .engine import Pic1dp, charge_quantum, checkpoint_info, checkpoint_verify, host_digest, host_select, load_origin, load_uniforms, device_count, diag_convert, diag_quanta, diag_quantise, field_transform_supported, make_input, moments_convert, moments_limbs_len, moments_quanta, power_convert, power_limbs_len, power_quantum, select_thin, tuning_build, host_zoom, make_zoom, zoom_convert, zoom_len, make_hermite, hermite_len, host_hermite, hermite_tables, hermite_functions, hermite_series  # noqa: E402,F401
 from . import parallel  # noqa: E402,F401
 
-__all__ = ["Pic1dp", "make_input", "checkpoint_info", "checkpoint_verify", "host_digest", "host_select", "select_thin", "host_zoom", "zoom_convert", "zoom_len", "make_zoom", "Zoom", "load_origin", "load_uniforms", "charge_quantum", "diag_quanta", "diag_quantise", "diag_convert", "moments_quanta", "moments_limbs_len", "moments_convert", "power_quantum", "power_limbs_len", "power_convert", "device_count", "field_transform_supported", "tuning_build", "Input", "Layout", "Select", "Pic1dpError", "parallel"]
+__all__ = ["Pic1dp", "make_input", "checkpoint_info", "checkpoint_verify", "host_digest", "host_select", "select_thin", "host_zoom", "zoom_convert", "zoom_len", "make_zoom", "Zoom", "make_hermite", "hermite_len", "host_hermite", "hermite_tables", "hermite_functions", "hermite_series", "Hermite", "load_origin", "load_uniforms", "charge_quantum", "diag_quanta", "diag_quantise", "diag_convert", "moments_quanta", "moments_limbs_len", "moments_convert", "power_quantum", "power_limbs_len", "power_convert", "device_count", "field_transform_supported", "tuning_build", "Input", "Layout", "Select", "Pic1dpError", "parallel"]

@@ -88,6 +88,11 @@ class Zoom(C.Structure):
                 ("nxb", C.c_int32), ("nvb", C.c_int32)]
 
 
+class Hermite(C.Structure):
+    """struct pic1dp_hermite: the Hermite rows, the Fourier modes and the scaling u = (v - v0) / vt of a spectrum"""
+    _fields_ = [("nherm", C.c_int32), ("nmodes", C.c_int32), ("modes", C.c_int32 * 8), ("v0", C.c_double), ("vt", C.c_double)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _INP = C.POINTER(Input)
@@ -205,6 +210,11 @@ SIGNATURES = {
     "pic1dp_hip_zoom": [_P, C.c_int32, C.POINTER(Zoom), C.c_int32, _P],
     "pic1dp_hip_host_zoom": [_INP, C.c_int32, C.POINTER(Zoom), C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P],
     "pic1dp_hip_zoom_stats": [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "pic1dp_hip_hermite_len": [C.POINTER(Hermite), C.c_int32, C.POINTER(C.c_int64)],
+    "pic1dp_hip_hermite": [_P, C.c_int32, C.c_int32, C.POINTER(Hermite), _P],
+    "pic1dp_hip_host_hermite": [_INP, C.c_int32, C.c_int32, C.POINTER(Hermite), C.c_int64, _P, _P, _P, _P, _P],
+    "pic1dp_hip_hermite_tables": [C.c_int32, _P, _P],
+    "pic1dp_hip_hermite_stats": [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
     "pic1dp_hip_state_digest": [_P, _P],
     "pic1dp_hip_host_digest": [_P, C.c_int64, C.POINTER(C.c_uint64)],
     "pic1dp_hip_checkpoint_write": [_P, C.c_char_p],

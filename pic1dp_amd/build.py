@@ -27,14 +27,14 @@ STEP_DISTS = (0, 1, 2, 3, 4, 5)
 # (source, extra flags, object stem)
 PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_step_d%d" % d) for d in STEP_DISTS] + [
     ("kernels_push.hip", [], "kernels_push"), ("kernels_field.hip", [], "kernels_field"), ("kernels_fft.hip", [], "kernels_fft"),
-    ("kernels_diag.hip", [], "kernels_diag"), ("kernels_moments.hip", [], "kernels_moments"), ("kernels_power.hip", [], "kernels_power"), ("kernels_select.hip", [], "kernels_select"), ("kernels_zoom.hip", [], "kernels_zoom"), ("kernels_digest.hip", [], "kernels_digest"), ("kernels_load.hip", [], "kernels_load"), ("kernels_opt.hip", [], "kernels_opt"), ("step_dispatch.cpp", [], "step_dispatch"),
-    ("capi.cpp", [], "capi"), ("capi_step.cpp", [], "capi_step"), ("launch_policy.cpp", [], "launch_policy"), ("step_plan.cpp", [], "step_plan"), ("call_plan.cpp", [], "call_plan"), ("settings.cpp", [], "settings"), ("context_plan.cpp", [], "context_plan"), ("capi_comm.cpp", [], "capi_comm"), ("capi_diag.cpp", [], "capi_diag"), ("capi_products.cpp", [], "capi_products"), ("capi_timing.cpp", [], "capi_timing"), ("capi_select.cpp", [], "capi_select"), ("select_host.cpp", [], "select_host"), ("capi_zoom.cpp", [], "capi_zoom"), ("zoom_fx.cpp", [], "zoom_fx"), ("moments_fx.cpp", [], "moments_fx"), ("power_fx.cpp", [], "power_fx"), ("load_seq.cpp", [], "load_seq"),
+    ("kernels_diag.hip", [], "kernels_diag"), ("kernels_moments.hip", [], "kernels_moments"), ("kernels_power.hip", [], "kernels_power"), ("kernels_select.hip", [], "kernels_select"), ("kernels_zoom.hip", [], "kernels_zoom"), ("kernels_hermite.hip", [], "kernels_hermite"), ("kernels_digest.hip", [], "kernels_digest"), ("kernels_load.hip", [], "kernels_load"), ("kernels_opt.hip", [], "kernels_opt"), ("step_dispatch.cpp", [], "step_dispatch"),
+    ("capi.cpp", [], "capi"), ("capi_step.cpp", [], "capi_step"), ("launch_policy.cpp", [], "launch_policy"), ("step_plan.cpp", [], "step_plan"), ("call_plan.cpp", [], "call_plan"), ("settings.cpp", [], "settings"), ("context_plan.cpp", [], "context_plan"), ("capi_comm.cpp", [], "capi_comm"), ("capi_diag.cpp", [], "capi_diag"), ("capi_products.cpp", [], "capi_products"), ("capi_timing.cpp", [], "capi_timing"), ("capi_select.cpp", [], "capi_select"), ("select_host.cpp", [], "select_host"), ("capi_zoom.cpp", [], "capi_zoom"), ("capi_hermite.cpp", [], "capi_hermite"), ("zoom_fx.cpp", [], "zoom_fx"), ("moments_fx.cpp", [], "moments_fx"), ("power_fx.cpp", [], "power_fx"), ("load_seq.cpp", [], "load_seq"),
     ("capi_optimize.cpp", [], "capi_optimize"), ("loader.cpp", [], "loader"), ("multirand.cpp", [], "multirand"),
     ("optimize.cpp", [], "optimize"), ("species.cpp", [], "species"), ("hostcheck.cpp", [], "hostcheck"), ("const_mul.cpp", [], "const_mul"),
     ("exact_charge.cpp", [], "exact_charge"), ("capi_checkpoint.cpp", [], "capi_checkpoint"), ("checkpoint.cpp", [], "checkpoint")]
 PROBE_UNITS = [("probe.hip", [], "probe"), ("optcheck.cpp", [], "optcheck"), ("policy_probe.cpp", [], "policy_probe")]
 PROBE_SHARED = ["species", "hostcheck", "const_mul", "optimize", "multirand", "launch_policy", "step_plan", "call_plan", "settings", "context_plan", "loader", "load_seq"]      # objects of the product the probe library links as well
-HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_moments.hpp", "device_power.hpp", "device_select.hpp", "select_rule.hpp", "device_zoom.hpp", "zoom_fx.hpp", "device_sweep.hpp", "device_fxsum.hpp", "fx_limbs.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "const_mul.hpp", "loader.hpp",
+HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_moments.hpp", "device_power.hpp", "device_select.hpp", "select_rule.hpp", "device_zoom.hpp", "device_hermite.hpp", "zoom_fx.hpp", "device_sweep.hpp", "device_fxsum.hpp", "fx_limbs.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "const_mul.hpp", "loader.hpp",
            "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "timing.hpp", "launch_policy.hpp", "step_plan.hpp", "call_plan.hpp", "field_lds.hpp", "settings.hpp", "context_plan.hpp", "device_mem.hpp", "digest.hpp", "checkpoint.hpp", "moments_fx.hpp", "power_fx.hpp", "load_seq.hpp", "device_load.hpp",
            os.path.join("..", "..", "include", "pic1dp_hip.h"), os.path.join("..", "..", "include", "pic1dp_probe.h")]
 

@@ -176,6 +176,15 @@ int pic1dp_hip_zoom_stats(pic1dp_ctx *c, double *ms, int64_t *passes, int64_t *r
   return 0;
 }
 
+// ... and the Hermite spectrum's
+int pic1dp_hip_hermite_stats(pic1dp_ctx *c, double *ms, int64_t *passes) {
+  CHECK_CTX(c);
+  if (int rc = ev_resolve(c->tm)) return rc;
+  if (ms) *ms = c->tm.acc_ms[kTagHermite];
+  if (passes) *passes = c->cnt.hermite_passes;
+  return 0;
+}
+
 int pic1dp_hip_kernel_bytes(pic1dp_ctx *c, int32_t which, double *read_bytes, double *written_bytes, double *carry_bytes,
                             char *name, int32_t name_len) {
   CHECK_CTX(c);

@@ -15,6 +15,7 @@
 //   capi_select.cpp    select and gather markers on the device (pic1dp_hip_select_count, _select, _gather); the rule on the
 //                      host and the thinning threshold: select_host.cpp (select_rule.hpp; no HIP call)
 //   capi_zoom.cpp      the exact phase-space histogram on a caller's window and grid (pic1dp_hip_zoom; its host arithmetic: zoom_fx.cpp, no HIP call)
+//   capi_hermite.cpp   the Fourier-Hermite spectrum of the markers, summed on the matrix unit (pic1dp_hip_hermite)
 //   capi_optimize.cpp  marker optimisation events (merge / remove / split)
 //   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
@@ -111,6 +112,7 @@ struct Counters {
   int64_t power_exact_rejected = 0;        // terms they did not sum so far (the same)
   int64_t zoom_passes = 0;                 // k_zoom passes that swept markers so far (pic1dp_hip_zoom_stats)
   int64_t zoom_rejected = 0;               // terms they did not sum so far (the same)
+  int64_t hermite_passes = 0;              // k_hermite passes launched so far (pic1dp_hip_hermite_stats)
 };
 
 }  // namespace pic1dp_host
@@ -228,6 +230,7 @@ struct pic1dp_ctx {
   // the marker products on demand (capi_products.cpp): one device buffer for whichever runs, grow-only, zeroed by every call over what it uses
   double *d_prod = nullptr;
   size_t d_prod_words = 0;                 // its capacity in 8-byte words
+  double *d_herm = nullptr;                // the Hermite spectrum's tables ra, rb [2][256] and its words [256][16] (capi_hermite.cpp; allocated at the first call)
   int chain_selftest = 0;                  // create()'s verdict on the serial sums through the matrix unit: 1 identical, 0 differs, -1 could not run
   int32_t itime = 0;
   double time = 0.0;

@@ -799,6 +799,41 @@ struct ZoomArgs {
 hipError_t launch_zoom(const double *x, const double *v, const double *p, const double *w, int64_t np, const ZoomGeom &zg,
                        int which, const ZoomArgs &a, const ZoomPass &ps, int dyn_tail, hipStream_t st);
 
+// ---- the Fourier-Hermite spectrum of the markers (kernels_hermite.hip; the definition: include/pic1dp_hip.h
+// pic1dp_hip_hermite) ----
+constexpr int HERM_MAX_N = 256, HERM_MAX_COLS = 16, HERM_MAX_MODES = 8;
+constexpr int HERM_TILE_LD = 66;   // doubles between two rows of a wave's LDS tile [16][64]: the pad that spreads the fragment reads over the banks
+constexpr size_t HERM_WAVE_LDS = sizeof(double) * 2 * 16 * HERM_TILE_LD;   // a wave's two tiles: the columns Y and a block of Psi
+// The one pass of a call (launch_policy.hpp hermite_plan; kernels_hermite.hip k_hermite): nb blocks of sixteen Hermite rows
+// in every wave's accumulator registers.  partials: the partial sums the launch merges into one output word -- every wave's
+// accumulator (into its workgroup's LDS), every workgroup's word (into memory).  blocks = 0: arguments out of range.
+struct HermitePlan {
+  int blocks, threads;
+  bool nt;          // non-temporal marker loads
+  size_t bytes;     // dynamic LDS: a wave's two tiles, threads / 64 times
+  int nb;           // 4, 8 or 16
+  int64_t partials;
+};
+// The call's constants and device words.  tab: ra[256] then rb[256] (pic1dp_hip_hermite_tables); acc: [16 nb][16] doubles,
+// acc[n * 16 + c] the sum of psi_n times column c, zeroed by the caller on the stream.  Column c = (set * nmodes + a) * 2 + t.
+struct HermiteArgs {
+  const double *tab;
+  double *acc;
+  double v0, ivt, lx;
+  double kk[HERM_MAX_MODES];
+  int nmodes, nherm;
+};
+// ra[n] = 1 / sqrt(n + 1), rb[n] = sqrt(n) / sqrt(n + 1), n < nherm: IEEE sqrt and division, one rounding each (host)
+inline void hermite_tables_host(int nherm, double *ra, double *rb) {
+  for (int n = 0; n < nherm; ++n) {
+    const double s1 = __builtin_sqrt(static_cast<double>(n + 1));
+    ra[n] = 1.0 / s1;
+    rb[n] = __builtin_sqrt(static_cast<double>(n)) / s1;
+  }
+}
+hipError_t launch_hermite(const double *x, const double *v, const double *p, const double *w, int64_t np, bool with_p, bool with_w,
+                          const HermiteArgs &a, const HermitePlan &pl, hipStream_t st);
+
 // ---- marker optimisation events (kernels_opt.hip; host side of the sequential part: optimize.hpp plan_*) ----
 // one reference rank block of a species inside the species' packed (tiled) arrays: block-local marker i lies at global
 // marker voff + i while i < nvalid0 (the block's valid markers when the event began), else at toff + (i - nvalid0) (its

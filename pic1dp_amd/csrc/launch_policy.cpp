@@ -214,6 +214,24 @@ PowerPlan power_plan_exact(int nx, int nx_opd, int nv_opd, int which, int deltaf
   return m;
 }
 
+HermitePlan hermite_plan(int nherm, int nmodes, int which, int deltaf, int64_t np, int num_cu) {
+  HermitePlan h{};
+  const int sets = which == 3 ? 2 : 1;
+  if (which < 1 || which > 3 || ((which & 2) && !deltaf) || nherm < 1 || nherm > HERM_MAX_N || nmodes < 1 ||
+      sets * nmodes > HERM_MAX_MODES || np < 0 || num_cu < 1)
+    return h;
+  h.threads = 256;
+  const int waves = h.threads / 64;
+  h.nb = nherm <= 64 ? 4 : (nherm <= 128 ? 8 : 16);
+  h.bytes = HERM_WAVE_LDS * static_cast<size_t>(waves);
+  // two workgroups fit a CU's LDS; a workgroup gets at least sixteen trips per wave before another one is started
+  const int64_t chunks = (np + 63) >> 6, per_block = static_cast<int64_t>(waves) * kHermiteMinTrips;
+  h.blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(2 * static_cast<int64_t>(num_cu), (chunks + per_block - 1) / per_block)));
+  h.nt = 8.0 * (2 + sets) * static_cast<double>(np) > 288.0 * 1048576.0;
+  h.partials = static_cast<int64_t>(h.blocks) * (waves + 1);
+  return h;
+}
+
 ZoomPlan zoom_plan(int nxb, int nvb, int which, int deltaf, int64_t np, int num_cu, int pass_cap) {
   ZoomPlan m{};
   if (which < 1 || which > 7 || ((which & 4) && !deltaf) || nxb < 1 || nvb < 1 || nxb > ZOOM_MAX_BINS || nvb > ZOOM_MAX_BINS ||

@@ -120,6 +120,18 @@ SelectPlan select_plan(int64_t np, int num_cu, int threads_req, int bpc_req);
 constexpr int kZoomPassCap = 4;
 ZoomPlan zoom_plan(int nxb, int nvb, int which, int deltaf, int64_t np, int num_cu, int pass_cap = kZoomPassCap);
 
+// ---- the Fourier-Hermite spectrum (kernels_hermite.hip; include/pic1dp_hip.h pic1dp_hip_hermite) ----
+// One pass whatever is asked: workgroups of 256 threads, every wave with its two LDS tiles (HERM_WAVE_LDS: 66 KiB a
+// workgroup, two a CU) and nb = 4 (nherm <= 64), 8 (<= 128) or 16 blocks of sixteen Hermite rows in its accumulator registers.
+// The grid: two workgroups per CU, but a workgroup sweeps at least kHermiteMinTrips chunks of 64 markers per wave before
+// another one is started (its flush is up to 16 nherm global atomics); at least one.  Non-temporal loads once the arrays
+// the pass reads (x, v and p and / or w: 24 or 32 B per marker) exceed the threshold of diag_launch.  partials: what is
+// merged into one output word, blocks * (waves + 1) -- every wave's accumulator into its workgroup's LDS word, every
+// workgroup's word into memory.  blocks = 0: an unknown `which`, w asked of a full-f run (deltaf = 0), nherm outside
+// 1..256, nmodes < 1 or more than sixteen columns.
+constexpr int kHermiteMinTrips = 16;
+HermitePlan hermite_plan(int nherm, int nmodes, int which, int deltaf, int64_t np, int num_cu);
+
 // ---- the state digest (kernels_digest.hip) ----
 // one streaming pass over the nalloc slots of a species, marker pairs as double2: workgroups of 256 threads, eight per CU
 // (no LDS to speak of, few registers: the CUs fill with waves whose loads cover the latency), never more than the pairs

@@ -135,6 +135,15 @@ extern "C" int pic1dp_probe_host_zoom_plan(int32_t nxb, int32_t nvb, int32_t whi
   return 0;
 }
 
+extern "C" int pic1dp_probe_host_hermite_plan(int32_t nherm, int32_t nmodes, int32_t which, int32_t deltaf, int64_t np, int32_t num_cu,
+                                               int64_t out[6]) {
+  if (!out) return 1;
+  const HermitePlan h = hermite_plan(nherm, nmodes, which, deltaf, np, num_cu);
+  const int64_t v[6] = {h.blocks, h.threads, h.nt, static_cast<int64_t>(h.bytes), h.nb, h.partials};
+  for (int k = 0; k < 6; ++k) out[k] = v[k];
+  return 0;
+}
+
 extern "C" int pic1dp_probe_host_select_plan(int64_t np, int32_t num_cu, int32_t threads_req, int32_t bpc_req, int64_t out[6]) {
   if (!out) return 1;
   const SelectPlan s = select_plan(np, num_cu, threads_req, bpc_req);

@@ -14,6 +14,7 @@
 #include "check_values.hpp"
 #include "device_diag.hpp"
 #include "device_fx.hpp"
+#include "device_hermite.hpp"
 #include "device_load.hpp"
 #include "device_math.hpp"
 #include "launch_policy.hpp"
@@ -281,6 +282,12 @@ __global__ void __launch_bounds__(256) k_exp_array(const double *x, double *y, i
   __syncthreads();
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = pexp(x[i]);
+}
+
+// the Hermite recurrence on its own, as k_hermite runs it (device_hermite.hpp): y[i][0 .. nherm) = psi_n(u[i]); tab: ra, rb
+__global__ void __launch_bounds__(256) k_hermite_array(const double *u, const double *tab, double *y, int64_t n, int nherm) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) herm_all(u[i], nherm, tab, y + i * nherm);
 }
 
 // -f0'/f0 on its own, as the marker kernels evaluate it: FORM 0 the reference's operation order (with the exact
@@ -632,6 +639,25 @@ int pic1dp_probe_exp(int32_t device, const double *x, double *y, int64_t n) {
   PROBE_TRY(launch_exp_array(dx, dx + n, n, nullptr));
   PROBE_TRY(hipDeviceSynchronize());
   PROBE_TRY(hipMemcpy(y, dx + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pic1dp_probe_hermite(const double *u, int64_t n, int32_t nherm, double *out) {
+  if (!u || !out || n < 0 || nherm < 1 || nherm > HERM_MAX_N) return pfail("bad argument");
+  if (n == 0) return 0;
+  DevBuf d;
+  const size_t nn = static_cast<size_t>(n);
+  PROBE_TRY(hipMalloc(&d.p, sizeof(double) * (nn + 2 * HERM_MAX_N + nn * nherm)));
+  double *du = static_cast<double *>(d.p), *dtab = du + nn, *dy = dtab + 2 * HERM_MAX_N;
+  double tab[2 * HERM_MAX_N];
+  hermite_tables_host(HERM_MAX_N, tab, tab + HERM_MAX_N);
+  PROBE_TRY(hipMemcpy(du, u, sizeof(double) * nn, hipMemcpyHostToDevice));
+  PROBE_TRY(hipMemcpy(dtab, tab, sizeof tab, hipMemcpyHostToDevice));
+  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>(1024, (n + 255) / 256));
+  PROBE_TRY(launch_kernel(k_hermite_array, dim3(blocks), dim3(256), 0, nullptr, static_cast<const double *>(du),
+                          static_cast<const double *>(dtab), dy, n, static_cast<int>(nherm)));
+  PROBE_TRY(hipDeviceSynchronize());
+  PROBE_TRY(hipMemcpy(out, dy, sizeof(double) * nn * nherm, hipMemcpyDeviceToHost));
   return 0;
 }
 

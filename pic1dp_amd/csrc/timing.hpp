@@ -14,7 +14,7 @@ namespace pic1dp_host {
 int fail(int code, const char *fmt, ...);  // (ctx.hpp: the error convention)
 
 constexpr int kTagFused = 100, kTagPush = 101, kTagDeposit = 102, kTagStepHalf = 103, kTagStepFull = 104, kTagStepOne = 106,
-              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kTagSelect = 111, kTagGather = 112, kTagPowerExact = 113, kTagZoom = 114, kNumTags = 128;
+              kTagMoments = 107, kTagMomentsExact = 108, kTagLoad = 109, kTagPower = 110, kTagSelect = 111, kTagGather = 112, kTagPowerExact = 113, kTagZoom = 114, kTagHermite = 115, kNumTags = 128;
 
 struct EvPair {
   hipEvent_t a, b;

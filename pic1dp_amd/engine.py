@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Input, Layout, Pic1dpError, Select, Zoom, check  # noqa: F401
+from ._lib import Hermite, Input, Layout, Pic1dpError, Select, Zoom, check  # noqa: F401
 
 
 def make_input(**kw):
@@ -230,6 +230,26 @@ class Pic1dp:
         out = np.zeros((_zoom_planes(which),) + _zoom_shape(z))
         check(self.L.pic1dp_hip_zoom(self._ctx, int(ispecies), C.byref(z), int(which), _ptr(out)))
         return _split_zoom(out, self.inp, z, which)
+
+    def hermite(self, ispecies=0, modes=(1,), nherm=64, v0=0.0, vt=1.0, which=3):
+        """the Fourier-Hermite spectrum g_{k,n} = sum_i q_i psi_n((v_i - v0) / vt) exp(-i k x_i) of a species' markers for
+        the Fourier modes `modes` and n < nherm, summed on the GPU's FP64 matrix unit (include/pic1dp_hip.h
+        pic1dp_hip_hermite).  which: 1 the weights p (total f), 2 the weights w (delta f), 3 both.  Returns {"total":
+        complex128 (nmodes, nherm), "pertb": ...} with only the sets asked for, each entry C - iS: the coefficient of
+        exp(+ikx) psi_n(u) exp(-u^2 / 2) / sqrt(2 pi).  |g|^2 against n is the free-energy spectrum of the mode.  The sums
+        are raw and local to this context (ranks: add element by element).  Between time steps the call changes nothing;
+        inside one it first puts a noted push into memory."""
+        h = make_hermite(modes, nherm, v0, vt)
+        out = np.zeros(_hermite_shape(h, which))
+        check(self.L.pic1dp_hip_hermite(self._ctx, int(ispecies), int(which), C.byref(h), _ptr(out)))
+        return _split_hermite(out, which)
+
+    def hermite_stats(self):
+        """(device ms of the spectrum's passes while kernel stats were enabled, passes launched so far) --
+        pic1dp_hip_hermite_stats; kernel_stats has no row for them"""
+        ms, n = C.c_double(), C.c_int64()
+        check(self.L.pic1dp_hip_hermite_stats(self._ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def zoom_local_exact(self, ispecies=0, x=None, v=None, bins=(64, 64), which=7):
         """this context's exact sums as int64 limbs of shape (nplanes, 2, nvb, nxb): [j, 0] the hi limb, [j, 1] the lo limb,
@@ -916,6 +936,79 @@ def host_zoom(inp, xs, vs, ps=None, ws=None, x=None, v=None, bins=(64, 64), whic
     check(_lib.load().pic1dp_hip_host_zoom(C.byref(inp), int(ispecies), C.byref(z), int(which), *[None if a is None else _ptr(a) for a in arrs],
                                            n, _ptr(limbs), _ptr(rej)))
     return limbs, rej
+
+
+def make_hermite(modes=(1,), nherm=64, v0=0.0, vt=1.0):
+    """struct pic1dp_hermite from the Fourier modes (at most eight), the number of Hermite rows and the scaling
+    u = (v - v0) / vt; more than eight modes are left to the library to refuse (nmodes says how many were given)"""
+    modes = [int(m) for m in modes]
+    h = Hermite(int(nherm), len(modes), (C.c_int32 * 8)(*modes[:8]), float(v0), float(vt))
+    return h
+
+
+def _hermite_shape(h, which):
+    """(nsets, nmodes, 2, nherm), or zeros for a shape the library will refuse"""
+    nsets = 2 if which == 3 else 1
+    ok = 1 <= h.nherm <= 256 and 1 <= h.nmodes and nsets * h.nmodes <= 8
+    return (nsets, h.nmodes, 2, h.nherm) if ok else (0, 0, 2, 0)
+
+
+def _split_hermite(out, which):
+    names = [n for bit, n in ((1, "total"), (2, "pertb")) if which & bit]
+    return {name: out[j, :, 0, :] - 1j * out[j, :, 1, :] for j, name in enumerate(names)}
+
+
+def hermite_len(modes=(1,), nherm=64, which=3, v0=0.0, vt=1.0):
+    """doubles pic1dp_hip_hermite hands out: nsets * nmodes * 2 * nherm (host only)"""
+    h, n = make_hermite(modes, nherm, v0, vt), C.c_int64()
+    check(_lib.load().pic1dp_hip_hermite_len(C.byref(h), int(which), C.byref(n)))
+    return n.value
+
+
+def hermite_tables(nherm):
+    """(ra, rb) of the recurrence psi_(n+1) = (u psi_n) ra[n] - psi_(n-1) rb[n]: 1 / sqrt(n + 1) and sqrt(n) / sqrt(n + 1)
+    as the library rounds them (host only)"""
+    ra, rb = np.zeros(max(int(nherm), 0)), np.zeros(max(int(nherm), 0))
+    check(_lib.load().pic1dp_hip_hermite_tables(int(nherm), _ptr(ra), _ptr(rb)))
+    return ra, rb
+
+
+def host_hermite(inp, xs, vs, ps=None, ws=None, modes=(1,), nherm=64, v0=0.0, vt=1.0, which=3, ispecies=0):
+    """the spectrum's terms on host arrays of valid markers, summed in marker order in doubles (include/pic1dp_hip.h
+    pic1dp_hip_host_hermite; no device): the raw sums, shape (nsets, nmodes, 2, nherm), [..., 0, :] cos and [..., 1, :] sin"""
+    h = make_hermite(modes, nherm, v0, vt)
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (xs, vs, ps, ws)]
+    n = arrs[0].size
+    if any(a is not None and a.size != n for a in arrs):
+        raise ValueError("the marker arrays must have one length")
+    out = np.zeros(_hermite_shape(h, which))
+    check(_lib.load().pic1dp_hip_host_hermite(C.byref(inp), int(ispecies), int(which), C.byref(h), n,
+                                              *[None if a is None else _ptr(a) for a in arrs], _ptr(out)))
+    return out
+
+
+def hermite_functions(u, nherm):
+    """psi_0 .. psi_(nherm-1), the orthonormal probabilists' Hermite polynomials, at every u by the library's recurrence in
+    numpy -- the same bits as the device's: shape (nherm,) + u.shape"""
+    u = np.asarray(u, dtype=np.float64)
+    n1 = np.arange(1, int(nherm) + 1, dtype=np.float64)
+    ra, rb = 1.0 / np.sqrt(n1), np.sqrt(n1 - 1.0) / np.sqrt(n1)
+    psi = np.empty((int(nherm),) + u.shape)
+    prev, cur = np.zeros_like(u), np.ones_like(u)
+    for n in range(int(nherm)):
+        psi[n] = cur
+        nxt = u.copy() if n == 0 else (u * cur) * ra[n] - prev * rb[n]
+        prev, cur = cur, nxt
+    return psi
+
+
+def hermite_series(g, v, v0=0.0, vt=1.0):
+    """sum_n g[n] psi_n(u) exp(-u^2 / 2) / (sqrt(2 pi) vt) at every v, u = (v - v0) / vt: the velocity profile delta f_k(v)
+    a row of Pic1dp.hermite() stands for (g real or complex, last axis n)"""
+    g = np.asarray(g)
+    u = (np.asarray(v, dtype=np.float64) - v0) * (1.0 / vt)
+    psi = hermite_functions(u, g.shape[-1])
+    return np.tensordot(g, psi, axes=([-1], [0])) * (np.exp(-0.5 * u * u) / (np.sqrt(2.0 * np.pi) * vt))
 
 
 def make_select(x=(-np.inf, np.inf), v=(-np.inf, np.inf), fraction=1.0, key=0, origin=0, thin=None):

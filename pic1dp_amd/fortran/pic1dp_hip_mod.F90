@@ -75,6 +75,12 @@ type, bind(C) :: pic1dp_zoom_t
   real(c_double) :: x_lo, x_hi, v_lo, v_hi
   integer(c_int32_t) :: nxb, nvb
 end type pic1dp_zoom_t
+! struct pic1dp_hermite: Hermite rows n < nherm, the Fourier modes modes(1:nmodes), u = (v - v0) / vt
+type, bind(C) :: pic1dp_hermite_t
+  integer(c_int32_t) :: nherm, nmodes
+  integer(c_int32_t) :: modes(8)
+  real(c_double) :: v0, vt
+end type pic1dp_hermite_t
 
 interface
   ! state digest, checkpoint and restart (include/pic1dp_hip.h; file names are C strings: trim(name) // c_null_char)
@@ -309,6 +315,49 @@ interface
     integer(c_int64_t), intent(out) :: passes, rejected
     integer(c_int) :: ierr
   end function pic1dp_hip_zoom_stats
+  ! the Fourier-Hermite spectrum of a species' markers, summed on the FP64 matrix unit: which is 1 (p), 2 (w) or 3 (both, p
+  ! first); out(nherm, 2, nmodes, sets selected) with (:, 1, a, j) the cos sums C and (:, 2, a, j) the sin sums S, g = C - i S.
+  ! The sums are raw and local to the context.  Ranks: add out element by element (MPI_SUM on MPI_DOUBLE_PRECISION)
+  function pic1dp_hip_hermite_len(h, which, n) bind(C, name="pic1dp_hip_hermite_len") result(ierr)
+    import
+    type(pic1dp_hermite_t), intent(in) :: h
+    integer(c_int32_t), value :: which
+    integer(c_int64_t), intent(out) :: n
+    integer(c_int) :: ierr
+  end function pic1dp_hip_hermite_len
+  function pic1dp_hip_hermite(ctx, ispecies, which, h, out) bind(C, name="pic1dp_hip_hermite") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_hermite_t), intent(in) :: h
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_hermite
+  ! the same terms on host arrays, summed in marker order; p / w not wanted (their set not selected): c_null_ptr
+  function pic1dp_hip_host_hermite(inp, ispecies, which, h, np, x, v, p, w, out) bind(C, name="pic1dp_hip_host_hermite") result(ierr)
+    import
+    type(pic1dp_input_t), intent(in) :: inp
+    integer(c_int32_t), value :: ispecies, which
+    type(pic1dp_hermite_t), intent(in) :: h
+    integer(c_int64_t), value :: np
+    real(c_double), intent(in) :: x(*), v(*)
+    type(c_ptr), value :: p, w
+    real(c_double), intent(inout) :: out(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_host_hermite
+  function pic1dp_hip_hermite_tables(nherm, ra, rb) bind(C, name="pic1dp_hip_hermite_tables") result(ierr)
+    import
+    integer(c_int32_t), value :: nherm
+    real(c_double), intent(inout) :: ra(*), rb(*)
+    integer(c_int) :: ierr
+  end function pic1dp_hip_hermite_tables
+  function pic1dp_hip_hermite_stats(ctx, ms, passes) bind(C, name="pic1dp_hip_hermite_stats") result(ierr)
+    import
+    type(c_ptr), value :: ctx
+    real(c_double), intent(out) :: ms
+    integer(c_int64_t), intent(out) :: passes
+    integer(c_int) :: ierr
+  end function pic1dp_hip_hermite_stats
   function pic1dp_hip_host_digest(a, n, out) bind(C, name="pic1dp_hip_host_digest") result(ierr)
     import
     real(c_double), intent(in) :: a(*)

@@ -73,6 +73,8 @@ SIGNATURES = {
     "pic1dp_probe_host_power_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_power_plan_exact": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_select_plan": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _I64],
+    "pic1dp_probe_host_hermite_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_hermite": [_D, C.c_int64, C.c_int32, _D],
     "pic1dp_probe_host_zoom_plan": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _I64],
     "pic1dp_probe_host_dist_scale": [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _I32],
     "pic1dp_probe_host_context_plan": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int64, _D],
@@ -307,6 +309,26 @@ def host_zoom_plan(nxb, nvb, which, deltaf, np_, num_cu, pass_cap=0):
     if load().pic1dp_probe_host_zoom_plan(int(nxb), int(nvb), int(which), int(deltaf), int(np_), int(num_cu), int(pass_cap), out) != 0:
         raise ValueError("pic1dp_probe_host_zoom_plan")
     return dict(selected=out[1], pass_cap=out[2], passes=[dict(zip(ZOOM_PASS_FIELDS, out[3 + 8 * i:11 + 8 * i])) for i in range(out[0])])
+
+
+HERMITE_PLAN_FIELDS = ("blocks", "threads", "nt", "bytes", "nb", "partials")
+
+
+def host_hermite_plan(nherm, nmodes, which, deltaf, np_, num_cu):
+    """the pass of one hermite call (csrc/launch_policy.hpp hermite_plan), on the host: a dict of HERMITE_PLAN_FIELDS
+    (partials: the partial sums merged into one output word -- B of the error bound); blocks 0: arguments out of range"""
+    out = (C.c_int64 * 6)()
+    if load().pic1dp_probe_host_hermite_plan(int(nherm), int(nmodes), int(which), int(deltaf), int(np_), int(num_cu), out) != 0:
+        raise ValueError("pic1dp_probe_host_hermite_plan")
+    return dict(zip(HERMITE_PLAN_FIELDS, out[:]))
+
+
+def hermite(u, nherm):
+    """psi_0 .. psi_(nherm-1) at every u by the DEVICE's recurrence (csrc/device_hermite.hpp), shape (len(u), nherm)"""
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    out = np.zeros((u.size, int(nherm)))
+    _check(load().pic1dp_probe_hermite(u.ctypes.data_as(_D), u.size, int(nherm), out.ctypes.data_as(_D)))
+    return out
 
 
 SELECT_PLAN_FIELDS = ("chunk_pairs", "nchunk", "blocks", "threads", "nt", "scan_threads")
