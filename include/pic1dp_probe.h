@@ -234,6 +234,11 @@ int pic1dp_probe_host_call_plan(const int32_t state[9], const int32_t moment[14]
  * out = {workgroups, threads, non-temporal stores, markers a workgroup takes at a time}.  Workgroup b takes the chunks b,
  * b + workgroups, ... of [0, nalloc).  Nonzero: null argument, nalloc < 0 or num_cu < 1. */
 int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int64_t out[4]);
+/* Where the owned reference blocks of one species lie in its packed arrays (pic1dp_amd/csrc/block_layout.hpp), on the HOST:
+ * from the slots blk_alloc[nblk] and the valid markers blk_np[nblk] of the blocks, out[4 nblk] = per block {voff, np, toff,
+ * ntail} -- valid markers [voff, voff + np), tail slots [toff, toff + ntail) -- and *np the species' valid markers.
+ * Nonzero: null argument or nblk < 1. */
+int pic1dp_probe_host_block_layout(const int64_t *blk_alloc, const int64_t *blk_np, int32_t nblk, int64_t *out, int64_t *np);
 /* The 64-pair chunks at the head of a species' slab that a one-pass launch accesses with plain loads and stores while the
  * rest streams non-temporally (launch_policy.hpp stream_plain_chunks), on the HOST; nt: the launch is a non-temporal one.
  * Nonzero: null argument or a negative count. */

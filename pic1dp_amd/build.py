@@ -35,7 +35,7 @@ PRODUCT_UNITS = [("kernels_step.hip", ["-DPIC1DP_STEP_DIST=%d" % d], "kernels_st
 PROBE_UNITS = [("probe.hip", [], "probe"), ("optcheck.cpp", [], "optcheck"), ("policy_probe.cpp", [], "policy_probe")]
 PROBE_SHARED = ["species", "hostcheck", "const_mul", "optimize", "multirand", "launch_policy", "step_plan", "call_plan", "settings", "context_plan", "loader", "load_seq"]      # objects of the product the probe library links as well
 HEADERS = ["kernels.hpp", "device_math.hpp", "device_field.hpp", "device_diag.hpp", "device_moments.hpp", "device_power.hpp", "device_select.hpp", "select_rule.hpp", "device_zoom.hpp", "device_hermite.hpp", "zoom_fx.hpp", "device_sweep.hpp", "device_fxsum.hpp", "fx_limbs.hpp", "device_fx.hpp", "device_xchg.hpp", "step_args.hpp", "check_values.hpp", "const_mul.hpp", "loader.hpp",
-           "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "timing.hpp", "launch_policy.hpp", "step_plan.hpp", "call_plan.hpp", "field_lds.hpp", "settings.hpp", "context_plan.hpp", "device_mem.hpp", "digest.hpp", "checkpoint.hpp", "moments_fx.hpp", "power_fx.hpp", "load_seq.hpp", "device_load.hpp",
+           "multirand.hpp", "optimize.hpp", "rccl_dyn.hpp", "ctx.hpp", "timing.hpp", "launch_policy.hpp", "step_plan.hpp", "call_plan.hpp", "field_lds.hpp", "settings.hpp", "context_plan.hpp", "device_mem.hpp", "digest.hpp", "checkpoint.hpp", "moments_fx.hpp", "power_fx.hpp", "load_seq.hpp", "device_load.hpp", "block_layout.hpp", "opt_grid.hpp",
            os.path.join("..", "..", "include", "pic1dp_hip.h"), os.path.join("..", "..", "include", "pic1dp_probe.h")]
 
 # -ffp-contract=off : products and sums round separately, like the reference's

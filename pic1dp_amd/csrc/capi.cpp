@@ -74,16 +74,24 @@ int validate(const pic1dp_input &in, const pic1dp_layout &lay) {
 
 namespace pic1dp_host {
 
-// second particle set of the RK ping-pong (sub-step kernels only): a slab of the same
-// geometry as the first (its p tiles stay unused)
+// x, v, w, p of a species lie interleaved in tiles in ONE slab (kernels.hpp "Marker storage"), the RK ping-pong set in a
+// second one of the same geometry (its p tiles stay unused)
+void wire_species(Species &S, const pic1dp_input &in) {
+  const int64_t as = slab_array_stride(S.nalloc + 2);
+  S.set[0] = PSet{S.slab[0], S.slab[0] + as, S.slab[0] + 2 * as};
+  S.p = S.slab[0] + 3 * as;
+  if (!S.slab[1]) return;
+  S.set[1].x = S.slab[1];
+  S.set[1].v = in.linear == 1 ? S.set[0].v : S.slab[1] + as;      // v is never pushed in a linear run
+  S.set[1].w = in.deltaf == 0 ? S.set[0].w : S.slab[1] + 2 * as;  // w is not evolved in a full-f run
+}
+
+// second particle set of the RK ping-pong (sub-step kernels only)
 int ensure_second_set(pic1dp_ctx *c) {
   for (Species &S : c->sp) {
     if (S.slab[1]) continue;
     HIP_TRY(c->mem.alloc(&S.slab[1], static_cast<size_t>(slab_doubles(S.nalloc + 2))));
-    const int64_t as = slab_array_stride(S.nalloc + 2);
-    S.set[1].x = S.slab[1];
-    S.set[1].v = c->in.linear == 1 ? S.set[0].v : S.slab[1] + as;      // v is never pushed in a linear run
-    S.set[1].w = c->in.deltaf == 0 ? S.set[0].w : S.slab[1] + 2 * as;  // w is not evolved in a full-f run
+    wire_species(S, c->in);
   }
   return 0;
 }
@@ -373,11 +381,7 @@ static int create_filled(pic1dp_ctx *c) {
     HIP_TRY(M.alloc(&S.slab[0], static_cast<size_t>(slab_doubles(P.nalloc + 2))));
     HIP_TRY(M.alloc(&S.fxb, 4));   // two bounds, a 64-bit count (kernel_stats 13), one word spare
     HIP_TRY(hipMemsetAsync(S.fxb, 0, 4 * sizeof(double), c->st));
-    const int64_t as = slab_array_stride(P.nalloc + 2);
-    S.set[0].x = S.slab[0];
-    S.set[0].v = S.slab[0] + as;
-    S.set[0].w = S.slab[0] + 2 * as;
-    S.p = S.slab[0] + 3 * as;
+    wire_species(S, in);
   }
   HIP_TRY(M.alloc(&c->d_charge, nx));
   HIP_TRY(M.alloc(&c->d_chargeden, nx));
@@ -609,8 +613,8 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
   for (int s = 0; s < ns; ++s) c->sp[s].np = P.np[s];
   c->imerge = P.imerge, c->iremove = P.iremove, c->isplit = P.isplit;
   c->rng_ready = false;
-  std::vector<int64_t> voff(ns, 0), toff(ns);
-  for (int s = 0; s < ns; ++s) toff[s] = c->sp[s].np;
+  std::vector<BlockLayout> lay;
+  for (int s = 0; s < ns; ++s) lay.push_back(block_layout(P.blk_alloc, P.blk_np[s]));
   std::vector<double> fxb(2 * static_cast<size_t>(ns), 0.0);
   int rc = 0;
   for (int b = 0; b < c->plan.nblk && !rc; ++b) {
@@ -621,18 +625,16 @@ int pic1dp_hip_particle_load(pic1dp_ctx *c) {
     for (int s = 0; s < ns && !rc; ++s) {
       Species &S = c->sp[s];
       load_block_species(in, s, g, n, hx, hv, hp, hw, nthreads);
-      const int64_t np = P.blk_np[s][b], nt = n - np;
-      fx_bounds_of(in, s, hp, hw, np, &fxb[2 * static_cast<size_t>(s)]);
+      const BlockSpan &B = lay[s].blk[b];
+      fx_bounds_of(in, s, hp, hw, B.np, &fxb[2 * static_cast<size_t>(s)]);
       struct {
         double *d;
         const double *h;
       } arr[4] = {{S.set[0].x, hx}, {S.set[0].v, hv}, {S.p, hp}, {S.set[0].w, hw}};
       for (auto &a : arr) {
-        if ((rc = put_range(c, a.d, voff[s], a.h, np)) != 0) break;
-        if ((rc = put_range(c, a.d, toff[s], a.h + np, nt)) != 0) break;
+        if ((rc = put_range(c, a.d, B.voff, a.h, B.np)) != 0) break;
+        if ((rc = put_range(c, a.d, B.toff, a.h + B.np, B.ntail)) != 0) break;
       }
-      voff[s] += np;
-      toff[s] += nt;
     }
     if (!rc) c->blk_rng[b] = g;  // remove / split continue this block's stream
   }

@@ -16,7 +16,7 @@
 //                      host and the thinning threshold: select_host.cpp (select_rule.hpp; no HIP call)
 //   capi_zoom.cpp      the exact phase-space histogram on a caller's window and grid (pic1dp_hip_zoom; its host arithmetic: zoom_fx.cpp, no HIP call)
 //   capi_hermite.cpp   the Fourier-Hermite spectrum of the markers, summed on the matrix unit (pic1dp_hip_hermite)
-//   capi_optimize.cpp  marker optimisation events (merge / remove / split)
+//   capi_optimize.cpp  marker optimisation events (merge / remove / split): one |delta f|(v), one driver of the blocks' workers, one piece per kind (the blocks' places in a species' arrays: block_layout.hpp; the per-marker lookups: opt_grid.hpp)
 //   capi_checkpoint.cpp  the state digest, checkpoint and restart (the file itself: checkpoint.cpp, no HIP call)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/pic1dp_hip.h"
+#include "block_layout.hpp"
 #include "call_plan.hpp"
 #include "context_plan.hpp"
 #include "device_mem.hpp"
@@ -68,6 +69,7 @@ int fail(int code, const char *fmt, ...);
 constexpr double kPi = 3.14159265358979323846264;        // PETSC_PI
 constexpr double kSqrtEps = 1.490116119384766e-08;       // PETSC_SQRT_MACHINE_EPSILON
 constexpr int64_t kHistCap = 1 << 20;
+struct OptWorker;  // capi_optimize.cpp
 struct Species {
   int64_t nalloc = 0, np = 0;
   PSet set[2] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
@@ -226,7 +228,7 @@ struct pic1dp_ctx {
   size_t h_pin_doubles = 0;                // pageable copies cost a synchronous call each, ~20 us; grow-only, capi_diag.cpp pinned)
   DistGeom dist_geom_v{};                  // output_ptcldist's histogram geometry (capi_diag.cpp dist_geom)
   bool dist_geom_ready = false;
-  std::vector<void *> opt_workers;         // streams and staging of the events' block workers (capi_optimize.cpp OptWorker), kept between events
+  std::vector<OptWorker *> opt_workers;    // streams and staging of the events' block workers (capi_optimize.cpp OptWorker), kept between events
   // the marker products on demand (capi_products.cpp): one device buffer for whichever runs, grow-only, zeroed by every call over what it uses
   double *d_prod = nullptr;
   size_t d_prod_words = 0;                 // its capacity in 8-byte words
@@ -283,6 +285,7 @@ inline bool fp64_rank_sum(const pic1dp_ctx *c) { return c->charge_sum == 0 && se
 
 // ---- capi.cpp ----
 int ensure_second_set(pic1dp_ctx *c);     // the second slab (RK ping-pong set; re-packing target of the optimiser)
+void wire_species(Species &S, const pic1dp_input &in);  // set[0], p and -- where slab[1] exists -- set[1] from the slabs: THE array bases of a species
 int put_range(pic1dp_ctx *c, double *arr, int64_t off, const double *host, int64_t cnt);
 int get_range(pic1dp_ctx *c, const double *arr, int64_t off, double *host, int64_t cnt);
 // ---- capi_step.cpp (the hot path and the executor of the lazy call sites' state machine) ----

@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "kernels.hpp"
+#include "opt_grid.hpp"
 
 namespace pic1dp {
 
@@ -30,35 +31,6 @@ constexpr int OPT_THREADS = 256;
 // block-local marker i of a reference rank block -> offset inside the species' (tiled) arrays
 __device__ __forceinline__ int64_t opt_at(const OptBlock &b, int64_t i) {
   return tidx(i < b.nvalid0 ? b.voff + i : b.toff + (i - b.nvalid0));
-}
-
-// position of velocity v on the nv-point grid over [-v_max, v_max] and the |delta f| there: linear interpolation
-// inside, end values outside (src/pic1dp_particle.F90:449-463, repeated at :552-566 and :660-674) -- the operations of
-// optimize.cpp VGrid::at, one for one
-__device__ __forceinline__ double opt_df(const OptGrid &g, const double *hist, double v, int &cell) {
-  const int last = g.nv - 1;
-  const double pos = (v + g.v_max) / (g.v_max * 2.0) * static_cast<double>(last);
-  const double fl = floor(pos);
-  // (the comparison on the double: a velocity far outside must not overflow the conversion)
-  if (fl < 0.0) {
-    cell = 0;
-    return hist[0];
-  }
-  if (fl >= static_cast<double>(last)) {
-    cell = last;
-    return hist[last];
-  }
-  const int c = static_cast<int>(fl);
-  cell = c;
-  const double left = 1.0 - (pos - static_cast<double>(c));
-  return hist[c] * left + hist[c + 1] * (1.0 - left);
-}
-
-// x = mod(x, lx); if (x < 0) x = x + lx   (:473-475)
-__device__ __forceinline__ double opt_wrap(double x, double lx) {
-  double xx = fmod(x, lx);
-  if (xx < 0.0) xx = xx + lx;
-  return xx;
 }
 
 // ---- |delta f|(v) ----------------------------------------------------------
@@ -126,7 +98,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_merge_keys(const OptBlock b
     const int64_t o = opt_at(b, i);
     int vc;
     uint32_t key = OPT_KEY_IMPORTANT;
-    if (!(opt_df(g, hist, b.v[o], vc) >= limit)) {
+    if (!(opt_df(hist, g.nv, g.v_max, b.v[o], vc) >= limit)) {
       const double xx = opt_wrap(b.x[o], g.lx);
       int xc = static_cast<int>(floor(xx / g.lx * static_cast<double>(g.nx)));
       if (xc >= g.nx) xc = g.nx - 1;  // memory safety (xx == lx), as optimize.cpp
@@ -145,7 +117,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_remove_vals(const OptBlock 
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < np;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     int vc;
-    double df = opt_df(g, hist, b.v[opt_at(b, i)], vc);
+    double df = opt_df(hist, g.nv, g.v_max, b.v[opt_at(b, i)], vc);
     if (by_threshold)
       skip[i] = df >= limit ? 1 : 0;
     else
@@ -159,7 +131,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_split_flags(const OptBlock 
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < np;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     int vc;
-    flag[i] = opt_df(g, hist, b.v[opt_at(b, i)], vc) <= limit ? 0 : 1;
+    flag[i] = opt_df(hist, g.nv, g.v_max, b.v[opt_at(b, i)], vc) <= limit ? 0 : 1;
   }
 }
 
@@ -222,7 +194,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_merge_wrap(const OptBlock b
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const int64_t o = opt_at(b, i);
     int vc;
-    if (!(opt_df(g, hist, b.v[o], vc) >= limit)) b.x[o] = opt_wrap(b.x[o], g.lx);
+    if (!(opt_df(hist, g.nv, g.v_max, b.v[o], vc) >= limit)) b.x[o] = opt_wrap(b.x[o], g.lx);
   }
 }
 // ... and j, at its final position dst, takes k in
@@ -248,7 +220,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_remove_scale(const OptBlock
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const int64_t o = opt_at(b, i);
     int vc;
-    double df = opt_df(g, hist, b.v[o], vc);
+    double df = opt_df(hist, g.nv, g.v_max, b.v[o], vc);
     if (by_threshold) {
       if (df >= limit) continue;
       b.p[o] = b.p[o] / keep_scale;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "check_values.hpp"
+#include "opt_grid.hpp"
 #include "optimize.hpp"
 
 namespace pic1dp {
@@ -17,29 +18,8 @@ namespace {
 struct Grid {
   const pic1dp_input &in;
   const double *hist;
-  double at(double v, int &cell) const {  // (kernels_opt.hip opt_df)
-    const int last = in.nv - 1;
-    const double pos = (v + in.v_max) / (in.v_max * 2.0) * static_cast<double>(last);
-    const double fl = std::floor(pos);
-    if (fl < 0.0) {
-      cell = 0;
-      return hist[0];
-    }
-    if (fl >= static_cast<double>(last)) {
-      cell = last;
-      return hist[last];
-    }
-    const int c = static_cast<int>(fl);
-    cell = c;
-    const double left = 1.0 - (pos - static_cast<double>(c));
-    return hist[c] * left + hist[c + 1] * (1.0 - left);
-  }
+  double at(double v, int &cell) const { return opt_df(hist, in.nv, in.v_max, v, cell); }
 };
-double wrap(double x, double lx) {
-  double xx = std::fmod(x, lx);
-  if (xx < 0.0) xx = xx + lx;
-  return xx;
-}
 struct Arrays {
   std::vector<double> x, v, p, w;
 };
@@ -95,7 +75,7 @@ int64_t host_optimize_check(const pic1dp_input &in, int kind, double threshold, 
       int vc;
       keys[i] = 0xFFFFFFFFu;
       if (!(grid.at(d.v[i], vc) >= limit)) {
-        const double xx = wrap(d.x[i], in.lx);
+        const double xx = opt_wrap(d.x[i], in.lx);
         int xc = static_cast<int>(std::floor(xx / in.lx * static_cast<double>(in.nx)));
         if (xc >= in.nx) xc = in.nx - 1;
         if (xc < 0) xc = 0;
@@ -108,7 +88,7 @@ int64_t host_optimize_check(const pic1dp_input &in, int kind, double threshold, 
     std::vector<double> save(4 * npairs);
     for (size_t t = 0; t < npairs; ++t) {  // k_opt_merge_save
       const uint32_t k = plan.idk[t];
-      save[4 * t] = wrap(d.x[k], in.lx), save[4 * t + 1] = d.v[k], save[4 * t + 2] = d.p[k], save[4 * t + 3] = d.w[k];
+      save[4 * t] = opt_wrap(d.x[k], in.lx), save[4 * t + 1] = d.v[k], save[4 * t + 2] = d.p[k], save[4 * t + 3] = d.w[k];
     }
     std::vector<uint8_t> gone(static_cast<size_t>(std::max<int64_t>(plan.np_new, 1)), 0);
     for (uint32_t k : plan.idk)
@@ -117,7 +97,7 @@ int64_t host_optimize_check(const pic1dp_input &in, int kind, double threshold, 
     const int64_t nwrap = plan.np_new + (plan.moves.ghost >= 0 ? 1 : 0);
     for (int64_t i = 0; i < nwrap; ++i) {  // k_opt_merge_wrap
       int vc;
-      if (!(grid.at(d.v[i], vc) >= limit)) d.x[i] = wrap(d.x[i], in.lx);
+      if (!(grid.at(d.v[i], vc) >= limit)) d.x[i] = opt_wrap(d.x[i], in.lx);
     }
     for (size_t t = 0; t < npairs; ++t) {  // k_opt_merge_combine
       const uint32_t o = plan.dst[t];

@@ -5,36 +5,19 @@
 #include <cmath>
 #include <vector>
 
+#include "opt_grid.hpp"
+
 namespace pic1dp {
 
 namespace {
 
-// position of velocity v on the nv-point grid over [-v_max, v_max] and the
-// |delta f| there: linear interpolation inside, end values outside
-// (src/pic1dp_particle.F90:449-463, repeated at :552-566 and :660-674)
+// |delta f|(v) of one species, its peak, and the |delta f| at a marker's velocity (opt_grid.hpp opt_df)
 struct VGrid {
   const pic1dp_input &in;
   const double *hist;
   double peak;
   VGrid(const pic1dp_input &i, const double *h) : in(i), hist(h), peak(*std::max_element(h, h + i.nv)) {}
-  double at(double v, int &cell) const {
-    const int last = in.nv - 1;
-    const double pos = (v + in.v_max) / (in.v_max * 2.0) * static_cast<double>(last);
-    const double fl = std::floor(pos);
-    // (the comparison on the double, as kernels_opt.hip opt_df: a velocity far outside must not overflow the conversion)
-    if (fl < 0.0) {
-      cell = 0;
-      return hist[0];
-    }
-    if (fl >= static_cast<double>(last)) {
-      cell = last;
-      return hist[last];
-    }
-    const int c = static_cast<int>(fl);
-    cell = c;
-    const double left = 1.0 - (pos - static_cast<double>(c));
-    return hist[c] * left + hist[c + 1] * (1.0 - left);
-  }
+  double at(double v, int &cell) const { return opt_df(hist, in.nv, in.v_max, v, cell); }
 };
 
 // "remove marker k": the last valid marker takes its place (and will be visited
@@ -81,8 +64,7 @@ void opt_merge(const pic1dp_input &in, double threshold, const double *hist, int
   for (int64_t k = 0; k < np; ++k) {
     int vc;
     if (grid.at(v[k], vc) >= limit) continue;  // important marker: leave alone
-    double xx = std::fmod(x[k], in.lx);
-    if (xx < 0.0) xx = xx + in.lx;
+    const double xx = opt_wrap(x[k], in.lx);
     x[k] = xx;
     int xc = static_cast<int>(std::floor(xx / in.lx * static_cast<double>(nx)));
     if (xc >= nx) xc = nx - 1;  // memory safety (xx == lx)

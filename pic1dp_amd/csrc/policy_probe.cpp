@@ -1,11 +1,12 @@
 // policy_probe.cpp -- the launch policy (launch_policy.hpp), the LDS layouts of the field kernels (field_lds.hpp) and the
 // decisions of create() (settings.hpp, context_plan.hpp) behind the C ABI of the probe library, for the host tests that pin
 // them (tests/test_launch_policy_host.py, tests/test_field_lds_host.py, tests/test_diag_launch_host.py,
-// tests/test_context_plan_host.py, tests/test_step_plan_host.py, tests/test_call_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
+// tests/test_context_plan_host.py, tests/test_step_plan_host.py, tests/test_call_plan_host.py, tests/test_moments_host.py, tests/test_moments_exact_host.py, tests/test_load_device_host.py), and the layout of a species' blocks (block_layout.hpp; tests/test_block_layout_host.py).  Test support (libpic1dp_probe.so), no GPU needed.
 #include <cmath>
 #include <cstdio>
 
 #include "../../include/pic1dp_probe.h"
+#include "block_layout.hpp"
 #include "call_plan.hpp"
 #include "context_plan.hpp"
 #include "field_lds.hpp"
@@ -67,6 +68,17 @@ extern "C" int pic1dp_probe_host_load_launch(int64_t nalloc, int32_t num_cu, int
   out[1] = l.threads;
   out[2] = l.nt;
   out[3] = LOAD_CHUNK;
+  return 0;
+}
+
+extern "C" int pic1dp_probe_host_block_layout(const int64_t *blk_alloc, const int64_t *blk_np, int32_t nblk, int64_t *out, int64_t *np) {
+  if (!blk_alloc || !blk_np || !out || !np || nblk < 1) return 1;
+  const BlockLayout L = block_layout(std::vector<int64_t>(blk_alloc, blk_alloc + nblk), std::vector<int64_t>(blk_np, blk_np + nblk));
+  for (int b = 0; b < nblk; ++b) {
+    const int64_t v[4] = {L.blk[b].voff, L.blk[b].np, L.blk[b].toff, L.blk[b].ntail};
+    for (int k = 0; k < 4; ++k) out[4 * b + k] = v[k];
+  }
+  *np = L.np;
   return 0;
 }
 

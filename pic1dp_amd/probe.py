@@ -83,6 +83,7 @@ SIGNATURES = {
     "pic1dp_probe_host_call_plan": [_I32, _I32, _I32, C.c_int32, _I32],
     "pic1dp_probe_host_load_launch": [C.c_int64, C.c_int32, _I64],
     "pic1dp_probe_host_plain_chunks": [C.c_int64, C.c_int64, C.c_int32, _I64],
+    "pic1dp_probe_host_block_layout": [_I64, _I64, C.c_int32, _I64, _I64],
     "pic1dp_probe_write_stream": [C.c_int32, C.c_int64, C.c_int32, _D],
     "pic1dp_probe_load_uniforms": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
 }
@@ -493,6 +494,17 @@ def host_plain_chunks(np_all_species, np_species, nt=True):
     if load().pic1dp_probe_host_plain_chunks(int(np_all_species), int(np_species), int(bool(nt)), C.byref(out)) != 0:
         raise ValueError("pic1dp_probe_host_plain_chunks: bad argument")
     return out.value
+
+
+def host_block_layout(blk_alloc, blk_np):
+    """where the blocks of one species lie in its packed arrays (csrc/block_layout.hpp), on the host:
+    ([(voff, np, toff, ntail) per block], the species' valid markers)"""
+    n = len(blk_alloc)
+    out, total = (C.c_int64 * (4 * n))(), C.c_int64(-1)
+    if len(blk_np) != n or load().pic1dp_probe_host_block_layout((C.c_int64 * n)(*blk_alloc), (C.c_int64 * n)(*blk_np), n, out,
+                                                                 C.byref(total)) != 0:
+        raise ValueError("pic1dp_probe_host_block_layout: bad argument")
+    return [tuple(out[4 * b:4 * b + 4]) for b in range(n)], total.value
 
 
 def load_uniforms(kind, g, seed_offset=0, ispecies=0, device=0):

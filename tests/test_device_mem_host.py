@@ -12,8 +12,9 @@ EXCEPTIONS = {
     # the exchange area: fine-grained / uncached allocators with a fall-back to hipMalloc, IPC handles, and a life cycle of
     # its own (connect / disconnect while the context lives): comm_release
     "capi_comm.cpp": {"hipMalloc": 2, "hipFree": 3, "hipHostMalloc": 1, "hipHostFree": 1},
-    # the optimisation events' workers: grow-only scratch with per-worker lifetime and streams of their own (DevBuf, HostPin)
-    "capi_optimize.cpp": {"hipMalloc": 1, "hipFree": 2, "hipHostMalloc": 1, "hipHostFree": 2},
+    # the optimisation events' workers: grow-only scratch with per-worker lifetime and streams of their own, grown on the
+    # workers' threads (GrowBuf: DevBuf, HostPin); the event's own scratch is the owner's
+    "capi_optimize.cpp": {"hipMalloc": 1, "hipFree": 1, "hipHostMalloc": 1, "hipHostFree": 1},
     # particle_load's pinned stage of one block's markers, freed before the call returns (up to GBs: not kept);
     # chain_selftest's scratch: an optional self-test that must not fail create(), freed before it returns;
     # cell_indices' scratch (a debugging call): two buffers sized by the call, freed before it returns
